@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Benchmark of the solver hot path on MI355X: BASELINE.json's restart job.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--restarts R]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--restarts R] [--dump-outputs DIR] [--full]
 
 The job (BASELINE.json configs[2]; reference loop demethify/demethify.py:195-203):
 R = 64 random restarts of the partial-reference solver on ONE synthetic problem, 1e6 CpG x 256 samples, 12 known + 4
@@ -16,8 +16,15 @@ cost, :204), the K outer iterations, the per-restart cost_f_w (demethify.py:199)
 R-element cost vector and the broadcast of the winner's (u, alpha).  Total work is fixed as N grows: strong scaling,
 value = R * K outer iterations / wall time (max over ranks).
 
-Prints ONE JSON line on rank 0 (fields: see the driver contract; plus "roofline", "cpu_baseline" and "loop_only" =
-the rate of the K-iteration loops alone, which is what round 1 reported as value).
+Prints ONE JSON line on rank 0: metric, value, unit, higher_is_better, dtype, ms_per_step (= wall time of the timed
+region / K), the configuration, and "loop_only" = the rate of the K-iteration loops alone (what round 1 reported as
+value).  A plain run does nothing else.  --full adds what takes measurements of its own: HIP events around the kernel
+families inside the timed region and an untimed solve after it ("roofline": per-kernel times, bytes and bounds) and,
+on one GPU unless --no-cpu-baseline, the oracle timed on the host ("cpu_baseline", about a minute).
+
+--dump-outputs DIR writes what the job hands its caller, from the last timed step: the winning restart's profiles
+(u.npy, N x n_u) and proportions (alpha.npy, K x S), and every restart's cost_f_w (restart_costs.npy, R), float64.
+The inputs depend only on the arguments, so two builds can be compared output for output.
 """
 from __future__ import annotations
 
@@ -149,6 +156,109 @@ def git_head():
         return None
 
 
+DUMP_BUDGET = 64_000_000  # bytes, all --dump-outputs files together (.npy headers included)
+
+
+def dump_outputs(out_dir, u, alpha, costs):
+    """--dump-outputs: the job's result as float64 .npy files.  If the profiles would take the dump over its budget,
+    a fixed sample of their rows (RandomState(0), sorted) is written instead, with its row indices."""
+    out_dir = Path(out_dir)
+    out_dir.mkdir(parents=True, exist_ok=True)
+    arrays = {"alpha": alpha, "restart_costs": costs}
+    room = DUMP_BUDGET - 4096 - sum(np.asarray(a).nbytes for a in arrays.values())
+    if u.nbytes <= room:
+        arrays["u"] = u
+    else:
+        m = room // (8 * (u.shape[1] + 1))
+        rows = np.sort(np.random.RandomState(0).choice(u.shape[0], m, replace=False))
+        arrays["u_sample"], arrays["u_sample_rows"] = u[rows], rows
+    for name, a in arrays.items():
+        np.save(out_dir / f"{name}.npy", np.ascontiguousarray(a, dtype=np.float64))
+
+
+def roofline_figures(workload, fam, kernels, N, S, n_c, n_u, loop_rate):
+    """--full: the dominant kernel against the HBM and FP64 roofs, from the per-family HIP-event times `fam`."""
+    b_alg = algorithmic_bytes(N, S, n_c, n_u)
+    fam_ms = {k: (v[0] / max(v[1], 1), v[1]) for k, v in fam.items()}
+    names = dict(tok.split("=", 1) for tok in kernels.split() if "=" in tok and tok.split("=")[0] in ("rowpass", "gram", "alpha"))
+    n_p = n_u * (n_u + 1) // 2
+    nd = 2 if "nd=2" in names.get("gram", "") else 1
+    # Algorithmic (compulsory) HBM bytes per launch of each streaming kernel, 1 unit = 1 outer iteration per launch.
+    # SURVEY.md 8(d) counts V and the counts at 8 bytes each (B_alg = 16 N S + 8 N (n_c + 3 n_u)); the second-
+    # generation kernels read the counts as u16 (row pass) and as 8-bit digit planes (integer Gram), an exact
+    # re-encoding, so THEIR compulsory bytes are what `achieved` is computed from -- pricing them at 16 bytes per
+    # element would report bytes that are never moved.
+    if names.get("rowpass", "").startswith("k_rowpass_v2"):
+        row_bytes = N * S * (8 + 2) + N * 8 * (n_c + 4 * n_u)       # V f64, counts u16, R_trunc, u + u_ in and out
+        gram_bytes = N * S * nd + N * 8 * (n_c + n_u)               # count digit planes, R_trunc, u
+        row_flop = N * S * (2 * n_c + 4 * n_u + 2 * n_p + 2) + T2 * N * (2 * n_u * n_u + 8 * n_u)
+    else:
+        row_bytes = N * S * 16 + N * 8 * (n_c + 4 * n_u)
+        gram_bytes = 0 if names.get("gram") == "fused" else N * S * 16 + N * 8 * (n_c + n_u)
+        row_flop = algorithmic_flops(N, S, n_c, n_u) if names.get("gram") == "fused" else \
+            N * S * (2 * n_c + 4 * n_u + 2 * n_p + 2) + T2 * N * (2 * n_u * n_u + 8 * n_u)
+    per_launch_bytes = {"rowpass": row_bytes, "gram": gram_bytes}
+    dom = max(("rowpass", "gram"), key=lambda k: fam[k][0])
+    dom_kernel = names.get(dom, dom)
+    if dom == "gram" and dom_kernel == "fused":
+        dom_kernel = "k_gram_reduce"
+    dom_ms = fam_ms[dom][0]
+    achieved = per_launch_bytes[dom] / (dom_ms * 1e-3) / 1e9 if dom_ms > 0 else 0.0
+    # Counter figures of the dominant kernel: NOT measured in this run (counters need rocprofv3 passes of their own,
+    # one group per pass) but taken from profiles/counters.json, which tools/collect_counters.py writes from such
+    # passes and stamps with the commit they were taken at (profiles/README.md).
+    traffic, traffic_source, pmc = None, None, {}
+    for name in ("counters.json", "traffic.json"):
+        tfile = ROOT / "profiles" / name
+        if traffic is not None or not tfile.exists():
+            continue
+        try:
+            tj = json.loads(tfile.read_text())
+            entry = tj.get(workload, {}).get(dom_kernel.split("<")[0], {})
+            traffic = entry.get("hbm_bytes_per_launch")
+            if traffic is not None:
+                traffic_source = f"profiles/{name}@{tj.get('_commit', 'unknown')} (rocprofv3 --pmc, separate run)"
+                pmc = {k: entry.get(k) for k in ("issue_frac", "wait_frac", "mfma_busy_frac") if entry.get(k) is not None}
+        except Exception:
+            traffic = None
+    # What bounds the dominant kernel, from the data: the roof it sits closest to if it reaches 0.7 of it -- HBM bytes,
+    # FP64 rate (this run), issue slots or matrix-pipe time (counters) -- otherwise none of them does: "latency"
+    # (dependency and memory stalls that the resident waves do not cover; see wait_frac).
+    hbm_frac = achieved / HBM_PEAK_GBS
+    fp64_frac = row_flop / (fam_ms["rowpass"][0] * 1e-3) / 1e12 / FP64_PEAK_TFLOPS if fam_ms["rowpass"][0] > 0 and dom == "rowpass" else 0.0
+    shares = {"hbm": hbm_frac, "fp64": fp64_frac, "issue": pmc.get("issue_frac", 0.0), "mfma": pmc.get("mfma_busy_frac", 0.0)}
+    top = max(shares, key=shares.get)
+    bound = top if shares[top] >= 0.7 else "latency"
+    iter_bytes = row_bytes + gram_bytes
+    gram_ms = fam_ms["gram"][0]
+    return {
+        # achieved / peak / frac: against the HBM roof (the bytes the kernel must move), whatever `bound` says
+        "bound": bound, "bound_shares": {k: round(v, 4) for k, v in shares.items()},
+        "kernel": dom_kernel, "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+        "frac": achieved / HBM_PEAK_GBS, "traffic": traffic, "traffic_source": traffic_source,
+        "issue_frac": pmc.get("issue_frac"), "wait_frac": pmc.get("wait_frac"), "mfma_busy_frac": pmc.get("mfma_busy_frac"),
+        "algorithmic_bytes_per_launch": per_launch_bytes[dom],
+        "avg_launch_ms": dom_ms,
+        # the same launch against the FP64 roof: flops the row pass executes in this formulation (FP64 MFMA and
+        # FP64 VALU share one pipe on gfx950, DESIGN.md section 5)
+        "fp64": {"flop_per_launch": row_flop, "achieved": row_flop / (fam_ms["rowpass"][0] * 1e-3) / 1e12 if fam_ms["rowpass"][0] > 0 else 0.0,
+                 "peak": FP64_PEAK_TFLOPS, "unit": "TFLOP/s",
+                 "frac": row_flop / (fam_ms["rowpass"][0] * 1e-3) / 1e12 / FP64_PEAK_TFLOPS if fam_ms["rowpass"][0] > 0 else 0.0},
+        # second kernel of the outer iteration (family "gram": the integer-matrix-core GEMM + its reduction)
+        "gram": {"kernel": names.get("gram"), "avg_ms": gram_ms, "algorithmic_bytes": gram_bytes,
+                 "achieved": gram_bytes / (gram_ms * 1e-3) / 1e9 if gram_ms > 0 else 0.0, "unit": "GB/s",
+                 "int8_ops": 2 * N * S * (n_c * n_u + n_p) * 7 * nd if "i8" in names.get("gram", "") else None},
+        "whole_iteration": {"algorithmic_bytes": iter_bytes, "achieved": iter_bytes * loop_rate / 1e9,
+                            "frac": iter_bytes * loop_rate / 1e9 / HBM_PEAK_GBS,
+                            # SURVEY 8(d)'s f64-layout figure (16 B per element) times the same rate: what the
+                            # iteration would have to stream without the integer re-encoding; NOT bytes moved
+                            "sec8d_f64_layout_bytes": b_alg, "sec8d_f64_layout_equivalent": b_alg * loop_rate / 1e9},
+        "family_avg_ms": {k: round(v[0], 4) for k, v in fam_ms.items()},
+        "family_timed": "HIP events inside the timed region: rowpass every launch, gram and cost one restart's (the middle one); alpha: one restart's launches after it",
+        "family_launches": {k: v[1] for k, v in fam_ms.items()},
+    }
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -156,13 +266,18 @@ def main():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--restarts", type=int, default=64, help="restarts of the whole job (BASELINE config 3: 64)")
     ap.add_argument("--workload", default="headline_1e6x256_12+4", choices=sorted(WORKLOADS))
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also the per-kernel HIP-event times, the roofline and (one GPU) the CPU baseline")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave out the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the job's result (winner's u, alpha; restart costs) as .npy")
     ap.add_argument("--kernels", type=int, default=0, choices=[0, 1, 2, 3],
                     help="kernel selection level (dmf_context_set_generic): 0 = fastest (default)")
     ap.add_argument("--backend", default="nccl", choices=["nccl", "gloo"],
                     help="collective backend; gloo + --share-gpu rehearses the N > 1 path on a one-GPU box")
     ap.add_argument("--share-gpu", action="store_true", help="rehearsal only: every rank uses cuda:0")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     import torch
     import torch.distributed as dist
@@ -217,9 +332,10 @@ def main():
     # region's first restarts run while the clocks still ramp: their Gram launches take 0.17 ms against 0.145 later): an event
     # record between two kernels leaves the GPU idle for a few microseconds, which long kernels hide (the command processor
     # works ahead) and short ones do not -- four records per outer iteration were 13 % of config 2's 85 us iteration.  The
-    # KB-sized alpha phase is timed after the job.
-    ctx.set_profiling(True, families=(L.KERNEL_ROWPASS,))
-    ctx.reset_kernel_time()
+    # KB-sized alpha phase is timed after the job.  (--full only: a plain run records no events.)
+    if args.full:
+        ctx.set_profiling(True, families=(L.KERNEL_ROWPASS,))
+        ctx.reset_kernel_time()
 
     mine = shard.my_items(R, rank, world)
     if world > 1:
@@ -249,14 +365,14 @@ def main():
         s = Solver(problem, u0, a0, L.DMF_MODE_PARTIAL)  # (set up while the GPU takes the previous restart's cost)
         if waiting is not None:
             settle(*waiting)
-        if k == sampled:
+        if args.full and k == sampled:
             ctx.set_profiling(True, families=(L.KERNEL_ROWPASS, L.KERNEL_GRAM, L.KERNEL_COST))
         tl = time.perf_counter()
         it, _ = s.step(args.steps, T2, 0.0)  # returns after the last iteration's state has been read back
         loop_s += time.perf_counter() - tl
         iters_total += it
         s.cost_begin()
-        if k == sampled:
+        if args.full and k == sampled:
             ctx.set_profiling(True, families=(L.KERNEL_ROWPASS,))
         waiting = (k, s)
     if waiting is not None:
@@ -282,72 +398,23 @@ def main():
     assert iters_total == len(mine) * args.steps, (iters_total, len(mine), args.steps)
     assert np.isfinite(costs).all() and (rank != 0 or u_w.shape == (N, n_u))
 
-    fam = {name: ctx.kernel_time(i) for i, name in enumerate(L.KERNEL_FAMILIES)}
-    ctx.reset_kernel_time()
-    ctx.set_profiling(True, families=(L.KERNEL_ALPHA,))
-    u0, a0 = restart_init(rank, N, S, n_c, n_u)
-    with Solver(problem, u0, a0, L.DMF_MODE_PARTIAL) as s:
-        s.step(args.steps, T2, 0.0)  # untimed: fills in the small family of the per-family table
-    ctx.synchronize()
-    fam[L.KERNEL_FAMILIES[L.KERNEL_ALPHA]] = ctx.kernel_time(L.KERNEL_ALPHA)
-    ctx.set_profiling(False)
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, u_w, a_w, costs)
+
+    if args.full:
+        fam = {name: ctx.kernel_time(i) for i, name in enumerate(L.KERNEL_FAMILIES)}
+        ctx.reset_kernel_time()
+        ctx.set_profiling(True, families=(L.KERNEL_ALPHA,))
+        u0, a0 = restart_init(rank, N, S, n_c, n_u)
+        with Solver(problem, u0, a0, L.DMF_MODE_PARTIAL) as s:
+            s.step(args.steps, T2, 0.0)  # untimed: fills in the small family of the per-family table
+        ctx.synchronize()
+        fam[L.KERNEL_FAMILIES[L.KERNEL_ALPHA]] = ctx.kernel_time(L.KERNEL_ALPHA)
+        ctx.set_profiling(False)
 
     if rank == 0:
-        b_alg = algorithmic_bytes(N, S, n_c, n_u)
-        fam_ms = {k: (v[0] / max(v[1], 1), v[1]) for k, v in fam.items()}
-        names = dict(tok.split("=", 1) for tok in kernels.split() if "=" in tok and tok.split("=")[0] in ("rowpass", "gram", "alpha"))
-        n_p = n_u * (n_u + 1) // 2
-        nd = 2 if "nd=2" in names.get("gram", "") else 1
-        # Algorithmic (compulsory) HBM bytes per launch of each streaming kernel, 1 unit = 1 outer iteration per launch.
-        # SURVEY.md 8(d) counts V and the counts at 8 bytes each (B_alg = 16 N S + 8 N (n_c + 3 n_u)); the second-
-        # generation kernels read the counts as u16 (row pass) and as 8-bit digit planes (integer Gram), an exact
-        # re-encoding, so THEIR compulsory bytes are what `achieved` is computed from -- pricing them at 16 bytes per
-        # element would report bytes that are never moved.
-        if names.get("rowpass", "").startswith("k_rowpass_v2"):
-            row_bytes = N * S * (8 + 2) + N * 8 * (n_c + 4 * n_u)       # V f64, counts u16, R_trunc, u + u_ in and out
-            gram_bytes = N * S * nd + N * 8 * (n_c + n_u)               # count digit planes, R_trunc, u
-            row_flop = N * S * (2 * n_c + 4 * n_u + 2 * n_p + 2) + T2 * N * (2 * n_u * n_u + 8 * n_u)
-        else:
-            row_bytes = N * S * 16 + N * 8 * (n_c + 4 * n_u)
-            gram_bytes = 0 if names.get("gram") == "fused" else N * S * 16 + N * 8 * (n_c + n_u)
-            row_flop = algorithmic_flops(N, S, n_c, n_u) if names.get("gram") == "fused" else \
-                N * S * (2 * n_c + 4 * n_u + 2 * n_p + 2) + T2 * N * (2 * n_u * n_u + 8 * n_u)
-        per_launch_bytes = {"rowpass": row_bytes, "gram": gram_bytes}
-        dom = max(("rowpass", "gram"), key=lambda k: fam[k][0])
-        dom_kernel = names.get(dom, dom)
-        if dom == "gram" and dom_kernel == "fused":
-            dom_kernel = "k_gram_reduce"
-        dom_ms = fam_ms[dom][0]
-        achieved = per_launch_bytes[dom] / (dom_ms * 1e-3) / 1e9 if dom_ms > 0 else 0.0
-        # Counter figures of the dominant kernel: NOT measured in this run (counters need rocprofv3 passes of their own,
-        # one group per pass) but taken from profiles/counters.json, which tools/collect_counters.py writes from such
-        # passes and stamps with the commit they were taken at (profiles/README.md).
-        traffic, traffic_source, pmc = None, None, {}
-        for name in ("counters.json", "traffic.json"):
-            tfile = ROOT / "profiles" / name
-            if traffic is not None or not tfile.exists():
-                continue
-            try:
-                tj = json.loads(tfile.read_text())
-                entry = tj.get(args.workload, {}).get(dom_kernel.split("<")[0], {})
-                traffic = entry.get("hbm_bytes_per_launch")
-                if traffic is not None:
-                    traffic_source = f"profiles/{name}@{tj.get('_commit', 'unknown')} (rocprofv3 --pmc, separate run)"
-                    pmc = {k: entry.get(k) for k in ("issue_frac", "wait_frac", "mfma_busy_frac") if entry.get(k) is not None}
-            except Exception:
-                traffic = None
-        # What bounds the dominant kernel, from the data: the roof it sits closest to if it reaches 0.7 of it -- HBM bytes,
-        # FP64 rate (this run), issue slots or matrix-pipe time (counters) -- otherwise none of them does: "latency"
-        # (dependency and memory stalls that the resident waves do not cover; see wait_frac).
-        hbm_frac = achieved / HBM_PEAK_GBS
-        fp64_frac = row_flop / (fam_ms["rowpass"][0] * 1e-3) / 1e12 / FP64_PEAK_TFLOPS if fam_ms["rowpass"][0] > 0 and dom == "rowpass" else 0.0
-        shares = {"hbm": hbm_frac, "fp64": fp64_frac, "issue": pmc.get("issue_frac", 0.0), "mfma": pmc.get("mfma_busy_frac", 0.0)}
-        top = max(shares, key=shares.get)
-        bound = top if shares[top] >= 0.7 else "latency"
         ms_per_step = elapsed / args.steps * 1e3
         loop_rate = iters_total / loop_s if loop_s > 0 else 0.0
-        iter_bytes = row_bytes + gram_bytes
-        gram_ms = fam_ms["gram"][0]
         out = {
             "metric": "NMF update iters/sec (1e6 CpG x 256 samples x 16 types)" if args.workload.startswith("headline")
                       else f"NMF update iters/sec ({args.workload})",
@@ -361,6 +428,7 @@ def main():
             "scaling": "strong",
             "vs_baseline": None,
             "dtype": "f64",
+            "full": args.full,
             "data": "synthetic (SURVEY 8d recipe; small factors legacy numpy, N x S draws torch Philox on device)",
             "config": {"workload": args.workload, "N_cpg": N, "S_samples": S, "n_known": n_c, "n_unknown": n_u,
                        "inner_iters": T2, "restarts": R, "restart_seed": "1 + k", "restart_placement": "k mod n_gpus",
@@ -372,34 +440,9 @@ def main():
             # rank 0's K-iteration loops alone (what a single solve sustains; round 1 reported this as value)
             "loop_only": {"value": loop_rate, "unit": "outer iters/s per GPU", "ms_per_outer_iteration": 1e3 / loop_rate if loop_rate else None,
                           "restarts_on_rank0": len(mine), "job_seconds": elapsed, "loop_seconds_rank0": loop_s},
-            "roofline": {
-                # achieved / peak / frac: against the HBM roof (the bytes the kernel must move), whatever `bound` says
-                "bound": bound, "bound_shares": {k: round(v, 4) for k, v in shares.items()},
-                "kernel": dom_kernel, "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                "frac": achieved / HBM_PEAK_GBS, "traffic": traffic, "traffic_source": traffic_source,
-                "issue_frac": pmc.get("issue_frac"), "wait_frac": pmc.get("wait_frac"), "mfma_busy_frac": pmc.get("mfma_busy_frac"),
-                "algorithmic_bytes_per_launch": per_launch_bytes[dom],
-                "avg_launch_ms": dom_ms,
-                # the same launch against the FP64 roof: flops the row pass executes in this formulation (FP64 MFMA and
-                # FP64 VALU share one pipe on gfx950)
-                "fp64": {"flop_per_launch": row_flop, "achieved": row_flop / (fam_ms["rowpass"][0] * 1e-3) / 1e12 if fam_ms["rowpass"][0] > 0 else 0.0,
-                         "peak": FP64_PEAK_TFLOPS, "unit": "TFLOP/s",
-                         "frac": row_flop / (fam_ms["rowpass"][0] * 1e-3) / 1e12 / FP64_PEAK_TFLOPS if fam_ms["rowpass"][0] > 0 else 0.0},
-                # second kernel of the outer iteration (family "gram": the integer-matrix-core GEMM + its reduction)
-                "gram": {"kernel": names.get("gram"), "avg_ms": gram_ms, "algorithmic_bytes": gram_bytes,
-                         "achieved": gram_bytes / (gram_ms * 1e-3) / 1e9 if gram_ms > 0 else 0.0, "unit": "GB/s",
-                         "int8_ops": 2 * N * S * (n_c * n_u + n_p) * 7 * nd if "i8" in names.get("gram", "") else None},
-                "whole_iteration": {"algorithmic_bytes": iter_bytes, "achieved": iter_bytes * loop_rate / 1e9,
-                                    "frac": iter_bytes * loop_rate / 1e9 / HBM_PEAK_GBS,
-                                    # SURVEY 8(d)'s f64-layout figure (16 B per element) times the same rate: what the
-                                    # iteration would have to stream without the integer re-encoding; NOT bytes moved
-                                    "sec8d_f64_layout_bytes": b_alg, "sec8d_f64_layout_equivalent": b_alg * loop_rate / 1e9},
-                "family_avg_ms": {k: round(v[0], 4) for k, v in fam_ms.items()},
-                "family_timed": "HIP events inside the timed region: rowpass every launch, gram and cost one restart's (the middle one); alpha: one restart's launches after it",
-                "family_launches": {k: v[1] for k, v in fam_ms.items()},
-            },
+            "roofline": roofline_figures(args.workload, fam, kernels, N, S, n_c, n_u, loop_rate) if args.full else None,
         }
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(V, D, Rt, n_u, N)
         else:
             out["cpu_baseline"] = None

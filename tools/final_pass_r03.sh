@@ -4,9 +4,9 @@ set -e
 cd $GRAFT_REPO_ROOT
 O=gpurun_out/final6
 mkdir -p $O
-python bench.py > $O/bench_line.json 2> $O/bench.err
-python bench.py --workload config2_1e5x64_6+2 --no-cpu-baseline > $O/config2_bench_line.json 2> $O/config2.err
-DMF_BENCH_DEPTH=120 python bench.py --no-cpu-baseline --restarts 8 > $O/deep_coverage_bench_line.json 2> $O/deep.err
+python bench.py --full > $O/bench_line.json 2> $O/bench.err
+python bench.py --full --workload config2_1e5x64_6+2 --no-cpu-baseline > $O/config2_bench_line.json 2> $O/config2.err
+DMF_BENCH_DEPTH=120 python bench.py --full --no-cpu-baseline --restarts 8 > $O/deep_coverage_bench_line.json 2> $O/deep.err
 (cd /tmp && export TMPDIR=/tmp && rocprofv3 --kernel-trace --stats --output-format csv -d $GRAFT_REPO_ROOT/$O/stats -o r03 -- python3 $GRAFT_REPO_ROOT/bench.py --steps 20 --warmup 3 --restarts 8 --no-cpu-baseline > $GRAFT_REPO_ROOT/$O/stats.log 2>&1)
 echo stats done
 bash tools/pmc_shape.sh final6/pmc_headline 1000000 256 12 4 6 > /dev/null
