@@ -14,6 +14,7 @@ DMF_OK = 0
 DMF_PTR_DEVICE = 1
 DMF_INIT_IN_UNIT_RANGE = 4
 DMF_SELECT_COUNTS_F32_EXACT, DMF_SELECT_PURITY, DMF_SELECT_ALPHA_OUTSIDE_UNIT, DMF_SELECT_V_UNALIGNED = 1, 2, 4, 8
+DMF_SELECT_X16 = 16
 DMF_COUNTS_F64 = 2
 DMF_MODE_PARTIAL = 0
 DMF_MODE_UNSUPERVISED = 1
@@ -37,6 +38,7 @@ SIGNATURES = {
     "dmf_context_kernel_time": (C.c_int, [_p, C.c_int, _dbl_p, C.POINTER(_i64)]),
     "dmf_context_reset_kernel_time": (C.c_int, [_p]),
     "dmf_context_set_generic": (C.c_int, [_p, C.c_int]),
+    "dmf_context_set_x16": (C.c_int, [_p, C.c_int]),
     "dmf_context_set_stop_confirmation": (C.c_int, [_p, C.c_int]),
     "dmf_problem_create": (C.c_int, [_p, _i64, _i64, _i64, _p, _p, _p, C.c_int, C.POINTER(_p)]),
     "dmf_problem_gather": (C.c_int, [_p, _p, _p, _i64, C.POINTER(_p)]),

@@ -58,6 +58,7 @@ struct dmf_context {
     int stop_confirmation = 0;  // dmf_context_set_stop_confirmation: 0 by error bound, 1 always, 2 never
     int generic_level = 0;  // 0 fused row pass, 1 any-shape Gram-form kernels, 2 schedule-faithful u steps,
                             // 3 separate MFMA row pass + one-pass Gram (the pieces the fused kernel is made of)
+    bool x16 = true;        // dmf_context_set_x16: problems created from now on get the X16 copy when their data allow
     double* scratch = nullptr;  // 4096 doubles of reduction scratch
     hipMemPool_t pool = nullptr;  // the context's own stream-ordered pool (the device's default pool is not touched)
     std::unordered_map<void*, size_t> live;                // large blocks handed out by pool_alloc (size by address)
@@ -88,6 +89,11 @@ struct dmf_problem {
     int ND = 0;                     // count digits: 0 = no integer copies, 1 (d <= 127), 2 (d <= 32639)
     int SD = 0;
     int64_t N16 = 0, plane_stride = 0;
+    // the methylated read counts x = rint(v d) as u16 in D16's layout, when every element is exact to kX16MaxDev
+    // (dmf_internal.h): the row pass then reads (X16, D16) instead of (V, D16).  x16_dev: the largest |v d - x| / max(x, 1)
+    // seen, x16_sum: sum of x -- their product bounds what the substitution changes in the Gram-form cost.
+    unsigned short* X16 = nullptr;
+    double x16_dev = 0.0, x16_sum = 0.0;
     bool d_f32_exact = false;    // every count survives a round trip through f32 (the fused tile stores D as f32)
     double* gb_known = nullptr;  // [(n_c+1)(n_c+2)/2][S]
 };
@@ -334,8 +340,29 @@ int problem_finalize(dmf_problem* p, bool counts_done = false) {
         p->plane_stride = ((N + 31) / 32) * (p->SD / 32) * 1024;
         HIP_TRY(pool_alloc(ctx, (void**)&p->D16, (size_t)p->N16 * p->SD * sizeof(unsigned short)));
         HIP_TRY(pool_alloc(ctx, (void**)&p->Dt8, (size_t)p->plane_stride * p->ND));
-        HIP_TRY(dmf::launch_build_counts_int(p->D, N, (int)S, p->ND, p->D16, p->N16, p->SD, p->Dt8, p->plane_stride,
-                                             ctx->stream));
+        unsigned long long* x_stats = nullptr;
+        if (ctx->x16) {
+            HIP_TRY(pool_alloc(ctx, (void**)&p->X16, (size_t)p->N16 * p->SD * sizeof(unsigned short)));
+            HIP_TRY(pool_alloc(ctx, (void**)&x_stats, 3 * sizeof(unsigned long long)));
+        }
+        hipError_t e = dmf::launch_build_counts_int(p->D, p->V, N, (int)S, p->ND, p->D16, p->X16, p->N16, p->SD, p->Dt8,
+                                                    p->plane_stride, x_stats, ctx->stream);
+        unsigned long long got[3] = {1, 0, 0};
+        if (e == hipSuccess && x_stats != nullptr) e = hipMemcpyAsync(got, x_stats, sizeof(got), hipMemcpyDeviceToHost, ctx->stream);
+        if (e == hipSuccess && x_stats != nullptr) e = hipStreamSynchronize(ctx->stream);
+        pool_free(ctx, x_stats);
+        if (e != hipSuccess) return hip_fail(e, "integer count copies", __LINE__);
+        if (p->X16 != nullptr) {
+            if (got[0] != 0) {  // some element is not an exact x / d: every kernel reads V
+                pool_free(ctx, p->X16);
+                p->X16 = nullptr;
+            } else {
+                double dev;
+                std::memcpy(&dev, &got[1], sizeof(dev));
+                p->x16_dev = dev;
+                p->x16_sum = (double)got[2];
+            }
+        }
     }
 
     // padded copy of R_trunc for the shape-specialised kernels (aligned, branch-free row loads)
@@ -603,15 +630,17 @@ int enqueue_outer_iteration(dmf_solver* s, int n_iter2) {
     // which kernels: dmf_select.hip (one table for create / enqueue / describe)
     const dmf::IterationPlan plan = dmf::plan_iteration(s->key, s->spec, n_iter2, s->purity != nullptr);
     if (plan.row == dmf::RowKind::RowpassV2) {
-        // Second generation: one read of V (f64) and of the u16 counts for the u phase and b_u, then the exact
+        // Second generation: one read of V (f64) -- or of the u16 methylated read counts X16 -- and of the u16 counts for
+        // the u phase and b_u, then the exact
         // integer-matrix-core GEMM for the u-dependent Gram entries on the 8-bit count planes.
         const int S = (int)p->S, n_c = (int)p->n_c, n_u = (int)s->n_u;
         const int nf = n_c * n_u + n_u * (n_u + 1) / 2;
         int grid = 0, ny = 0;
         {
             FamilyScope scope(ctx, DMF_KERNEL_ROWPASS);
-            HIP_TRY(dmf::launch_rowpass_v2(p->V, p->D16, p->SD, p->Rtp, s->alpha, s->u, s->u_prev, s->state, p->N, S,
-                                           n_c, n_u, n_iter2, s->mode, p->ND, s->slab, s->u2_partials, &grid, ctx->stream));
+            HIP_TRY(dmf::launch_rowpass_v2(p->V, p->D16, s->key.x16 ? p->X16 : nullptr, p->SD, p->Rtp, s->alpha, s->u,
+                                           s->u_prev, s->state, p->N, S, n_c, n_u, n_iter2, s->mode, p->ND, s->slab,
+                                           s->u2_partials, &grid, ctx->stream));
         }
         {
             FamilyScope scope(ctx, DMF_KERNEL_GRAM);
@@ -877,6 +906,12 @@ int dmf_context_set_generic(dmf_context* ctx, int enabled) {
     return DMF_OK;
 }
 
+int dmf_context_set_x16(dmf_context* ctx, int enabled) {
+    if (ctx == nullptr || enabled < 0 || enabled > 1) return DMF_ERR_BAD_ARG;
+    ctx->x16 = enabled != 0;
+    return DMF_OK;
+}
+
 int dmf_context_set_stop_confirmation(dmf_context* ctx, int mode) {
     if (ctx == nullptr || mode < 0 || mode > 2) return DMF_ERR_BAD_ARG;
     ctx->stop_confirmation = mode;
@@ -974,7 +1009,9 @@ static int problem_gather(dmf_context* ctx, const dmf_problem* src, const int64_
     // source, so none of the scans of problem_finalize has to run again
     bool counts_done = false;
     unsigned int* d_max = nullptr;
+    unsigned long long* d_xsum = nullptr;
     if (e == hipSuccess && src->D16 != nullptr && src->ND > 0 && ctx->generic_level == 0) {
+        const bool x16 = src->X16 != nullptr && ctx->x16;
         p->ND = src->ND;
         p->SD = src->SD;
         p->N16 = (n_idx + 15) / 16 * 16;
@@ -982,19 +1019,26 @@ static int problem_gather(dmf_context* ctx, const dmf_problem* src, const int64_
         e = pool_alloc(ctx, (void**)&p->D16, (size_t)p->N16 * p->SD * sizeof(unsigned short));
         if (e == hipSuccess) e = pool_alloc(ctx, (void**)&p->Dt8, (size_t)p->plane_stride * p->ND);
         if (e == hipSuccess) e = pool_alloc(ctx, (void**)&d_max, sizeof(unsigned int));
+        if (e == hipSuccess && x16) e = pool_alloc(ctx, (void**)&p->X16, (size_t)p->N16 * p->SD * sizeof(unsigned short));
+        if (e == hipSuccess && x16) e = pool_alloc(ctx, (void**)&d_xsum, sizeof(unsigned long long));
         if (e == hipSuccess)
-            e = dmf::launch_gather_counts_int(src->D16, d_idx, n_idx, p->SD, p->ND, p->D16, p->N16, p->Dt8, p->plane_stride,
-                                              d_max, ctx->stream);
+            e = dmf::launch_gather_counts_int(src->D16, x16 ? src->X16 : nullptr, d_idx, n_idx, p->SD, p->ND, p->D16, p->X16,
+                                              p->N16, p->Dt8, p->plane_stride, d_max, d_xsum, ctx->stream);
         unsigned int h_max = 0;
+        unsigned long long h_xsum = 0;
         if (e == hipSuccess) e = hipMemcpyAsync(&h_max, d_max, sizeof(h_max), hipMemcpyDeviceToHost, ctx->stream);
+        if (e == hipSuccess && x16) e = hipMemcpyAsync(&h_xsum, d_xsum, sizeof(h_xsum), hipMemcpyDeviceToHost, ctx->stream);
         if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
         if (e == hipSuccess) {
             p->h_consts[2] = p->h_consts[4] = (double)h_max;
             p->h_consts[3] = src->h_consts[3];
             p->h_consts[5] = src->h_consts[5];
+            p->x16_dev = x16 ? src->x16_dev : 0.0;  // (a bound over the source's elements: holds for any subset)
+            p->x16_sum = (double)h_xsum;
             counts_done = true;
         }
         pool_free(ctx, d_max);
+        pool_free(ctx, d_xsum);
     }
     if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
     if (!idx_dev) pool_free(ctx, d_idx);
@@ -1037,6 +1081,7 @@ int dmf_problem_destroy(dmf_problem* p) {
     pool_free(ctx, p->consts);
     pool_free(ctx, p->gb_known);
     pool_free(ctx, p->D16);
+    pool_free(ctx, p->X16);
     pool_free(ctx, p->Dt8);
     delete p;
     return DMF_OK;
@@ -1074,6 +1119,7 @@ int dmf_solver_create(dmf_context* ctx, const dmf_problem* p, const double* u0, 
     key.n_u = (int)n_u;
     key.nd = (p->ND > 0 && p->D16 != nullptr) ? p->ND : 0;
     key.SD = p->SD;
+    key.x16 = key.nd > 0 && p->X16 != nullptr;
     key.level = ctx->generic_level;
     key.d_f32_exact = p->d_f32_exact;
     key.rtp_present = n_c == 0 || p->Rtp != nullptr;
@@ -1292,7 +1338,9 @@ int dmf_solver_step(dmf_solver* s, int64_t n_outer, int64_t n_iter2, double tol,
     DMF_TRY(check_ctx(ctx));
     const dmf_problem* p = s->p;
     // Stops are confirmed with streaming costs where the Gram form's error bound is not far below the threshold.
-    const double gram_err = kGramCostRelErr * (double)p->N * (double)p->S * p->h_consts[2];
+    // (the row pass on X16 forms b_u from x instead of d v: |x - d v| <= x16_dev x per element, u and alpha in [0, 1])
+    const double gram_err = kGramCostRelErr * (double)p->N * (double)p->S * p->h_consts[2] +
+                            (s->key.x16 ? p->x16_dev * p->x16_sum : 0.0);
     s->confirm_stops = tol > 0.0 && ctx->stop_confirmation != 2 && (ctx->stop_confirmation == 1 || gram_err >= tol / 20.0);
     hipLaunchKernelGGL(k_set_tol, dim3(1), dim3(1), 0, ctx->stream, s->state, tol, s->confirm_stops ? kConfirmBand : 1.0);
     HIP_TRY(hipGetLastError());
@@ -1505,6 +1553,7 @@ int dmf_select_describe(int64_t N, int64_t S, int64_t n_c, int64_t n_u, int nd, 
     key.d_f32_exact = (flags & DMF_SELECT_COUNTS_F32_EXACT) != 0;
     key.rtp_present = true;
     key.v_align = (flags & DMF_SELECT_V_UNALIGNED) ? 8 : 0;
+    key.x16 = key.nd > 0 && (flags & DMF_SELECT_X16) != 0;
     key.rtp_align = 0;
     key.alpha_unit = !(flags & DMF_SELECT_ALPHA_OUTSIDE_UNIT);
     const dmf::PathSpec spec = dmf::select_path(key);

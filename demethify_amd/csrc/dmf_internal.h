@@ -209,17 +209,27 @@ int64_t gram_mfma_slab_doubles(int64_t N, int S, int n_jobs);
 // ---- second-generation row pass (dmf_kernels_rowpass2.hip) + integer-matrix-core Gram (dmf_kernels_gram_i8.hip)
 // counts as u16 (D16[N16][SD], zero padded: N16 = N rounded up to 16, SD = S rounded up to 64) and as balanced 8-bit
 // digit planes in the MFMA B layout (Dt8[ND][ceil(N/32)][SD/32][32][32]); ND = 1 (d <= 127) or 2 (d <= 32639)
-hipError_t launch_gather_counts_int(const unsigned short* src16, const long long* idx, int64_t n_idx, int SD, int ND,
-                                    unsigned short* D16, int64_t N16, signed char* Dt8, int64_t plane_stride,
-                                    unsigned int* max_out, hipStream_t st);
-hipError_t launch_build_counts_int(const double* D, int64_t N, int S, int ND, unsigned short* D16, int64_t N16, int SD,
-                                   signed char* Dt8, int64_t plane_stride, hipStream_t st);
+// X16 (optional, D16's layout): the methylated read counts x = rint(v d), when every element is exact (see
+// launch_build_counts_int); the gather carries it along (src_x16 / X16 null: no copy) and sums the gathered x into *xsum_out
+hipError_t launch_gather_counts_int(const unsigned short* src16, const unsigned short* src_x16, const long long* idx,
+                                    int64_t n_idx, int SD, int ND, unsigned short* D16, unsigned short* X16, int64_t N16,
+                                    signed char* Dt8, int64_t plane_stride, unsigned int* max_out,
+                                    unsigned long long* xsum_out, hipStream_t st);
+// X16 != null: also x = rint(v d) per element, accepted when 0 <= x <= d and |fma(v, d, -x)| <= kX16MaxDev max(x, 1)
+// (d = 0: x = 0 whatever v is); x_stats[3] (zeroed here) <- { elements that fail, bits of the largest |fma(v, d, -x)| /
+// max(x, 1), sum of x }
+constexpr double kX16MaxDev = 8.0 * 0x1p-53;
+hipError_t launch_build_counts_int(const double* D, const double* V, int64_t N, int S, int ND, unsigned short* D16,
+                                   unsigned short* X16, int64_t N16, int SD, signed char* Dt8, int64_t plane_stride,
+                                   unsigned long long* x_stats, hipStream_t st);
 bool rowpass_v2_supported(int S, int n_c, int n_u, int n_iter2);
 int rowpass_v2_grid(int64_t N, int S);
-// u phase + b_u slab ([grid][n_u][S] doubles) + per-workgroup ||u||^2 shares in one read of V (f64) and D16
-hipError_t launch_rowpass_v2(const double* V, const unsigned short* D16, int SD, const double* Rtp, const double* alpha,
-                             double* u, double* u_prev, SolverState* state, int64_t N, int S, int n_c, int n_u,
-                             int n_iter2, int mode, int nd, double* slab, double* u2_partials, int* grid_out, hipStream_t st);
+// u phase + b_u slab ([grid][n_u][S] doubles) + per-workgroup ||u||^2 shares in one read of V (f64) and D16 -- or, when
+// X16 is not null, of X16 and D16 (V is not read)
+hipError_t launch_rowpass_v2(const double* V, const unsigned short* D16, const unsigned short* X16, int SD,
+                             const double* Rtp, const double* alpha, double* u, double* u_prev, SolverState* state, int64_t N,
+                             int S, int n_c, int n_u, int n_iter2, int mode, int nd, double* slab, double* u2_partials,
+                             int* grid_out, hipStream_t st);
 bool gram_i8_supported(int n_c, int n_u, int ND, int64_t N, int SD);
 int64_t gram_i8_slab_words(int64_t N, int SD, int n_c, int n_u);  // i64 words of the slab
 int64_t gram_i8_acc_words(int S, int n_c, int n_u);               // i64 words of the reduction scratch (zero-initialised)

@@ -41,24 +41,74 @@ constexpr int kMaxFeat = 576;  // (64 per launch; 32 unknowns without known type
 }  // namespace
 
 // ------------------------------------------------------------------------------------------------ builders
-// counts (f64, integral, 0 <= d <= 65535) -> D16[N16][SD], zero padded (rows to a multiple of 16, columns to SD)
-__global__ __launch_bounds__(256) void k_build_d16(const double* __restrict__ D, int64_t N, int S,
-                                                   unsigned short* __restrict__ D16, int64_t N16, int SD) {
+// counts (f64, integral, 0 <= d <= 65535) -> D16[N16][SD], zero padded (rows to a multiple of 16, columns to SD).
+// X16 != null: the methylated read counts x = rint(v d) -> X16 in the same layout, checked as launch_build_counts_int says
+// (dmf_internal.h); one atomic per workgroup and statistic.
+__global__ __launch_bounds__(256) void k_build_d16(const double* __restrict__ D, const double* __restrict__ V, int64_t N, int S,
+                                                   unsigned short* __restrict__ D16, unsigned short* __restrict__ X16,
+                                                   int64_t N16, int SD, unsigned long long* __restrict__ x_stats) {
     const int64_t chunks = N16 * (SD / 8);
+    unsigned long long bad = 0, xsum = 0;
+    double dev = 0.0;
     for (int64_t c = (int64_t)blockIdx.x * 256 + threadIdx.x; c < chunks; c += (int64_t)gridDim.x * 256) {
         const int64_t row = c / (SD / 8);
         const int col0 = (int)(c - row * (SD / 8)) * 8;
-        unsigned int w[4];
+        unsigned int w[4], xw[4];
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
-            unsigned int lo = 0, hi = 0;
-            if (row < N) {
-                if (col0 + 2 * e < S) lo = (unsigned int)D[row * S + col0 + 2 * e];
-                if (col0 + 2 * e + 1 < S) hi = (unsigned int)D[row * S + col0 + 2 * e + 1];
+            unsigned int dh[2] = {0, 0}, xh[2] = {0, 0};
+#pragma unroll
+            for (int h = 0; h < 2; ++h) {
+                const int col = col0 + 2 * e + h;
+                if (row < N && col < S) {
+                    const double d = D[row * S + col];
+                    dh[h] = (unsigned int)d;
+                    if (X16 != nullptr && d > 0.0) {  // (d = 0: weighed by 0 in the reference; x = 0)
+                        const double v = V[row * S + col];
+                        const double x = rint(v * d);
+                        const double err = fabs(fma(v, d, -x));
+                        const double xm = fmax(x, 1.0);
+                        if (x >= 0.0 && x <= d && err <= kX16MaxDev * xm) {  // (false for NaN / inf)
+                            xh[h] = (unsigned int)x;
+                            xsum += xh[h];
+                            dev = fmax(dev, err / xm);
+                        } else {
+                            ++bad;
+                        }
+                    }
+                }
             }
-            w[e] = lo | (hi << 16);
+            w[e] = dh[0] | (dh[1] << 16);
+            xw[e] = xh[0] | (xh[1] << 16);
         }
         *reinterpret_cast<v4u*>(D16 + row * SD + col0) = v4u{w[0], w[1], w[2], w[3]};
+        if (X16 != nullptr) *reinterpret_cast<v4u*>(X16 + row * SD + col0) = v4u{xw[0], xw[1], xw[2], xw[3]};
+    }
+    if (X16 == nullptr) return;
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+        bad += __shfl_xor(bad, off, 64);
+        xsum += __shfl_xor(xsum, off, 64);
+        dev = fmax(dev, __shfl_xor(dev, off, 64));
+    }
+    __shared__ unsigned long long wst[4][3];
+    const int wave = threadIdx.x >> 6;
+    if ((threadIdx.x & 63) == 0) {
+        wst[wave][0] = bad;
+        wst[wave][1] = (unsigned long long)__double_as_longlong(dev);
+        wst[wave][2] = xsum;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        unsigned long long b = 0, m = 0, x = 0;
+        for (int w = 0; w < 4; ++w) {
+            b += wst[w][0];
+            m = m > wst[w][1] ? m : wst[w][1];  // (non-negative doubles order as their bit patterns)
+            x += wst[w][2];
+        }
+        if (b > 0) atomicAdd(x_stats, b);
+        if (m > 0) atomicMax(x_stats + 1, m);
+        if (x > 0) atomicAdd(x_stats + 2, x);
     }
 }
 
@@ -93,13 +143,19 @@ __global__ __launch_bounds__(256) void k_build_dt8(const unsigned short* __restr
     }
 }
 
-hipError_t launch_build_counts_int(const double* D, int64_t N, int S, int ND, unsigned short* D16, int64_t N16, int SD,
-                                   signed char* Dt8, int64_t plane_stride, hipStream_t st) {
+hipError_t launch_build_counts_int(const double* D, const double* V, int64_t N, int S, int ND, unsigned short* D16,
+                                   unsigned short* X16, int64_t N16, int SD, signed char* Dt8, int64_t plane_stride,
+                                   unsigned long long* x_stats, hipStream_t st) {
     const int64_t chunks = N16 * (SD / 8);
     int64_t g = (chunks + 255) / 256;
     if (g > 8192) g = 8192;
     if (g < 1) g = 1;
-    hipLaunchKernelGGL(k_build_d16, dim3((unsigned)g), dim3(256), 0, st, D, N, S, D16, N16, SD);
+    if (X16 != nullptr) {
+        if (V == nullptr || x_stats == nullptr) return hipErrorInvalidValue;
+        const hipError_t e = hipMemsetAsync(x_stats, 0, 3 * sizeof(unsigned long long), st);
+        if (e != hipSuccess) return e;
+    }
+    hipLaunchKernelGGL(k_build_d16, dim3((unsigned)g), dim3(256), 0, st, D, V, N, S, D16, X16, N16, SD, x_stats);
     if (Dt8 != nullptr) {
         const int64_t n_tiles = ((N + 31) / 32) * (SD / 32);
         int64_t gt = (n_tiles + 3) / 4;
@@ -111,14 +167,18 @@ hipError_t launch_build_counts_int(const double* D, int64_t N, int S, int ND, un
 
 // Row-resampled copy of the u16 counts (a bootstrap replicate, bootstrap.py:28): dst[r][:] = src[idx[r]][:] for r < n_idx,
 // zero rows up to N16; the largest count of the copy goes to *max_out (atomicMax; the caller zeroes it) -- max(D) of the
-// resampled counts is what the reference's d = max(D)^2 is taken from.  One wave per destination row.
+// resampled counts is what the reference's d = max(D)^2 is taken from.  One wave per destination row.  src_x / dst_x (both
+// or neither): the same copy of X16, its sum to *xsum_out (atomicAdd; the caller zeroes it).
 __global__ __launch_bounds__(256) void k_gather_rows_u16(const unsigned short* __restrict__ src, unsigned short* __restrict__ dst,
+                                                         const unsigned short* __restrict__ src_x, unsigned short* __restrict__ dst_x,
                                                          const long long* __restrict__ idx, int64_t n_idx, int64_t N16, int SD,
-                                                         unsigned int* __restrict__ max_out) {
+                                                         unsigned int* __restrict__ max_out, unsigned long long* __restrict__ xsum_out) {
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
     unsigned int mx = 0u;
+    unsigned long long xs = 0;
     for (int64_t r = (int64_t)blockIdx.x * 4 + wave; r < N16; r += (int64_t)gridDim.x * 4) {
-        const unsigned short* __restrict__ s = r < n_idx ? src + idx[r] * SD : nullptr;
+        const int64_t r_src = r < n_idx ? idx[r] : -1;
+        const unsigned short* __restrict__ s = r_src >= 0 ? src + r_src * SD : nullptr;
         for (int c = lane * 8; c < SD; c += 512) {
             v4u w = v4u{0u, 0u, 0u, 0u};
             if (s != nullptr) w = *reinterpret_cast<const v4u*>(s + c);
@@ -129,33 +189,48 @@ __global__ __launch_bounds__(256) void k_gather_rows_u16(const unsigned short* _
                 mx = mx > lo ? mx : lo;
                 mx = mx > hi ? mx : hi;
             }
+            if (dst_x != nullptr) {
+                v4u x = v4u{0u, 0u, 0u, 0u};
+                if (s != nullptr) x = *reinterpret_cast<const v4u*>(src_x + r_src * SD + c);
+                *reinterpret_cast<v4u*>(dst_x + r * SD + c) = x;
+#pragma unroll
+                for (int e = 0; e < 4; ++e) xs += (x[e] & 0xFFFFu) + (x[e] >> 16);
+            }
         }
     }
 #pragma unroll
     for (int off = 32; off > 0; off >>= 1) {
         const unsigned int o = (unsigned int)__shfl_xor((int)mx, off, 64);
         mx = mx > o ? mx : o;
+        xs += __shfl_xor(xs, off, 64);
     }
     // one atomic per workgroup (a quarter of a million waves on one address took 2.7 ms of a 0.3 ms copy)
     __shared__ unsigned int wmax[4];
-    if (lane == 0) wmax[wave] = mx;
+    __shared__ unsigned long long wsum[4];
+    if (lane == 0) wmax[wave] = mx, wsum[wave] = xs;
     __syncthreads();
     if (threadIdx.x == 0) {
         unsigned int m = wmax[0];
-        for (int w = 1; w < 4; ++w) m = m > wmax[w] ? m : wmax[w];
+        unsigned long long x = wsum[0];
+        for (int w = 1; w < 4; ++w) m = m > wmax[w] ? m : wmax[w], x += wsum[w];
         if (m > 0u) atomicMax(max_out, m);
+        if (dst_x != nullptr && x > 0) atomicAdd(xsum_out, x);
     }
 }
 
-hipError_t launch_gather_counts_int(const unsigned short* src16, const long long* idx, int64_t n_idx, int SD, int ND,
-                                    unsigned short* D16, int64_t N16, signed char* Dt8, int64_t plane_stride,
-                                    unsigned int* max_out, hipStream_t st) {
+hipError_t launch_gather_counts_int(const unsigned short* src16, const unsigned short* src_x16, const long long* idx,
+                                    int64_t n_idx, int SD, int ND, unsigned short* D16, unsigned short* X16, int64_t N16,
+                                    signed char* Dt8, int64_t plane_stride, unsigned int* max_out,
+                                    unsigned long long* xsum_out, hipStream_t st) {
     int64_t g = (N16 + 3) / 4;
     if (g > 2048) g = 2048;
     if (g < 1) g = 1;
+    if ((src_x16 == nullptr) != (X16 == nullptr) || (X16 != nullptr && xsum_out == nullptr)) return hipErrorInvalidValue;
     hipError_t e = hipMemsetAsync(max_out, 0, sizeof(unsigned int), st);
+    if (e == hipSuccess && X16 != nullptr) e = hipMemsetAsync(xsum_out, 0, sizeof(unsigned long long), st);
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(k_gather_rows_u16, dim3((unsigned)g), dim3(256), 0, st, src16, D16, idx, n_idx, N16, SD, max_out);
+    hipLaunchKernelGGL(k_gather_rows_u16, dim3((unsigned)g), dim3(256), 0, st, src16, D16, src_x16, X16, idx, n_idx, N16, SD,
+                       max_out, xsum_out);
     if (Dt8 != nullptr) {
         const int64_t n_tiles = ((n_idx + 31) / 32) * (SD / 32);
         int64_t gt = (n_tiles + 3) / 4;

@@ -13,6 +13,7 @@
 // Per 16-row block, per workgroup (waves = column groups):
 //   tile    prefetched global loads (V: 16 B per lane, two rows per instruction; D16: 16 B = 8 counts per lane)
 //           -> LDS tile of the wave's own column group (V f64, the counts as the u16 they arrive as)
+//           (XS, the problem carries X16: x = d v loaded and stored like the counts, V not read -- see the template)
 //   phase A FP64-MFMA contractions on the tile in the row-on-lane layout (as dmf_kernels_rowpass_mfma.hip):
 //           E = V - Rt a_known (16x16x4), c = a_unk (D*E)^T (4x4x4, 4 blocks); M = D P^T exactly on the i8 MFMA
 //           (16x16x64, counts and P = alpha_j alpha_l as balanced 8-bit digits) -> partial c / M
@@ -31,6 +32,7 @@
 #include "dmf_phaseb.h"
 #include "dmf_fixedpoint.h"
 #include <cstdlib>
+#include <type_traits>
 
 namespace dmf {
 
@@ -73,6 +75,7 @@ constexpr int kRowD = 72;  // count tile row: 64 samples as u16 + 16 B pad (36 d
 constexpr int kTileVBytes2 = 16 * kRowV * 8;
 constexpr int kTileDBytes2 = 16 * kRowD * 2;
 constexpr int kTileBytes2 = kTileVBytes2 + kTileDBytes2;  // one column group: V (f64), counts (u16, as they arrive)
+constexpr int kTileBytesX = 2 * kTileDBytes2;               // X16 form: counts and methylated counts, both u16
 }  // namespace
 
 // One accelerated projected-gradient step of a row group (deconvolution.py:83-88): (cur, prev) = (u, u_) in,
@@ -124,9 +127,13 @@ __device__ __forceinline__ void inner_steps(double& uu, double& up, double cj, c
 // MAXW: most waves (64-sample column groups) a workgroup may have.  4: S <= 256, two workgroups per CU.  8: S <= 512, ONE
 // workgroup of up to eight waves per CU -- nothing hides its phase B, but a block then carries twice the samples, so the
 // time per element is that of the four-wave form (measured: DESIGN.md section 5).
-template <int NKC, int NU, int MAXW = 4>
+// XS: the problem's methylated read counts x = d v are exact integers (X16, u16, D16's layout; dmf_problem_create checks
+// |fma(v, d, -x)| <= 8 ulp of x): the kernel never needs V itself, only d v -- phase A forms w = d (v - Rt a1) as
+// fma(d, -Rt a1, x), phase C multiplies u by x -- and reads 4 bytes per element instead of 10.  V is not read.
+template <int NKC, int NU, int MAXW = 4, bool XS = false>
 __global__ __launch_bounds__(64 * MAXW, MAXW == 4 ? 2 : 1) void k_rowpass_v2(
-    const double* __restrict__ V, const unsigned short* __restrict__ D16, int SD, const double* __restrict__ Rtp,
+    const double* __restrict__ V, const unsigned short* __restrict__ D16, const unsigned short* __restrict__ X16, int SD,
+    const double* __restrict__ Rtp,
     const double* __restrict__ alpha, double* __restrict__ u, double* __restrict__ u_prev,
     const SolverState* __restrict__ state, int64_t N, int S, int n_c, int n_iter2, int mode, int nd,
     double* __restrict__ slab, double* __restrict__ u2_partials
@@ -150,18 +157,20 @@ __global__ __launch_bounds__(64 * MAXW, MAXW == 4 ? 2 : 1) void k_rowpass_v2(
     const int wcol0 = wave * 64;
 
     // LDS carve-up (doubles unless noted): beta[n_iter2 (even)] | ubuf[16][NU] | red[MAXW][16][NU][SLOT] | u2[MAXW] |
-    //   tiles[NW]{ V f64 [16][66], counts u16 [16][72] }
+    //   tiles[NW]{ V f64 [16][66], counts u16 [16][72] }  (XS: tiles[NW]{ counts u16 [16][72], x u16 [16][72] })
     double* __restrict__ beta_tab = lds_dyn;
     double* __restrict__ ubuf = beta_tab + ((n_iter2 + 1) & ~1);
     double* __restrict__ red = ubuf + 16 * NU;
     double* __restrict__ u2red = red + MAXW * NV * 16;
     char* __restrict__ tile0 = reinterpret_cast<char*>(u2red + MAXW);
-    char* __restrict__ tile = tile0 + (size_t)wave * kTileBytes2;
+    char* __restrict__ tile = tile0 + (size_t)wave * (XS ? kTileBytesX : kTileBytes2);
     double* __restrict__ tileV = reinterpret_cast<double*>(tile);
     // the counts stay u16 in the tile (LINEAR rows: no piece swap): phase A and phase C convert what they read, the integer
     // product builds its balanced byte digits from 32 bytes of a row -- converting at the tile store (f32 copy + two digit
     // planes: 52 vector instructions and 8 LDS writes per block and wave, on every wave's critical path) cost 9 % of the kernel
-    unsigned short* __restrict__ tileD = reinterpret_cast<unsigned short*>(tile + kTileVBytes2);
+    unsigned short* __restrict__ tileD = reinterpret_cast<unsigned short*>(tile + (XS ? 0 : kTileVBytes2));
+    // (XS) x in the same linear layout as the counts, read with the same offsets: no swizzle
+    unsigned short* __restrict__ tileX = tileD + 16 * kRowD;
 
     // momentum coefficients of the inner steps (deconvolution.py:83-85): from the host's row of ratios when there is one
     // (SolverState), else the recurrence itself by one thread -- n_iter2 square roots and divisions in a row, ~5 us
@@ -274,8 +283,8 @@ __global__ __launch_bounds__(64 * MAXW, MAXW == 4 ? 2 : 1) void k_rowpass_v2(
     const int d_row = lane >> 3, d_col = (lane & 7) * 8;
     // (tile swizzle at the stores: V rows 2 i, 2 i + 1 are swapped rows for i = 2..5)
     const int ld_col_sw = ((lane & 31) ^ 2) * 2;
-    v2d pv[8];
-    v4u pd[2];
+    v2d pv[XS ? 1 : 8];  // (XS: V is not read)
+    v4u pd[2], px[XS ? 2 : 1];
     double nrt[NKC > 0 ? NKC : 1];
     double pu, pup;  // u / u_ of lane (row, unknown) for the wave that runs the block's inner iterations
     constexpr int RPWB = 64 / NU;  // >= 16 rows per wave: one phase-B pass covers the block
@@ -313,13 +322,18 @@ __global__ __launch_bounds__(64 * MAXW, MAXW == 4 ? 2 : 1) void k_rowpass_v2(
                 nrt[kc] = __hiloint2double((int)a.y, (int)a.x);
             }
         }
-        {
+        if constexpr (!XS) {
             const __amdgpu_buffer_rsrc_t rv = __builtin_amdgcn_make_buffer_rsrc((void*)(V + r0 * S), 0, span(left * S * 8), 0x00020000);
 #pragma unroll
             for (int i = 0; i < 8; ++i) {
                 const v4u a = __builtin_amdgcn_raw_buffer_load_b128(rv, v_off, 2 * i * S * 8, 0);
                 pv[i] = v2d{__hiloint2double((int)a.y, (int)a.x), __hiloint2double((int)a.w, (int)a.z)};
             }
+        } else {
+            // (X16 is zero-padded like the counts: always in range)
+            const __amdgpu_buffer_rsrc_t rx = __builtin_amdgcn_make_buffer_rsrc((void*)(X16 + r0 * SD), 0, span((int64_t)16 * SD * 2), 0x00020000);
+            px[0] = __builtin_amdgcn_raw_buffer_load_b128(rx, d_off, 0, 0);
+            px[1] = __builtin_amdgcn_raw_buffer_load_b128(rx, d_off, 8 * SD * 2, 0);
         }
         {
             // (the count copy is zero-padded to whole blocks of 16 rows: always in range)
@@ -345,9 +359,14 @@ __global__ __launch_bounds__(64 * MAXW, MAXW == 4 ? 2 : 1) void k_rowpass_v2(
         const int64_t row0 = blk * 16;
         // ---- tile store (waits for the prefetched loads)
         __builtin_amdgcn_s_setprio(1);
+        if constexpr (XS) {
 #pragma unroll
-        for (int i = 0; i < 8; ++i)
-            *reinterpret_cast<v2d*>(tileV + (2 * i + ld_row) * kRowV + ((i >= 2 && i < 6) ? ld_col_sw : ld_col)) = pv[i];
+            for (int i = 0; i < 2; ++i) *reinterpret_cast<v4u*>(tileX + (8 * i + d_row) * kRowD + d_col) = px[i];
+        } else {
+#pragma unroll
+            for (int i = 0; i < 8; ++i)
+                *reinterpret_cast<v2d*>(tileV + (2 * i + ld_row) * kRowV + ((i >= 2 && i < 6) ? ld_col_sw : ld_col)) = pv[i];
+        }
 #ifndef DMF_ABLATE_DSTORE
 #pragma unroll
         for (int i = 0; i < 2; ++i) *reinterpret_cast<v4u*>(tileD + (8 * i + d_row) * kRowD + d_col) = pd[i];
@@ -367,22 +386,41 @@ __global__ __launch_bounds__(64 * MAXW, MAXW == 4 ? 2 : 1) void k_rowpass_v2(
         // ---- phase A: strips of 16 samples; the LDS reads of strip t + 1 are issued before the MFMAs of strip t,
         // and the E chain of strip t + 1 is slotted between the c / M MFMAs of strip t (a dependent FP64 MFMA
         // stalls behind its producer)
-        struct Strip {
+        struct StripV {
             v2d v01, v23;
             v2u dw;  // the four counts of the piece, u16
         };
+        struct StripX {
+            v2u dw, xw;  // the four counts and the four x = d v of the piece, u16
+        };
+        using Strip = std::conditional_t<XS, StripX, StripV>;
         auto load_strip = [&](int t, Strip& R) {
-            const double* __restrict__ tv = tileV + m16 * kRowV + t * 16 + 4 * qs;
-            R.v01 = *reinterpret_cast<const v2d*>(tv);
-            R.v23 = *reinterpret_cast<const v2d*>(tv + 2);
+            if constexpr (XS) {
+                R.xw = *reinterpret_cast<const v2u*>(tileX + m16 * kRowD + t * 16 + 4 * q);
+            } else {
+                const double* __restrict__ tv = tileV + m16 * kRowV + t * 16 + 4 * qs;
+                R.v01 = *reinterpret_cast<const v2d*>(tv);
+                R.v23 = *reinterpret_cast<const v2d*>(tv + 2);
+            }
             R.dw = *reinterpret_cast<const v2u*>(tileD + m16 * kRowD + t * 16 + 4 * q);
         };
         double csm0 = 0.0, csm1 = 0.0;  // c[unknown q][row m16], one double per lane
-        auto e_init = [&](const Strip& R) { return v4d{R.v01.x, R.v01.y, R.v23.x, R.v23.y}; };
+        // E = V - Rt a_known; XS: E = -Rt a_known, and V enters through x below
+        auto e_init = [&](const Strip& R) {
+            if constexpr (XS) return v4d{0.0, 0.0, 0.0, 0.0};
+            else return v4d{R.v01.x, R.v01.y, R.v23.x, R.v23.y};
+        };
         auto run_strip = [&](const Strip& R, v4d e, const Strip& Rn, const double (&a1n)[NKC > 0 ? NKC : 1],
                              const double (&a2)[4], bool has_next) {
             const v4d d = {(double)(R.dw.x & 0xFFFFu), (double)(R.dw.x >> 16), (double)(R.dw.y & 0xFFFFu), (double)(R.dw.y >> 16)};
-            const v4d w = d * e;
+            v4d w;
+            if constexpr (XS) {  // w = d (v - Rt a1) = fma(d, -Rt a1, x)
+                const v4d x = {(double)(R.xw.x & 0xFFFFu), (double)(R.xw.x >> 16), (double)(R.xw.y & 0xFFFFu), (double)(R.xw.y >> 16)};
+#pragma unroll
+                for (int r = 0; r < 4; ++r) w[r] = fma(d[r], e[r], x[r]);
+            } else {
+                w = d * e;
+            }
             v4d en = e_init(Rn);
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
@@ -393,7 +431,7 @@ __global__ __launch_bounds__(64 * MAXW, MAXW == 4 ? 2 : 1) void k_rowpass_v2(
             return en;
         };
 #ifdef DMF_ABLATE_E
-        const double csm = tileV[m16 * kRowV + 4 * qs];
+        const double csm = XS ? (double)tileX[m16 * kRowD + 4 * q] : tileV[m16 * kRowV + 4 * qs];
 #else
         Strip sa, sb;
         load_strip(0, sa);
@@ -559,14 +597,18 @@ __global__ __launch_bounds__(64 * MAXW, MAXW == 4 ? 2 : 1) void k_rowpass_v2(
 #pragma unroll
         for (int half = 0; half < 2; ++half) {
             double vv[2][4], ua[2];
-            unsigned short dd[2][4];
+            unsigned short dd[2][4];  // (XS: x)
 #pragma unroll
             for (int rr = 0; rr < 2; ++rr) {
                 const int row = 2 * half + rr + c_row;
 #pragma unroll
                 for (int t = 0; t < 4; ++t) {
-                    vv[rr][t] = tileV[row * kRowV + 16 * t + mC];
-                    dd[rr][t] = tileD[row * kRowD + 16 * t + m16];
+                    if constexpr (XS) {
+                        dd[rr][t] = tileX[row * kRowD + 16 * t + m16];
+                    } else {
+                        vv[rr][t] = tileV[row * kRowV + 16 * t + mC];
+                        dd[rr][t] = tileD[row * kRowD + 16 * t + m16];
+                    }
                 }
                 ua[rr] = (m16 & 3) < NU ? ubuf[row * NU + (m16 & 3)] : 0.0;
             }
@@ -574,7 +616,7 @@ __global__ __launch_bounds__(64 * MAXW, MAXW == 4 ? 2 : 1) void k_rowpass_v2(
             for (int rr = 0; rr < 2; ++rr)
 #pragma unroll
                 for (int t = 0; t < 4; ++t)
-                    bu[t] = __builtin_amdgcn_mfma_f64_4x4x4f64(ua[rr], (double)dd[rr][t] * vv[rr][t], bu[t], 0, 0, 0);
+                    bu[t] = __builtin_amdgcn_mfma_f64_4x4x4f64(ua[rr], XS ? (double)dd[rr][t] : (double)dd[rr][t] * vv[rr][t], bu[t], 0, 0, 0);
         }
 #endif
         __builtin_amdgcn_s_setprio(0);
@@ -602,18 +644,19 @@ __global__ __launch_bounds__(64 * MAXW, MAXW == 4 ? 2 : 1) void k_rowpass_v2(
     }
 }
 
-size_t rowpass_v2_lds_bytes(int S, int n_u, int n_iter2) {
+size_t rowpass_v2_lds_bytes(int S, int n_u, int n_iter2, bool x16) {
     const int NW = (S + 63) / 64;
     const int maxw = NW <= 4 ? 4 : 8;
     const int nv = n_u * ((n_u + 2) & ~1);  // a row's partial-sum slots (k_rowpass_v2: NV)
     const size_t doubles = (size_t)((n_iter2 + 1) & ~1) + 16 * n_u + (size_t)maxw * nv * 16 + maxw;
-    return doubles * sizeof(double) + (size_t)NW * kTileBytes2;
+    return doubles * sizeof(double) + (size_t)NW * (x16 ? kTileBytesX : kTileBytes2);
 }
 
 bool rowpass_v2_supported(int S, int n_c, int n_u, int n_iter2) {
     if (S < 2 || S > 512 || n_c > 16 || n_u < 1 || n_u > 4) return false;
     // up to 256 samples: two workgroups per CU within 160 KB; beyond: one workgroup of up to eight waves
-    return rowpass_v2_lds_bytes(S, n_u, n_iter2) <= (size_t)(S <= 256 ? 80 : 160) * 1024;
+    // (checked on the V form: the X16 form's tile is smaller)
+    return rowpass_v2_lds_bytes(S, n_u, n_iter2, false) <= (size_t)(S <= 256 ? 80 : 160) * 1024;
 }
 
 int rowpass_v2_grid(int64_t N, int S) {
@@ -627,12 +670,12 @@ int rowpass_v2_grid(int64_t N, int S) {
     return (int)(nblk < g ? nblk : g);
 }
 
-template <int NKC, int NU, int MAXW>
-static hipError_t launch_v2_t(const double* V, const unsigned short* D16, int SD, const double* Rtp, const double* alpha,
-                              double* u, double* u_prev, SolverState* state, int64_t N, int S, int n_c, int n_iter2,
-                              int mode, int nd, double* slab, double* u2_partials, int* grid_out, hipStream_t st) {
+template <int NKC, int NU, int MAXW, bool XS>
+static hipError_t launch_v2_t(const double* V, const unsigned short* D16, const unsigned short* X16, int SD, const double* Rtp,
+                              const double* alpha, double* u, double* u_prev, SolverState* state, int64_t N, int S, int n_c,
+                              int n_iter2, int mode, int nd, double* slab, double* u2_partials, int* grid_out, hipStream_t st) {
     const int NW = (S + 63) / 64;
-    const size_t lds = rowpass_v2_lds_bytes(S, NU, n_iter2);
+    const size_t lds = rowpass_v2_lds_bytes(S, NU, n_iter2, XS);
     constexpr size_t kLdsCap = (size_t)(MAXW == 4 ? 80 : 160) * 1024;
     if (NW > MAXW || (MAXW == 8 && NW <= 4) || lds > kLdsCap || N < 1 || SD < NW * 64 || (SD & 7) != 0 || nd < 1 || nd > 2)
         return hipErrorInvalidValue;
@@ -640,14 +683,14 @@ static hipError_t launch_v2_t(const double* V, const unsigned short* D16, int SD
     int dev = 0;
     if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) dev = 0;
     if (lds > 48 * 1024 && !lds_limit_raised[dev]) {
-        hipError_t e = hipFuncSetAttribute((const void*)k_rowpass_v2<NKC, NU, MAXW>,
+        hipError_t e = hipFuncSetAttribute((const void*)k_rowpass_v2<NKC, NU, MAXW, XS>,
                                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsCap);
         if (e != hipSuccess) return e;
         lds_limit_raised[dev] = true;
     }
     const int grid = rowpass_v2_grid(N, S);
     *grid_out = grid;
-    hipLaunchKernelGGL((k_rowpass_v2<NKC, NU, MAXW>), dim3(grid), dim3(NW * 64), lds, st, V, D16, SD, Rtp, alpha, u, u_prev,
+    hipLaunchKernelGGL((k_rowpass_v2<NKC, NU, MAXW, XS>), dim3(grid), dim3(NW * 64), lds, st, V, D16, X16, SD, Rtp, alpha, u, u_prev,
                        state, N, S, n_c, n_iter2, mode, nd, slab, u2_partials
 #ifdef DMF_STAMPS
                        , (unsigned long long*)nullptr
@@ -656,32 +699,35 @@ static hipError_t launch_v2_t(const double* V, const unsigned short* D16, int SD
     return hipGetLastError();
 }
 
-template <int NKC>
-static hipError_t launch_v2_nkc(int n_u, const double* V, const unsigned short* D16, int SD, const double* Rtp,
-                                const double* alpha, double* u, double* u_prev, SolverState* state, int64_t N, int S,
-                                int n_c, int n_iter2, int mode, int nd, double* slab, double* u2_partials, int* grid_out,
-                                hipStream_t st) {
+template <int NKC, bool XS>
+static hipError_t launch_v2_nkc(int n_u, const double* V, const unsigned short* D16, const unsigned short* X16, int SD,
+                                const double* Rtp, const double* alpha, double* u, double* u_prev, SolverState* state,
+                                int64_t N, int S, int n_c, int n_iter2, int mode, int nd, double* slab, double* u2_partials,
+                                int* grid_out, hipStream_t st) {
     switch (n_u) {
 #define DMF_CASE(NU_)                                                                                                   \
     case NU_:                                                                                                           \
-        return S <= 256 ? launch_v2_t<NKC, NU_, 4>(V, D16, SD, Rtp, alpha, u, u_prev, state, N, S, n_c, n_iter2, mode, nd, \
-                                                   slab, u2_partials, grid_out, st)                                     \
-                        : launch_v2_t<NKC, NU_, 8>(V, D16, SD, Rtp, alpha, u, u_prev, state, N, S, n_c, n_iter2, mode, nd, \
-                                                   slab, u2_partials, grid_out, st);
+        return S <= 256 ? launch_v2_t<NKC, NU_, 4, XS>(V, D16, X16, SD, Rtp, alpha, u, u_prev, state, N, S, n_c, n_iter2, \
+                                                       mode, nd, slab, u2_partials, grid_out, st)                       \
+                        : launch_v2_t<NKC, NU_, 8, XS>(V, D16, X16, SD, Rtp, alpha, u, u_prev, state, N, S, n_c, n_iter2, \
+                                                       mode, nd, slab, u2_partials, grid_out, st);
         DMF_CASE(1) DMF_CASE(2) DMF_CASE(3) DMF_CASE(4)
 #undef DMF_CASE
         default: return hipErrorInvalidValue;
     }
 }
 
-hipError_t launch_rowpass_v2(const double* V, const unsigned short* D16, int SD, const double* Rtp, const double* alpha,
-                             double* u, double* u_prev, SolverState* state, int64_t N, int S, int n_c, int n_u,
-                             int n_iter2, int mode, int nd, double* slab, double* u2_partials, int* grid_out, hipStream_t st) {
+hipError_t launch_rowpass_v2(const double* V, const unsigned short* D16, const unsigned short* X16, int SD,
+                             const double* Rtp, const double* alpha, double* u, double* u_prev, SolverState* state, int64_t N,
+                             int S, int n_c, int n_u, int n_iter2, int mode, int nd, double* slab, double* u2_partials,
+                             int* grid_out, hipStream_t st) {
     switch ((n_c + 3) / 4) {
-#define DMF_NKC(X)                                                                                                \
-    case X:                                                                                                       \
-        return launch_v2_nkc<X>(n_u, V, D16, SD, Rtp, alpha, u, u_prev, state, N, S, n_c, n_iter2, mode, nd, slab, \
-                                u2_partials, grid_out, st);
+#define DMF_NKC(X)                                                                                                    \
+    case X:                                                                                                           \
+        return X16 != nullptr ? launch_v2_nkc<X, true>(n_u, V, D16, X16, SD, Rtp, alpha, u, u_prev, state, N, S, n_c,   \
+                                                       n_iter2, mode, nd, slab, u2_partials, grid_out, st)            \
+                              : launch_v2_nkc<X, false>(n_u, V, D16, X16, SD, Rtp, alpha, u, u_prev, state, N, S, n_c,  \
+                                                        n_iter2, mode, nd, slab, u2_partials, grid_out, st);
         DMF_NKC(0) DMF_NKC(1) DMF_NKC(2) DMF_NKC(3) DMF_NKC(4)
 #undef DMF_NKC
         default: return hipErrorInvalidValue;

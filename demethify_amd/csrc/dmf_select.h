@@ -21,6 +21,7 @@ struct ShapeKey {
     int nd = 0;                // count digit planes of the problem's integer copies (0: none -- counts not integral,
                                // beyond 32639, more than 2048 samples, R_trunc outside [0, 1])
     int SD = 0;                // padded sample count of those copies
+    bool x16 = false;          // the problem carries X16 (the row pass reads x = d v as u16 instead of V)
     int level = 0;             // kernel selection level (dmf_context_set_generic): 0 fastest .. 4
     bool d_f32_exact = false;  // every count survives a round trip through f32
     bool rtp_present = true;   // the padded copy of R_trunc exists (n_c > 0)

@@ -41,7 +41,8 @@ PathSpec select_path(const ShapeKey& k) {
     s.use_u_big = fast && s.u_path != 0 && u_phase_big_supported(S, n_c, n_u, 64);
 
     // ---- second generation: one-launch row pass on u16 counts + integer-matrix-core Gram (level 0 only)
-    s.use_v2 = k.level == 0 && ints && (n_c == 0 || k.rtp_present) && k.v_align == 0 && k.rtp_align == 0 &&
+    // (on X16 the row pass does not read V: its alignment does not matter)
+    s.use_v2 = k.level == 0 && ints && (n_c == 0 || k.rtp_present) && (k.v_align == 0 || k.x16) && k.rtp_align == 0 &&
                rowpass_v2_supported(S, n_c, n_u, 20) && gram_i8_supported(n_c, n_u, k.nd, k.N, k.SD);
 
     // ---- wide row groups (5..32 unknowns; narrow ones beyond the row pass's 512 samples or 16 known types): the split u
@@ -126,8 +127,8 @@ int describe_plan(const ShapeKey& k, const IterationPlan& plan, char* buf, size_
     const int S = k.S, n_c = k.n_c, n_u = k.n_u;
     switch (plan.row) {
         case RowKind::RowpassV2:
-            snprintf(row, sizeof(row), "k_rowpass_v2<%d,%d> nw=%d grid=%d tail=%d", (n_c + 3) / 4, n_u, (S + 63) / 64,
-                     rowpass_v2_grid(k.N, S), (int)(k.N & 15));
+            snprintf(row, sizeof(row), "k_rowpass_v2<%d,%d> nw=%d grid=%d tail=%d%s", (n_c + 3) / 4, n_u, (S + 63) / 64,
+                     rowpass_v2_grid(k.N, S), (int)(k.N & 15), k.x16 ? " x16" : "");
             break;
         case RowKind::RowpassFused:
             snprintf(row, sizeof(row), "k_rowpass_fused<%d,%d> nw=%d grid=%d tail=%d", (n_c + 3) / 4, n_u, (S + 63) / 64,

@@ -75,6 +75,11 @@ class Context:
         MFMA row pass + one-pass Gram pair, 4 the first-generation fused FP64 row pass.  Set before creating Problems."""
         L.check(self._lib.dmf_context_set_generic(self._h, int(level)), "dmf_context_set_generic")
 
+    def set_x16(self, enabled: bool):
+        """Whether Problems created from now on carry X16, the methylated read counts x = rint(v d) as u16, when every
+        element is an exact x / d (the row pass then reads x instead of V).  On by default; off for A/B runs and tests."""
+        L.check(self._lib.dmf_context_set_x16(self._h, int(bool(enabled))), "dmf_context_set_x16")
+
     def set_stop_confirmation(self, mode: int):
         """How step() decides |cf - cf_0| < tol: 0 (default) Gram-form cost, confirmed on the streaming cost where the
         Gram form's error bound reaches tol / 20; 1 always on streaming costs near the threshold; 2 Gram form only."""

@@ -52,7 +52,8 @@ enum {
     DMF_SELECT_COUNTS_F32_EXACT = 1,   /* every count survives a round trip through f32                  */
     DMF_SELECT_PURITY = 2,             /* a purity vector is set (Frank-Wolfe alpha phase)               */
     DMF_SELECT_ALPHA_OUTSIDE_UNIT = 4, /* the starting alpha does not lie inside [0, 1]                  */
-    DMF_SELECT_V_UNALIGNED = 8         /* meth_frequency starts 8 bytes off a 16-byte boundary           */
+    DMF_SELECT_V_UNALIGNED = 8,        /* meth_frequency starts 8 bytes off a 16-byte boundary           */
+    DMF_SELECT_X16 = 16                /* the problem carries X16: every v d is an exact count (with nd > 0) */
 };
 
 /* solver variants */
@@ -96,6 +97,10 @@ int dmf_context_reset_kernel_time(dmf_context* ctx);
  * Gram), 4 = the first-generation fused FP64 row pass (level 0's fall-back for counts beyond 32639 or reference
  * profiles outside [0, 1]).  Set it before creating problems: the integer count copies are built at level 0 only. */
 int dmf_context_set_generic(dmf_context* ctx, int level);
+/* 1 (default): problems created from now on (and their row gathers) carry X16, the methylated read counts x = rint(v d)
+ * as u16, when every element with d > 0 has 0 <= x <= d and |v d - x| <= 8 ulp of max(x, 1) (meth_frequency = X / D);
+ * the row pass then reads x and the counts instead of v.  0: they do not, and every kernel reads V.  Tests and A/B runs. */
+int dmf_context_set_x16(dmf_context* ctx, int enabled);
 /* How dmf_solver_step decides |cf - cf_0| < tol (deconvolution.py:218-220) for the solvers of this context:
  * 0 (default) = on the Gram-form cost of the loop, with the decisions near the threshold confirmed on the streaming
  * cost of deconvolution.py:15-17 where the Gram form's error bound (1e-15 N S max(counts)) reaches tol / 20;
