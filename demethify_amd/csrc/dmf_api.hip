@@ -59,6 +59,7 @@ struct dmf_context {
     int generic_level = 0;  // 0 fused row pass, 1 any-shape Gram-form kernels, 2 schedule-faithful u steps,
                             // 3 separate MFMA row pass + one-pass Gram (the pieces the fused kernel is made of)
     bool x16 = true;        // dmf_context_set_x16: problems created from now on get the X16 copy when their data allow
+    bool rowpass_pair = true;  // dmf_context_set_rowpass_pair: solvers created from now on run the row pass two blocks per phase B
     double* scratch = nullptr;  // 4096 doubles of reduction scratch
     hipMemPool_t pool = nullptr;  // the context's own stream-ordered pool (the device's default pool is not touched)
     std::unordered_map<void*, size_t> live;                // large blocks handed out by pool_alloc (size by address)
@@ -150,6 +151,7 @@ struct dmf_solver {
     bool confirm_stops = false;
     double cf_stream = 0.0;
     long long cf_stream_iter = -1;
+    long long n_rowpass = 0, n_rowpass_pair = 0;  // k_rowpass_v2 launches so far / of them on the pair schedule
     long long n_confirmed = 0, n_unconfirmed = 0;  // stop tests decided on streaming costs / on the Gram form inside the band
 };
 
@@ -636,11 +638,14 @@ int enqueue_outer_iteration(dmf_solver* s, int n_iter2) {
         const int S = (int)p->S, n_c = (int)p->n_c, n_u = (int)s->n_u;
         const int nf = n_c * n_u + n_u * (n_u + 1) / 2;
         int grid = 0, ny = 0;
+        bool paired = false;
         {
             FamilyScope scope(ctx, DMF_KERNEL_ROWPASS);
             HIP_TRY(dmf::launch_rowpass_v2(p->V, p->D16, s->key.x16 ? p->X16 : nullptr, p->SD, p->Rtp, s->alpha, s->u,
                                            s->u_prev, s->state, p->N, S, n_c, n_u, n_iter2, s->mode, p->ND, s->slab,
-                                           s->u2_partials, &grid, ctx->stream));
+                                           s->u2_partials, &grid, s->key.rowpass_pair, &paired, ctx->stream));
+            ++s->n_rowpass;
+            s->n_rowpass_pair += paired ? 1 : 0;
         }
         {
             FamilyScope scope(ctx, DMF_KERNEL_GRAM);
@@ -912,6 +917,12 @@ int dmf_context_set_x16(dmf_context* ctx, int enabled) {
     return DMF_OK;
 }
 
+int dmf_context_set_rowpass_pair(dmf_context* ctx, int enabled) {
+    if (ctx == nullptr || enabled < 0 || enabled > 1) return DMF_ERR_BAD_ARG;
+    ctx->rowpass_pair = enabled != 0;
+    return DMF_OK;
+}
+
 int dmf_context_set_stop_confirmation(dmf_context* ctx, int mode) {
     if (ctx == nullptr || mode < 0 || mode > 2) return DMF_ERR_BAD_ARG;
     ctx->stop_confirmation = mode;
@@ -1120,6 +1131,7 @@ int dmf_solver_create(dmf_context* ctx, const dmf_problem* p, const double* u0, 
     key.nd = (p->ND > 0 && p->D16 != nullptr) ? p->ND : 0;
     key.SD = p->SD;
     key.x16 = key.nd > 0 && p->X16 != nullptr;
+    key.rowpass_pair = ctx->rowpass_pair;
     key.level = ctx->generic_level;
     key.d_f32_exact = p->d_f32_exact;
     key.rtp_present = n_c == 0 || p->Rtp != nullptr;
@@ -1534,6 +1546,13 @@ int dmf_solver_stop_info(const dmf_solver* s, int* confirm_stops, int64_t* n_con
     if (n_confirmed) *n_confirmed = s->n_confirmed;
     if (n_unconfirmed) *n_unconfirmed = s->n_unconfirmed;
     if (last_stream_cost) *last_stream_cost = s->cf_stream_iter >= 0 ? s->cf_stream : std::nan("");
+    return DMF_OK;
+}
+
+int dmf_solver_rowpass_launches(const dmf_solver* s, int64_t* total, int64_t* paired) {
+    if (s == nullptr) return DMF_ERR_BAD_ARG;
+    if (total) *total = s->n_rowpass;
+    if (paired) *paired = s->n_rowpass_pair;
     return DMF_OK;
 }
 

@@ -225,11 +225,14 @@ hipError_t launch_build_counts_int(const double* D, const double* V, int64_t N, 
 bool rowpass_v2_supported(int S, int n_c, int n_u, int n_iter2);
 int rowpass_v2_grid(int64_t N, int S);
 // u phase + b_u slab ([grid][n_u][S] doubles) + per-workgroup ||u||^2 shares in one read of V (f64) and D16 -- or, when
-// X16 is not null, of X16 and D16 (V is not read)
+// X16 is not null, of X16 and D16 (V is not read).  pair: two blocks per phase B where the X16 form allows it
+// (rowpass_v2_pair_fits); the same results bit for bit.  *paired_out (may be null): whether the pair schedule was launched
 hipError_t launch_rowpass_v2(const double* V, const unsigned short* D16, const unsigned short* X16, int SD,
                              const double* Rtp, const double* alpha, double* u, double* u_prev, SolverState* state, int64_t N,
                              int S, int n_c, int n_u, int n_iter2, int mode, int nd, double* slab, double* u2_partials,
-                             int* grid_out, hipStream_t st);
+                             int* grid_out, bool pair, bool* paired_out, hipStream_t st);
+// the X16 row pass can run two blocks per phase B at this shape: 2..4 waves, and the grid's workgroups per CU fit the LDS
+bool rowpass_v2_pair_fits(int S, int n_u, int n_iter2);
 bool gram_i8_supported(int n_c, int n_u, int ND, int64_t N, int SD);
 int64_t gram_i8_slab_words(int64_t N, int SD, int n_c, int n_u);  // i64 words of the slab
 int64_t gram_i8_acc_words(int S, int n_c, int n_u);               // i64 words of the reduction scratch (zero-initialised)

@@ -80,6 +80,11 @@ class Context:
         element is an exact x / d (the row pass then reads x instead of V).  On by default; off for A/B runs and tests."""
         L.check(self._lib.dmf_context_set_x16(self._h, int(bool(enabled))), "dmf_context_set_x16")
 
+    def set_rowpass_pair(self, enabled: bool):
+        """Whether Solvers created from now on run the X16 row pass two 16-row blocks per barrier cycle (65..256 samples).
+        On by default; off for A/B runs and tests.  Both forms compute the same results bit for bit."""
+        L.check(self._lib.dmf_context_set_rowpass_pair(self._h, int(bool(enabled))), "dmf_context_set_rowpass_pair")
+
     def set_stop_confirmation(self, mode: int):
         """How step() decides |cf - cf_0| < tol: 0 (default) Gram-form cost, confirmed on the streaming cost where the
         Gram form's error bound reaches tol / 20; 1 always on streaming costs near the threshold; 2 Gram form only."""
@@ -369,6 +374,13 @@ class Solver:
                 "dmf_solver_stop_info")
         return {"confirm_stops": bool(on.value), "n_confirmed": nc.value, "n_unconfirmed": nu.value,
                 "last_stream_cost": cs.value}
+
+    def rowpass_launches(self):
+        """(k_rowpass_v2 launches so far, how many of them ran the pair schedule) -- dmf_solver_rowpass_launches."""
+        total, paired = C.c_int64(), C.c_int64()
+        L.check(self._lib.dmf_solver_rowpass_launches(self._h, C.byref(total), C.byref(paired)),
+                "dmf_solver_rowpass_launches")
+        return total.value, paired.value
 
     def get_alpha(self):
         """The current proportions (K x S) as a fresh host array; u stays on the device."""

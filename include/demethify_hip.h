@@ -101,6 +101,10 @@ int dmf_context_set_generic(dmf_context* ctx, int level);
  * as u16, when every element with d > 0 has 0 <= x <= d and |v d - x| <= 8 ulp of max(x, 1) (meth_frequency = X / D);
  * the row pass then reads x and the counts instead of v.  0: they do not, and every kernel reads V.  Tests and A/B runs. */
 int dmf_context_set_x16(dmf_context* ctx, int enabled);
+/* 1 (default): solvers created from now on run the X16 form of the row pass (65..256 samples; at 65..128 samples up to
+ * three unknowns, where the LDS of four workgroups per CU allows it) two 16-row blocks per barrier cycle, the two blocks' inner iterations at the same time on two waves; 0: one block at a time.  Both compute the
+ * same results bit for bit.  Tests and A/B runs. */
+int dmf_context_set_rowpass_pair(dmf_context* ctx, int enabled);
 /* How dmf_solver_step decides |cf - cf_0| < tol (deconvolution.py:218-220) for the solvers of this context:
  * 0 (default) = on the Gram-form cost of the loop, with the decisions near the threshold confirmed on the streaming
  * cost of deconvolution.py:15-17 where the Gram form's error bound (1e-15 N S max(counts)) reaches tol / 20;
@@ -200,6 +204,9 @@ int dmf_select_describe(int64_t N, int64_t S, int64_t n_c, int64_t n_u, int nd, 
  * last_stream_cost = the latest streaming cost taken for a stop test (NaN: none).  Any pointer may be NULL. */
 int dmf_solver_stop_info(const dmf_solver* s, int* confirm_stops, int64_t* n_confirmed, int64_t* n_unconfirmed,
                          double* last_stream_cost);
+/* How many k_rowpass_v2 launches this solver's steps have enqueued (total) and how many of them ran the pair schedule
+ * (paired; see dmf_context_set_rowpass_pair).  Tests and A/B runs.  Either pointer may be NULL. */
+int dmf_solver_rowpass_launches(const dmf_solver* s, int64_t* total, int64_t* paired);
 /* One-shot convenience: create + step(n_iter1) + get + destroy. */
 int dmf_solve(dmf_context* ctx, const dmf_problem* p, const double* u0, const double* alpha0,
               int64_t n_u, int mode, int64_t n_iter1, int64_t n_iter2, double tol, int flags,

@@ -2,6 +2,7 @@
 //   hipcc -O3 -std=c++17 --offload-arch=gfx950 tools/rowpass2_probe.hip -o tools/rowpass2_probe && tools/rowpass2_probe [T2] [wg per CU]
 //   -DPROBE_NO_STAMPS: the kernel as it ships (launch times only); -DPROBE_KERNEL_SRC="\"file\"": another version of the source
 //   -DPROBE_X16: the form on the methylated read counts (X16 + D16, V not read)
+//   -DPROBE_PAIR (with -DPROBE_X16): the pair schedule, two blocks per phase B; cycles then also per pair of blocks
 #ifndef PROBE_NO_STAMPS
 #define DMF_STAMPS 1
 #endif
@@ -18,6 +19,12 @@ using namespace dmf;
 constexpr bool kXS = true;
 #else
 constexpr bool kXS = false;
+#endif
+#ifdef PROBE_PAIR
+constexpr bool kPair = true;
+static_assert(kXS, "the pair schedule is an X16 form");
+#else
+constexpr bool kPair = false;
 #endif
 int main(int argc, char** argv) {
     const int64_t N = 1000000; const int S = 256, n_c = 12, n_u = 4, K = 16;
@@ -40,15 +47,15 @@ int main(int argc, char** argv) {
     hipMemcpy(up, hu.data(), hu.size() * 8, hipMemcpyHostToDevice); hipMemcpy(a, ha.data(), ha.size() * 8, hipMemcpyHostToDevice);
     SolverState h{}; h.a1 = 1; h.a2 = 1; h.l_w = 1e4; h.l_w_prev = 1e4; h.l_h = 1e6; h.l_h_prev = 1e6; h.dsq = 6400;
     hipMemcpy(st, &h, sizeof(h), hipMemcpyHostToDevice); hipMemset(stamps, 0, (size_t)grid * 4 * 16 * 8);
-    const size_t lds = rowpass_v2_lds_bytes(S, n_u, T2, kXS);
-    hipFuncSetAttribute((const void*)k_rowpass_v2<3, 4, 4, kXS>, hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024);
+    const size_t lds = rowpass_v2_lds_bytes(S, n_u, T2, kXS, kPair);
+    hipFuncSetAttribute((const void*)k_rowpass_v2<3, 4, 4, kXS, kPair>, hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024);
     hipEvent_t e0, e1; hipEventCreate(&e0); hipEventCreate(&e1);
     for (int rep = 0; rep < (argc > 3 ? atoi(argv[3]) : 3); ++rep) {
         hipEventRecord(e0);
 #ifdef PROBE_NO_STAMPS
-        hipLaunchKernelGGL((k_rowpass_v2<3, 4, 4, kXS>), dim3(grid), dim3(256), lds, 0, V, D, X, 256, R, a, u, up, st, N, S, n_c, T2, 0, 1, slab, u2);
+        hipLaunchKernelGGL((k_rowpass_v2<3, 4, 4, kXS, kPair>), dim3(grid), dim3(256), lds, 0, V, D, X, 256, R, a, u, up, st, N, S, n_c, T2, 0, 1, slab, u2);
 #else
-        hipLaunchKernelGGL((k_rowpass_v2<3, 4, 4, kXS>), dim3(grid), dim3(256), lds, 0, V, D, X, 256, R, a, u, up, st, N, S, n_c, T2, 0, 1, slab, u2, stamps);
+        hipLaunchKernelGGL((k_rowpass_v2<3, 4, 4, kXS, kPair>), dim3(grid), dim3(256), lds, 0, V, D, X, 256, R, a, u, up, st, N, S, n_c, T2, 0, 1, slab, u2, stamps);
 #endif
         hipEventRecord(e1); hipEventSynchronize(e1);
         float ms; hipEventElapsedTime(&ms, e0, e1); printf("launch %d: %.3f ms  (%s)\n", rep, ms, hipGetErrorString(hipGetLastError()));
@@ -58,12 +65,26 @@ int main(int argc, char** argv) {
 #endif
     std::vector<unsigned long long> hs((size_t)grid * 4 * 16);
     hipMemcpy(hs.data(), stamps, hs.size() * 8, hipMemcpyDeviceToHost);
-    const char* an[16] = {"tile store (vmcnt wait)", "phase A (MFMA)", "prefetch issue + partials", "wait X", "phase B / nothing", "wait Y", "phase C", "prefetch issue", "B: partial sums", "B: inner steps", "B: stores", "-", "-", "-", "-", "-"};
+    const char* an[16] = {"tile store (vmcnt wait)", "phase A (MFMA)", "partials", "wait X", "phase B / nothing", "wait Y", "phase C", "prefetch issue", "B: partial sums", "B: inner steps", "B: stores", "phase A, 2nd block", "partials, 2nd block", "phase C, 2nd block", "-", "-"};
     double sum[16] = {0}; int cnt = 0;
-    for (int b = 0; b < grid; ++b) for (int w = 0; w < 4; ++w) { for (int i = 0; i < 16; ++i) sum[i] += (double)hs[((size_t)b * 4 + w) * 16 + i]; ++cnt; }
-    double tot = 0; for (int i = 0; i < 8; ++i) tot += sum[i];  // (8..15: sub-segments of phase B, already inside segment 4)
+    for (int b = 0; b < grid; ++b) for (int w = 0; w < 4; ++w) { for (int i = 0; i < 15; ++i) sum[i] += (double)hs[((size_t)b * 4 + w) * 16 + i]; ++cnt; }
+    double tot = 0; for (int i = 0; i < 8; ++i) tot += sum[i];  // (8..10: sub-segments of phase B, already inside segment 4)
+    for (int i = 11; i < 14; ++i) tot += sum[i];
     const double steps = (N / 16.0) / grid;
-    printf("T2 = %d, %d workgroups per CU: mean cycles per wave %.0f over the kernel, %.0f per block\n", T2, per_cu, tot / cnt, tot / cnt / steps);
-    for (int i = 0; i < 11; ++i) if (an[i][0] != '-') printf("   %-28s %6.1f %%  (%.0f cycles per block)\n", an[i], 100 * sum[i] / tot, sum[i] / cnt / steps);
+    printf("T2 = %d, %d workgroups per CU%s: mean cycles per wave %.0f over the kernel, %.0f per block, %.0f per pair of blocks\n", T2, per_cu,
+           kPair ? ", pair schedule" : "", tot / cnt, tot / cnt / steps, 2 * tot / cnt / steps);
+    for (int i = 0; i < 14; ++i) if (an[i][0] != '-' && (kPair || i < 11)) printf("   %-28s %6.1f %%  (%.0f cycles per block, %.0f per pair)\n", an[i], 100 * sum[i] / tot, sum[i] / cnt / steps, 2 * sum[i] / cnt / steps);
+    // where the waves sit: HW_ID bits 5:4 = SIMD.  Phase B of block s runs on wave s % 4: the pair schedule wants waves
+    // w and w + 1 (mod 4) on different SIMDs
+    int distinct = 0, adjacent_apart = 0;
+    for (int b = 0; b < grid; ++b) {
+        int simd[4], mask = 0;
+        for (int w = 0; w < 4; ++w) { simd[w] = (int)((hs[((size_t)b * 4 + w) * 16 + 15] >> 4) & 3); mask |= 1 << simd[w]; }
+        distinct += mask == 15;
+        bool ok = true;
+        for (int w = 0; w < 4; ++w) ok = ok && simd[w] != simd[(w + 1) % 4];
+        adjacent_apart += ok;
+    }
+    printf("SIMD placement (HW_ID): %d of %d workgroups have their four waves on four SIMDs, %d have waves w, w + 1 apart\n", distinct, grid, adjacent_apart);
     return 0;
 }
