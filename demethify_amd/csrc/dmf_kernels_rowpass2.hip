@@ -175,9 +175,15 @@ __global__ __launch_bounds__(64 * MAXW, MAXW == 4 ? 2 : 1) void k_rowpass_v2(
     // product builds its balanced byte digits from 32 bytes of a row -- converting at the tile store (f32 copy + two digit
     // planes: 52 vector instructions and 8 LDS writes per block and wave, on every wave's critical path) cost 9 % of the kernel.
     // (XS) x in the same linear layout as the counts, read with the same offsets: no swizzle
-    double* __restrict__ tileV = reinterpret_cast<double*>(tile);
-    unsigned short* __restrict__ tileD = reinterpret_cast<unsigned short*>(tile + (XS ? 0 : kTileVBytes2));
-    unsigned short* __restrict__ tileX = tileD + 16 * kRowD;
+    struct BlockTile {
+        double* V;              // (V form)
+        unsigned short *D, *X;  // counts; (XS) x
+    };
+    auto block_tile = [&](int set) {  // this wave's tile of set `set`
+        char* const t = tile + (size_t)set * NW * TB;
+        unsigned short* const d = reinterpret_cast<unsigned short*>(t + (XS ? 0 : kTileVBytes2));
+        return BlockTile{reinterpret_cast<double*>(t), d, d + 16 * kRowD};
+    };
 
     // momentum coefficients of the inner steps (deconvolution.py:83-85): from the host's row of ratios when there is one
     // (SolverState), else the recurrence itself by one thread -- n_iter2 square roots and divisions in a row, ~5 us
@@ -276,711 +282,401 @@ __global__ __launch_bounds__(64 * MAXW, MAXW == 4 ? 2 : 1) void k_rowpass_v2(
     double bu[4] = {0.0, 0.0, 0.0, 0.0};  // b_u[unknown q][sample 16 t + m16] of this wave's column group, t = 0..3
     double u2_acc = 0.0;
     DMF2_STAMP_DECL
-    // One block at a time: the loop as it was before the pair schedule, kept as written so that these instantiations
-    // compile to the same code (the pair schedule below has its phases as lambdas of its own).
-    if constexpr (!PAIR) {
-        const int64_t nblk = (N + 15) / 16;
-        const int nk = (int)((nblk - blockIdx.x + gridDim.x - 1) / gridDim.x);  // blocks of this workgroup
+    const int64_t nblk = (N + 15) / 16;
+    const int nk = (int)((nblk - blockIdx.x + gridDim.x - 1) / gridDim.x);  // blocks of this workgroup
 
-        // global -> register staging: V load i covers rows 2i, 2i+1 (lane -> row half, 2 samples);
-        // D16 load i covers rows 8i .. 8i+7 (lane -> row lane >> 3, 8 samples)
-        const int ld_row = lane >> 5;
-        const int ld_col = (lane & 31) * 2;
-        int ld_gcol = wcol0 + ld_col;
-        // ragged last column group: clamped samples meet zero counts.  Odd S: the row's last sample shares its pair with the
-        // next row's first element (or, on the last row, with a zero from the descriptor's range check) -- a finite value
-        // against a zero count; rows then start 8 bytes off a 16-byte boundary every other time, which 16-byte buffer loads
-        // take (tools/align_probe.hip).
-        const int last_pair = (S - 1) & ~1;
-        if (ld_gcol > last_pair) ld_gcol = last_pair;
-        const int d_row = lane >> 3, d_col = (lane & 7) * 8;
-        // (tile swizzle at the stores: V rows 2 i, 2 i + 1 are swapped rows for i = 2..5)
-        const int ld_col_sw = ((lane & 31) ^ 2) * 2;
-        v2d pv[XS ? 1 : 8];  // (XS: V is not read)
-        v4u pd[2], px[XS ? 2 : 1];
-        double nrt[NKC > 0 ? NKC : 1];
-        double pu, pup;  // u / u_ of lane (row, unknown) for the wave that runs the block's inner iterations
-        constexpr int RPWB = 64 / NU;  // >= 16 rows per wave: one phase-B pass covers the block
-        const int rl = lane / NU, jb = lane - rl * NU;
-        const bool b_lane = rl < 16 && rl < RPWB;
-        // The block's loads are BUFFER loads: address = descriptor base (scalar: array + block offset, recomputed per block on
-        // the scalar unit) + a loop-invariant per-lane byte offset + a scalar / immediate offset per instruction -- no vector
-        // address arithmetic at all (the flat-address form of this prefetch cost ~80 vector instructions per block and wave,
-        // and the row pass is bound by the SIMD's issue slots).  The descriptor's range check replaces the clamps of the
-        // last, partial block: rows at or beyond N read as zero, and their counts are zero.
-        const unsigned int v_off = (unsigned int)(ld_row * S + ld_gcol) * 8u;               // V: row ld_row of a row pair
-        const unsigned int d_off = (unsigned int)(d_row * SD + wcol0 + d_col) * 2u;         // counts: row d_row of eight
-        const unsigned int r_off = (unsigned int)(m16 * NCT + q) * 8u;                      // R_trunc (padded copy): row m16
-        const unsigned int u_off = b_lane ? (unsigned int)lane * 8u : 0xFFFFFFF0u;          // u / u_: (row, unknown) = lane
-        auto span = [](int64_t bytes) { return (unsigned int)(bytes < 0 ? 0 : (bytes > 0x7FFFFFFF ? 0x7FFFFFFF : bytes)); };
-        auto prefetch = [&](int64_t blk) {
-            const int64_t r0 = blk * 16;
-            const int64_t left = N - r0;  // rows of the arrays from this block on (> 0)
-            {
-                // FIRST in the batch: the tile store's wait for the (younger) tile loads then covers them, and phase B
-                // finds its u / u_ complete without a vmcnt wait of its own -- a wait there would also cover the NEXT
-                // block's prefetch, issued just before barrier X, and put a whole HBM round trip on the critical path.
-                const __amdgpu_buffer_rsrc_t ru = __builtin_amdgcn_make_buffer_rsrc((void*)(u + r0 * NU), 0, span(left * NU * 8), 0x00020000);
-                const __amdgpu_buffer_rsrc_t rp = __builtin_amdgcn_make_buffer_rsrc((void*)(u_prev + r0 * NU), 0, span(left * NU * 8), 0x00020000);
-                const v2u a = __builtin_amdgcn_raw_buffer_load_b64(ru, u_off, 0, 0);
-                const v2u b = __builtin_amdgcn_raw_buffer_load_b64(rp, u_off, 0, 0);
-                pu = __hiloint2double((int)a.y, (int)a.x);
-                pup = __hiloint2double((int)b.y, (int)b.x);
+    // global -> register staging: V load i covers rows 2i, 2i+1 (lane -> row half, 2 samples);
+    // D16 / X16 load i covers rows 8i .. 8i+7 (lane -> row lane >> 3, 8 samples); one staging set per block in flight
+    const int ld_row = lane >> 5;
+    const int ld_col = (lane & 31) * 2;
+    int ld_gcol = wcol0 + ld_col;
+    // ragged last column group: clamped samples meet zero counts.  Odd S: the row's last sample shares its pair with the
+    // next row's first element (or, on the last row, with a zero from the descriptor's range check) -- a finite value
+    // against a zero count; rows then start 8 bytes off a 16-byte boundary every other time, which 16-byte buffer loads
+    // take (tools/align_probe.hip).
+    const int last_pair = (S - 1) & ~1;
+    if (ld_gcol > last_pair) ld_gcol = last_pair;
+    const int d_row = lane >> 3, d_col = (lane & 7) * 8;
+    // (tile swizzle at the stores: V rows 2 i, 2 i + 1 are swapped rows for i = 2..5)
+    const int ld_col_sw = ((lane & 31) ^ 2) * 2;
+    v2d pv[NSET][XS ? 1 : 8];  // (XS: V is not read)
+    v4u pd[NSET][2], px[NSET][XS ? 2 : 1];
+    double nrt[NSET][NKC > 0 ? NKC : 1];
+    double pu, pup;  // u / u_ of lane (row, unknown) for the wave that runs the block's inner iterations
+    constexpr int RPWB = 64 / NU;  // >= 16 rows per wave: one phase-B pass covers the block
+    const int rl = lane / NU, jb = lane - rl * NU;
+    const bool b_lane = rl < 16 && rl < RPWB;
+    // The block's loads are BUFFER loads: address = descriptor base (scalar: array + block offset, recomputed per block on
+    // the scalar unit) + a loop-invariant per-lane byte offset + a scalar / immediate offset per instruction -- no vector
+    // address arithmetic at all (the flat-address form of this prefetch cost ~80 vector instructions per block and wave,
+    // and the row pass is bound by the SIMD's issue slots).  The descriptor's range check replaces the clamps of the
+    // last, partial block: rows at or beyond N read as zero, and their counts are zero.
+    const unsigned int v_off = (unsigned int)(ld_row * S + ld_gcol) * 8u;               // V: row ld_row of a row pair
+    const unsigned int d_off = (unsigned int)(d_row * SD + wcol0 + d_col) * 2u;         // counts: row d_row of eight
+    const unsigned int r_off = (unsigned int)(m16 * NCT + q) * 8u;                      // R_trunc (padded copy): row m16
+    const unsigned int u_off = b_lane ? (unsigned int)lane * 8u : 0xFFFFFFF0u;          // u / u_: (row, unknown) = lane
+    auto span = [](int64_t bytes) { return (unsigned int)(bytes < 0 ? 0 : (bytes > 0x7FFFFFFF ? 0x7FFFFFFF : bytes)); };
+    // u / u_ of block blk.  FIRST in a prefetch's batch: the tile store's wait for the (younger) tile loads then covers
+    // them, and phase B finds its u / u_ complete without a vmcnt wait of its own -- a wait there would also cover the
+    // NEXT block's prefetch, issued just before barrier X, and put a whole HBM round trip on the critical path.
+    auto prefetch_u = [&](int64_t blk) {
+        const int64_t r0 = blk * 16;
+        const int64_t left = N - r0;  // rows of the arrays from this block on (> 0)
+        const __amdgpu_buffer_rsrc_t ru = __builtin_amdgcn_make_buffer_rsrc((void*)(u + r0 * NU), 0, span(left * NU * 8), 0x00020000);
+        const __amdgpu_buffer_rsrc_t rp = __builtin_amdgcn_make_buffer_rsrc((void*)(u_prev + r0 * NU), 0, span(left * NU * 8), 0x00020000);
+        const v2u a = __builtin_amdgcn_raw_buffer_load_b64(ru, u_off, 0, 0);
+        const v2u b = __builtin_amdgcn_raw_buffer_load_b64(rp, u_off, 0, 0);
+        pu = __hiloint2double((int)a.y, (int)a.x);
+        pup = __hiloint2double((int)b.y, (int)b.x);
+    };
+    // R_trunc rows and the tile data of block blk into staging set `set`
+    auto prefetch_tile = [&](int64_t blk, int set) {
+        const int64_t r0 = blk * 16;
+        const int64_t left = N - r0;
+        if (NKC > 0) {
+            const __amdgpu_buffer_rsrc_t rr = __builtin_amdgcn_make_buffer_rsrc((void*)(Rtp + r0 * NCT), 0, span(left * NCT * 8), 0x00020000);
+#pragma unroll
+            for (int kc = 0; kc < NKC; ++kc) {
+                const v2u a = __builtin_amdgcn_raw_buffer_load_b64(rr, r_off, kc * 32, 0);
+                nrt[set][kc] = __hiloint2double((int)a.y, (int)a.x);
             }
-            if (NKC > 0) {
-                const __amdgpu_buffer_rsrc_t rr = __builtin_amdgcn_make_buffer_rsrc((void*)(Rtp + r0 * NCT), 0, span(left * NCT * 8), 0x00020000);
-#pragma unroll
-                for (int kc = 0; kc < NKC; ++kc) {
-                    const v2u a = __builtin_amdgcn_raw_buffer_load_b64(rr, r_off, kc * 32, 0);
-                    nrt[kc] = __hiloint2double((int)a.y, (int)a.x);
-                }
-            }
-            if constexpr (!XS) {
-                const __amdgpu_buffer_rsrc_t rv = __builtin_amdgcn_make_buffer_rsrc((void*)(V + r0 * S), 0, span(left * S * 8), 0x00020000);
-#pragma unroll
-                for (int i = 0; i < 8; ++i) {
-                    const v4u a = __builtin_amdgcn_raw_buffer_load_b128(rv, v_off, 2 * i * S * 8, 0);
-                    pv[i] = v2d{__hiloint2double((int)a.y, (int)a.x), __hiloint2double((int)a.w, (int)a.z)};
-                }
-            } else {
-                // (X16 is zero-padded like the counts: always in range)
-                const __amdgpu_buffer_rsrc_t rx = __builtin_amdgcn_make_buffer_rsrc((void*)(X16 + r0 * SD), 0, span((int64_t)16 * SD * 2), 0x00020000);
-                px[0] = __builtin_amdgcn_raw_buffer_load_b128(rx, d_off, 0, 0);
-                px[1] = __builtin_amdgcn_raw_buffer_load_b128(rx, d_off, 8 * SD * 2, 0);
-            }
-            {
-                // (the count copy is zero-padded to whole blocks of 16 rows: always in range)
-                const __amdgpu_buffer_rsrc_t rd = __builtin_amdgcn_make_buffer_rsrc((void*)(D16 + r0 * SD), 0, span((int64_t)16 * SD * 2), 0x00020000);
-                pd[0] = __builtin_amdgcn_raw_buffer_load_b128(rd, d_off, 0, 0);
-                pd[1] = __builtin_amdgcn_raw_buffer_load_b128(rd, d_off, 8 * SD * 2, 0);
-            }
-        };
-        if (nk > 0) prefetch(blockIdx.x);
-
-        // this lane's places in its wave's partial-sum slots: c[unknown q][row m16]; M[pair m16 = (pj, pl)][rows 4 q ..] twice
-        // (M is symmetric), a slot's M entries in ROTATED order -- slot (row, j) entry r is M[j][(j + r) % NU], the order in
-        // which phase B's quad rotations deliver the iterate; rows 4 q + rr at immediate offsets
-        double* __restrict__ const mine_c = red + (size_t)wave * NV * 16 + (m16 * NU + q) * SLOT;
-        double* __restrict__ const mine_m1 = red + (size_t)wave * NV * 16 + (4 * q * NU + pl) * SLOT + 1 + (pj - pl + NU) % NU;
-        double* __restrict__ const mine_m2 = red + (size_t)wave * NV * 16 + (4 * q * NU + pj) * SLOT + 1 + (pl - pj) % NU;
-
-        for (int s = 0; s < nk; ++s) {
-            const int64_t blk = blockIdx.x + (int64_t)s * gridDim.x;
-            const int64_t row0 = blk * 16;
-            // ---- tile store (waits for the prefetched loads)
-            __builtin_amdgcn_s_setprio(1);
-            if constexpr (XS) {
-#pragma unroll
-                for (int i = 0; i < 2; ++i) *reinterpret_cast<v4u*>(tileX + (8 * i + d_row) * kRowD + d_col) = px[i];
-            } else {
-#pragma unroll
-                for (int i = 0; i < 8; ++i)
-                    *reinterpret_cast<v2d*>(tileV + (2 * i + ld_row) * kRowV + ((i >= 2 && i < 6) ? ld_col_sw : ld_col)) = pv[i];
-            }
-#ifndef DMF_ABLATE_DSTORE
-#pragma unroll
-            for (int i = 0; i < 2; ++i) *reinterpret_cast<v4u*>(tileD + (8 * i + d_row) * kRowD + d_col) = pd[i];
-#endif
-            double rtop[NKC > 0 ? NKC : 1];
-#pragma unroll
-            for (int kc = 0; kc < NKC; ++kc) rtop[kc] = nrt[kc];  // B operand of the first product: Rt^T[k = 4 kc + q][n = row]
-            // the block's u / u_ arrived with the tile (the next prefetch reuses pu / pup before phase B runs)
-            const bool my_turn = wave == s % NW;
-            const bool ok = b_lane && row0 + rl < N;
-            const double uu0 = pu;
-            const double up0 = pup;
-            __builtin_amdgcn_wave_barrier();
-            __builtin_amdgcn_s_setprio(0);
-            DMF2_STAMP(0)  // tile store (vmcnt wait for the prefetch)
-
-            // ---- phase A: strips of 16 samples; the LDS reads of strip t + 1 are issued before the MFMAs of strip t,
-            // and the E chain of strip t + 1 is slotted between the c / M MFMAs of strip t (a dependent FP64 MFMA
-            // stalls behind its producer)
-            struct StripV {
-                v2d v01, v23;
-                v2u dw;  // the four counts of the piece, u16
-            };
-            struct StripX {
-                v2u dw, xw;  // the four counts and the four x = d v of the piece, u16
-            };
-            using Strip = std::conditional_t<XS, StripX, StripV>;
-            auto load_strip = [&](int t, Strip& R) {
-                if constexpr (XS) {
-                    R.xw = *reinterpret_cast<const v2u*>(tileX + m16 * kRowD + t * 16 + 4 * q);
-                } else {
-                    const double* __restrict__ tv = tileV + m16 * kRowV + t * 16 + 4 * qs;
-                    R.v01 = *reinterpret_cast<const v2d*>(tv);
-                    R.v23 = *reinterpret_cast<const v2d*>(tv + 2);
-                }
-                R.dw = *reinterpret_cast<const v2u*>(tileD + m16 * kRowD + t * 16 + 4 * q);
-            };
-            double csm0 = 0.0, csm1 = 0.0;  // c[unknown q][row m16], one double per lane
-            // E = V - Rt a_known; XS: E = -Rt a_known, and V enters through x below
-            auto e_init = [&](const Strip& R) {
-                if constexpr (XS) return v4d{0.0, 0.0, 0.0, 0.0};
-                else return v4d{R.v01.x, R.v01.y, R.v23.x, R.v23.y};
-            };
-            auto run_strip = [&](const Strip& R, v4d e, const Strip& Rn, const double (&a1n)[NKC > 0 ? NKC : 1],
-                                 const double (&a2)[4], bool has_next) {
-                const v4d d = {(double)(R.dw.x & 0xFFFFu), (double)(R.dw.x >> 16), (double)(R.dw.y & 0xFFFFu), (double)(R.dw.y >> 16)};
-                v4d w;
-                if constexpr (XS) {  // w = d (v - Rt a1) = fma(d, -Rt a1, x)
-                    const v4d x = {(double)(R.xw.x & 0xFFFFu), (double)(R.xw.x >> 16), (double)(R.xw.y & 0xFFFFu), (double)(R.xw.y >> 16)};
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) w[r] = fma(d[r], e[r], x[r]);
-                } else {
-                    w = d * e;
-                }
-                v4d en = e_init(Rn);
-#pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    if (r & 1) csm1 = __builtin_amdgcn_mfma_f64_4x4x4f64(a2[r], w[r], csm1, 0, 0, 0);
-                    else csm0 = __builtin_amdgcn_mfma_f64_4x4x4f64(a2[r], w[r], csm0, 0, 0, 0);
-                    if (has_next && r < NKC) en = __builtin_amdgcn_mfma_f64_16x16x4f64(a1n[r], rtop[r], en, 0, 0, 0);
-                }
-                return en;
-            };
-#ifdef DMF_ABLATE_E
-            const double csm = XS ? (double)tileX[m16 * kRowD + 4 * q] : tileV[m16 * kRowV + 4 * qs];
-#else
-            Strip sa, sb;
-            load_strip(0, sa);
-            load_strip(1, sb);
-            __builtin_amdgcn_sched_barrier(0);
-            v4d e0 = e_init(sa);
-#pragma unroll
-            for (int kc = 0; kc < NKC; ++kc) e0 = __builtin_amdgcn_mfma_f64_16x16x4f64(a1r[0][kc], rtop[kc], e0, 0, 0, 0);
-            const v4d e1 = run_strip(sa, e0, sb, a1r[1], a2r[0], true);
-            load_strip(2, sa);
-            __builtin_amdgcn_sched_barrier(0);
-            const v4d e2 = run_strip(sb, e1, sa, a1r[2], a2r[1], true);
-            load_strip(3, sb);
-            __builtin_amdgcn_sched_barrier(0);
-            const v4d e3 = run_strip(sa, e2, sb, a1r[3], a2r[2], true);
-            (void)run_strip(sb, e3, sb, a1r[3], a2r[3], false);
-            const double csm = csm0 + csm1;
-#endif
-            // M on the integer matrix cores: digit weights 256^0 .. 256^7 (count digit d + P digit t -> weight t + d)
-            v4i mw[8];
-#pragma unroll
-            for (int w8 = 0; w8 < 8; ++w8) mw[w8] = v4i{0, 0, 0, 0};
-#ifndef DMF_ABLATE_M  // (diagnostic builds of tools/rowpass2_probe.hip leave pieces out to see what they cost)
-            {
-                // A: counts [row m16][samples 16 q .. 16 q + 15] as balanced digits: d + 128 = b0 + 256 b1, digit 0 = b0 - 128
-                // (b0 ^ 0x80 as i8), digit 1 = b1
-                const v4u wa = *reinterpret_cast<const v4u*>(tileD + m16 * kRowD + 16 * q);
-                const v4u wb = *reinterpret_cast<const v4u*>(tileD + m16 * kRowD + 16 * q + 8);
-                const unsigned int e0 = wa.x + 0x00800080u, e1 = wa.y + 0x00800080u, e2 = wa.z + 0x00800080u, e3 = wa.w + 0x00800080u;
-                const unsigned int e4 = wb.x + 0x00800080u, e5 = wb.y + 0x00800080u, e6 = wb.z + 0x00800080u, e7 = wb.w + 0x00800080u;
-                const v4i c0 = {(int)(__builtin_amdgcn_perm(e1, e0, 0x06040200u) ^ 0x80808080u),
-                                (int)(__builtin_amdgcn_perm(e3, e2, 0x06040200u) ^ 0x80808080u),
-                                (int)(__builtin_amdgcn_perm(e5, e4, 0x06040200u) ^ 0x80808080u),
-                                (int)(__builtin_amdgcn_perm(e7, e6, 0x06040200u) ^ 0x80808080u)};
-#pragma unroll
-                for (int t = 0; t < 7; ++t) mw[t] = __builtin_amdgcn_mfma_i32_16x16x64_i8(c0, pdg[t], mw[t], 0, 0, 0);
-                if (nd == 2) {
-                    const v4i c1 = {(int)__builtin_amdgcn_perm(e1, e0, 0x07050301u), (int)__builtin_amdgcn_perm(e3, e2, 0x07050301u),
-                                    (int)__builtin_amdgcn_perm(e5, e4, 0x07050301u), (int)__builtin_amdgcn_perm(e7, e6, 0x07050301u)};
-#pragma unroll
-                    for (int t = 0; t < 7; ++t) mw[t + 1] = __builtin_amdgcn_mfma_i32_16x16x64_i8(c1, pdg[t], mw[t + 1], 0, 0, 0);
-                }
-            }
-#endif
-            // lane (pair m16, q) holds rows 4 q + reg: the exact integer sum_w 256^w mw[w] in two halves that fit a double
-            // without rounding (|mw| < 2^21 per digit product sum), one rounding when they are joined
-            double mrow[4];
-#ifdef DMF_ABLATE_M
-#pragma unroll
-            for (int rr = 0; rr < 4; ++rr) mrow[rr] = 0.25 * (rr == (m16 & 3));
-#else
-#pragma unroll
-            for (int rr = 0; rr < 4; ++rr) {
-                const double lo = fma(fma(fma((double)mw[3][rr], 256.0, (double)mw[2][rr]), 256.0, (double)mw[1][rr]), 256.0, (double)mw[0][rr]);
-                const double hi = fma(fma(fma((double)mw[7][rr], 256.0, (double)mw[6][rr]), 256.0, (double)mw[5][rr]), 256.0, (double)mw[4][rr]);
-                mrow[rr] = fma(hi, 0x1p32, lo) * m_scale;
-            }
-#endif
-            DMF2_STAMP(1)  // phase A
-            // The next block's global loads (their staging registers were free during phase A).  A workgroup's waves reach
-            // this point together, and 42 KB of loads take the CU's one address unit ~700 cycles: only the wave that runs
-            // phase B issues its loads here; the others issue theirs behind barrier X, while they wait for phase B anyway.
-            {
-                if (q < NU) *mine_c = csm;  // c[unknown q][row m16]
-                if (m16 < NP) {  // C layout of the 16x16x64 tile: col = pair m16 = (pj, pl), rows 4 q + reg; M is symmetric
-#pragma unroll
-                    for (int rr = 0; rr < 4; ++rr) mine_m1[rr * NU * SLOT] = mrow[rr];
-                    if (pj != pl) {
-#pragma unroll
-                        for (int rr = 0; rr < 4; ++rr) mine_m2[rr * NU * SLOT] = mrow[rr];
-                    }
-                }
-            }
-            DMF2_STAMP(2)  // partials
-            // (a bare barrier behind an LDS-only wait: __syncthreads() would also drain vmcnt)
-            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-            __builtin_amdgcn_s_barrier();  // ---- barrier X
-            DMF2_STAMP(3)  // wait X
-            // The next block's global loads (their staging registers were free during phase A).  42 KB of loads take the CU's
-            // one address unit ~700 cycles when a workgroup's waves issue them together: the wave that runs phase B goes
-            // first, the others -- who wait for phase B anyway -- a little later.  (ONE place for all waves: with the loads in
-            // two branches the register allocator gave them different destinations and put copies -- and the waits for the
-            // data -- behind one of them.)
-#ifndef DMF_V2_NO_STAGGER
-            if (!my_turn) __builtin_amdgcn_s_sleep(DMF_V2_STAGGER);
-#endif
-            if (s + 1 < nk) prefetch(blk + gridDim.x);
-            DMF2_STAMP(7)  // prefetch issue
-
-            // ---- phase B: row-local inner iterations, lane = (row, unknown j); c and M pre-scaled by 1 / l_w
-            if (my_turn) {
-                __builtin_amdgcn_s_setprio(3);  // a dependent chain on the workgroup's critical path
-                DMF2_SUB_BEGIN
-                const int lane0 = lane - jb;
-                const int rlc = rl < 16 ? rl : 15;
-                double cj = 0.0, Ms[NU];
-#pragma unroll
-                for (int l = 0; l < NU; ++l) Ms[l] = 0.0;
-                {
-                    // this lane's slot of every column group, in column-group order (a fixed summation order); the values
-                    // are already c / l_w and -M / l_w
-                    const double* __restrict__ slot = red + (rlc * NU + jb) * SLOT;
-#pragma unroll 1
-                    for (int w0 = 0; w0 < MAXW; w0 += 4) {  // (batches of four column groups: registers)
-                        v2d part[4][SLOT / 2];
-#pragma unroll
-                        for (int w = 0; w < 4; ++w)
-#pragma unroll
-                            for (int h = 0; h < SLOT / 2; ++h)
-                                part[w][h] = *reinterpret_cast<const v2d*>(slot + (w0 + w) * NV * 16 + 2 * h);
-#pragma unroll
-                        for (int w = 0; w < 4; ++w) {
-                            cj += part[w][0].x;
-#pragma unroll
-                            for (int l = 0; l < NU; ++l) Ms[l] += (l & 1) ? part[w][(l + 1) / 2].x : part[w][l / 2].y;
-                        }
-                    }
-                }
-                double uu = uu0, up = up0;
-                DMF2_SUB(8)
-                // The momentum coefficients ride in a VGPR (lane t holds beta_t) and reach the loop through
-                // v_readlane: an LDS read here would sit on the dependent chain every step.
-                for (int t0 = 0; t0 < n_iter2; t0 += 64) {
-                    const int tl = t0 + lane < n_iter2 ? t0 + lane : n_iter2 - 1;
-                    const double bvec = beta_tab[tl];  // (lane t: beta_t; the first read goes out with the partial-sum reads)
-                    const int b_lo = __double2loint(bvec), b_hi = __double2hiint(bvec);
-                    const int t_end = n_iter2 - t0 < 64 ? n_iter2 - t0 : 64;
-                    // (u, u_) swap roles every step: written out in pairs so that no register copies sit on the chain
-                    // (the loop holds v_readlane, a convergent operation the unroller will not split by itself)
-                    if (mode == 1) {
-                        inner_steps<NU, true>(uu, up, cj, Ms, b_lo, b_hi, t_end, lane0);
-                    } else {
-                        if (t0 == 0) Ms[0] += 1.0;  // the step's own "+ ut" (deconvolution.py:88), folded into the diagonal
-                        inner_steps<NU, false>(uu, up, cj, Ms, b_lo, b_hi, t_end, lane0);
-                    }
-                }
-                DMF2_SUB(9)
-                if (b_lane) ubuf[rl * NU + jb] = ok ? uu : 0.0;  // rows beyond N: phase C multiplies them by zero counts
-                if (ok) {
-                    // (buffer stores, like the loads: scalar base of the block + this lane's constant offset)
-                    const __amdgpu_buffer_rsrc_t ru = __builtin_amdgcn_make_buffer_rsrc((void*)(u + row0 * NU), 0, span((N - row0) * NU * 8), 0x00020000);
-                    const __amdgpu_buffer_rsrc_t rp = __builtin_amdgcn_make_buffer_rsrc((void*)(u_prev + row0 * NU), 0, span((N - row0) * NU * 8), 0x00020000);
-                    __builtin_amdgcn_raw_buffer_store_b64(v2u{(unsigned int)__double2loint(uu), (unsigned int)__double2hiint(uu)}, ru, u_off, 0, 0);
-                    __builtin_amdgcn_raw_buffer_store_b64(v2u{(unsigned int)__double2loint(up), (unsigned int)__double2hiint(up)}, rp, u_off, 0, 0);
-                    u2_acc = fma(uu, uu, u2_acc);
-                }
-                DMF2_SUB(10)
-                __builtin_amdgcn_s_setprio(0);
-            }
-            DMF2_STAMP(4)  // phase B (or nothing)
-            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-            __builtin_amdgcn_s_barrier();  // ---- barrier Y
-            DMF2_STAMP(5)  // wait Y
-
-            // ---- phase C: b_u[j][s] += sum_rows u[row][j] (d v)[row][s] on the 4x4x4 (4 blocks) FP64 MFMA: block = sample
-            // quad of a 16-sample strip, i = unknown, j = sample in the quad, k = row in a quad of rows (A[b][i][k] sits
-            // at lane 16 k + 4 b + i, B[b][k][j] at lane 16 k + 4 b + j, the result D[b][i][j] at lane 16 i + 4 b + j:
-            // tools/mfma_probe.hip).  k may number the rows of a quad in any order: lane (q, m16) reads (d v) of row
-            // R + c_row(q), sample 16 t + m16 (at its swizzled place) and u of that row, unknown m16 & 3; the 32 tile reads of
-            // the block are independent and go out in two batches (a lane = sample loop with per-row broadcast reads of u
-            // spent ~1.6k cycles per block on LDS round trips).
-#ifndef DMF_ABLATE_C
-#pragma unroll
-            for (int half = 0; half < 2; ++half) {
-                double vv[2][4], ua[2];
-                unsigned short dd[2][4];  // (XS: x)
-#pragma unroll
-                for (int rr = 0; rr < 2; ++rr) {
-                    const int row = 2 * half + rr + c_row;
-#pragma unroll
-                    for (int t = 0; t < 4; ++t) {
-                        if constexpr (XS) {
-                            dd[rr][t] = tileX[row * kRowD + 16 * t + m16];
-                        } else {
-                            vv[rr][t] = tileV[row * kRowV + 16 * t + mC];
-                            dd[rr][t] = tileD[row * kRowD + 16 * t + m16];
-                        }
-                    }
-                    ua[rr] = (m16 & 3) < NU ? ubuf[row * NU + (m16 & 3)] : 0.0;
-                }
-#pragma unroll
-                for (int rr = 0; rr < 2; ++rr)
-#pragma unroll
-                    for (int t = 0; t < 4; ++t)
-                        bu[t] = __builtin_amdgcn_mfma_f64_4x4x4f64(ua[rr], XS ? (double)dd[rr][t] : (double)dd[rr][t] * vv[rr][t], bu[t], 0, 0, 0);
-            }
-#endif
-            __builtin_amdgcn_s_setprio(0);
-            DMF2_STAMP(6)  // phase C
-            // (the next iteration's tile store touches this wave's own tile only; ubuf and red are rewritten behind
-            // the next barrier X / by phase A after this wave's own phase C)
         }
-    } else {
-        // (the pair schedule: the X16 form only -- static_assert above)  this wave's tiles of set `set`: counts, then x
-        struct BlockTile {
-            unsigned short *D, *X;
-        };
-        auto block_tile = [&](int set) {
-            unsigned short* const d = reinterpret_cast<unsigned short*>(tile + (size_t)set * NW * TB);
-            return BlockTile{d, d + 16 * kRowD};
-        };
-        const int64_t nblk = (N + 15) / 16;
-        const int nk = (int)((nblk - blockIdx.x + gridDim.x - 1) / gridDim.x);  // blocks of this workgroup
-
-        // (the X16 form only: V is not read.)  global -> register staging: D16 / X16 load i covers rows 8i .. 8i+7
-        // (lane -> row lane >> 3, 8 samples); one staging set per block of the pair
-        const int d_row = lane >> 3, d_col = (lane & 7) * 8;
-        v4u pd[NSET][2], px[NSET][2];
-        double nrt[NSET][NKC > 0 ? NKC : 1];
-        double pu, pup;  // u / u_ of lane (row, unknown) for the wave that runs the block's inner iterations
-        constexpr int RPWB = 64 / NU;  // >= 16 rows per wave: one phase-B pass covers the block
-        const int rl = lane / NU, jb = lane - rl * NU;
-        const bool b_lane = rl < 16 && rl < RPWB;
-        // The block's loads are BUFFER loads: address = descriptor base (scalar: array + block offset, recomputed per block on
-        // the scalar unit) + a loop-invariant per-lane byte offset + a scalar / immediate offset per instruction -- no vector
-        // address arithmetic at all (the flat-address form of this prefetch cost ~80 vector instructions per block and wave,
-        // and the row pass is bound by the SIMD's issue slots).  The descriptor's range check replaces the clamps of the
-        // last, partial block: rows at or beyond N read as zero, and their counts are zero.
-        const unsigned int d_off = (unsigned int)(d_row * SD + wcol0 + d_col) * 2u;         // counts: row d_row of eight
-        const unsigned int r_off = (unsigned int)(m16 * NCT + q) * 8u;                      // R_trunc (padded copy): row m16
-        const unsigned int u_off = b_lane ? (unsigned int)lane * 8u : 0xFFFFFFF0u;          // u / u_: (row, unknown) = lane
-        auto span = [](int64_t bytes) { return (unsigned int)(bytes < 0 ? 0 : (bytes > 0x7FFFFFFF ? 0x7FFFFFFF : bytes)); };
-        // u / u_ of block blk.  FIRST in a prefetch's batch: the tile store's wait for the (younger) tile loads then covers
-        // them, and phase B finds its u / u_ complete without a vmcnt wait of its own -- a wait there would also cover the
-        // NEXT block's prefetch, issued just before barrier X, and put a whole HBM round trip on the critical path.
-        auto prefetch_u = [&](int64_t blk) {
-            const int64_t r0 = blk * 16;
-            const int64_t left = N - r0;  // rows of the arrays from this block on (> 0)
-            const __amdgpu_buffer_rsrc_t ru = __builtin_amdgcn_make_buffer_rsrc((void*)(u + r0 * NU), 0, span(left * NU * 8), 0x00020000);
-            const __amdgpu_buffer_rsrc_t rp = __builtin_amdgcn_make_buffer_rsrc((void*)(u_prev + r0 * NU), 0, span(left * NU * 8), 0x00020000);
-            const v2u a = __builtin_amdgcn_raw_buffer_load_b64(ru, u_off, 0, 0);
-            const v2u b = __builtin_amdgcn_raw_buffer_load_b64(rp, u_off, 0, 0);
-            pu = __hiloint2double((int)a.y, (int)a.x);
-            pup = __hiloint2double((int)b.y, (int)b.x);
-        };
-        // R_trunc rows and the tile data of block blk into staging set `set`
-        auto prefetch_tile = [&](int64_t blk, int set) {
-            const int64_t r0 = blk * 16;
-            const int64_t left = N - r0;
-            if (NKC > 0) {
-                const __amdgpu_buffer_rsrc_t rr = __builtin_amdgcn_make_buffer_rsrc((void*)(Rtp + r0 * NCT), 0, span(left * NCT * 8), 0x00020000);
+        if constexpr (!XS) {
+            const __amdgpu_buffer_rsrc_t rv = __builtin_amdgcn_make_buffer_rsrc((void*)(V + r0 * S), 0, span(left * S * 8), 0x00020000);
 #pragma unroll
-                for (int kc = 0; kc < NKC; ++kc) {
-                    const v2u a = __builtin_amdgcn_raw_buffer_load_b64(rr, r_off, kc * 32, 0);
-                    nrt[set][kc] = __hiloint2double((int)a.y, (int)a.x);
-                }
+            for (int i = 0; i < 8; ++i) {
+                const v4u a = __builtin_amdgcn_raw_buffer_load_b128(rv, v_off, 2 * i * S * 8, 0);
+                pv[set][i] = v2d{__hiloint2double((int)a.y, (int)a.x), __hiloint2double((int)a.w, (int)a.z)};
             }
-            {
-                // (X16 is zero-padded like the counts: always in range)
-                const __amdgpu_buffer_rsrc_t rx = __builtin_amdgcn_make_buffer_rsrc((void*)(X16 + r0 * SD), 0, span((int64_t)16 * SD * 2), 0x00020000);
-                px[set][0] = __builtin_amdgcn_raw_buffer_load_b128(rx, d_off, 0, 0);
-                px[set][1] = __builtin_amdgcn_raw_buffer_load_b128(rx, d_off, 8 * SD * 2, 0);
-            }
-            {
-                // (the count copy is zero-padded to whole blocks of 16 rows: always in range)
-                const __amdgpu_buffer_rsrc_t rd = __builtin_amdgcn_make_buffer_rsrc((void*)(D16 + r0 * SD), 0, span((int64_t)16 * SD * 2), 0x00020000);
-                pd[set][0] = __builtin_amdgcn_raw_buffer_load_b128(rd, d_off, 0, 0);
-                pd[set][1] = __builtin_amdgcn_raw_buffer_load_b128(rd, d_off, 8 * SD * 2, 0);
-            }
-        };
-        // the block of the pair that starts at block index s whose phase B this wave runs (1: block s + 1), and so the
-        // block whose u / u_ it prefetches (a wave that runs neither loads block s's: never used)
-        auto pair_set = [&](int s) { return (s + 1 < nk && wave == (s + 1) % NW) ? 1 : 0; };
-        if (nk > 0) {
-            prefetch_u(blockIdx.x + (int64_t)pair_set(0) * gridDim.x);
-            prefetch_tile(blockIdx.x, 0);
-            if (nk > 1) prefetch_tile(blockIdx.x + gridDim.x, 1);
+        } else {
+            // (X16 is zero-padded like the counts: always in range)
+            const __amdgpu_buffer_rsrc_t rx = __builtin_amdgcn_make_buffer_rsrc((void*)(X16 + r0 * SD), 0, span((int64_t)16 * SD * 2), 0x00020000);
+            px[set][0] = __builtin_amdgcn_raw_buffer_load_b128(rx, d_off, 0, 0);
+            px[set][1] = __builtin_amdgcn_raw_buffer_load_b128(rx, d_off, 8 * SD * 2, 0);
         }
+        {
+            // (the count copy is zero-padded to whole blocks of 16 rows: always in range)
+            const __amdgpu_buffer_rsrc_t rd = __builtin_amdgcn_make_buffer_rsrc((void*)(D16 + r0 * SD), 0, span((int64_t)16 * SD * 2), 0x00020000);
+            pd[set][0] = __builtin_amdgcn_raw_buffer_load_b128(rd, d_off, 0, 0);
+            pd[set][1] = __builtin_amdgcn_raw_buffer_load_b128(rd, d_off, 8 * SD * 2, 0);
+        }
+    };
+    // the block of a barrier cycle starting at block index s whose phase B this wave runs (1: block s + 1, pairs only), and
+    // so the block whose u / u_ it prefetches (a wave that runs none loads block s's: never used)
+    auto pair_set = [&](int s) { return (PAIR && s + 1 < nk && wave == (s + 1) % NW) ? 1 : 0; };
+    if (nk > 0) {
+        prefetch_u(blockIdx.x + (int64_t)pair_set(0) * gridDim.x);
+        prefetch_tile(blockIdx.x, 0);
+        if (PAIR && nk > 1) prefetch_tile(blockIdx.x + gridDim.x, 1);
+    }
 
-        // this lane's places in its wave's partial-sum slots: c[unknown q][row m16]; M[pair m16 = (pj, pl)][rows 4 q ..] twice
-        // (M is symmetric), a slot's M entries in ROTATED order -- slot (row, j) entry r is M[j][(j + r) % NU], the order in
-        // which phase B's quad rotations deliver the iterate; rows 4 q + rr at immediate offsets (slot set 0; set 1 follows)
-        double* __restrict__ const mine_c = red + (size_t)wave * NV * 16 + (m16 * NU + q) * SLOT;
-        double* __restrict__ const mine_m1 = red + (size_t)wave * NV * 16 + (4 * q * NU + pl) * SLOT + 1 + (pj - pl + NU) % NU;
-        double* __restrict__ const mine_m2 = red + (size_t)wave * NV * 16 + (4 * q * NU + pj) * SLOT + 1 + (pl - pj) % NU;
+    // this lane's places in its wave's partial-sum slots: c[unknown q][row m16]; M[pair m16 = (pj, pl)][rows 4 q ..] twice
+    // (M is symmetric), a slot's M entries in ROTATED order -- slot (row, j) entry r is M[j][(j + r) % NU], the order in
+    // which phase B's quad rotations deliver the iterate; rows 4 q + rr at immediate offsets (slot set 0; set 1 follows)
+    double* __restrict__ const mine_c = red + (size_t)wave * NV * 16 + (m16 * NU + q) * SLOT;
+    double* __restrict__ const mine_m1 = red + (size_t)wave * NV * 16 + (4 * q * NU + pl) * SLOT + 1 + (pj - pl + NU) % NU;
+    double* __restrict__ const mine_m2 = red + (size_t)wave * NV * 16 + (4 * q * NU + pj) * SLOT + 1 + (pl - pj) % NU;
 
-        // ---- tile store of staging set `set` into the wave's tile of that set (waits for the prefetched loads)
-        auto tile_store = [&](int set) {
-            const BlockTile T = block_tile(set);
+    // ---- tile store of staging set `set` into the wave's tile of that set (waits for the prefetched loads)
+    auto tile_store = [&](int set) {
+        const BlockTile T = block_tile(set);
+        if constexpr (XS) {
 #pragma unroll
             for (int i = 0; i < 2; ++i) *reinterpret_cast<v4u*>(T.X + (8 * i + d_row) * kRowD + d_col) = px[set][i];
+        } else {
+#pragma unroll
+            for (int i = 0; i < 8; ++i)
+                *reinterpret_cast<v2d*>(T.V + (2 * i + ld_row) * kRowV + ((i >= 2 && i < 6) ? ld_col_sw : ld_col)) = pv[set][i];
+        }
 #ifndef DMF_ABLATE_DSTORE
 #pragma unroll
-            for (int i = 0; i < 2; ++i) *reinterpret_cast<v4u*>(T.D + (8 * i + d_row) * kRowD + d_col) = pd[set][i];
+        for (int i = 0; i < 2; ++i) *reinterpret_cast<v4u*>(T.D + (8 * i + d_row) * kRowD + d_col) = pd[set][i];
 #endif
-        };
+    };
 
-        // ---- phase A of the block in tile set `set` (R_trunc rows: staging set `set`) -> partial sums in slot set `set`
-        auto phase_a = [&](int set, int st_a, int st_p) {
-            const BlockTile T = block_tile(set);
-            unsigned short* __restrict__ const tileD = T.D;
-            unsigned short* __restrict__ const tileX = T.X;
-            const double (&rtop)[NKC > 0 ? NKC : 1] = nrt[set];  // B operand of the first product: Rt^T[k = 4 kc + q][n = row]
-            // phase A: strips of 16 samples; the LDS reads of strip t + 1 are issued before the MFMAs of strip t,
-            // and the E chain of strip t + 1 is slotted between the c / M MFMAs of strip t (a dependent FP64 MFMA
-            // stalls behind its producer)
-            struct Strip {
-                v2u dw, xw;  // the four counts and the four x = d v of the piece, u16
-            };
-            auto load_strip = [&](int t, Strip& R) {
+    // ---- phase A of the block in tile set `set` (R_trunc rows: staging set `set`) -> partial sums in slot set `set`
+    auto phase_a = [&](int set, int st_a, int st_p) {
+        const BlockTile T = block_tile(set);
+        const double* __restrict__ const tileV = T.V;
+        unsigned short* __restrict__ const tileD = T.D;
+        unsigned short* __restrict__ const tileX = T.X;
+        const double (&rtop)[NKC > 0 ? NKC : 1] = nrt[set];  // B operand of the first product: Rt^T[k = 4 kc + q][n = row]
+        // strips of 16 samples; the LDS reads of strip t + 1 are issued before the MFMAs of strip t, and the E chain of
+        // strip t + 1 is slotted between the c / M MFMAs of strip t (a dependent FP64 MFMA stalls behind its producer)
+        struct StripV {
+            v2d v01, v23;
+            v2u dw;  // the four counts of the piece, u16
+        };
+        struct StripX {
+            v2u dw, xw;  // the four counts and the four x = d v of the piece, u16
+        };
+        using Strip = std::conditional_t<XS, StripX, StripV>;
+        auto load_strip = [&](int t, Strip& R) {
+            if constexpr (XS) {
                 R.xw = *reinterpret_cast<const v2u*>(tileX + m16 * kRowD + t * 16 + 4 * q);
-                R.dw = *reinterpret_cast<const v2u*>(tileD + m16 * kRowD + t * 16 + 4 * q);
-            };
-            double csm0 = 0.0, csm1 = 0.0;  // c[unknown q][row m16], one double per lane
-            // E = -Rt a_known (V enters through x below)
-            auto e_init = [&](const Strip&) { return v4d{0.0, 0.0, 0.0, 0.0}; };
-            auto run_strip = [&](const Strip& R, v4d e, const Strip& Rn, const double (&a1n)[NKC > 0 ? NKC : 1],
-                                 const double (&a2)[4], bool has_next) {
-                const v4d d = {(double)(R.dw.x & 0xFFFFu), (double)(R.dw.x >> 16), (double)(R.dw.y & 0xFFFFu), (double)(R.dw.y >> 16)};
-                // w = d (v - Rt a1) = fma(d, -Rt a1, x)
+            } else {
+                const double* __restrict__ tv = tileV + m16 * kRowV + t * 16 + 4 * qs;
+                R.v01 = *reinterpret_cast<const v2d*>(tv);
+                R.v23 = *reinterpret_cast<const v2d*>(tv + 2);
+            }
+            R.dw = *reinterpret_cast<const v2u*>(tileD + m16 * kRowD + t * 16 + 4 * q);
+        };
+        double csm0 = 0.0, csm1 = 0.0;  // c[unknown q][row m16], one double per lane
+        // E = V - Rt a_known; XS: E = -Rt a_known, and V enters through x below
+        auto e_init = [&](const Strip& R) {
+            if constexpr (XS) return v4d{0.0, 0.0, 0.0, 0.0};
+            else return v4d{R.v01.x, R.v01.y, R.v23.x, R.v23.y};
+        };
+        auto run_strip = [&](const Strip& R, v4d e, const Strip& Rn, const double (&a1n)[NKC > 0 ? NKC : 1],
+                             const double (&a2)[4], bool has_next) {
+            const v4d d = {(double)(R.dw.x & 0xFFFFu), (double)(R.dw.x >> 16), (double)(R.dw.y & 0xFFFFu), (double)(R.dw.y >> 16)};
+            v4d w;
+            if constexpr (XS) {  // w = d (v - Rt a1) = fma(d, -Rt a1, x)
                 const v4d x = {(double)(R.xw.x & 0xFFFFu), (double)(R.xw.x >> 16), (double)(R.xw.y & 0xFFFFu), (double)(R.xw.y >> 16)};
-                v4d w;
 #pragma unroll
                 for (int r = 0; r < 4; ++r) w[r] = fma(d[r], e[r], x[r]);
-                v4d en = e_init(Rn);
-#pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    if (r & 1) csm1 = __builtin_amdgcn_mfma_f64_4x4x4f64(a2[r], w[r], csm1, 0, 0, 0);
-                    else csm0 = __builtin_amdgcn_mfma_f64_4x4x4f64(a2[r], w[r], csm0, 0, 0, 0);
-                    if (has_next && r < NKC) en = __builtin_amdgcn_mfma_f64_16x16x4f64(a1n[r], rtop[r], en, 0, 0, 0);
-                }
-                return en;
-            };
-#ifdef DMF_ABLATE_E
-            const double csm = (double)tileX[m16 * kRowD + 4 * q];
-#else
-            Strip sa, sb;
-            load_strip(0, sa);
-            load_strip(1, sb);
-            __builtin_amdgcn_sched_barrier(0);
-            v4d e0 = e_init(sa);
-#pragma unroll
-            for (int kc = 0; kc < NKC; ++kc) e0 = __builtin_amdgcn_mfma_f64_16x16x4f64(a1r[0][kc], rtop[kc], e0, 0, 0, 0);
-            const v4d e1 = run_strip(sa, e0, sb, a1r[1], a2r[0], true);
-            load_strip(2, sa);
-            __builtin_amdgcn_sched_barrier(0);
-            const v4d e2 = run_strip(sb, e1, sa, a1r[2], a2r[1], true);
-            load_strip(3, sb);
-            __builtin_amdgcn_sched_barrier(0);
-            const v4d e3 = run_strip(sa, e2, sb, a1r[3], a2r[2], true);
-            (void)run_strip(sb, e3, sb, a1r[3], a2r[3], false);
-            const double csm = csm0 + csm1;
-#endif
-            // M on the integer matrix cores: digit weights 256^0 .. 256^7 (count digit d + P digit t -> weight t + d)
-            v4i mw[8];
-#pragma unroll
-            for (int w8 = 0; w8 < 8; ++w8) mw[w8] = v4i{0, 0, 0, 0};
-#ifndef DMF_ABLATE_M  // (diagnostic builds of tools/rowpass2_probe.hip leave pieces out to see what they cost)
-            {
-                // A: counts [row m16][samples 16 q .. 16 q + 15] as balanced digits: d + 128 = b0 + 256 b1, digit 0 = b0 - 128
-                // (b0 ^ 0x80 as i8), digit 1 = b1
-                const v4u wa = *reinterpret_cast<const v4u*>(tileD + m16 * kRowD + 16 * q);
-                const v4u wb = *reinterpret_cast<const v4u*>(tileD + m16 * kRowD + 16 * q + 8);
-                const unsigned int e0 = wa.x + 0x00800080u, e1 = wa.y + 0x00800080u, e2 = wa.z + 0x00800080u, e3 = wa.w + 0x00800080u;
-                const unsigned int e4 = wb.x + 0x00800080u, e5 = wb.y + 0x00800080u, e6 = wb.z + 0x00800080u, e7 = wb.w + 0x00800080u;
-                const v4i c0 = {(int)(__builtin_amdgcn_perm(e1, e0, 0x06040200u) ^ 0x80808080u),
-                                (int)(__builtin_amdgcn_perm(e3, e2, 0x06040200u) ^ 0x80808080u),
-                                (int)(__builtin_amdgcn_perm(e5, e4, 0x06040200u) ^ 0x80808080u),
-                                (int)(__builtin_amdgcn_perm(e7, e6, 0x06040200u) ^ 0x80808080u)};
-#pragma unroll
-                for (int t = 0; t < 7; ++t) mw[t] = __builtin_amdgcn_mfma_i32_16x16x64_i8(c0, pdg[t], mw[t], 0, 0, 0);
-                if (nd == 2) {
-                    const v4i c1 = {(int)__builtin_amdgcn_perm(e1, e0, 0x07050301u), (int)__builtin_amdgcn_perm(e3, e2, 0x07050301u),
-                                    (int)__builtin_amdgcn_perm(e5, e4, 0x07050301u), (int)__builtin_amdgcn_perm(e7, e6, 0x07050301u)};
-#pragma unroll
-                    for (int t = 0; t < 7; ++t) mw[t + 1] = __builtin_amdgcn_mfma_i32_16x16x64_i8(c1, pdg[t], mw[t + 1], 0, 0, 0);
-                }
+            } else {
+                w = d * e;
             }
+            v4d en = e_init(Rn);
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                if (r & 1) csm1 = __builtin_amdgcn_mfma_f64_4x4x4f64(a2[r], w[r], csm1, 0, 0, 0);
+                else csm0 = __builtin_amdgcn_mfma_f64_4x4x4f64(a2[r], w[r], csm0, 0, 0, 0);
+                if (has_next && r < NKC) en = __builtin_amdgcn_mfma_f64_16x16x4f64(a1n[r], rtop[r], en, 0, 0, 0);
+            }
+            return en;
+        };
+#ifdef DMF_ABLATE_E
+        const double csm = XS ? (double)tileX[m16 * kRowD + 4 * q] : tileV[m16 * kRowV + 4 * qs];
+#else
+        Strip sa, sb;
+        load_strip(0, sa);
+        load_strip(1, sb);
+        __builtin_amdgcn_sched_barrier(0);
+        v4d e0 = e_init(sa);
+#pragma unroll
+        for (int kc = 0; kc < NKC; ++kc) e0 = __builtin_amdgcn_mfma_f64_16x16x4f64(a1r[0][kc], rtop[kc], e0, 0, 0, 0);
+        const v4d e1 = run_strip(sa, e0, sb, a1r[1], a2r[0], true);
+        load_strip(2, sa);
+        __builtin_amdgcn_sched_barrier(0);
+        const v4d e2 = run_strip(sb, e1, sa, a1r[2], a2r[1], true);
+        load_strip(3, sb);
+        __builtin_amdgcn_sched_barrier(0);
+        const v4d e3 = run_strip(sa, e2, sb, a1r[3], a2r[2], true);
+        (void)run_strip(sb, e3, sb, a1r[3], a2r[3], false);
+        const double csm = csm0 + csm1;
 #endif
-            // lane (pair m16, q) holds rows 4 q + reg: the exact integer sum_w 256^w mw[w] in two halves that fit a double
-            // without rounding (|mw| < 2^21 per digit product sum), one rounding when they are joined
-            double mrow[4];
+        // M on the integer matrix cores: digit weights 256^0 .. 256^7 (count digit d + P digit t -> weight t + d)
+        v4i mw[8];
+#pragma unroll
+        for (int w8 = 0; w8 < 8; ++w8) mw[w8] = v4i{0, 0, 0, 0};
+#ifndef DMF_ABLATE_M  // (diagnostic builds of tools/rowpass2_probe.hip leave pieces out to see what they cost)
+        {
+            // A: counts [row m16][samples 16 q .. 16 q + 15] as balanced digits: d + 128 = b0 + 256 b1, digit 0 = b0 - 128
+            // (b0 ^ 0x80 as i8), digit 1 = b1
+            const v4u wa = *reinterpret_cast<const v4u*>(tileD + m16 * kRowD + 16 * q);
+            const v4u wb = *reinterpret_cast<const v4u*>(tileD + m16 * kRowD + 16 * q + 8);
+            const unsigned int e0 = wa.x + 0x00800080u, e1 = wa.y + 0x00800080u, e2 = wa.z + 0x00800080u, e3 = wa.w + 0x00800080u;
+            const unsigned int e4 = wb.x + 0x00800080u, e5 = wb.y + 0x00800080u, e6 = wb.z + 0x00800080u, e7 = wb.w + 0x00800080u;
+            const v4i c0 = {(int)(__builtin_amdgcn_perm(e1, e0, 0x06040200u) ^ 0x80808080u),
+                            (int)(__builtin_amdgcn_perm(e3, e2, 0x06040200u) ^ 0x80808080u),
+                            (int)(__builtin_amdgcn_perm(e5, e4, 0x06040200u) ^ 0x80808080u),
+                            (int)(__builtin_amdgcn_perm(e7, e6, 0x06040200u) ^ 0x80808080u)};
+#pragma unroll
+            for (int t = 0; t < 7; ++t) mw[t] = __builtin_amdgcn_mfma_i32_16x16x64_i8(c0, pdg[t], mw[t], 0, 0, 0);
+            if (nd == 2) {
+                const v4i c1 = {(int)__builtin_amdgcn_perm(e1, e0, 0x07050301u), (int)__builtin_amdgcn_perm(e3, e2, 0x07050301u),
+                                (int)__builtin_amdgcn_perm(e5, e4, 0x07050301u), (int)__builtin_amdgcn_perm(e7, e6, 0x07050301u)};
+#pragma unroll
+                for (int t = 0; t < 7; ++t) mw[t + 1] = __builtin_amdgcn_mfma_i32_16x16x64_i8(c1, pdg[t], mw[t + 1], 0, 0, 0);
+            }
+        }
+#endif
+        // lane (pair m16, q) holds rows 4 q + reg: the exact integer sum_w 256^w mw[w] in two halves that fit a double
+        // without rounding (|mw| < 2^21 per digit product sum), one rounding when they are joined
+        double mrow[4];
 #ifdef DMF_ABLATE_M
 #pragma unroll
-            for (int rr = 0; rr < 4; ++rr) mrow[rr] = 0.25 * (rr == (m16 & 3));
+        for (int rr = 0; rr < 4; ++rr) mrow[rr] = 0.25 * (rr == (m16 & 3));
 #else
 #pragma unroll
-            for (int rr = 0; rr < 4; ++rr) {
-                const double lo = fma(fma(fma((double)mw[3][rr], 256.0, (double)mw[2][rr]), 256.0, (double)mw[1][rr]), 256.0, (double)mw[0][rr]);
-                const double hi = fma(fma(fma((double)mw[7][rr], 256.0, (double)mw[6][rr]), 256.0, (double)mw[5][rr]), 256.0, (double)mw[4][rr]);
-                mrow[rr] = fma(hi, 0x1p32, lo) * m_scale;
-            }
-#endif
-            DMF2_STAMP(st_a)  // phase A
-            {
-                const size_t so = (size_t)set * MAXW * NV * 16;  // this block's slot set
-                if (q < NU) mine_c[so] = csm;  // c[unknown q][row m16]
-                if (m16 < NP) {  // C layout of the 16x16x64 tile: col = pair m16 = (pj, pl), rows 4 q + reg; M is symmetric
-#pragma unroll
-                    for (int rr = 0; rr < 4; ++rr) mine_m1[so + rr * NU * SLOT] = mrow[rr];
-                    if (pj != pl) {
-#pragma unroll
-                        for (int rr = 0; rr < 4; ++rr) mine_m2[so + rr * NU * SLOT] = mrow[rr];
-                    }
-                }
-            }
-            DMF2_STAMP(st_p)  // partials
-        };
-
-        // ---- phase B of the block at row0 (its partial sums in slot set `set`, its u in ubuf set `set`): row-local inner
-        // iterations, lane = (row, unknown j); c and M pre-scaled by 1 / l_w
-        auto phase_b = [&](int set, int64_t row0, double uu0, double up0) {
-            __builtin_amdgcn_s_setprio(3);  // a dependent chain on the workgroup's critical path
-            DMF2_SUB_BEGIN
-            const bool ok = b_lane && row0 + rl < N;
-            const int lane0 = lane - jb;
-            const int rlc = rl < 16 ? rl : 15;
-            double cj = 0.0, Ms[NU];
-#pragma unroll
-            for (int l = 0; l < NU; ++l) Ms[l] = 0.0;
-            {
-                // this lane's slot of every column group, in column-group order (a fixed summation order); the values
-                // are already c / l_w and -M / l_w
-                const double* __restrict__ slot = red + (size_t)set * MAXW * NV * 16 + (rlc * NU + jb) * SLOT;
-#pragma unroll 1
-                for (int w0 = 0; w0 < MAXW; w0 += 4) {  // (batches of four column groups: registers)
-                    v2d part[4][SLOT / 2];
-#pragma unroll
-                    for (int w = 0; w < 4; ++w)
-#pragma unroll
-                        for (int h = 0; h < SLOT / 2; ++h)
-                            part[w][h] = *reinterpret_cast<const v2d*>(slot + (w0 + w) * NV * 16 + 2 * h);
-#pragma unroll
-                    for (int w = 0; w < 4; ++w) {
-                        cj += part[w][0].x;
-#pragma unroll
-                        for (int l = 0; l < NU; ++l) Ms[l] += (l & 1) ? part[w][(l + 1) / 2].x : part[w][l / 2].y;
-                    }
-                }
-            }
-            double uu = uu0, up = up0;
-            DMF2_SUB(8)
-            // The momentum coefficients ride in a VGPR (lane t holds beta_t) and reach the loop through
-            // v_readlane: an LDS read here would sit on the dependent chain every step.
-            for (int t0 = 0; t0 < n_iter2; t0 += 64) {
-                const int tl = t0 + lane < n_iter2 ? t0 + lane : n_iter2 - 1;
-                const double bvec = beta_tab[tl];  // (lane t: beta_t; the first read goes out with the partial-sum reads)
-                const int b_lo = __double2loint(bvec), b_hi = __double2hiint(bvec);
-                const int t_end = n_iter2 - t0 < 64 ? n_iter2 - t0 : 64;
-                // (u, u_) swap roles every step: written out in pairs so that no register copies sit on the chain
-                // (the loop holds v_readlane, a convergent operation the unroller will not split by itself)
-                if (mode == 1) {
-                    inner_steps<NU, true>(uu, up, cj, Ms, b_lo, b_hi, t_end, lane0);
-                } else {
-                    if (t0 == 0) Ms[0] += 1.0;  // the step's own "+ ut" (deconvolution.py:88), folded into the diagonal
-                    inner_steps<NU, false>(uu, up, cj, Ms, b_lo, b_hi, t_end, lane0);
-                }
-            }
-            DMF2_SUB(9)
-            if (b_lane) ubuf[set * 16 * NU + rl * NU + jb] = ok ? uu : 0.0;  // rows beyond N: phase C multiplies them by zero counts
-            if (ok) {
-                // (buffer stores, like the loads: scalar base of the block + this lane's constant offset)
-                const __amdgpu_buffer_rsrc_t ru = __builtin_amdgcn_make_buffer_rsrc((void*)(u + row0 * NU), 0, span((N - row0) * NU * 8), 0x00020000);
-                const __amdgpu_buffer_rsrc_t rp = __builtin_amdgcn_make_buffer_rsrc((void*)(u_prev + row0 * NU), 0, span((N - row0) * NU * 8), 0x00020000);
-                __builtin_amdgcn_raw_buffer_store_b64(v2u{(unsigned int)__double2loint(uu), (unsigned int)__double2hiint(uu)}, ru, u_off, 0, 0);
-                __builtin_amdgcn_raw_buffer_store_b64(v2u{(unsigned int)__double2loint(up), (unsigned int)__double2hiint(up)}, rp, u_off, 0, 0);
-                u2_acc = fma(uu, uu, u2_acc);
-            }
-            DMF2_SUB(10)
-            __builtin_amdgcn_s_setprio(0);
-        };
-
-        // ---- phase C of the block in tile set `set`, u from ubuf set `set`: b_u[j][s] += sum_rows u[row][j] (d v)[row][s] on
-        // the 4x4x4 (4 blocks) FP64 MFMA: block = sample quad of a 16-sample strip, i = unknown, j = sample in the quad, k = row
-        // in a quad of rows (A[b][i][k] sits at lane 16 k + 4 b + i, B[b][k][j] at lane 16 k + 4 b + j, the result D[b][i][j]
-        // at lane 16 i + 4 b + j: tools/mfma_probe.hip).  k may number the rows of a quad in any order: lane (q, m16) reads
-        // (d v) of row R + c_row(q), sample 16 t + m16 (at its swizzled place) and u of that row, unknown m16 & 3; the 32 tile
-        // reads of the block are independent and go out in two batches (a lane = sample loop with per-row broadcast reads of
-        // u spent ~1.6k cycles per block on LDS round trips).
-        auto phase_c = [&](int set) {
-#ifndef DMF_ABLATE_C
-            const BlockTile T = block_tile(set);
-            const double* __restrict__ const ub = ubuf + set * 16 * NU;
-#pragma unroll
-            for (int half = 0; half < 2; ++half) {
-                double ua[2];
-                unsigned short dd[2][4];  // x
-#pragma unroll
-                for (int rr = 0; rr < 2; ++rr) {
-                    const int row = 2 * half + rr + c_row;
-#pragma unroll
-                    for (int t = 0; t < 4; ++t) {
-                        dd[rr][t] = T.X[row * kRowD + 16 * t + m16];
-                    }
-                    ua[rr] = (m16 & 3) < NU ? ub[row * NU + (m16 & 3)] : 0.0;
-                }
-#pragma unroll
-                for (int rr = 0; rr < 2; ++rr)
-#pragma unroll
-                    for (int t = 0; t < 4; ++t)
-                        bu[t] = __builtin_amdgcn_mfma_f64_4x4x4f64(ua[rr], (double)dd[rr][t], bu[t], 0, 0, 0);
-            }
-#endif
-        };
-
-        // Two blocks per barrier cycle: blocks s and s + 1 run their phases A and C one after the other on every wave,
-        // their phases B at the same time on waves s % NW and (s + 1) % NW (different waves for NW >= 2, so different
-        // SIMDs).  Each block keeps its own tile, slot and ubuf set, the wave and the order of every sum stay those of the
-        // one-block loop (phase C adds block s before block s + 1), so the results are the same bit for bit.  A workgroup
-        // with an odd number of blocks runs its last one alone.
-        for (int s = 0; s < nk; s += 2) {
-            const bool has2 = s + 1 < nk;
-            const int64_t blk = blockIdx.x + (int64_t)s * gridDim.x;
-            __builtin_amdgcn_s_setprio(1);
-            tile_store(0);
-            if (has2) tile_store(1);
-            const int bset = pair_set(s);
-            const bool my_turn = bset == 1 || wave == s % NW;
-            const double uu0 = pu;  // (this wave's own block of the pair)
-            const double up0 = pup;
-            __builtin_amdgcn_wave_barrier();
-            __builtin_amdgcn_s_setprio(0);
-            DMF2_STAMP(0)  // tile stores
-            phase_a(0, 1, 2);
-            if (has2) phase_a(1, 11, 12);
-            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-            __builtin_amdgcn_s_barrier();  // ---- barrier X
-            DMF2_STAMP(3)  // wait X
-#ifndef DMF_V2_NO_STAGGER
-            if (!my_turn) __builtin_amdgcn_s_sleep(DMF_V2_STAGGER);
-#endif
-            if (s + 2 < nk) {
-                const int64_t nb = blk + 2 * (int64_t)gridDim.x;
-                prefetch_u(nb + (int64_t)pair_set(s + 2) * gridDim.x);
-                prefetch_tile(nb, 0);
-                if (s + 3 < nk) prefetch_tile(nb + gridDim.x, 1);
-            }
-            DMF2_STAMP(7)  // prefetch issue
-            if (my_turn) phase_b(bset, (blk + (int64_t)bset * gridDim.x) * 16, uu0, up0);
-            DMF2_STAMP(4)  // phase B (or nothing)
-            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-            __builtin_amdgcn_s_barrier();  // ---- barrier Y
-            DMF2_STAMP(5)  // wait Y
-            phase_c(0);
-            DMF2_STAMP(6)  // phase C, block s
-            if (has2) phase_c(1);
-            __builtin_amdgcn_s_setprio(0);
-            DMF2_STAMP(13)  // phase C, block s + 1
+        for (int rr = 0; rr < 4; ++rr) {
+            const double lo = fma(fma(fma((double)mw[3][rr], 256.0, (double)mw[2][rr]), 256.0, (double)mw[1][rr]), 256.0, (double)mw[0][rr]);
+            const double hi = fma(fma(fma((double)mw[7][rr], 256.0, (double)mw[6][rr]), 256.0, (double)mw[5][rr]), 256.0, (double)mw[4][rr]);
+            mrow[rr] = fma(hi, 0x1p32, lo) * m_scale;
         }
+#endif
+        DMF2_STAMP(st_a)  // phase A
+        {
+            const size_t so = (size_t)set * MAXW * NV * 16;  // this block's slot set
+            if (q < NU) mine_c[so] = csm;  // c[unknown q][row m16]
+            if (m16 < NP) {  // C layout of the 16x16x64 tile: col = pair m16 = (pj, pl), rows 4 q + reg; M is symmetric
+#pragma unroll
+                for (int rr = 0; rr < 4; ++rr) mine_m1[so + rr * NU * SLOT] = mrow[rr];
+                if (pj != pl) {
+#pragma unroll
+                    for (int rr = 0; rr < 4; ++rr) mine_m2[so + rr * NU * SLOT] = mrow[rr];
+                }
+            }
+        }
+        DMF2_STAMP(st_p)  // partials
+    };
+
+    // ---- phase B of the block at row0 (its partial sums in slot set `set`, its u in ubuf set `set`): row-local inner
+    // iterations, lane = (row, unknown j); c and M pre-scaled by 1 / l_w
+    auto phase_b = [&](int set, int64_t row0, double uu0, double up0) {
+        __builtin_amdgcn_s_setprio(3);  // a dependent chain on the workgroup's critical path
+        DMF2_SUB_BEGIN
+        const bool ok = b_lane && row0 + rl < N;
+        const int lane0 = lane - jb;
+        const int rlc = rl < 16 ? rl : 15;
+        double cj = 0.0, Ms[NU];
+#pragma unroll
+        for (int l = 0; l < NU; ++l) Ms[l] = 0.0;
+        {
+            // this lane's slot of every column group, in column-group order (a fixed summation order); the values
+            // are already c / l_w and -M / l_w
+            const double* __restrict__ slot = red + (size_t)set * MAXW * NV * 16 + (rlc * NU + jb) * SLOT;
+#pragma unroll 1
+            for (int w0 = 0; w0 < MAXW; w0 += 4) {  // (batches of four column groups: registers)
+                v2d part[4][SLOT / 2];
+#pragma unroll
+                for (int w = 0; w < 4; ++w)
+#pragma unroll
+                    for (int h = 0; h < SLOT / 2; ++h)
+                        part[w][h] = *reinterpret_cast<const v2d*>(slot + (w0 + w) * NV * 16 + 2 * h);
+#pragma unroll
+                for (int w = 0; w < 4; ++w) {
+                    cj += part[w][0].x;
+#pragma unroll
+                    for (int l = 0; l < NU; ++l) Ms[l] += (l & 1) ? part[w][(l + 1) / 2].x : part[w][l / 2].y;
+                }
+            }
+        }
+        double uu = uu0, up = up0;
+        DMF2_SUB(8)
+        // The momentum coefficients ride in a VGPR (lane t holds beta_t) and reach the loop through
+        // v_readlane: an LDS read here would sit on the dependent chain every step.
+        for (int t0 = 0; t0 < n_iter2; t0 += 64) {
+            const int tl = t0 + lane < n_iter2 ? t0 + lane : n_iter2 - 1;
+            const double bvec = beta_tab[tl];  // (lane t: beta_t; the first read goes out with the partial-sum reads)
+            const int b_lo = __double2loint(bvec), b_hi = __double2hiint(bvec);
+            const int t_end = n_iter2 - t0 < 64 ? n_iter2 - t0 : 64;
+            // (u, u_) swap roles every step: written out in pairs so that no register copies sit on the chain
+            // (the loop holds v_readlane, a convergent operation the unroller will not split by itself)
+            if (mode == 1) {
+                inner_steps<NU, true>(uu, up, cj, Ms, b_lo, b_hi, t_end, lane0);
+            } else {
+                if (t0 == 0) Ms[0] += 1.0;  // the step's own "+ ut" (deconvolution.py:88), folded into the diagonal
+                inner_steps<NU, false>(uu, up, cj, Ms, b_lo, b_hi, t_end, lane0);
+            }
+        }
+        DMF2_SUB(9)
+        if (b_lane) ubuf[set * 16 * NU + rl * NU + jb] = ok ? uu : 0.0;  // rows beyond N: phase C multiplies them by zero counts
+        if (ok) {
+            // (buffer stores, like the loads: scalar base of the block + this lane's constant offset)
+            const __amdgpu_buffer_rsrc_t ru = __builtin_amdgcn_make_buffer_rsrc((void*)(u + row0 * NU), 0, span((N - row0) * NU * 8), 0x00020000);
+            const __amdgpu_buffer_rsrc_t rp = __builtin_amdgcn_make_buffer_rsrc((void*)(u_prev + row0 * NU), 0, span((N - row0) * NU * 8), 0x00020000);
+            __builtin_amdgcn_raw_buffer_store_b64(v2u{(unsigned int)__double2loint(uu), (unsigned int)__double2hiint(uu)}, ru, u_off, 0, 0);
+            __builtin_amdgcn_raw_buffer_store_b64(v2u{(unsigned int)__double2loint(up), (unsigned int)__double2hiint(up)}, rp, u_off, 0, 0);
+            u2_acc = fma(uu, uu, u2_acc);
+        }
+        DMF2_SUB(10)
+        __builtin_amdgcn_s_setprio(0);
+    };
+
+    // ---- phase C of the block in tile set `set`, u from ubuf set `set`: b_u[j][s] += sum_rows u[row][j] (d v)[row][s] on
+    // the 4x4x4 (4 blocks) FP64 MFMA: block = sample quad of a 16-sample strip, i = unknown, j = sample in the quad, k = row
+    // in a quad of rows (A[b][i][k] sits at lane 16 k + 4 b + i, B[b][k][j] at lane 16 k + 4 b + j, the result D[b][i][j]
+    // at lane 16 i + 4 b + j: tools/mfma_probe.hip).  k may number the rows of a quad in any order: lane (q, m16) reads
+    // (d v) of row R + c_row(q), sample 16 t + m16 (at its swizzled place) and u of that row, unknown m16 & 3; the 32 tile
+    // reads of the block are independent and go out in two batches (a lane = sample loop with per-row broadcast reads of
+    // u spent ~1.6k cycles per block on LDS round trips).
+    auto phase_c = [&](int set) {
+#ifndef DMF_ABLATE_C
+        const BlockTile T = block_tile(set);
+        const double* __restrict__ const ub = ubuf + set * 16 * NU;
+#pragma unroll
+        for (int half = 0; half < 2; ++half) {
+            double vv[2][4], ua[2];
+            unsigned short dd[2][4];  // (XS: x)
+#pragma unroll
+            for (int rr = 0; rr < 2; ++rr) {
+                const int row = 2 * half + rr + c_row;
+#pragma unroll
+                for (int t = 0; t < 4; ++t) {
+                    if constexpr (XS) {
+                        dd[rr][t] = T.X[row * kRowD + 16 * t + m16];
+                    } else {
+                        vv[rr][t] = T.V[row * kRowV + 16 * t + mC];
+                        dd[rr][t] = T.D[row * kRowD + 16 * t + m16];
+                    }
+                }
+                ua[rr] = (m16 & 3) < NU ? ub[row * NU + (m16 & 3)] : 0.0;
+            }
+#pragma unroll
+            for (int rr = 0; rr < 2; ++rr)
+#pragma unroll
+                for (int t = 0; t < 4; ++t)
+                    bu[t] = __builtin_amdgcn_mfma_f64_4x4x4f64(ua[rr], XS ? (double)dd[rr][t] : (double)dd[rr][t] * vv[rr][t], bu[t], 0, 0, 0);
+        }
+#endif
+    };
+
+    // The block loop: NSET blocks per barrier cycle.  One block (NSET = 1): its phase B runs on wave s % NW while the
+    // other waves wait at barrier Y.  A pair (NSET = 2): blocks s and s + 1 run their phases A and C one after the other
+    // on every wave, their phases B at the same time on waves s % NW and (s + 1) % NW (different waves for NW >= 2, so
+    // different SIMDs).  Each block keeps its own tile, slot and ubuf set, the wave and the order of every sum stay those
+    // of one block at a time (phase C adds block s before block s + 1), so the results are the same bit for bit.  A
+    // workgroup with an odd number of blocks runs its last one alone.
+    for (int s = 0; s < nk; s += NSET) {
+        const bool has2 = PAIR && s + 1 < nk;
+        const int64_t blk = blockIdx.x + (int64_t)s * gridDim.x;
+        __builtin_amdgcn_s_setprio(1);
+        tile_store(0);
+        if (has2) tile_store(1);
+        const int bset = pair_set(s);
+        const bool my_turn = bset == 1 || wave == s % NW;
+        // the u / u_ of this wave's own block arrived with the tiles (the next prefetch reuses pu / pup before phase B runs)
+        const double uu0 = pu;
+        const double up0 = pup;
+        __builtin_amdgcn_wave_barrier();
+        __builtin_amdgcn_s_setprio(0);
+        DMF2_STAMP(0)  // tile stores (vmcnt wait for the prefetch)
+        phase_a(0, 1, 2);
+        if (has2) phase_a(1, 11, 12);
+        // (a bare barrier behind an LDS-only wait: __syncthreads() would also drain vmcnt)
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+        __builtin_amdgcn_s_barrier();  // ---- barrier X
+        DMF2_STAMP(3)  // wait X
+        // The next cycle's global loads (their staging registers were free during phase A).  42 KB of loads take the CU's
+        // one address unit ~700 cycles when a workgroup's waves issue them together: the waves that run phase B go
+        // first, the others -- who wait for phase B anyway -- a little later.  (ONE place for all waves: with the loads in
+        // two branches the register allocator gave them different destinations and put copies -- and the waits for the
+        // data -- behind one of them.)
+#ifndef DMF_V2_NO_STAGGER
+        if (!my_turn) __builtin_amdgcn_s_sleep(DMF_V2_STAGGER);
+#endif
+        if (s + NSET < nk) {
+            const int64_t nb = blk + NSET * (int64_t)gridDim.x;
+            prefetch_u(nb + (int64_t)pair_set(s + NSET) * gridDim.x);
+            prefetch_tile(nb, 0);
+            if (PAIR && s + 3 < nk) prefetch_tile(nb + gridDim.x, 1);
+        }
+        DMF2_STAMP(7)  // prefetch issue
+        if (my_turn) phase_b(bset, (blk + (int64_t)bset * gridDim.x) * 16, uu0, up0);
+        DMF2_STAMP(4)  // phase B (or nothing)
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+        __builtin_amdgcn_s_barrier();  // ---- barrier Y
+        DMF2_STAMP(5)  // wait Y
+        phase_c(0);
+        DMF2_STAMP(6)  // phase C, block s
+        if (has2) phase_c(1);
+        __builtin_amdgcn_s_setprio(0);
+        DMF2_STAMP(13)  // phase C, block s + 1
+        // (the next cycle's tile stores touch this wave's own tiles only; ubuf and red are rewritten behind the next
+        // barrier X / by phase A after this wave's own phase C)
     }
 
     DMF2_STAMP_FLUSH
@@ -1043,14 +739,30 @@ int rowpass_v2_grid(int64_t N, int S) {
     return (int)(nblk < g ? nblk : g);
 }
 
+namespace {
+// one launch's arguments, as launch_rowpass_v2 receives them, handed down its dispatch on the template parameters
+struct V2Args {
+    const double* V;
+    const unsigned short *D16, *X16;
+    int SD;
+    const double *Rtp, *alpha;
+    double *u, *u_prev;
+    SolverState* state;
+    int64_t N;
+    int S, n_c, n_iter2, mode, nd;
+    double *slab, *u2_partials;
+    int* grid_out;
+    hipStream_t st;
+};
+}  // namespace
+
 template <int NKC, int NU, int MAXW, bool XS, bool PAIR = false>
-static hipError_t launch_v2_t(const double* V, const unsigned short* D16, const unsigned short* X16, int SD, const double* Rtp,
-                              const double* alpha, double* u, double* u_prev, SolverState* state, int64_t N, int S, int n_c,
-                              int n_iter2, int mode, int nd, double* slab, double* u2_partials, int* grid_out, hipStream_t st) {
-    const int NW = (S + 63) / 64;
-    const size_t lds = rowpass_v2_lds_bytes(S, NU, n_iter2, XS, PAIR);
+static hipError_t launch_v2_t(const V2Args& a) {
+    const int NW = (a.S + 63) / 64;
+    const size_t lds = rowpass_v2_lds_bytes(a.S, NU, a.n_iter2, XS, PAIR);
     constexpr size_t kLdsCap = (size_t)(MAXW == 4 ? 80 : 160) * 1024;
-    if (NW > MAXW || (MAXW == 8 && NW <= 4) || (PAIR && NW < 2) || lds > kLdsCap || N < 1 || SD < NW * 64 || (SD & 7) != 0 || nd < 1 || nd > 2)
+    if (NW > MAXW || (MAXW == 8 && NW <= 4) || (PAIR && NW < 2) || lds > kLdsCap || a.N < 1 || a.SD < NW * 64 || (a.SD & 7) != 0 ||
+        a.nd < 1 || a.nd > 2)
         return hipErrorInvalidValue;
     static bool lds_limit_raised[64] = {};
     int dev = 0;
@@ -1061,10 +773,10 @@ static hipError_t launch_v2_t(const double* V, const unsigned short* D16, const 
         if (e != hipSuccess) return e;
         lds_limit_raised[dev] = true;
     }
-    const int grid = rowpass_v2_grid(N, S);
-    *grid_out = grid;
-    hipLaunchKernelGGL((k_rowpass_v2<NKC, NU, MAXW, XS, PAIR>), dim3(grid), dim3(NW * 64), lds, st, V, D16, X16, SD, Rtp, alpha, u, u_prev,
-                       state, N, S, n_c, n_iter2, mode, nd, slab, u2_partials
+    const int grid = rowpass_v2_grid(a.N, a.S);
+    *a.grid_out = grid;
+    hipLaunchKernelGGL((k_rowpass_v2<NKC, NU, MAXW, XS, PAIR>), dim3(grid), dim3(NW * 64), lds, a.st, a.V, a.D16, a.X16, a.SD,
+                       a.Rtp, a.alpha, a.u, a.u_prev, a.state, a.N, a.S, a.n_c, a.n_iter2, a.mode, a.nd, a.slab, a.u2_partials
 #ifdef DMF_STAMPS
                        , (unsigned long long*)nullptr
 #endif
@@ -1073,42 +785,33 @@ static hipError_t launch_v2_t(const double* V, const unsigned short* D16, const 
 }
 
 template <int NKC, bool XS>
-static hipError_t launch_v2_nkc(int n_u, bool pair, const double* V, const unsigned short* D16, const unsigned short* X16,
-                                int SD, const double* Rtp, const double* alpha, double* u, double* u_prev,
-                                SolverState* state, int64_t N, int S, int n_c, int n_iter2, int mode, int nd, double* slab,
-                                double* u2_partials, int* grid_out, bool* paired_out, hipStream_t st) {
-    // the pair schedule where it applies (rowpass_v2_pair_fits), else the one-block loop
-    pair = pair && XS && rowpass_v2_pair_fits(S, n_u, n_iter2);
+static hipError_t launch_v2_nkc(const V2Args& a, int n_u, bool pair, bool* paired_out) {
+    // the pair schedule where it applies (rowpass_v2_pair_fits), else one block per barrier cycle
+    pair = pair && XS && rowpass_v2_pair_fits(a.S, n_u, a.n_iter2);
     if (paired_out != nullptr) *paired_out = pair;
-#define DMF_ARGS V, D16, X16, SD, Rtp, alpha, u, u_prev, state, N, S, n_c, n_iter2, mode, nd, slab, u2_partials, grid_out, st
     switch (n_u) {
 #define DMF_CASE(NU_)                                                                                                   \
     case NU_:                                                                                                           \
-        if (S > 256) return launch_v2_t<NKC, NU_, 8, XS>(DMF_ARGS);                                                     \
+        if (a.S > 256) return launch_v2_t<NKC, NU_, 8, XS>(a);                                                          \
         if constexpr (XS) {                                                                                             \
-            if (pair) return launch_v2_t<NKC, NU_, 4, XS, true>(DMF_ARGS);                                              \
+            if (pair) return launch_v2_t<NKC, NU_, 4, XS, true>(a);                                                     \
         }                                                                                                               \
-        return launch_v2_t<NKC, NU_, 4, XS>(DMF_ARGS);
+        return launch_v2_t<NKC, NU_, 4, XS>(a);
         DMF_CASE(1) DMF_CASE(2) DMF_CASE(3) DMF_CASE(4)
 #undef DMF_CASE
         default: return hipErrorInvalidValue;
     }
-#undef DMF_ARGS
 }
 
 hipError_t launch_rowpass_v2(const double* V, const unsigned short* D16, const unsigned short* X16, int SD,
                              const double* Rtp, const double* alpha, double* u, double* u_prev, SolverState* state, int64_t N,
                              int S, int n_c, int n_u, int n_iter2, int mode, int nd, double* slab, double* u2_partials,
                              int* grid_out, bool pair, bool* paired_out, hipStream_t st) {
+    const V2Args a{V, D16, X16, SD, Rtp, alpha, u, u_prev, state, N, S, n_c, n_iter2, mode, nd, slab, u2_partials, grid_out, st};
     switch ((n_c + 3) / 4) {
 #define DMF_NKC(X)                                                                                                    \
     case X:                                                                                                           \
-        return X16 != nullptr ? launch_v2_nkc<X, true>(n_u, pair, V, D16, X16, SD, Rtp, alpha, u, u_prev, state, N, S, \
-                                                       n_c, n_iter2, mode, nd, slab, u2_partials, grid_out,           \
-                                                       paired_out, st)                                                \
-                              : launch_v2_nkc<X, false>(n_u, pair, V, D16, X16, SD, Rtp, alpha, u, u_prev, state, N, S, \
-                                                        n_c, n_iter2, mode, nd, slab, u2_partials, grid_out,          \
-                                                        paired_out, st);
+        return X16 != nullptr ? launch_v2_nkc<X, true>(a, n_u, pair, paired_out) : launch_v2_nkc<X, false>(a, n_u, pair, paired_out);
         DMF_NKC(0) DMF_NKC(1) DMF_NKC(2) DMF_NKC(3) DMF_NKC(4)
 #undef DMF_NKC
         default: return hipErrorInvalidValue;
