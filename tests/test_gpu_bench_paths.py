@@ -39,17 +39,23 @@ def _oracle(V, D, Rt, n_c, n_u, T1, seed):
     return u0, a0, wu, wa
 
 
-def _solve_at_level(ctx, level, V, D, Rt, u0, a0, mode, T1, expect):
+def _solve_at_level(ctx, level, V, D, Rt, u0, a0, mode, T1, expect, x16=None):
     """(u, alpha, Gram-form cost, direct cost, path) with the kernel selection `level`; the Problem is created under
-    that level because the integer count copies of the second-generation kernels are built at level 0 only."""
+    that level because the integer count copies of the second-generation kernels are built at level 0 only.
+    x16 True / False: the context's X16 switch for this Problem, and the path must / must not carry the " x16 " token
+    (the row pass on the methylated read counts or on V); None leaves the switch alone."""
     from demethify_amd.device import Problem, Solver
 
     ctx.set_generic(level)
+    if x16 is not None:
+        ctx.set_x16(x16)
     try:
         with Problem(ctx, V, D, Rt) as p, Solver(p, u0, a0, mode) as s:
             path = s.describe(20)
             for token in expect:
                 assert token in path, (token, path)
+            if x16 is not None:
+                assert (" x16 " in path) if x16 else ("x16" not in path), path
             it, _ = s.step(T1, 20, 0.0)
             assert it == T1
             u, alpha, cost, _ = s.get()
@@ -57,12 +63,23 @@ def _solve_at_level(ctx, level, V, D, Rt, u0, a0, mode, T1, expect):
             assert direct == p.cost(u, alpha)  # the device-resident and the host-array entry points agree bit for bit
     finally:
         ctx.set_generic(0)
+        ctx.set_x16(True)
     return u, alpha, cost, direct, path
 
 
 @pytest.mark.parametrize("level,kernel", [(0, "k_rowpass_v2"), (4, "k_rowpass_fused")])
 @pytest.mark.parametrize("N,S,n_c,n_u,T1,why", FUSED_CASES)
 def test_fused_instantiations_against_oracle(ctx, N, S, n_c, n_u, T1, why, level, kernel):
+    _fused_case(ctx, N, S, n_c, n_u, T1, why, level, kernel, True if level == 0 else None)
+
+
+@pytest.mark.parametrize("N,S,n_c,n_u,T1,why", FUSED_CASES)
+def test_fused_instantiations_on_v_against_oracle(ctx, N, S, n_c, n_u, T1, why):
+    """Level 0 with the X16 switch off: k_rowpass_v2's V form (what inexact frequencies get)."""
+    _fused_case(ctx, N, S, n_c, n_u, T1, why, 0, "k_rowpass_v2", False)
+
+
+def _fused_case(ctx, N, S, n_c, n_u, T1, why, level, kernel, x16):
     from demethify_amd import _lib as L
 
     V, D, Rt = osol.synthetic_problem(N, S, n_c, n_u, seed=31, depth=40)
@@ -71,7 +88,7 @@ def test_fused_instantiations_against_oracle(ctx, N, S, n_c, n_u, T1, why, level
     expect = [f"rowpass={kernel}<{(n_c + 3) // 4},{n_u}>", f"nw={(S + 63) // 64}", f"tail={N % 16}"]
     if level == 0:
         expect.append("gram=k_gram_i8<nd=1>")
-    u, alpha, cost, direct, _ = _solve_at_level(ctx, level, V, D, Rt if n_c else None, u0, a0, mode, T1, expect)
+    u, alpha, cost, direct, _ = _solve_at_level(ctx, level, V, D, Rt if n_c else None, u0, a0, mode, T1, expect, x16=x16)
     assert rel_err(alpha, wa) < TIGHT and np.abs(alpha - wa).max() < TIGHT, why
     assert np.abs(u - wu).max() < TIGHT, why
     want = osol.weighted_cost(V, np.c_[Rt, wu] if n_c else wu, wa, D)
@@ -96,6 +113,15 @@ V2_CASES = [
 
 @pytest.mark.parametrize("N,S,n_c,n_u,T1,depth,why", V2_CASES)
 def test_second_generation_shapes_against_oracle(ctx, N, S, n_c, n_u, T1, depth, why):
+    _second_generation_case(ctx, N, S, n_c, n_u, T1, depth, why, True)
+
+
+@pytest.mark.parametrize("N,S,n_c,n_u,T1,depth,why", V2_CASES)
+def test_second_generation_shapes_on_v_against_oracle(ctx, N, S, n_c, n_u, T1, depth, why):
+    _second_generation_case(ctx, N, S, n_c, n_u, T1, depth, why, False)
+
+
+def _second_generation_case(ctx, N, S, n_c, n_u, T1, depth, why, x16):
     from demethify_amd import _lib as L
 
     V, D, Rt = osol.synthetic_problem(N, S, n_c, n_u, seed=17, depth=depth)
@@ -105,7 +131,7 @@ def test_second_generation_shapes_against_oracle(ctx, N, S, n_c, n_u, T1, depth,
     mode = L.DMF_MODE_PARTIAL if n_c else L.DMF_MODE_UNSUPERVISED
     nd = 1 if D.max() <= 127 else 2
     u, alpha, cost, direct, _ = _solve_at_level(ctx, 0, V, D, Rt if n_c else None, u0, a0, mode, T1,
-                                                ["rowpass=k_rowpass_v2<", f"gram=k_gram_i8<nd={nd}>"])
+                                                ["rowpass=k_rowpass_v2<", f"gram=k_gram_i8<nd={nd}>"], x16=x16)
     assert rel_err(alpha, wa) < TIGHT and np.abs(alpha - wa).max() < TIGHT, why
     assert np.abs(u - wu).max() < TIGHT, why
     want = osol.weighted_cost(V, np.c_[Rt, wu] if n_c else wu, wa, D)
@@ -218,6 +244,22 @@ def test_in_launch_hand_overs_are_race_free(ctx, N, S, n_c, n_u, depth):
     its own now (k_gram_v2_finish).  The sums involved are exact integers or fixed-order f64 sums, so every repetition of
     a solve must give the SAME BITS; a missed or late contribution (seen once with no-return atomics: 1e-5 relative, one
     run in three) shows up as a difference."""
+    _same_bits_every_time(ctx, N, S, n_c, n_u, depth, None, [])
+
+
+@pytest.mark.parametrize("N,S,n_c,n_u,depth,x16,expect", [
+    (16 * (2048 * 2 + 5) + 3, 64, 6, 2, 40, False, ["k_rowpass_v2<2,2> nw=1 "]),       # 2..3 blocks per workgroup
+    (16 * (512 * 3 + 1) + 5, 256, 12, 4, 60, False, ["k_rowpass_v2<3,4> nw=4 "]),      # 3..4 blocks per workgroup
+    (16 * (256 * 3 + 1) + 9, 448, 12, 4, 40, False, ["k_rowpass_v2<3,4> nw=7 "]),      # eight-wave V form, 3..4 blocks
+    (16 * (256 * 3 + 1) + 9, 448, 12, 4, 40, True, ["k_rowpass_v2<3,4> nw=7 "]),       # eight-wave X16 form
+])
+def test_row_pass_forms_are_race_free(ctx, N, S, n_c, n_u, depth, x16, expect):
+    """The same on the V form and at eight waves, with workgroups that run several blocks: a barrier missing from the
+    row pass's block loop (tile store, phases A / B / C) shows up as different bits between repetitions."""
+    _same_bits_every_time(ctx, N, S, n_c, n_u, depth, x16, expect)
+
+
+def _same_bits_every_time(ctx, N, S, n_c, n_u, depth, x16, expect):
     from demethify_amd import _lib as L
     from demethify_amd.device import Problem, Solver
 
@@ -226,18 +268,28 @@ def test_in_launch_hand_overs_are_race_free(ctx, N, S, n_c, n_u, depth):
     u0 = rng.uniform(size=(N, n_u))
     a0 = rng.dirichlet(np.ones(n_c + n_u), S).T.copy()
     first = None
-    with Problem(ctx, V, D, Rt) as p:
-        for rep in range(40):
-            with Solver(p, u0, a0, L.DMF_MODE_PARTIAL) as s:
-                assert "gram=k_gram_i8" in s.describe(20)
-                s.step(4, 20, 0.0)
-                u, alpha, cost, _ = s.get()
-            if first is None:
-                first = (u, alpha, cost)
-            else:
-                assert cost == first[2], rep
-                np.testing.assert_array_equal(alpha, first[1], err_msg=f"repetition {rep}")
-                np.testing.assert_array_equal(u, first[0], err_msg=f"repetition {rep}")
+    if x16 is not None:
+        ctx.set_x16(x16)
+    try:
+        with Problem(ctx, V, D, Rt) as p:
+            for rep in range(40):
+                with Solver(p, u0, a0, L.DMF_MODE_PARTIAL) as s:
+                    path = s.describe(20)
+                    assert "gram=k_gram_i8" in path
+                    for token in expect:
+                        assert token in path, (token, path)
+                    if x16 is not None:
+                        assert (" x16 " in path) if x16 else ("x16" not in path), path
+                    s.step(4, 20, 0.0)
+                    u, alpha, cost, _ = s.get()
+                if first is None:
+                    first = (u, alpha, cost)
+                else:
+                    assert cost == first[2], rep
+                    np.testing.assert_array_equal(alpha, first[1], err_msg=f"repetition {rep}")
+                    np.testing.assert_array_equal(u, first[0], err_msg=f"repetition {rep}")
+    finally:
+        ctx.set_x16(True)
 
 
 @pytest.mark.parametrize("N,S,n_c,n_u,depth,expect", [

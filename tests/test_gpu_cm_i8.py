@@ -163,6 +163,16 @@ ODD_S_CASES = [
 
 @pytest.mark.parametrize("N,S,n_c,n_u,T1,depth,expect,why", ODD_S_CASES)
 def test_odd_sample_counts_against_oracle(ctx, N, S, n_c, n_u, T1, depth, expect, why):
+    _odd_s_case(ctx, N, S, n_c, n_u, T1, depth, expect, why, True if "k_rowpass_v2" in expect[0] else None)
+
+
+@pytest.mark.parametrize("N,S,n_c,n_u,T1,depth,expect,why", [c for c in ODD_S_CASES if "k_rowpass_v2" in c[6][0]])
+def test_odd_sample_counts_on_v_against_oracle(ctx, N, S, n_c, n_u, T1, depth, expect, why):
+    """The k_rowpass_v2 rows with the X16 switch off: the row pass's V form."""
+    _odd_s_case(ctx, N, S, n_c, n_u, T1, depth, expect, why, False)
+
+
+def _odd_s_case(ctx, N, S, n_c, n_u, T1, depth, expect, why, x16):
     from demethify_amd import _lib as L
 
     V, D, Rt = osol.synthetic_problem(N, S, n_c, n_u, seed=37, depth=depth)
@@ -170,7 +180,7 @@ def test_odd_sample_counts_against_oracle(ctx, N, S, n_c, n_u, T1, depth, expect
     V = np.where(D == 0, 0.0, V)
     u0, a0, wu, wa = _oracle(V, D, Rt, n_c, n_u, T1, seed=6)
     mode = L.DMF_MODE_PARTIAL if n_c else L.DMF_MODE_UNSUPERVISED
-    u, alpha, cost, direct, _ = _solve_at_level(ctx, 0, V, D, Rt if n_c else None, u0, a0, mode, T1, expect)
+    u, alpha, cost, direct, _ = _solve_at_level(ctx, 0, V, D, Rt if n_c else None, u0, a0, mode, T1, expect, x16=x16)
     assert rel_err(alpha, wa) < TIGHT and np.abs(alpha - wa).max() < TIGHT, why
     assert np.abs(u - wu).max() < TIGHT, why
     want = osol.weighted_cost(V, np.c_[Rt, wu] if n_c else wu, wa, D)

@@ -33,3 +33,14 @@ def test_random_many_known_types_against_oracle():
                           capture_output=True, text=True, timeout=900)
     assert proc.returncode == 0 and "MISMATCH" not in proc.stdout, (proc.stdout[-3000:], proc.stderr[-2000:])
     assert "50 cases" in proc.stdout and "k_cm_i8" in proc.stdout
+
+
+def test_random_shapes_on_v_against_oracle():
+    """... and with two-decimal frequencies, round(100 x / d, 2) / 100: no exact x / d, so no methylated read counts,
+    and the row pass runs on V (its V form, mostly 1..4 unknowns up to 512 samples)."""
+    proc = subprocess.run([sys.executable, str(ROOT / "tools" / "fuzz_parity.py"), "60", "11", "v"], cwd=ROOT,
+                          capture_output=True, text=True, timeout=900)
+    assert proc.returncode == 0 and "MISMATCH" not in proc.stdout, (proc.stdout[-3000:], proc.stderr[-2000:])
+    assert "60 cases" in proc.stdout
+    summary = proc.stdout.split(" cases, worst ")[1]
+    assert "rowpass=k_rowpass_v2 gram=" in summary and "x16" not in summary, summary

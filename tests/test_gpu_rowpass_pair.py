@@ -18,11 +18,15 @@ pytestmark = pytest.mark.gpu
 TIGHT = 1e-8  # oracle parity, as in tests/test_gpu_bench_paths.py
 
 
-def _run(ctx, V, D, Rt, u0, a0, n_iter2, n_calls, pair):
+def _run(ctx, V, D, Rt, u0, a0, n_iter2, n_calls, pair, x16=True):
+    """(describe, the get() trail of n_calls one-iteration steps, direct_cost(), rowpass_launches()) with the context's
+    pair and X16 switches set before the Problem is created (X16 is built, or not, at creation); both are reset after.
+    Shared with tests/test_gpu_rowpass_forms.py."""
     from demethify_amd import _lib as L
     from demethify_amd.device import Problem, Solver
 
     mode = L.DMF_MODE_PARTIAL if Rt is not None else L.DMF_MODE_UNSUPERVISED
+    ctx.set_x16(x16)
     ctx.set_rowpass_pair(pair)
     try:
         with Problem(ctx, V, D, Rt) as p, Solver(p, u0, a0, mode) as s:
@@ -34,6 +38,7 @@ def _run(ctx, V, D, Rt, u0, a0, n_iter2, n_calls, pair):
             return desc, trail, s.direct_cost(), s.rowpass_launches()
     finally:
         ctx.set_rowpass_pair(True)
+        ctx.set_x16(True)
 
 
 def _problem(N, S, n_c, n_u, depth, seed=0):

@@ -1,6 +1,10 @@
 """Randomised differential run: the device solver against the CPU oracle on random small shapes (kernel selection level 0),
 including ragged sample counts, partial last blocks, zero-coverage cells, one and two count digits, wide and narrow
-reference blocks.   python tools/fuzz_parity.py [cases] [seed] [wide|many]"""
+reference blocks.   python tools/fuzz_parity.py [cases] [seed] [wide|many|v]
+
+v: frequencies as a two-decimal bedMethyl file prints them, round(100 x / d, 2) / 100, which are not exact x / d: the
+problem keeps no methylated read counts (X16) and the row pass runs on V; biased towards the row pass's 1..4 unknowns and
+up to 512 samples."""
 import sys
 import time
 from pathlib import Path
@@ -16,6 +20,7 @@ n_cases = int(sys.argv[1]) if len(sys.argv) > 1 else 100
 rng = np.random.RandomState(int(sys.argv[2]) if len(sys.argv) > 2 else 0)
 many = len(sys.argv) > 3 and sys.argv[3] == "many"  # bias towards 17..48 known types
 wide = len(sys.argv) > 3 and sys.argv[3] in ("wide", "many")  # bias towards 5..16 unknowns on shapes k_cm_i8 / k_inner_bu take
+vform = len(sys.argv) > 3 and sys.argv[3] == "v"  # two-decimal frequencies: k_rowpass_v2 on V instead of X16
 ctx = Context(0)
 worst, t0, paths = 0.0, time.time(), {}
 for case in range(n_cases):
@@ -32,10 +37,17 @@ for case in range(n_cases):
     n_u = min(n_u, 64 - n_c)
     depth = int(rng.choice([5, 40, 120, 900, 20000]))
     T1 = int(rng.randint(1, 4))
+    if vform:
+        if rng.rand() < 0.7:
+            n_u = int(rng.randint(1, 5))
+        if rng.rand() < 0.3:
+            S = int(rng.randint(257, 513))  # the row pass's eight-wave forms
     V, D, Rt = osol.synthetic_problem(N, S, max(n_c, 1), n_u, seed=int(rng.randint(1 << 30)), depth=depth)
     if rng.rand() < 0.5:
         D[:: int(rng.randint(2, 9)), :: int(rng.randint(1, 5))] = 0
         V = np.where(D == 0, 0.0, V)
+    if vform:
+        V = np.round(100.0 * np.rint(V * D) / np.maximum(D, 1), 2) / 100.0
     Rt = Rt[:, :n_c] if n_c else None
     rs = np.random.RandomState(case)
     u0 = rs.uniform(size=(N, n_u))
