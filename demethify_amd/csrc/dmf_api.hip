@@ -1566,7 +1566,8 @@ int dmf_select_describe(int64_t N, int64_t S, int64_t n_c, int64_t n_u, int nd, 
     key.S = (int)S;
     key.n_c = (int)n_c;
     key.n_u = (int)n_u;
-    key.nd = (S <= 2048) ? nd : 0;  // (dmf_problem_create builds no integer copies beyond 2048 samples)
+    // (dmf_problem_create builds no integer copies for one sample, beyond 2048 samples or beyond 48 known types)
+    key.nd = (S >= 2 && S <= 2048 && n_c <= 48) ? nd : 0;
     key.SD = key.nd > 0 ? (int)((S + 63) / 64 * 64) : 0;
     key.level = level;
     key.d_f32_exact = (flags & DMF_SELECT_COUNTS_F32_EXACT) != 0;

@@ -1,7 +1,8 @@
 // Per-row c_i / M_i of the split u phase for wide row groups (5 <= n_u <= 16), gfx950:
 //     c_i = alpha_unk (d_i * (v_i - Rt_i alpha_known))^T       FP64 matrix cores (as dmf_kernels_rowpass_mfma.hip)
 //     M_i[pair (j,l)] = sum_s (alpha_js alpha_ls) d_is          INTEGER matrix cores, exactly (as dmf_kernels_rowpass2.hip):
-// the counts are one or two balanced 8-bit digits, P = alpha_j alpha_l in [0, 1] seven digits of rint(P 2^52)
+// the counts are one or two balanced 8-bit digits, P = alpha_j alpha_l in [0, 1] seven digits of rint(P 2^52), each
+// alpha row scaled by a power of two first (esc[] below)
 // (dmf_fixedpoint.h); one v_mfma_i32_16x16x64_i8 per digit covers 16 rows x 64 samples x 16 pairs.  With n_u unknowns
 // there are n_u (n_u + 1) / 2 pairs (78 at 12): on the FP64 cores that product is 64 cycles per 16 x 4 x 16 piece and
 // was nine tenths of k_u_phase_mfma / k_u_phase_big; here it is 16 cycles per 16 x 64 x 16 piece and digit.
@@ -50,7 +51,8 @@ __host__ __device__ inline CmLayout cm_layout(int S, int n_c, int n_u, int n_til
     L.AS = 64 * ncg + 4;
     L.n_rows = (n_c + 3) / 4 * 4 + n_u;
     L.pd_dwords4 = ncg * nmt * 7 * 64;
-    L.bytes = (size_t)L.pd_dwords4 * 16 + (size_t)L.n_rows * L.AS * sizeof(double);
+    // (+ one binary exponent per unknown: the scale of its alpha row in the P digits, see k_cm_i8)
+    L.bytes = (size_t)L.pd_dwords4 * 16 + (size_t)L.n_rows * L.AS * sizeof(double) + 32 * sizeof(int);
     return L;
 }
 
@@ -83,6 +85,7 @@ __global__ __launch_bounds__(512) void k_cm_i8(const double* __restrict__ V, con
     v4i* __restrict__ pd = reinterpret_cast<v4i*>(lds_raw);
     double* __restrict__ alds = reinterpret_cast<double*>(lds_raw + (size_t)L.pd_dwords4 * 16);
     const int AS = L.AS;
+    int* __restrict__ esc = reinterpret_cast<int*>(alds + (size_t)L.n_rows * AS);
 
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int lane = threadIdx.x & 63;
@@ -99,6 +102,22 @@ __global__ __launch_bounds__(512) void k_cm_i8(const double* __restrict__ V, con
         }
         alds[i] = val;
     }
+    // Scale of the P digits.  rint(P 2^52) is an ABSOLUTE 2^-53: with many types alpha_j alpha_l is small (1/64^2 at
+    // K = 64) and the digits would hold it to 1e-13 .. 1e-12 of its value only -- a fixed perturbation of M_i that a
+    // problem with more unknowns than samples (u not identified) integrates over its momentum steps: 5e-8 in u after
+    // 2 x 500 of them at 40+24 types and 3 samples.  So every alpha row enters the digits times 2^esc[j], the power of two
+    // that puts the row's largest entry of this panel into [1/2, 1] (exact), and M_i leaves them times 2^-(esc[j] + esc[l]).
+    __syncthreads();
+    for (int j = wave; j < n_u; j += kCmWaves) {
+        double mx = 0.0;
+        for (int c = lane; c < Sp; c += 64) mx = fmax(mx, alds[(nct + j) * AS + c]);
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1) mx = fmax(mx, __shfl_xor(mx, off, 64));
+        int x = 0;
+        if (mx > 0.0) (void)frexp(mx, &x);  // mx = f 2^x, 1/2 <= f < 1
+        if (lane == 0) esc[j] = x < 0 ? (-x < 200 ? -x : 200) : 0;
+    }
+    __syncthreads();
     // P digits: item (column group, pair tile) per wave; lane (pair m16, q), register g = strip, byte i:
     // sample 64 cg + 16 g + 4 q + i  (the k order in which the row loop packs the counts)
     for (int item = wave; item < ncg * ntl; item += kCmWaves) {
@@ -108,6 +127,7 @@ __global__ __launch_bounds__(512) void k_cm_i8(const double* __restrict__ V, con
         while ((pl + 1) * (pl + 2) / 2 <= p) ++pl;
         const int pj = p - pl * (pl + 1) / 2;
         const bool pair_ok = p < NP;
+        const int ej = pair_ok ? esc[pj] : 0, el = pair_ok ? esc[pl] : 0;
         v4i dg[7];
 #pragma unroll
         for (int g = 0; g < 4; ++g) {
@@ -118,7 +138,7 @@ __global__ __launch_bounds__(512) void k_cm_i8(const double* __restrict__ V, con
                 const bool in = pair_ok && col < Sp;
                 const double aj = in ? alpha[(int64_t)(n_c + pj) * S + col0 + col] : 0.0;
                 const double al = in ? alpha[(int64_t)(n_c + pl) * S + col0 + col] : 0.0;
-                z_to_biased(aj, al, lo[i], hi[i]);
+                z_to_biased(ldexp(aj, ej), ldexp(al, el), lo[i], hi[i]);
             }
             transpose4(lo, tl);
             transpose4(hi, th);
@@ -303,6 +323,12 @@ __global__ __launch_bounds__(512) void k_cm_i8(const double* __restrict__ V, con
         constexpr int HJ = NCGX <= 2 ? 2 : 1;
         for (int mt = mt0; mt < mt1; ++mt) {
             const int p = mt * 16 + m16;
+            int m_exp = -52;  // 2^-52 of the digits and the pair's own scale
+            if (p < NP) {
+                int pl = 0;
+                while ((pl + 1) * (pl + 2) / 2 <= p) ++pl;
+                m_exp -= esc[p - pl * (pl + 1) / 2] + esc[pl];
+            }
 #pragma unroll
             for (int h0 = 0; h0 < 2; h0 += HJ) {
                 v4i acc[HJ][NWT];
@@ -337,7 +363,7 @@ __global__ __launch_bounds__(512) void k_cm_i8(const double* __restrict__ V, con
                                               256.0, (double)acc[h][0][rr]);
                         double hi = fma(fma((double)acc[h][6][rr], 256.0, (double)acc[h][5][rr]), 256.0, (double)acc[h][4][rr]);
                         if constexpr (ND == 2) hi = fma((double)acc[h][7][rr], 16777216.0, hi);
-                        const double m = fma(hi, 0x1p32, lo) * 0x1p-52;
+                        const double m = ldexp(fma(hi, 0x1p32, lo), m_exp);
                         const int64_t row = row00 + 16 * (h0 + h) + 4 * q + rr;
                         if (p < NP && row < N) {
                             double* __restrict__ dst = cm_out + row * NV + n_u + p;

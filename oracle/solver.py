@@ -381,8 +381,48 @@ def frank_wolfe_alpha(W1, W2, V, alpha1, alpha2, purity, max_iter, D):
     return alpha1, alpha2
 
 
-def solve_partial_purity(u, R, alpha, V, D, Rt, n_u, purity, n_iter1=100, n_iter2=500, tol=1e-3, trace=None):
-    """demethify/deconvolution.py:306-337 (`mdwbssmf_deconv_p`)."""
+def _relative_argmin_gaps(grad, scale):
+    """Per column: (second-smallest - smallest entry of grad) / scale; +inf for a block of one row."""
+    if grad.shape[0] < 2:
+        return np.full(grad.shape[1], np.inf)
+    two = np.partition(grad, 1, axis=0)[:2]
+    return (two[1] - two[0]) / scale
+
+
+def frank_wolfe_alpha_gaps(W1, W2, V, alpha1, alpha2, purity, max_iter, D, dtype=np.float64):
+    """frank_wolfe_alpha with the arithmetic carried in ``dtype`` and a record of how decided every argmin was.
+
+    Same formulas in the same order (gradients as -W^T (D * (V - W a)), :283-290).  The vertex masses ``purity`` and
+    ``1 - purity`` are taken in f64 as the reference takes them, then widened.  Returns (alpha1, alpha2, gap): gap is the
+    smallest, over the iterations, the columns and the blocks of at least two rows, of the distance between the smallest
+    and the second-smallest gradient entry of a block, relative to scale_s = max_k (W^T (D * V))_ks.  With
+    dtype=np.float64 alpha1 and alpha2 are frank_wolfe_alpha's bit for bit."""
+    purity = np.asarray(purity, dtype=np.float64)
+    m1, m2 = purity.astype(dtype), (1 - purity).astype(dtype)
+    W1, W2, V, D = (np.asarray(x).astype(dtype) for x in (W1, W2, V, D))
+    alpha1, alpha2 = alpha1.astype(dtype), alpha2.astype(dtype)
+    cols = np.arange(alpha1.shape[1])
+    DV = D * V
+    scale = np.maximum((W1.T @ DV).max(axis=0), (W2.T @ DV).max(axis=0))
+    gap = np.inf
+    for k in range(max_iter):
+        resid = D * (V - W1 @ alpha1 - W2 @ alpha2)
+        grad1 = -W1.T @ resid
+        grad2 = -W2.T @ resid
+        gap = min(gap, float(_relative_argmin_gaps(grad1, scale).min()), float(_relative_argmin_gaps(grad2, scale).min()))
+        s1 = np.zeros_like(alpha1)
+        s2 = np.zeros_like(alpha2)
+        s1[np.argmin(grad1, axis=0), cols] = m1
+        s2[np.argmin(grad2, axis=0), cols] = m2
+        gamma = dtype(2) / dtype(k + 2)
+        alpha1 = (1 - gamma) * alpha1 + gamma * s1
+        alpha2 = (1 - gamma) * alpha2 + gamma * s2
+    return alpha1, alpha2, gap
+
+
+def solve_partial_purity(u, R, alpha, V, D, Rt, n_u, purity, n_iter1=100, n_iter2=500, tol=1e-3, trace=None, gaps=None):
+    """demethify/deconvolution.py:306-337 (`mdwbssmf_deconv_p`).  ``gaps`` (a list) receives frank_wolfe_alpha_gaps'
+    gap of every outer iteration (same iterates bit for bit)."""
     a1 = 1.0
     u_ = u.copy()
     alpha1, alpha2 = alpha[:-n_u], alpha[-n_u:]
@@ -394,8 +434,12 @@ def solve_partial_purity(u, R, alpha, V, D, Rt, n_u, purity, n_iter1=100, n_iter
         cf_0 = cf
         u, u_, a1, l_w_ = u_phase(u, alpha, n_iter2, a1, l_w_, l_w, u_, V, Rt, n_u, D)
         R = np.hstack((Rt, u.reshape(-1, n_u)))
-        alpha1, alpha2 = frank_wolfe_alpha(Rt, u, V, alpha1, alpha2, purity, n_iter2, D)
-        l_w = (np.linalg.norm(alpha2) ** 2) * d
+        if gaps is None:
+            alpha1, alpha2 = frank_wolfe_alpha(Rt, u, V, alpha1, alpha2, purity, n_iter2, D)
+        else:
+            alpha1, alpha2, gap = frank_wolfe_alpha_gaps(Rt, u, V, alpha1, alpha2, purity, n_iter2, D)
+            gaps.append(gap)
+        l_w =(np.linalg.norm(alpha2) ** 2) * d
         alpha = np.vstack((alpha1, alpha2))
         cf = weighted_cost(V, R, alpha, D)
         if trace is not None:
