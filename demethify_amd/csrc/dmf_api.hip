@@ -97,6 +97,12 @@ struct dmf_problem {
     double x16_dev = 0.0, x16_sum = 0.0;
     bool d_f32_exact = false;    // every count survives a round trip through f32 (the fused tile stores D as f32)
     double* gb_known = nullptr;  // [(n_c+1)(n_c+2)/2][S]
+    // a masked problem (dmf_problem_mask) keeps what dmf_solver_holdout_error needs: the train mask as it came (bit-packed,
+    // ceil(S / 8) bytes per row, 1 = kept), the number of held-out elements, and -- with integer count copies -- the
+    // hold-out weights (1 where held out) as u16 in D16's padded layout, which the u16 cost kernels read in D16's place
+    unsigned char* mask_bits = nullptr;
+    unsigned short* W16 = nullptr;
+    int64_t n_test = 0;
 };
 
 // page-locked per-solver block: the SolverState mirror, then one double for dmf_solver_cost_begin's result
@@ -486,6 +492,17 @@ hipError_t enqueue_cost(dmf_context* ctx, const dmf_problem* p, const double* u,
         return dmf::launch_cost_cols2_wide(p->V, p->D16, p->SD, p->Rtp, u, alpha, p->N, (int)p->S, (int)p->n_c, n_u, scratch,
                                            out, ctx->stream);
     return dmf::launch_cost(p->V, p->D, p->Rt, u, alpha, p->N, (int)p->S, (int)p->n_c, n_u, scratch, out, ctx->stream);
+}
+
+// Does enqueue_cost read the counts of this problem from D16 alone (never from the f64 D)?
+bool cost_reads_u16_only(dmf_context* ctx, const dmf_problem* p, int n_u) {
+    if (p->D16 == nullptr) return false;
+    const bool rtp_ok = p->n_c == 0 || p->Rtp != nullptr;
+    if ((ctx->generic_level == 0 || ctx->generic_level == 3 || ctx->generic_level == 4) && rtp_ok &&
+        dmf::cost_cols_supported((int)p->S, (int)p->n_c, n_u))
+        return true;  // (k_cost_cols / k_cost_cols2 take D16 wherever there is one)
+    return ctx->generic_level == 0 && rtp_ok &&
+           dmf::cost_cols2_wide_supported(p->V, p->D16, (int)p->S, p->SD, (int)p->n_c, n_u);
 }
 
 int check_ctx(dmf_context* ctx) {
@@ -1068,6 +1085,7 @@ int dmf_problem_gather(dmf_context* ctx, const dmf_problem* src, const int64_t* 
     DMF_TRY(check_ctx(ctx));
     if (src == nullptr || idx == nullptr || out == nullptr || n_idx <= 0) return DMF_ERR_BAD_ARG;
     *out = nullptr;
+    if (src->mask_bits != nullptr) return DMF_ERR_BAD_ARG;  // (the mask is not carried through a row gather)
     for (int64_t r = 0; r < n_idx; ++r)
         if (idx[r] < 0 || idx[r] >= src->N) return DMF_ERR_BAD_ARG;
     return problem_gather(ctx, src, idx, n_idx, false, out);
@@ -1078,7 +1096,82 @@ int dmf_problem_gather_device(dmf_context* ctx, const dmf_problem* src, const in
     DMF_TRY(check_ctx(ctx));
     if (src == nullptr || idx_dev == nullptr || out == nullptr || n_idx <= 0) return DMF_ERR_BAD_ARG;
     *out = nullptr;
+    if (src->mask_bits != nullptr) return DMF_ERR_BAD_ARG;
     return problem_gather(ctx, src, idx_dev, n_idx, true, out);
+}
+
+// The masked copy of a resident problem, modelled on problem_gather: one pass over the rows writes the masked V, D, D16 and
+// X16 and the hold-out weights and returns max(kept counts), the sum of the kept x and the number of held-out elements; the
+// digit planes are rebuilt from the new D16; integrality / range of the counts and of R_trunc carry over from the source,
+// so none of the scans of problem_finalize runs again.
+int dmf_problem_mask(dmf_context* ctx, const dmf_problem* src, const uint8_t* train_bits, int flags, dmf_problem** out) {
+    DMF_TRY(check_ctx(ctx));
+    if (src == nullptr || train_bits == nullptr || out == nullptr) return DMF_ERR_BAD_ARG;
+    *out = nullptr;
+    if (src->ctx != ctx || src->mask_bits != nullptr) return DMF_ERR_BAD_ARG;
+    dmf_problem* p = new (std::nothrow) dmf_problem();
+    if (p == nullptr) return DMF_ERR_BAD_ARG;
+    const int64_t N = src->N, S = src->S, n_c = src->n_c;
+    p->ctx = ctx;
+    p->N = N;
+    p->S = S;
+    p->n_c = n_c;
+    const size_t bit_bytes = (size_t)N * (size_t)((S + 7) / 8), elems = (size_t)N * S;
+    unsigned long long* d_stats = nullptr;
+    hipError_t e = pool_alloc(ctx, (void**)&p->mask_bits, bit_bytes);
+    if (e == hipSuccess)
+        e = hipMemcpyAsync(p->mask_bits, train_bits, bit_bytes,
+                           (flags & DMF_PTR_DEVICE) ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, ctx->stream);
+    if (e == hipSuccess) e = pool_alloc(ctx, (void**)&p->V, elems * sizeof(double));
+    if (e == hipSuccess) p->own_V = true, e = pool_alloc(ctx, (void**)&p->D, elems * sizeof(double));
+    if (e == hipSuccess) p->own_D = true;
+    if (e == hipSuccess && n_c > 0) {
+        e = pool_alloc(ctx, (void**)&p->Rt, (size_t)N * n_c * sizeof(double));
+        if (e == hipSuccess) p->own_Rt = true;
+        if (e == hipSuccess) e = hipMemcpyAsync(p->Rt, src->Rt, (size_t)N * n_c * sizeof(double), hipMemcpyDeviceToDevice, ctx->stream);
+    }
+    const bool ints = src->D16 != nullptr && src->ND > 0 && ctx->generic_level == 0;
+    const bool x16 = ints && src->X16 != nullptr && ctx->x16;
+    if (e == hipSuccess && ints) {
+        p->ND = src->ND;
+        p->SD = src->SD;
+        p->N16 = src->N16;
+        p->plane_stride = src->plane_stride;
+        const size_t u16_bytes = (size_t)p->N16 * p->SD * sizeof(unsigned short);
+        e = pool_alloc(ctx, (void**)&p->D16, u16_bytes);
+        if (e == hipSuccess) e = pool_alloc(ctx, (void**)&p->W16, u16_bytes);
+        if (e == hipSuccess) e = pool_alloc(ctx, (void**)&p->Dt8, (size_t)p->plane_stride * p->ND);
+        if (e == hipSuccess && x16) e = pool_alloc(ctx, (void**)&p->X16, u16_bytes);
+    }
+    if (e == hipSuccess) e = pool_alloc(ctx, (void**)&d_stats, 3 * sizeof(unsigned long long));
+    if (e == hipSuccess)
+        e = dmf::launch_mask_problem(src->V, src->D, ints ? src->D16 : nullptr, x16 ? src->X16 : nullptr, p->mask_bits, p->V, p->D,
+                                     p->D16, p->X16, p->W16, N, p->N16, (int)S, p->SD, d_stats, ctx->stream);
+    if (e == hipSuccess && ints) e = dmf::launch_build_dt8(p->D16, N, p->SD, p->ND, p->Dt8, p->plane_stride, ctx->stream);
+    unsigned long long h_stats[3] = {0, 0, 0};
+    if (e == hipSuccess) e = hipMemcpyAsync(h_stats, d_stats, sizeof(h_stats), hipMemcpyDeviceToHost, ctx->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);  // (a host mask belongs to the caller again from here on)
+    pool_free(ctx, d_stats);
+    int st = DMF_OK;
+    if (e != hipSuccess) st = hip_fail(e, "hold-out mask", __LINE__);
+    if (st == DMF_OK) {
+        double dmax;
+        std::memcpy(&dmax, &h_stats[0], sizeof(dmax));
+        p->h_consts[2] = dmax;
+        p->h_consts[3] = src->h_consts[3];
+        p->h_consts[4] = std::isfinite(src->h_consts[4]) ? dmax : src->h_consts[4];
+        p->h_consts[5] = src->h_consts[5];
+        p->x16_dev = x16 ? src->x16_dev : 0.0;  // (a bound over the source's elements: holds for any subset)
+        p->x16_sum = (double)h_stats[1];
+        p->n_test = (int64_t)h_stats[2];
+        st = problem_finalize(p, true);
+    }
+    if (st != DMF_OK) {
+        dmf_problem_destroy(p);
+        return st;
+    }
+    *out = p;
+    return DMF_OK;
 }
 
 int dmf_problem_destroy(dmf_problem* p) {
@@ -1094,6 +1187,8 @@ int dmf_problem_destroy(dmf_problem* p) {
     pool_free(ctx, p->D16);
     pool_free(ctx, p->X16);
     pool_free(ctx, p->Dt8);
+    pool_free(ctx, p->mask_bits);
+    pool_free(ctx, p->W16);
     delete p;
     return DMF_OK;
 }
@@ -1495,6 +1590,54 @@ int dmf_solver_cost_end(dmf_solver* s, double* out_cost) {
     HIP_TRY(hipEventSynchronize(s->cost_event));
     s->cost_pending = false;
     *out_cost = *reinterpret_cast<const double*>(reinterpret_cast<const char*>(s->h_state) + kPinnedStateBytes - 16);
+    return DMF_OK;
+}
+
+// cost_f_w with 0 / 1 weights: the cost kernels run on a view of the problem whose counts are the hold-out weights -- W16
+// in D16's place where the shape's cost kernel streams u16 counts, else f64 weights expanded from the mask into a pooled
+// temporary -- and whose meth_frequency is the unmasked one of `full`.
+int dmf_solver_holdout_error(dmf_solver* s, const dmf_problem* full, double* sum_sq, int64_t* n_test) {
+    if (s == nullptr || full == nullptr || sum_sq == nullptr || n_test == nullptr) return DMF_ERR_BAD_ARG;
+    dmf_context* ctx = s->ctx;
+    DMF_TRY(check_ctx(ctx));
+    const dmf_problem* p = s->p;
+    // (a masked `full` holds zeros where the error is taken)
+    if (p->mask_bits == nullptr || full->mask_bits != nullptr || full->ctx != ctx) return DMF_ERR_BAD_ARG;
+    if (full->N != p->N || full->S != p->S || full->n_c != p->n_c) return DMF_ERR_BAD_SHAPE;
+    *n_test = p->n_test;
+    *sum_sq = 0.0;
+    if (p->n_test == 0) return DMF_OK;
+    dmf_problem view;
+    view.ctx = ctx;
+    view.N = p->N;
+    view.S = p->S;
+    view.n_c = p->n_c;
+    view.V = full->V;
+    view.Rt = p->Rt;
+    view.Rtp = p->Rtp;
+    view.D16 = p->W16;
+    view.SD = p->SD;
+    double* w64 = nullptr;
+    if (!cost_reads_u16_only(ctx, &view, (int)s->n_u)) {
+        HIP_TRY(pool_alloc(ctx, (void**)&w64, (size_t)p->N * p->S * sizeof(double)));
+        hipError_t e = dmf::launch_holdout_weights_f64(p->mask_bits, w64, p->N, (int)p->S, ctx->stream);
+        if (e != hipSuccess) {
+            pool_free(ctx, w64);
+            return hip_fail(e, "hold-out weights", __LINE__);
+        }
+        view.D = w64;
+        view.D16 = nullptr;
+        view.SD = 0;
+    }
+    hipError_t e;
+    {
+        FamilyScope scope(ctx, DMF_KERNEL_COST);
+        e = enqueue_cost(ctx, &view, s->u, s->alpha, (int)s->n_u, ctx->scratch + 1024, ctx->scratch + 3072);
+    }
+    if (e == hipSuccess) e = hipMemcpyAsync(sum_sq, ctx->scratch + 3072, sizeof(double), hipMemcpyDeviceToHost, ctx->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+    pool_free(ctx, w64);
+    if (e != hipSuccess) return hip_fail(e, "hold-out error", __LINE__);
     return DMF_OK;
 }
 

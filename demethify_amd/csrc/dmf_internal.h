@@ -222,6 +222,19 @@ constexpr double kX16MaxDev = 8.0 * 0x1p-53;
 hipError_t launch_build_counts_int(const double* D, const double* V, int64_t N, int S, int ND, unsigned short* D16,
                                    unsigned short* X16, int64_t N16, int SD, signed char* Dt8, int64_t plane_stride,
                                    unsigned long long* x_stats, hipStream_t st);
+// the digit planes alone, from a D16 that is already in place (the second half of the two launchers above)
+hipError_t launch_build_dt8(const unsigned short* D16, int64_t N, int SD, int ND, signed char* Dt8, int64_t plane_stride,
+                            hipStream_t st);
+// hold-out masks (dmf_kernels_mask.hip).  bits: the N x S train mask, bit-packed row-major, ceil(S / 8) bytes per row,
+// sample s = bit (s & 7) of byte (s >> 3), 1 = kept.  dst = src where kept, 0 where held out, for V and D and -- src16 not
+// null -- D16 and X16 (srcX / dstX both or neither); W16 (D16's layout, zero padded) <- 1 where held out.  stats[3] (zeroed
+// here) <- { bits of max(kept counts, 0) as a double, sum of the kept x, number of held-out elements }
+hipError_t launch_mask_problem(const double* srcV, const double* srcD, const unsigned short* src16,
+                               const unsigned short* srcX, const unsigned char* bits, double* dstV, double* dstD,
+                               unsigned short* dst16, unsigned short* dstX, unsigned short* W16, int64_t N, int64_t N16, int S,
+                               int SD, unsigned long long* stats, hipStream_t st);
+// W[N][S] <- 1.0 where held out, 0.0 where kept
+hipError_t launch_holdout_weights_f64(const unsigned char* bits, double* W, int64_t N, int S, hipStream_t st);
 bool rowpass_v2_supported(int S, int n_c, int n_u, int n_iter2);
 int rowpass_v2_grid(int64_t N, int S);
 // u phase + b_u slab ([grid][n_u][S] doubles) + per-workgroup ||u||^2 shares in one read of V (f64) and D16 -- or, when

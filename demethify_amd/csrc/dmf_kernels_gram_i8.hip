@@ -165,6 +165,15 @@ hipError_t launch_build_counts_int(const double* D, const double* V, int64_t N, 
     return hipGetLastError();
 }
 
+hipError_t launch_build_dt8(const unsigned short* D16, int64_t N, int SD, int ND, signed char* Dt8, int64_t plane_stride,
+                            hipStream_t st) {
+    const int64_t n_tiles = ((N + 31) / 32) * (SD / 32);
+    int64_t gt = (n_tiles + 3) / 4;
+    if (gt > 16384) gt = 16384;
+    hipLaunchKernelGGL(k_build_dt8, dim3((unsigned)gt), dim3(256), 0, st, D16, N, SD, ND, Dt8, plane_stride, n_tiles);
+    return hipGetLastError();
+}
+
 // Row-resampled copy of the u16 counts (a bootstrap replicate, bootstrap.py:28): dst[r][:] = src[idx[r]][:] for r < n_idx,
 // zero rows up to N16; the largest count of the copy goes to *max_out (atomicMax; the caller zeroes it) -- max(D) of the
 // resampled counts is what the reference's d = max(D)^2 is taken from.  One wave per destination row.  src_x / dst_x (both

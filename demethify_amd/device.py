@@ -36,6 +36,15 @@ def _ptr(a):
     return a.ctypes.data_as(C.c_void_p)
 
 
+def pack_mask(mask) -> np.ndarray:
+    """The bit-packed form of a bool N x S mask that dmf_problem_mask reads: row-major, ceil(S / 8) bytes per row,
+    sample s in bit (s & 7) of byte (s >> 3); undo with ``np.unpackbits(bits, axis=1, bitorder="little")[:, :S]``."""
+    m = np.asarray(mask)
+    if m.ndim != 2:
+        raise ValueError(f"a mask is N x S, got shape {m.shape}")
+    return np.packbits(m.astype(bool, copy=False), axis=1, bitorder="little")
+
+
 class Context:
     """dmf_context: a GPU, a HIP stream and the kernel-family clocks."""
 
@@ -220,6 +229,46 @@ class Problem:
                 "dmf_problem_gather")
         return Problem._from_handle(self.ctx, h, int(idx.size), self.S, self.n_c)
 
+    def masked(self, train_mask) -> "Problem":
+        """A copy of this problem with the elements where ``train_mask`` is False held out (their counts are 0), derived
+        on the device (dmf_problem_mask): a bi-cross-validation fold (ic.py:68-75), or data with missing entries.
+        ``train_mask``: a bool N x S array, or the mask as ``pack_mask`` packs it (uint8, N x ceil(S / 8)) -- a host array,
+        a contiguous uint8 CUDA tensor, or a staged upload of those bytes (a DeviceArray carrying ``packed_mask``).
+        ``Solver.holdout_error`` of a solver on the result takes this problem as ``full``."""
+        nb = (self.S + 7) // 8
+        flags = 0
+        if getattr(train_mask, "is_cuda", False):
+            if _is_torch(train_mask):
+                import torch
+
+                ok = (train_mask.dtype == torch.uint8 and train_mask.is_contiguous()
+                      and tuple(train_mask.shape) == (self.N, nb) and train_mask.device.index == self.ctx.device)
+                if ok:
+                    torch.cuda.current_stream(train_mask.device).synchronize()
+            else:  # staging.mask_to_device
+                ok = getattr(train_mask, "packed_mask", None) == (self.N, nb) and train_mask.ctx is self.ctx
+            if not ok:
+                raise ValueError(f"a device mask must be the packed bits: contiguous uint8, shape {(self.N, nb)}, on the "
+                                 "context's GPU")
+            bits, flags = train_mask, L.DMF_PTR_DEVICE
+        else:
+            m = np.asarray(train_mask)
+            if m.dtype == np.bool_:
+                if m.shape != (self.N, self.S):
+                    raise ValueError(f"mask shape {m.shape} != problem shape {(self.N, self.S)}")
+                bits = pack_mask(m)
+            elif m.dtype == np.uint8:
+                if m.shape != (self.N, nb):
+                    raise ValueError(f"packed mask shape {m.shape} != {(self.N, nb)} (ceil(S / 8) bytes per row)")
+                bits = np.ascontiguousarray(m)
+            else:
+                raise TypeError("train_mask must be a bool N x S array or packed uint8 bits")
+        h = C.c_void_p()
+        L.check(self._lib.dmf_problem_mask(self.ctx._h, self._h, _ptr(bits), flags, C.byref(h)), "dmf_problem_mask")
+        out = Problem._from_handle(self.ctx, h, self.N, self.S, self.n_c)
+        out._keep = (self,)  # (the library copied data and bits; the parent is what holdout_error will be asked for)
+        return out
+
     def close(self):
         if getattr(self, "_h", None):
             self._lib.dmf_problem_destroy(self._h)
@@ -349,6 +398,14 @@ class Solver:
         out = C.c_double()
         L.check(self._lib.dmf_solver_cost(self._h, C.byref(out)), "dmf_solver_cost")
         return out.value
+
+    def holdout_error(self, full: Problem):
+        """(sum of squares, n_test) of this solver's masked problem (``full.masked(...)``): the sum over the held-out
+        elements of (meth_frequency - [R_trunc | u] @ alpha)**2 with ``full``'s frequencies -- ic.py:80 before its
+        division by the number of held-out elements -- computed where the iterate lives (dmf_solver_holdout_error)."""
+        ss, n = C.c_double(), C.c_int64()
+        L.check(self._lib.dmf_solver_holdout_error(self._h, full._h, C.byref(ss), C.byref(n)), "dmf_solver_holdout_error")
+        return ss.value, n.value
 
     def cost_begin(self):
         """Enqueue direct_cost() without waiting for it (dmf_solver_cost_begin): set up the next solver, then cost_end()."""

@@ -4,7 +4,9 @@ The information criteria are kept exactly as coded upstream (ic.py:11-22), inclu
 expression that is not the textbook one.  The sweep over candidate n_u (ic.py:169-218, hard-coded
 1..25 upstream) is embarrassingly parallel: with torch.distributed initialised the candidates are
 dealt to the ranks longest-first and only the per-candidate scores and the winner's factors are
-exchanged.
+exchanged.  CCC and BCV sweeps run on one rank from one resident upload; a bi-cross-validation fold
+(ic.py:58-89) is derived from it on the device (Problem.masked) and its hold-out error taken there
+(Solver.holdout_error), while the mask draws stay on the host, in the reference's order.
 """
 from __future__ import annotations
 
@@ -80,22 +82,93 @@ def run_deconvolution(meth_f, counts, ref, n_u, init_option, seed, iter1, iter2,
     return u, R, alpha
 
 
+def _bcv_draw_fold(meth_f, counts, ref, n_u, init_option, seed, fraction, stage=None):
+    """The host half of one bi-cross-validation fold, in the reference's draw order (ic.py:68-75): the train mask from
+    numpy's global generator, then the initialiser -- which reseeds -- on the masked data.  Returns None for a fold the
+    reference skips (empty train or test set: nothing further is drawn), else (train_mask, u0, alpha0, staged) with
+    ``staged = stage(train_mask)``: the device driver packs and uploads the mask here, on the drawing thread."""
+    train_mask = np.random.rand(*meth_f.shape) < fraction
+    n_train = int(np.sum(train_mask))
+    if n_train == train_mask.size or n_train == 0:
+        return None
+    if init_option == "uniform":
+        # the one initialiser in scope that reads the data (rb_alg on every sample column): it sees the masked arrays
+        init_f, init_c = meth_f * train_mask, counts * train_mask
+    else:
+        init_f, init_c = meth_f, counts  # (uniform_ / beta take the shapes only)
+    if ref is not None:
+        u0, _, a0 = init_BSSMF_md(init_option, init_f, init_c, ref, n_u, seed=seed, rb_alg=wls_intercept, _stack=False)
+    else:
+        u0, a0 = _init_unsupervised(init_option, init_f, n_u, seed)
+    return train_mask, u0, a0, stage(train_mask) if stage is not None else None
+
+
+class _DeviceFolds:
+    """The device half of a fold: the masked problem derived from the resident one (Problem.masked), the solve, and the
+    hold-out error where the iterate lives; (u, alpha) leave the device only for a fold that beats ``best``."""
+
+    def __init__(self, problem, unsupervised, iter1, iter2, tol):
+        self.problem = problem
+        self.mode = L.DMF_MODE_UNSUPERVISED if unsupervised else L.DMF_MODE_PARTIAL
+        self.steps = (iter1, iter2, tol)
+
+    def stage(self, train_mask):
+        from .device import pack_mask
+        from .staging import mask_to_device
+
+        return mask_to_device(pack_mask(train_mask), self.problem.ctx)
+
+    def __call__(self, fold, best):
+        _, u0, a0, bits = fold
+        try:
+            with self.problem.masked(bits) as fold_problem, Solver(fold_problem, u0, a0, self.mode) as s:
+                s.step(*self.steps)
+                sum_sq, n_test = s.holdout_error(self.problem)
+                test_error = sum_sq / n_test
+                factors = None
+                if test_error < best:
+                    u, alpha, _, _ = s.get()
+                    factors = (u, alpha)
+        finally:
+            bits.close()
+        return test_error, factors
+
+
 def bicross_validation(meth_f, n_u, counts, iter1, iter2, tol, n_folds=10, seed=None, ref=None,
-                       init_option="uniform_", fraction=0.3):
-    """ic.py:58-89: random-mask hold-out error (returns the SUM over folds, as upstream)."""
+                       init_option="uniform_", fraction=0.3, problem=None, _fold_solver=None):
+    """ic.py:58-89: random-mask hold-out error (returns the SUM over folds, as upstream).
+
+    The data are uploaded once (``problem``: a resident upload of (meth_f, counts, ref) to reuse; created here when
+    none is given); each fold derives its masked problem on the device and takes its error there.  The draws stay on the
+    host and in the reference's order -- seed once, then per fold the mask and the (reseeding) initialiser -- on ONE worker
+    thread (numpy's global generator), one fold ahead of the GPU.  ``_fold_solver(fold, best) -> (test_error, (u, alpha)
+    or None)`` replaces the device half (tests drive the draw order through it without a GPU)."""
     np.random.seed(seed)
     total_press, best_u, best_alpha, min_error = 0, None, None, float("inf")
-    for _ in range(n_folds):
-        train_mask = np.random.rand(*meth_f.shape) < fraction
-        test_mask = ~train_mask
-        if np.sum(test_mask) == 0 or np.sum(train_mask) == 0:
-            continue
-        u, R, alpha = run_deconvolution(meth_f * train_mask, counts * train_mask, ref, n_u, init_option, seed,
-                                        iter1, iter2, tol)
-        test_error = np.linalg.norm((meth_f - R @ alpha) * test_mask, "fro") ** 2 / np.sum(test_mask)
-        total_press += test_error
-        if test_error < min_error:
-            min_error, best_u, best_alpha = test_error, u, alpha
+    own = problem is None and _fold_solver is None
+    if own:
+        problem = Problem(get_context(), meth_f, counts, ref)
+    feed = None
+    try:
+        solve = _fold_solver if _fold_solver is not None else _DeviceFolds(problem, ref is None, iter1, iter2, tol)
+        stage = getattr(solve, "stage", None)
+
+        def draw(_):
+            return _bcv_draw_fold(meth_f, counts, ref, n_u, init_option, seed, fraction, stage)
+
+        feed = Prefetcher(range(n_folds), draw, depth=1, workers=1)
+        for _, fold in feed:
+            if fold is None:
+                continue
+            test_error, factors = solve(fold, min_error)
+            total_press += test_error
+            if test_error < min_error:
+                min_error, (best_u, best_alpha) = test_error, factors
+    finally:
+        if feed is not None:
+            feed.close()
+        if own:
+            problem.close()
     return total_press, best_u, best_alpha
 
 
@@ -120,21 +193,23 @@ def evaluate_best_ic(meth_f, ref, counts, init_option, ic, seed, iter1, iter2, t
     if ic in ("CCC", "BCV"):
         best_ic, best = float("inf"), (None, None, None)
         scores = []
-        for n_u in n_u_values:
-            if ic == "CCC":
-                runs = []
-                for restart in range(n_restarts):
-                    u, _, alpha = run_deconvolution(meth_f, counts, ref, n_u, init_option, seed + restart, iter1,
-                                                    iter2, tol)
-                    runs.append(alpha)
-                score = -compute_ccc(runs)
-            else:
-                score, u, alpha = bicross_validation(meth_f, n_u, counts, iter1, iter2, tol, fraction=0.3,
-                                                     n_folds=n_restarts, seed=seed, ref=ref,
-                                                     init_option=init_option)
-            scores.append(score)
-            if score < best_ic:
-                best_ic, best = score, (u, alpha, n_u)
+        # one resident upload for the whole sweep: every restart (CCC) and every fold (BCV) of every candidate solves on it
+        with Problem(get_context(), meth_f, counts, ref) as problem:
+            for n_u in n_u_values:
+                if ic == "CCC":
+                    runs = []
+                    for restart in range(n_restarts):
+                        u, _, alpha = run_deconvolution(meth_f, counts, ref, n_u, init_option, seed + restart, iter1,
+                                                        iter2, tol, problem=problem)
+                        runs.append(alpha)
+                    score = -compute_ccc(runs)
+                else:
+                    score, u, alpha = bicross_validation(meth_f, n_u, counts, iter1, iter2, tol, fraction=0.3,
+                                                         n_folds=n_restarts, seed=seed, ref=ref,
+                                                         init_option=init_option, problem=problem)
+                scores.append(score)
+                if score < best_ic:
+                    best_ic, best = score, (u, alpha, n_u)
         return best[0], best[1], best[2], scores
 
     # AIC / BIC: one solve per candidate; candidates dealt to ranks longest-first (cost grows with n_u)

@@ -147,6 +147,27 @@ def indices_to_device(idx, ctx):
     return DeviceArray(ctx, dev.value, idx.shape)
 
 
+def mask_to_device(bits, ctx):
+    """Upload a packed hold-out mask (device.pack_mask: uint8, N x ceil(S / 8)) the same way.  Problem.masked takes the
+    DeviceArray in place of the host bits (``packed_mask`` carries their shape)."""
+    import ctypes as C
+
+    from . import _lib as L
+
+    bits = np.ascontiguousarray(bits, dtype=np.uint8)
+    buf = _borrow(((bits.nbytes + 7) // 8,))  # (float64 staging buffers, filled bytewise)
+    try:
+        np.copyto(buf.view(np.uint8)[:bits.nbytes], bits.ravel())
+        dev = C.c_void_p()
+        L.check(ctx._lib.dmf_stage_upload(ctx._h, buf.ctypes.data_as(C.c_void_p), bits.nbytes, C.byref(dev)),
+                "dmf_stage_upload")
+    finally:
+        _give_back(buf)
+    out = DeviceArray(ctx, dev.value, bits.shape)
+    out.packed_mask = tuple(bits.shape)
+    return out
+
+
 def reserve(shapes, count: int = 1):
     """Page-lock ``count`` staging buffers per shape now (a restart job does this once, before its first restart,
     instead of inside the first uploads)."""

@@ -129,6 +129,16 @@ int dmf_problem_gather(dmf_context* ctx, const dmf_problem* src, const int64_t* 
  * the previous replicate's solve): range-checked on the device, DMF_ERR_BAD_ARG when one lies outside [0, N). */
 int dmf_problem_gather_device(dmf_context* ctx, const dmf_problem* src, const int64_t* idx_dev,
                               int64_t n_idx, dmf_problem** out);
+/* A copy of `src` with a set of elements held out: their counts are 0 in every copy of the counts the kernels read, which
+ * is what bi-cross-validation solves per fold (ic.py:68-75, `counts * train_mask`) and what data with missing entries
+ * need.  train_bits: the N x S mask, bit-packed row-major, ceil(S / 8) bytes per row, sample s = bit (s & 7) of byte
+ * (s >> 3) (numpy: packbits(mask, axis=1, bitorder="little")); 1 = kept, 0 = held out; padding bits are ignored;
+ * DMF_PTR_DEVICE in flags: the bits are in HBM.  The result is an ordinary problem for every solver mode, derived on the
+ * device in one pass over the rows: max(counts) -- the d = D.max()**2 of deconvolution.py:197 -- is that of the kept
+ * elements, the known Gram block is rebuilt; integrality and range of the counts carry over from `src` (a problem without
+ * integer count copies yields one without).  It is a full copy: `src` need not outlive it.  It also keeps the mask for
+ * dmf_solver_holdout_error.  src must not be a masked problem itself; dmf_problem_gather* refuse a masked source. */
+int dmf_problem_mask(dmf_context* ctx, const dmf_problem* src, const uint8_t* train_bits, int flags, dmf_problem** out);
 int dmf_problem_destroy(dmf_problem* p);
 int dmf_problem_shape(const dmf_problem* p, int64_t* N, int64_t* S, int64_t* n_c);
 
@@ -184,6 +194,12 @@ int dmf_solver_cost(dmf_solver* s, double* out_cost);
  * One cost in flight per solver; the iterate must not be stepped between the two calls. */
 int dmf_solver_cost_begin(dmf_solver* s);
 int dmf_solver_cost_end(dmf_solver* s, double* out_cost);
+/* Hold-out error of a solver on a masked problem (dmf_problem_mask): *sum_sq = sum over the held-out (i, s) of
+ * (v_is - sum_k R_ik alpha_ks)^2 with `full`'s meth_frequency and the solver's current iterate, R = [Rt | u] -- the squared
+ * Frobenius norm of ic.py:80, before its division by *n_test, the number of held-out elements.  It is cost_f_w with 0 / 1
+ * weights, run by the cost kernels where the iterate lives.  `full`: the problem the mask was applied to (same N, S, n_c:
+ * DMF_ERR_BAD_SHAPE otherwise).  DMF_ERR_BAD_ARG when the solver's problem is not a masked one.  Nothing held out: 0, 0. */
+int dmf_solver_holdout_error(dmf_solver* s, const dmf_problem* full, double* sum_sq, int64_t* n_test);
 int dmf_solver_destroy(dmf_solver* s);
 /* Which kernels a step with n_iter2 inner iterations would launch for this solver, as text, e.g.
  * "rowpass=k_rowpass_fused<3,4> nw=4 grid=256 tail=5 gram=fused alpha=k_alpha_phase_row16".  For tests (every
