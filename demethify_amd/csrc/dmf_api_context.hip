@@ -1,0 +1,308 @@
+// C-ABI of libdemethify_hip.so, part 1: the context -- errors, the per-family HIP-event timers, the memory pool that every
+// device buffer of the library comes from, and the upload staging of the restart loops.
+#include "dmf_api.h"
+
+namespace dmf_api {
+
+static thread_local char g_last_error[512] = "";
+
+int hip_fail(hipError_t e, const char* what, const char* file, int line) {
+    snprintf(g_last_error, sizeof(g_last_error), "%s failed at %s:%d: %s", what, file, line, hipGetErrorString(e));
+    return DMF_ERR_HIP;
+}
+
+int clock_drain(dmf_context* ctx, FamilyClock& c) {
+    if (c.used == 0) return DMF_OK;
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    for (int i = 0; i < c.used; ++i) {
+        float ms = 0.f;
+        HIP_TRY(hipEventElapsedTime(&ms, c.start[i], c.stop[i]));
+        c.total_ms += ms;
+    }
+    c.launches += c.used;
+    c.used = 0;
+    return DMF_OK;
+}
+
+// Device buffers come from a stream-ordered memory pool OF THE CONTEXT'S OWN on the context's stream.  The pool keeps
+// what is freed (release threshold raised in dmf_context_create; the device's default pool, which other users of a
+// borrowed device share, is left alone), so the multi-GB buffers of a problem or a solver that is destroyed and
+// re-created with the same sizes -- every bootstrap replicate does that -- are handed back without a trip to the
+// driver (hipMalloc / hipFree of 2 GB cost tens of milliseconds each).
+static bool pool_enabled() {  // DEMETHIFY_NO_POOL=1: plain hipMalloc / hipFree (debugging aid)
+    static const bool on = [] {
+        const char* v = getenv("DEMETHIFY_NO_POOL");
+        return !(v != nullptr && v[0] == '1');
+    }();
+    return on;
+}
+// Above the pool: freed blocks of 1 MB and more are kept by exact size and handed to the next allocation of that size
+// (a bootstrap replicate frees and re-allocates the same seven multi-GB buffers; hipFreeAsync + hipMallocFromPoolAsync
+// cost ~0.2 ms per large block even when the pool keeps the memory).  Everything that touches these blocks is enqueued
+// on the context's one stream, so a block can be reused the moment it is "freed".  At most kKeepPerSize blocks per size
+// and kKeepBytes in total are kept; the rest goes back to the pool.
+constexpr size_t kKeepMinBytes = (size_t)1 << 20, kKeepBytes = (size_t)24 << 30;
+constexpr int kKeepPerSize = 3;
+hipError_t pool_alloc(dmf_context* ctx, void** p, size_t bytes) {
+    if (!pool_enabled() || ctx->pool == nullptr) return hipMalloc(p, bytes);
+    if (bytes >= kKeepMinBytes) {
+        auto it = ctx->kept.find(bytes);
+        if (it != ctx->kept.end() && !it->second.empty()) {
+            *p = it->second.back();
+            it->second.pop_back();
+            ctx->kept_bytes -= bytes;
+            ctx->live[*p] = bytes;
+            return hipSuccess;
+        }
+    }
+    hipError_t e = hipMallocFromPoolAsync(p, bytes, ctx->pool, ctx->stream);
+    if (e != hipSuccess && ctx->kept_bytes > 0) {  // out of memory with blocks parked here: give them back, try again
+        (void)hipGetLastError();
+        for (auto& kv : ctx->kept)
+            for (void* q : kv.second) (void)hipFreeAsync(q, ctx->stream);
+        ctx->kept.clear();
+        ctx->kept_bytes = 0;
+        (void)hipStreamSynchronize(ctx->stream);
+        e = hipMallocFromPoolAsync(p, bytes, ctx->pool, ctx->stream);
+    }
+    if (e == hipSuccess && bytes >= kKeepMinBytes) ctx->live[*p] = bytes;
+    return e;
+}
+void pool_free(dmf_context* ctx, void* p) {
+    if (p == nullptr) return;
+    if (!pool_enabled() || ctx->pool == nullptr) {
+        (void)hipStreamSynchronize(ctx->stream);
+        (void)hipFree(p);
+        return;
+    }
+    auto it = ctx->live.find(p);
+    if (it != ctx->live.end()) {
+        const size_t bytes = it->second;
+        ctx->live.erase(it);
+        auto& slot = ctx->kept[bytes];
+        if ((int)slot.size() < kKeepPerSize && ctx->kept_bytes + bytes <= kKeepBytes) {
+            slot.push_back(p);
+            ctx->kept_bytes += bytes;
+            return;
+        }
+    }
+    (void)hipFreeAsync(p, ctx->stream);
+}
+
+// A block for the upload staging: from the pool on the given stream, past the kept lists (which belong to the thread that
+// drives `stream`; dmf_stage_upload runs on worker threads), and its release before anybody else has seen the block.
+static hipError_t stage_alloc(dmf_context* ctx, hipStream_t st, void** p, size_t bytes) {
+    if (!pool_enabled() || ctx->pool == nullptr) return hipMalloc(p, bytes);
+    return hipMallocFromPoolAsync(p, bytes, ctx->pool, st);
+}
+static void stage_release(dmf_context* ctx, hipStream_t st, void* p) {
+    if (!pool_enabled() || ctx->pool == nullptr) (void)hipFree(p);
+    else (void)hipFreeAsync(p, st);
+}
+
+int export_array(dmf_context* ctx, const void* dev_src, size_t bytes, int flags, void* dst) {
+    if (bytes == 0 || dst == nullptr) return DMF_OK;
+    const hipMemcpyKind kind = (flags & DMF_PTR_DEVICE) ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
+    HIP_TRY(hipMemcpyAsync(dst, dev_src, bytes, kind, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    return DMF_OK;
+}
+
+int check_ctx(dmf_context* ctx) {
+    if (ctx == nullptr) return DMF_ERR_BAD_ARG;
+    HIP_TRY(hipSetDevice(ctx->device));
+    return DMF_OK;
+}
+
+}  // namespace dmf_api
+
+using namespace dmf_api;
+
+extern "C" {
+
+const char* dmf_status_string(int status) {
+    switch (status) {
+        case DMF_OK: return "ok";
+        case DMF_ERR_BAD_ARG: return "bad argument";
+        case DMF_ERR_BAD_SHAPE: return "shape mismatch";
+        case DMF_ERR_HIP: return "HIP runtime error";
+        case DMF_ERR_NONFINITE: return "non-finite input";
+        case DMF_ERR_UNSUPPORTED: return "unsupported size";
+        case DMF_ERR_NO_DEVICE: return "no gfx950 device";
+        default: return "unknown status";
+    }
+}
+
+const char* dmf_last_error(void) { return g_last_error; }
+
+int dmf_abi_version(void) { return 1; }
+
+int dmf_context_create(int device, void* stream, dmf_context** out) {
+    if (out == nullptr) return DMF_ERR_BAD_ARG;
+    *out = nullptr;
+    int count = 0;
+    if (hipGetDeviceCount(&count) != hipSuccess || count <= 0) return DMF_ERR_NO_DEVICE;
+    if (device < 0 || device >= count) return DMF_ERR_BAD_ARG;
+    HIP_TRY(hipSetDevice(device));
+    hipDeviceProp_t prop;
+    HIP_TRY(hipGetDeviceProperties(&prop, device));
+    if (strncmp(prop.gcnArchName, "gfx950", 6) != 0) {
+        snprintf(g_last_error, sizeof(g_last_error), "device %d is %s, this library is built for gfx950",
+                 device, prop.gcnArchName);
+        return DMF_ERR_NO_DEVICE;
+    }
+    dmf_context* ctx = new (std::nothrow) dmf_context();
+    if (ctx == nullptr) return DMF_ERR_BAD_ARG;
+    ctx->device = device;
+    if (stream != nullptr) {
+        ctx->stream = (hipStream_t)stream;
+    } else {
+        hipError_t e = hipStreamCreateWithFlags(&ctx->stream, hipStreamNonBlocking);
+        if (e != hipSuccess) {
+            delete ctx;
+            return hip_fail(e, "hipStreamCreate", __FILE_NAME__, __LINE__);
+        }
+        ctx->own_stream = true;
+    }
+    hipError_t e = hipMalloc((void**)&ctx->scratch, 4096 * sizeof(double));
+    if (e != hipSuccess) {
+        if (ctx->own_stream) hipStreamDestroy(ctx->stream);
+        delete ctx;
+        return hip_fail(e, "hipMalloc(scratch)", __FILE_NAME__, __LINE__);
+    }
+    // a pool of the context's own that keeps freed memory for the next problem / solver of the same size (see
+    // pool_alloc); if the runtime cannot create one, plain hipMalloc / hipFree are used
+    if (pool_enabled()) {
+        hipMemPoolProps props = {};
+        props.allocType = hipMemAllocationTypePinned;
+        props.handleTypes = hipMemHandleTypeNone;
+        props.location.type = hipMemLocationTypeDevice;
+        props.location.id = device;
+        if (hipMemPoolCreate(&ctx->pool, &props) == hipSuccess && ctx->pool != nullptr) {
+            uint64_t keep = UINT64_MAX;
+            (void)hipMemPoolSetAttribute(ctx->pool, hipMemPoolAttrReleaseThreshold, &keep);
+        } else {
+            ctx->pool = nullptr;
+            (void)hipGetLastError();
+        }
+    }
+    *out = ctx;
+    return DMF_OK;
+}
+
+int dmf_context_destroy(dmf_context* ctx) {
+    if (ctx == nullptr) return DMF_OK;
+    hipSetDevice(ctx->device);
+    hipStreamSynchronize(ctx->stream);
+    for (auto& c : ctx->clocks) {
+        for (auto ev : c.start) hipEventDestroy(ev);
+        for (auto ev : c.stop) hipEventDestroy(ev);
+    }
+    hipFree(ctx->scratch);
+    for (auto& kv : ctx->kept)
+        for (void* q : kv.second) (void)hipFreeAsync(q, ctx->stream);
+    ctx->kept.clear();
+    (void)hipStreamSynchronize(ctx->stream);
+    for (void* h : ctx->pinned_states) (void)hipHostFree(h);
+    for (double* h : ctx->pinned_moms) (void)hipHostFree(h);
+    for (hipEvent_t ev : ctx->events) (void)hipEventDestroy(ev);
+    if (ctx->copy_stream != nullptr) {
+        hipStreamSynchronize(ctx->copy_stream);
+        hipStreamDestroy(ctx->copy_stream);
+    }
+    if (ctx->pool != nullptr) (void)hipMemPoolDestroy(ctx->pool);  // hands the cached buffers back to the driver
+    if (ctx->own_stream) hipStreamDestroy(ctx->stream);
+    delete ctx;
+    return DMF_OK;
+}
+
+/* Staging for a restart loop (demethify/demethify.py:165-171,195-201): the next restart's initialisation goes to the
+ * device from a worker thread, on a copy stream of the context's own, while `stream` runs the current restart; the
+ * solver is then created from the device copy (DMF_PTR_DEVICE).  Thread-safe; returns when the copy is complete. */
+int dmf_stage_upload(dmf_context* ctx, const void* host, size_t bytes, void** out_dev) {
+    if (ctx == nullptr || host == nullptr || out_dev == nullptr || bytes == 0) return DMF_ERR_BAD_ARG;
+    HIP_TRY(hipSetDevice(ctx->device));  // (the current device is per thread)
+    std::lock_guard<std::mutex> lock(ctx->copy_mutex);
+    if (ctx->copy_stream == nullptr) HIP_TRY(hipStreamCreateWithFlags(&ctx->copy_stream, hipStreamNonBlocking));
+    void* d = nullptr;
+    HIP_TRY(stage_alloc(ctx, ctx->copy_stream, &d, bytes));
+    hipError_t e = hipMemcpyAsync(d, host, bytes, hipMemcpyHostToDevice, ctx->copy_stream);
+    e = e != hipSuccess ? e : hipStreamSynchronize(ctx->copy_stream);
+    if (e != hipSuccess) {
+        stage_release(ctx, ctx->copy_stream, d);
+        return hip_fail(e, "dmf_stage_upload", __FILE_NAME__, __LINE__);
+    }
+    *out_dev = d;
+    return DMF_OK;
+}
+
+int dmf_stage_free(dmf_context* ctx, void* dev) {
+    if (ctx == nullptr) return DMF_ERR_BAD_ARG;
+    if (dev == nullptr) return DMF_OK;
+    HIP_TRY(hipSetDevice(ctx->device));
+    pool_free(ctx, dev);  // ordered behind the work of `stream` that read it
+    return DMF_OK;
+}
+
+int dmf_context_synchronize(dmf_context* ctx) {
+    DMF_TRY(check_ctx(ctx));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    return DMF_OK;
+}
+
+int dmf_context_set_profiling(dmf_context* ctx, int enabled) {
+    DMF_TRY(check_ctx(ctx));
+    if (!enabled)
+        for (auto& c : ctx->clocks) DMF_TRY(clock_drain(ctx, c));
+    // 0 = off, 1 = every family, otherwise a mask with bit (1 + family) set for the families to time
+    // (2 = DMF_KERNEL_ROWPASS only, ...): each timed launch costs two event records on the stream
+    ctx->profiling = enabled == 0 ? 0u : enabled == 1 ? ~0u : (unsigned)enabled >> 1;
+    return DMF_OK;
+}
+
+int dmf_context_kernel_time(dmf_context* ctx, int family, double* total_ms, int64_t* launches) {
+    DMF_TRY(check_ctx(ctx));
+    if (family < 0 || family >= DMF_KERNEL_FAMILIES) return DMF_ERR_BAD_ARG;
+    FamilyClock& c = ctx->clocks[family];
+    DMF_TRY(clock_drain(ctx, c));
+    if (total_ms) *total_ms = c.total_ms;
+    if (launches) *launches = c.launches;
+    return DMF_OK;
+}
+
+int dmf_context_reset_kernel_time(dmf_context* ctx) {
+    DMF_TRY(check_ctx(ctx));
+    for (auto& c : ctx->clocks) {
+        DMF_TRY(clock_drain(ctx, c));
+        c.total_ms = 0.0;
+        c.launches = 0;
+    }
+    return DMF_OK;
+}
+
+int dmf_context_set_generic(dmf_context* ctx, int enabled) {
+    if (ctx == nullptr) return DMF_ERR_BAD_ARG;
+    if (enabled < 0 || enabled > 4) return DMF_ERR_BAD_ARG;
+    ctx->generic_level = enabled;
+    return DMF_OK;
+}
+
+int dmf_context_set_x16(dmf_context* ctx, int enabled) {
+    if (ctx == nullptr || enabled < 0 || enabled > 1) return DMF_ERR_BAD_ARG;
+    ctx->x16 = enabled != 0;
+    return DMF_OK;
+}
+
+int dmf_context_set_rowpass_pair(dmf_context* ctx, int enabled) {
+    if (ctx == nullptr || enabled < 0 || enabled > 1) return DMF_ERR_BAD_ARG;
+    ctx->rowpass_pair = enabled != 0;
+    return DMF_OK;
+}
+
+int dmf_context_set_stop_confirmation(dmf_context* ctx, int mode) {
+    if (ctx == nullptr || mode < 0 || mode > 2) return DMF_ERR_BAD_ARG;
+    ctx->stop_confirmation = mode;
+    return DMF_OK;
+}
+
+}  // extern "C"

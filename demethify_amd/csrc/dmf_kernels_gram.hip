@@ -7,7 +7,7 @@
 //     cross[k][j] += d * Rt_ik * u_ij        (NCT x NU)
 //     uu[j<=l]    += d * u_ij * u_il         (NU (NU+1) / 2)
 //     bu[j]       += d * v * u_ij            (NU)
-// Job order of the slab = the solver's job table (dmf_api.hip: l = n_c..K, k <= l).
+// Job order of the slab = the solver's job table (dmf_api_solver.hip: l = n_c..K, k <= l).
 #include "dmf_device.h"
 #include "dmf_internal.h"
 

@@ -895,7 +895,7 @@ bool gram_i8_supported(int n_c, int n_u, int ND, int64_t N, int SD) {
     return rpw * 128 * 128 * ND < (int64_t)1 << 31;  // i32 accumulators cannot overflow within a row range
 }
 
-// The known block of a problem's packed Gram (dmf_api.hip, problem_finalize) through the same kernels: its dense pairs
+// The known block of a problem's packed Gram (dmf_api_problem.hip, problem_finalize) through the same kernels: its dense pairs
 // (R_trunc column k x column l) are features whose two factors both come from the R_trunc image (n_u = 0), its
 // right-hand sides sum_i Rt_ik d_is v_is are k_bu_cols with R_trunc in the place of u.
 bool gram_i8_known_supported(int n_c, int ND, int64_t N, int SD) {
