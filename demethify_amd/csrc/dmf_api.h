@@ -180,6 +180,15 @@ struct dmf_problem {
     dmf_api::DevBuf<unsigned char> mask_bits;
     dmf_api::DevBuf<unsigned short> W16;
     int64_t n_test = 0;
+    // the device arrays as the launch wrappers take them (dmf_internal.h)
+    dmf::ProblemView view() const {
+        dmf::ProblemView v;
+        v.V = V, v.D = D, v.D16 = D16, v.X16 = X16, v.Dt8 = Dt8;
+        v.plane_stride = plane_stride, v.SD = SD, v.ND = ND;
+        v.Rt = Rt, v.Rtp = Rtp;
+        v.N = N, v.S = (int)S, v.n_c = (int)n_c;
+        return v;
+    }
 };
 
 // page-locked per-solver block: the SolverState mirror, then one double for dmf_solver_cost_begin's result
@@ -232,6 +241,18 @@ struct dmf_solver {
     long long cf_stream_iter = -1;
     long long n_rowpass = 0, n_rowpass_pair = 0;  // k_rowpass_v2 launches so far / of them on the pair schedule
     long long n_confirmed = 0, n_unconfirmed = 0;  // stop tests decided on streaming costs / on the Gram form inside the band
+    // the iterate and the u phases' scratch as the launch wrappers take them (dmf_internal.h)
+    dmf::IterateView iterate() const {
+        dmf::IterateView it;
+        it.u = u, it.u_prev = u_prev, it.alpha = alpha, it.state = state;
+        it.n_u = (int)n_u, it.mode = mode;
+        return it;
+    }
+    dmf::UScratch scratch() const {
+        dmf::UScratch sc;
+        sc.cm = cm, sc.beta = beta_tab, sc.slab = slab, sc.u2_partials = u2_partials;
+        return sc;
+    }
 };
 
 namespace dmf_api {
@@ -293,11 +314,11 @@ int import_array(dmf_context* ctx, const void* src, size_t count, int flags, Dev
 int export_array(dmf_context* ctx, const void* dev_src, size_t bytes, int flags, void* dst);
 
 // dmf_api_problem.hip: the streaming cost of (u, alpha) on a problem's data
-hipError_t enqueue_cost(dmf_context* ctx, const dmf_problem* p, const double* u, const double* alpha, int n_u,
+hipError_t enqueue_cost(dmf_context* ctx, const dmf::ProblemView& p, const double* u, const double* alpha, int n_u,
                         double* scratch, double* out);
-bool cost_reads_u16_only(dmf_context* ctx, const dmf_problem* p, int n_u);
-int cost_to_host(dmf_context* ctx, const dmf_problem* p, const double* u, const double* alpha, int n_u, double* host_slot,
-                 bool wait);
+bool cost_reads_u16_only(dmf_context* ctx, const dmf::ProblemView& p, int n_u);
+int cost_to_host(dmf_context* ctx, const dmf::ProblemView& p, const double* u, const double* alpha, int n_u,
+                 double* host_slot, bool wait);
 
 // dmf_api_solver.hip: the phases of an outer iteration, for the single-function entry points
 int enqueue_u_phase(dmf_solver* s, int n_iter2, dmf::RowKind row);

@@ -85,7 +85,7 @@ int dmf_cost(dmf_context* ctx, const dmf_problem* p, const double* u, int64_t n_
     HIP_TRY(dout.alloc(ctx, 1));
     {
         FamilyScope scope(ctx, DMF_KERNEL_COST);
-        HIP_TRY(enqueue_cost(ctx, p, du, da, (int)n_u, ctx->scratch + 1024, dout));
+        HIP_TRY(enqueue_cost(ctx, p->view(), du, da, (int)n_u, ctx->scratch + 1024, dout));
     }
     HIP_TRY(hipMemcpyAsync(out_cost, dout, sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(hipStreamSynchronize(ctx->stream));

@@ -92,6 +92,7 @@ static int problem_finalize(dmf_problem* p, bool counts_done = false) {
     }
 
     // known block: packed triangle over the extended indices (Rt_0..Rt_{n_c-1}, v)
+    const dmf::ProblemView pv = p->view();
     JobTable jobs;
     jobs.build(0, (int)n_c, [](int, int) { return true; });
     const int n_jobs = jobs.n;
@@ -125,19 +126,16 @@ static int problem_finalize(dmf_problem* p, bool counts_done = false) {
         HIP_TRY(slab_bu.alloc(ctx, (size_t)dmf::bu_cols_grid(N) * (n_c + 1) * S));
         HIP_TRY(hipMemsetAsync(acc, 0, (size_t)acc_words * sizeof(long long), ctx->stream));
         int ny = 0, n_slabs = 0;
-        HIP_TRY(dmf::launch_gram_i8(p->Dt8, p->plane_stride, p->SD, p->ND, p->Rtp, nullptr, N, (int)n_c, 0, jobs.k, jobs.l,
-                                    n_dense, slab_i8, slab_words, nullptr, &ny, ctx->stream));
+        HIP_TRY(dmf::launch_gram_i8(pv, nullptr, 0, jobs.k, jobs.l, n_dense, slab_i8, slab_words, nullptr, &ny, ctx->stream));
         // (v^T D v rides along where the two-samples-per-lane form of the stream kernel runs)
-        HIP_TRY(dmf::launch_bu_cols(p->V, p->D16, p->SD, p->Rt, N, (int)S, (int)n_c, slab_bu, nullptr, &n_slabs, ctx->stream,
-                                    &vdv_done));
+        HIP_TRY(dmf::launch_bu_cols(pv, p->Rt, (int)n_c, slab_bu, nullptr, &n_slabs, ctx->stream, &vdv_done));
         // (dst lists the dense pairs first, then the n_c right-hand sides, then (v, v): the order of the reduce's jobs)
         HIP_TRY(dmf::launch_gram_v2_reduce(slab_i8, ny, n_dense, p->SD, slab_bu, n_slabs, (int)n_c + (vdv_done ? 1 : 0), (int)S,
                                            acc, jobs.dst, p->gb_known, nullptr, nullptr, 0, nullptr, ctx->stream));
     } else if (mfma) {
         dmf::GramJobTable fast{jobs.k, jobs.l, jobs.dst, n_fast};
         int ny = 0;
-        HIP_TRY(dmf::launch_gram_mfma(p->V, p->D, p->Rt, nullptr, N, (int)S, (int)n_c, 0, fast, n_dense, slab, slab_doubles,
-                                      nullptr, &ny, ctx->stream));
+        HIP_TRY(dmf::launch_gram_mfma(pv, nullptr, 0, fast, n_dense, slab, slab_doubles, nullptr, &ny, ctx->stream));
         HIP_TRY(dmf::launch_gram_reduce(slab, ny, n_fast, (int)S, jobs.dst, p->gb_known, nullptr, ctx->stream));
     }
     if (int_known && vdv_done) {
@@ -145,12 +143,10 @@ static int problem_finalize(dmf_problem* p, bool counts_done = false) {
     } else if (n_jobs - n_fast == 1 && ctx->generic_level != 1 && ctx->generic_level != 2 &&
                (int64_t)dmf::vdv_cols_grid(N) * S <= slab_doubles) {
         // what is left is v^T D v alone: a stream kernel of its own (the generic kernel took 2.7 ms for it at 1e6 x 256)
-        HIP_TRY(dmf::launch_vdv_cols(p->V, p->D, p->D16, p->SD, N, (int)S, slab,
-                                     p->gb_known + (int64_t)jobs.h_dst[n_jobs - 1] * S, ctx->stream));
+        HIP_TRY(dmf::launch_vdv_cols(pv, slab, p->gb_known + (int64_t)jobs.h_dst[n_jobs - 1] * S, ctx->stream));
     } else {
         dmf::GramJobTable rest{jobs.k + n_fast, jobs.l + n_fast, jobs.dst + n_fast, n_jobs - n_fast};
-        HIP_TRY(dmf::launch_gram(p->V, p->D, p->Rt, nullptr, N, (int)S, (int)n_c, 0, rest, slab, slab_doubles, p->gb_known,
-                                 nullptr, ctx->stream));
+        HIP_TRY(dmf::launch_gram(pv, nullptr, 0, rest, slab, slab_doubles, p->gb_known, nullptr, ctx->stream));
     }
     HIP_TRY(hipStreamSynchronize(ctx->stream));  // (the uploads of the job table read host memory of this frame)
     return DMF_OK;
@@ -159,40 +155,34 @@ static int problem_finalize(dmf_problem* p, bool counts_done = false) {
 enum class CostKind { Cols, Cols2Wide, Generic };
 
 // which kernel computes cost_f_w on this problem's data: the column-resident ones when the shape allows, else the generic
-static CostKind cost_kind(dmf_context* ctx, const dmf_problem* p, int n_u) {
-    const bool rtp_ok = p->n_c == 0 || p->Rtp != nullptr;
+static CostKind cost_kind(dmf_context* ctx, const dmf::ProblemView& p, int n_u) {
+    const bool rtp_ok = p.n_c == 0 || p.Rtp != nullptr;
     if ((ctx->generic_level == 0 || ctx->generic_level == 3 || ctx->generic_level == 4) && rtp_ok &&
-        dmf::cost_cols_supported((int)p->S, (int)p->n_c, n_u))
+        dmf::cost_cols_supported(p.S, p.n_c, n_u))
         return CostKind::Cols;
-    if (ctx->generic_level == 0 && rtp_ok && dmf::cost_cols2_wide_supported(p->V, p->D16, (int)p->S, p->SD, (int)p->n_c, n_u))
-        return CostKind::Cols2Wide;
+    if (ctx->generic_level == 0 && rtp_ok && dmf::cost_cols2_wide_supported(p, n_u)) return CostKind::Cols2Wide;
     return CostKind::Generic;
 }
 
-hipError_t enqueue_cost(dmf_context* ctx, const dmf_problem* p, const double* u, const double* alpha, int n_u,
+hipError_t enqueue_cost(dmf_context* ctx, const dmf::ProblemView& p, const double* u, const double* alpha, int n_u,
                         double* scratch, double* out) {
     switch (cost_kind(ctx, p, n_u)) {
-        case CostKind::Cols:
-            return dmf::launch_cost_cols(p->V, p->D, p->D16, p->SD, p->Rtp, u, alpha, p->N, (int)p->S, (int)p->n_c, n_u,
-                                         scratch, out, ctx->stream);
-        case CostKind::Cols2Wide:
-            return dmf::launch_cost_cols2_wide(p->V, p->D16, p->SD, p->Rtp, u, alpha, p->N, (int)p->S, (int)p->n_c, n_u,
-                                               scratch, out, ctx->stream);
-        default:
-            return dmf::launch_cost(p->V, p->D, p->Rt, u, alpha, p->N, (int)p->S, (int)p->n_c, n_u, scratch, out, ctx->stream);
+        case CostKind::Cols: return dmf::launch_cost_cols(p, u, alpha, n_u, scratch, out, ctx->stream);
+        case CostKind::Cols2Wide: return dmf::launch_cost_cols2_wide(p, u, alpha, n_u, scratch, out, ctx->stream);
+        default: return dmf::launch_cost(p, u, alpha, n_u, scratch, out, ctx->stream);
     }
 }
 
 // Does enqueue_cost read the counts of this problem from D16 alone (never from the f64 D)?
 // (k_cost_cols / k_cost_cols2 take D16 wherever there is one)
-bool cost_reads_u16_only(dmf_context* ctx, const dmf_problem* p, int n_u) {
-    return p->D16 != nullptr && cost_kind(ctx, p, n_u) != CostKind::Generic;
+bool cost_reads_u16_only(dmf_context* ctx, const dmf::ProblemView& p, int n_u) {
+    return p.D16 != nullptr && cost_kind(ctx, p, n_u) != CostKind::Generic;
 }
 
 // The streaming cost (deconvolution.py:15-17) of (u, alpha) on the problem's data into a host slot; without `wait` the
 // copy is only enqueued (a page-locked slot, and the caller's event behind it).
-int cost_to_host(dmf_context* ctx, const dmf_problem* p, const double* u, const double* alpha, int n_u, double* host_slot,
-                 bool wait) {
+int cost_to_host(dmf_context* ctx, const dmf::ProblemView& p, const double* u, const double* alpha, int n_u,
+                 double* host_slot, bool wait) {
     {
         FamilyScope scope(ctx, DMF_KERNEL_COST);
         HIP_TRY(enqueue_cost(ctx, p, u, alpha, n_u, ctx->scratch + 1024, ctx->scratch + 3072));

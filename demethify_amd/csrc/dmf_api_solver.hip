@@ -18,41 +18,32 @@ static int ensure_split_scratch(dmf_solver* s, int n_iter2) {
 
 int enqueue_u_phase(dmf_solver* s, int n_iter2, dmf::RowKind row) {
     dmf_context* ctx = s->ctx;
-    const dmf_problem* p = s->p;
+    const dmf::ProblemView pv = s->p->view();
     FamilyScope scope(ctx, DMF_KERNEL_ROWPASS);
     switch (row) {
         case dmf::RowKind::CmI8InnerRows:
             // wide row groups on u16 counts: per-row c_i / M_i with M_i on the integer matrix cores, then the inner
             // iterations chip-wide (dmf_kernels_cm_i8.hip)
             DMF_TRY(ensure_split_scratch(s, n_iter2));
-            HIP_TRY(dmf::launch_u_phase_split_i8(p->V, p->D16, p->SD, p->ND, p->Rtp, s->alpha, s->u, s->u_prev, s->state, p->N,
-                                                 (int)p->S, (int)p->n_c, (int)s->n_u, n_iter2, s->mode, s->cm, s->beta_tab,
-                                                 ctx->stream));
+            HIP_TRY(dmf::launch_u_phase_split_i8(pv, s->iterate(), n_iter2, s->scratch(), ctx->stream));
             return DMF_OK;
         case dmf::RowKind::UPhaseBig:
-            HIP_TRY(dmf::launch_u_phase_big(p->V, p->D, p->Rtp, s->alpha, s->u, s->u_prev, s->state, p->N, (int)p->S,
-                                            (int)p->n_c, (int)s->n_u, n_iter2, s->mode, ctx->stream));
+            HIP_TRY(dmf::launch_u_phase_big(pv, s->iterate(), n_iter2, ctx->stream));
             return DMF_OK;
         case dmf::RowKind::UPhaseMfmaSplit:
             // many inner steps or wide row groups: one wave per workgroup running the inner steps is the bottleneck
             DMF_TRY(ensure_split_scratch(s, n_iter2));
-            HIP_TRY(dmf::launch_u_phase_split(p->V, p->D, p->D16, p->SD, p->Rtp, s->alpha, s->u, s->u_prev, s->state, p->N,
-                                              (int)p->S, (int)p->n_c, (int)s->n_u, n_iter2, s->mode, s->cm, s->beta_tab,
-                                              ctx->stream));
+            HIP_TRY(dmf::launch_u_phase_split(pv, s->iterate(), n_iter2, s->scratch(), ctx->stream));
             return DMF_OK;
         case dmf::RowKind::UPhaseMfma:
-            HIP_TRY(dmf::launch_u_phase_mfma(p->V, p->D, p->D16, p->SD, p->Rtp, s->alpha, s->u, s->u_prev, s->state, p->N,
-                                             (int)p->S, (int)p->n_c, (int)s->n_u, n_iter2, s->mode, ctx->stream));
+            HIP_TRY(dmf::launch_u_phase_mfma(pv, s->iterate(), n_iter2, ctx->stream));
             return DMF_OK;
         case dmf::RowKind::UPhaseGram:
-            HIP_TRY(dmf::launch_u_phase_gram(p->V, p->D, p->Rt, s->alpha, s->u, s->u_prev, s->state, p->N,
-                                             (int)p->S, (int)p->n_c, (int)s->n_u, n_iter2, s->mode, ctx->stream));
+            HIP_TRY(dmf::launch_u_phase_gram(pv, s->iterate(), n_iter2, ctx->stream));
             return DMF_OK;
         case dmf::RowKind::UStepDirect:
             for (int t = 0; t < n_iter2; ++t) {
-                HIP_TRY(dmf::launch_u_step_direct(p->V, p->D, p->Rt, s->alpha, s->u, s->u_prev, s->u_next,
-                                                  s->state, p->N, (int)p->S, (int)p->n_c, (int)s->n_u, t,
-                                                  s->mode, ctx->stream));
+                HIP_TRY(dmf::launch_u_step_direct(pv, s->iterate(), s->u_next, t, ctx->stream));
                 std::swap(s->u_prev, s->u);   // (u_prev <- u, u <- u_next, u_next <- the old u_prev)
                 std::swap(s->u, s->u_next);
             }
@@ -77,8 +68,8 @@ static int gram_i8_and_reduce(dmf_solver* s, int n_slabs, const double* u2_parti
     const dmf_problem* p = s->p;
     const int S = (int)p->S, n_c = (int)p->n_c, n_u = (int)s->n_u, nf = n_c * n_u + n_u * (n_u + 1) / 2;
     int ny = 0;
-    HIP_TRY(dmf::launch_gram_i8(p->Dt8, p->plane_stride, p->SD, p->ND, p->Rtp, s->u, p->N, n_c, n_u, s->jobs.k, s->jobs.l, nf,
-                                s->slab_i8, s->slab_i8_words, &s->state->done, &ny, ctx->stream));
+    HIP_TRY(dmf::launch_gram_i8(p->view(), s->u, n_u, s->jobs.k, s->jobs.l, nf, s->slab_i8, s->slab_i8_words, &s->state->done,
+                                &ny, ctx->stream));
     HIP_TRY(dmf::launch_gram_v2_reduce(s->slab_i8, ny, nf, p->SD, s->slab, n_slabs, n_u, S, s->acc_i8, s->jobs.dst, s->gb,
                                        &s->state->done, u2_partials, n_u2, s->state, ctx->stream));
     return DMF_OK;
@@ -88,34 +79,29 @@ static int gram_i8_and_reduce(dmf_solver* s, int n_slabs, const double* u2_parti
 // fixed-point features need); the dmf_update_alpha entry point hands over the caller's u and passes an FP64 kind
 int enqueue_gram(dmf_solver* s, dmf::GramKind kind) {
     dmf_context* ctx = s->ctx;
-    const dmf_problem* p = s->p;
+    const dmf::ProblemView pv = s->p->view();
+    const int S = pv.S, n_u = (int)s->n_u;
+    const int* done = &s->state->done;
     FamilyScope scope(ctx, DMF_KERNEL_GRAM);
     if (kind == dmf::GramKind::BuColsI8) {
         int n_slabs = 0;
-        HIP_TRY(dmf::launch_bu_cols(p->V, p->D16, p->SD, s->u, p->N, (int)p->S, (int)s->n_u, s->slab, &s->state->done, &n_slabs,
-                                    ctx->stream));
+        HIP_TRY(dmf::launch_bu_cols(pv, s->u, n_u, s->slab, done, &n_slabs, ctx->stream));
         return gram_i8_and_reduce(s, n_slabs, nullptr, 0);
     }
     if (kind == dmf::GramKind::GramU) {
         int ny = 0;
-        HIP_TRY(dmf::launch_gram_u(p->V, p->D, p->Rtp, s->u, p->N, (int)p->S, (int)p->n_c, (int)s->n_u, s->slab,
-                                   &s->state->done, &ny, ctx->stream));
-        HIP_TRY(dmf::launch_gram_reduce(s->slab, ny, s->jobs.n, (int)p->S, s->jobs.dst, s->gb, &s->state->done,
-                                        ctx->stream));
+        HIP_TRY(dmf::launch_gram_u(pv, s->u, n_u, s->slab, done, &ny, ctx->stream));
+        HIP_TRY(dmf::launch_gram_reduce(s->slab, ny, s->jobs.n, S, s->jobs.dst, s->gb, done, ctx->stream));
         return DMF_OK;
     }
     dmf::GramJobTable jobs{s->jobs.k, s->jobs.l, s->jobs.dst, s->jobs.n};
     if (kind == dmf::GramKind::GramMfma) {
         int ny = 0;
-        HIP_TRY(dmf::launch_gram_mfma(p->V, p->D, p->Rt, s->u, p->N, (int)p->S, (int)p->n_c, (int)s->n_u, jobs,
-                                      s->jobs.n - (int)s->n_u, s->slab, s->slab_doubles, &s->state->done, &ny,
-                                      ctx->stream));
-        HIP_TRY(dmf::launch_gram_reduce(s->slab, ny, s->jobs.n, (int)p->S, s->jobs.dst, s->gb, &s->state->done,
-                                        ctx->stream));
+        HIP_TRY(dmf::launch_gram_mfma(pv, s->u, n_u, jobs, s->jobs.n - n_u, s->slab, s->slab_doubles, done, &ny, ctx->stream));
+        HIP_TRY(dmf::launch_gram_reduce(s->slab, ny, s->jobs.n, S, s->jobs.dst, s->gb, done, ctx->stream));
         return DMF_OK;
     }
-    HIP_TRY(dmf::launch_gram(p->V, p->D, p->Rt, s->u, p->N, (int)p->S, (int)p->n_c, (int)s->n_u, jobs,
-                             s->slab, s->slab_doubles, s->gb, &s->state->done, ctx->stream));
+    HIP_TRY(dmf::launch_gram(pv, s->u, n_u, jobs, s->slab, s->slab_doubles, s->gb, done, ctx->stream));
     return DMF_OK;
 }
 
@@ -151,7 +137,7 @@ static int enqueue_outer_iteration(dmf_solver* s, int n_iter2) {
     dmf_context* ctx = s->ctx;
     s->in_flight = true;
     const dmf_problem* p = s->p;
-    const int S = (int)p->S, n_c = (int)p->n_c, n_u = (int)s->n_u;
+    const int S = (int)p->S;
     // which kernels: dmf_select.hip (one table for create / enqueue / describe)
     const dmf::IterationPlan plan = dmf::plan_iteration(s->key, s->spec, n_iter2, s->purity != nullptr);
     if (plan.row == dmf::RowKind::RowpassV2) {
@@ -162,9 +148,10 @@ static int enqueue_outer_iteration(dmf_solver* s, int n_iter2) {
         bool paired = false;
         {
             FamilyScope scope(ctx, DMF_KERNEL_ROWPASS);
-            HIP_TRY(dmf::launch_rowpass_v2(p->V, p->D16, s->key.x16 ? p->X16.get() : nullptr, p->SD, p->Rtp, s->alpha, s->u,
-                                           s->u_prev, s->state, p->N, S, n_c, n_u, n_iter2, s->mode, p->ND, s->slab,
-                                           s->u2_partials, &grid, s->key.rowpass_pair, &paired, ctx->stream));
+            dmf::ProblemView pv = p->view();
+            if (!s->key.x16) pv.X16 = nullptr;
+            HIP_TRY(dmf::launch_rowpass_v2(pv, s->iterate(), n_iter2, s->scratch(), &grid, s->key.rowpass_pair, &paired,
+                                           ctx->stream));
             ++s->n_rowpass;
             s->n_rowpass_pair += paired ? 1 : 0;
         }
@@ -177,34 +164,28 @@ static int enqueue_outer_iteration(dmf_solver* s, int n_iter2) {
         DMF_TRY(ensure_split_scratch(s, n_iter2));
         {
             FamilyScope scope(ctx, DMF_KERNEL_ROWPASS);
-            HIP_TRY(dmf::launch_u_phase_split_i8_bu(p->V, p->D16, p->SD, p->ND, p->Rtp, s->alpha, s->u, s->u_prev, s->state,
-                                                    p->N, S, n_c, n_u, n_iter2, s->mode, s->cm, s->beta_tab, s->slab,
-                                                    s->u2_partials, &grid, ctx->stream));
+            HIP_TRY(dmf::launch_u_phase_split_i8_bu(p->view(), s->iterate(), n_iter2, s->scratch(), &grid, ctx->stream));
         }
         return enqueue_gram_i8_tail(s, n_iter2, grid);
     }
     if (plan.row == dmf::RowKind::RowpassFused) {
         // The fused kernel takes whole 16-row blocks; a ragged tail (< 16 rows) goes through the unfused
-        // pair on offset pointers and contributes extra slab rows and one more ||u||^2 share.
+        // pair on the rows' own views and contributes extra slab rows and one more ||u||^2 share.
         const int64_t n_full = p->N - (p->N & 15), n_tail = p->N - n_full;
-        const int nct = (n_c + 3) / 4 * 4;
+        const dmf::ProblemView pv = p->view();
         int grid = 0, ny_tail = 0;
         {
             FamilyScope scope(ctx, DMF_KERNEL_ROWPASS);
-            HIP_TRY(dmf::launch_rowpass_fused(p->V, p->D, p->Rtp, s->alpha, s->u, s->u_prev, s->state, n_full, S, n_c,
-                                              n_u, n_iter2, s->mode, s->slab, s->u2_partials, &grid, ctx->stream));
+            HIP_TRY(dmf::launch_rowpass_fused(pv.rows(0, n_full), s->iterate(), n_iter2, s->scratch(), &grid, ctx->stream));
         }
         if (n_tail > 0) {
-            const double* rt_tail = p->Rtp ? p->Rtp + n_full * nct : nullptr;
-            double* u_tail = s->u + n_full * n_u;
-            HIP_TRY(dmf::launch_u_phase_mfma(p->V + n_full * S, p->D + n_full * S, nullptr, 0, rt_tail, s->alpha, u_tail,
-                                             s->u_prev + n_full * n_u, s->state, n_tail, S, n_c, n_u, n_iter2,
-                                             s->mode, ctx->stream));
-            HIP_TRY(dmf::launch_sumsq_f64(u_tail, n_tail * n_u, ctx->scratch, s->u2_partials + grid, &s->state->done,
+            const dmf::ProblemView tail = pv.rows(n_full, n_tail);
+            const dmf::IterateView it_tail = s->iterate().rows(n_full);
+            HIP_TRY(dmf::launch_u_phase_mfma(tail, it_tail, n_iter2, ctx->stream));
+            HIP_TRY(dmf::launch_sumsq_f64(it_tail.u, n_tail * s->n_u, ctx->scratch, s->u2_partials + grid, &s->state->done,
                                           ctx->stream));
-            HIP_TRY(dmf::launch_gram_u(p->V + n_full * S, p->D + n_full * S, rt_tail, u_tail, n_tail, S, n_c, n_u,
-                                       s->slab + (int64_t)2 * grid * s->jobs.n * S, &s->state->done, &ny_tail,
-                                       ctx->stream));
+            HIP_TRY(dmf::launch_gram_u(tail, it_tail.u, it_tail.n_u, s->slab + (int64_t)2 * grid * s->jobs.n * S,
+                                       &s->state->done, &ny_tail, ctx->stream));
         }
         HIP_TRY(dmf::launch_finish_u_norm(s->u2_partials, grid + (n_tail > 0 ? 1 : 0), s->state, ctx->stream));
         {
@@ -468,7 +449,7 @@ int dmf_solver_step(dmf_solver* s, int64_t n_outer, int64_t n_iter2, double tol,
     if (s->cf_pending && tol > 0.0 && n_outer > 0) {
         // deconvolution.py:204: the cost before the loop, read by the first stop test only (a threshold of zero never fires)
         FamilyScope scope(ctx, DMF_KERNEL_COST);
-        HIP_TRY(enqueue_cost(ctx, p, s->u, s->alpha, (int)s->n_u, ctx->scratch + 1024, &s->state->cf));
+        HIP_TRY(enqueue_cost(ctx, p->view(), s->u, s->alpha, (int)s->n_u, ctx->scratch + 1024, &s->state->cf));
         s->cf_pending = false;
         s->cf_stream_iter = -2;  // (marks: state->cf of iteration 0 IS a streaming cost; resolved at the first fetch below)
     }
@@ -506,7 +487,7 @@ int dmf_solver_step(dmf_solver* s, int64_t n_outer, int64_t n_iter2, double tol,
             // The previous one is known when that iteration paused too (or was the starting point); the first
             // iteration inside the band has only the Gram form to go by.
             double cs = 0.0;
-            DMF_TRY(cost_to_host(ctx, p, s->u, s->alpha, (int)s->n_u, &cs, true));
+            DMF_TRY(cost_to_host(ctx, p->view(), s->u, s->alpha, (int)s->n_u, &cs, true));
             bool stop;
             if (s->cf_stream_iter == s->h_state->iters - 1) {
                 stop = std::fabs(cs - s->cf_stream) < tol;
@@ -552,7 +533,7 @@ int dmf_solver_get(dmf_solver* s, int flags, double* out_u, double* out_alpha, d
     DMF_TRY(export_array(ctx, s->alpha, (size_t)(p->n_c + s->n_u) * p->S * sizeof(double), flags, out_alpha));
     if (s->cf_pending && out_cost != nullptr) {  // no iteration has run: the cost of the starting point, now
         FamilyScope scope(ctx, DMF_KERNEL_COST);
-        HIP_TRY(enqueue_cost(ctx, p, s->u, s->alpha, (int)s->n_u, ctx->scratch + 1024, &s->state->cf));
+        HIP_TRY(enqueue_cost(ctx, p->view(), s->u, s->alpha, (int)s->n_u, ctx->scratch + 1024, &s->state->cf));
         s->cf_pending = false;
     }
     DMF_TRY(fetch_state(s));
@@ -564,7 +545,7 @@ int dmf_solver_get(dmf_solver* s, int flags, double* out_u, double* out_alpha, d
 int dmf_solver_cost(dmf_solver* s, double* out_cost) {
     if (s == nullptr || out_cost == nullptr) return DMF_ERR_BAD_ARG;
     DMF_TRY(check_ctx(s->ctx));
-    return cost_to_host(s->ctx, s->p, s->u, s->alpha, (int)s->n_u, out_cost, true);
+    return cost_to_host(s->ctx, s->p->view(), s->u, s->alpha, (int)s->n_u, out_cost, true);
 }
 
 int dmf_solver_cost_begin(dmf_solver* s) {
@@ -579,7 +560,7 @@ int dmf_solver_cost_begin(dmf_solver* s) {
             HIP_TRY(hipEventCreateWithFlags(&s->cost_event, hipEventDisableTiming));
         }
     }
-    DMF_TRY(cost_to_host(ctx, s->p, s->u, s->alpha, (int)s->n_u, cost_slot(s), false));
+    DMF_TRY(cost_to_host(ctx, s->p->view(), s->u, s->alpha, (int)s->n_u, cost_slot(s), false));
     HIP_TRY(hipEventRecord(s->cost_event, ctx->stream));
     s->cost_pending = true;
     return DMF_OK;
@@ -608,23 +589,17 @@ int dmf_solver_holdout_error(dmf_solver* s, const dmf_problem* full, double* sum
     *n_test = p->n_test;
     *sum_sq = 0.0;
     if (p->n_test == 0) return DMF_OK;
-    dmf_problem view;  // (borrows every array but the f64 weights)
-    view.ctx = ctx;
-    view.N = p->N;
-    view.S = p->S;
-    view.n_c = p->n_c;
-    view.V.borrow(full->V);
-    view.Rt.borrow(p->Rt);
-    view.Rtp.borrow(p->Rtp);
-    view.D16.borrow(p->W16);
-    view.SD = p->SD;
-    if (!cost_reads_u16_only(ctx, &view, (int)s->n_u)) {
-        HIP_TRY(view.D.alloc(ctx, (size_t)p->N * p->S));
-        HIP_TRY(dmf::launch_holdout_weights_f64(p->mask_bits, view.D, p->N, (int)p->S, ctx->stream));
-        view.D16.reset();
-        view.SD = 0;
+    dmf::ProblemView pv;
+    pv.N = p->N, pv.S = (int)p->S, pv.n_c = (int)p->n_c;
+    pv.V = full->V, pv.Rt = p->Rt, pv.Rtp = p->Rtp;
+    pv.D16 = p->W16, pv.SD = p->SD;
+    DevBuf<double> weights;  // (the f64 weights, where the cost kernel reads them: lives until the wait below)
+    if (!cost_reads_u16_only(ctx, pv, (int)s->n_u)) {
+        HIP_TRY(weights.alloc(ctx, (size_t)p->N * p->S));
+        HIP_TRY(dmf::launch_holdout_weights_f64(p->mask_bits, weights, p->N, (int)p->S, ctx->stream));
+        pv.D = weights, pv.D16 = nullptr, pv.SD = 0;
     }
-    return cost_to_host(ctx, &view, s->u, s->alpha, (int)s->n_u, sum_sq, true);
+    return cost_to_host(ctx, pv, s->u, s->alpha, (int)s->n_u, sum_sq, true);
 }
 
 int dmf_solver_destroy(dmf_solver* s) {

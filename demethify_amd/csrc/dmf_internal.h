@@ -64,8 +64,63 @@ struct PercentilePlan {
     int pad;
 };
 
+// ---- views: what the launch wrappers take instead of lists of pointers and sizes (plain structs, passed by const&)
+// The device arrays of a problem as the kernels read them (dmf_problem::view()).  D16 / X16 / Dt8 null: no integer copies
+// (counts as u16 [N16][SD], methylated read counts in the same layout, balanced 8-bit digit planes: see below).
+struct ProblemView {
+    const double* V = nullptr;
+    const double* D = nullptr;
+    const unsigned short* D16 = nullptr;
+    const unsigned short* X16 = nullptr;
+    const signed char* Dt8 = nullptr;
+    int64_t plane_stride = 0;
+    int SD = 0, ND = 0;
+    const double* Rt = nullptr;
+    const double* Rtp = nullptr;  // R_trunc with rows zero-padded to a multiple of 4 doubles
+    int64_t N = 0;
+    int S = 0, n_c = 0;
+    unsigned v_align() const { return (unsigned)(reinterpret_cast<uintptr_t>(V) & 15); }
+    // rows [first, first + count) through the f64 arrays alone (the integer copies are laid out in blocks of rows)
+    ProblemView rows(int64_t first, int64_t count) const {
+        ProblemView r;
+        r.V = V + first * S;
+        r.D = D + first * S;
+        r.Rt = Rt ? Rt + first * n_c : nullptr;
+        r.Rtp = Rtp ? Rtp + first * ((n_c + 3) / 4 * 4) : nullptr;
+        r.N = count;
+        r.S = S;
+        r.n_c = n_c;
+        return r;
+    }
+};
+
+// The iterate of a solver and its device state (dmf_solver::iterate()).
+struct IterateView {
+    double* u = nullptr;
+    double* u_prev = nullptr;
+    const double* alpha = nullptr;
+    SolverState* state = nullptr;
+    int n_u = 0, mode = 0;
+    IterateView rows(int64_t first) const {  // the same iterate from row `first` on
+        IterateView r = *this;
+        r.u = u + first * n_u;
+        r.u_prev = u_prev + first * n_u;
+        return r;
+    }
+};
+
+// Per-solver scratch that some u phases write: c_i / M_i per row and the momentum coefficients of the split u phase, the
+// b_u slab and the per-workgroup ||u||^2 shares of the one-launch row passes.
+struct UScratch {
+    double* cm = nullptr;
+    double* beta = nullptr;
+    double* slab = nullptr;
+    double* u2_partials = nullptr;
+};
+
 // ---- launch wrappers (dmf_kernels_*.hip) ---------------------------------------------------
-// All wrappers enqueue on `st` and return the hipGetLastError() of their launches.
+// All wrappers enqueue on `st` and return the hipGetLastError() of their launches.  Where a wrapper takes (u, n_u) beside
+// a ProblemView, they are the row features next to R_trunc: a solver's u, or none / R_trunc itself for the known block.
 
 hipError_t launch_convert_counts(const long long* src, double* dst, int64_t n, hipStream_t st);
 // max over a f64 array -> *out (device); scratch needs >= 1024 doubles
@@ -86,29 +141,23 @@ hipError_t launch_gather_rows(const double* src, double* dst, const long long* i
                               int64_t width, hipStream_t st);
 
 // direct weighted cost: *out = sum d (v - [Rt|u] alpha)^2
-hipError_t launch_cost(const double* V, const double* D, const double* Rt, const double* u,
-                       const double* alpha, int64_t N, int S, int n_c, int n_u,
-                       double* scratch, double* out, hipStream_t st);
+hipError_t launch_cost(const ProblemView& p, const double* u, const double* alpha, int n_u, double* scratch, double* out,
+                       hipStream_t st);
 
 // the same cost for n_c <= 16, n_u <= 4 with the lane's alpha column in registers: Rtp = padded R_trunc copy,
 // D16 (u16 counts, row stride SD) is read instead of D when it is not null
 bool cost_cols_supported(int S, int n_c, int n_u);
-bool cost_cols2_wide_supported(const double* V, const unsigned short* D16, int S, int SD, int n_c, int n_u);
-hipError_t launch_cost_cols2_wide(const double* V, const unsigned short* D16, int SD, const double* Rtp, const double* u,
-                                  const double* alpha, int64_t N, int S, int n_c, int n_u, double* scratch, double* out,
-                                  hipStream_t st);
+bool cost_cols2_wide_supported(const ProblemView& p, int n_u);
+hipError_t launch_cost_cols2_wide(const ProblemView& p, const double* u, const double* alpha, int n_u, double* scratch,
+                                  double* out, hipStream_t st);
 int vdv_cols_grid(int64_t N);
-hipError_t launch_vdv_cols(const double* V, const double* D, const unsigned short* D16, int SD, int64_t N, int S, double* slab,
-                           double* out, hipStream_t st);
-hipError_t launch_cost_cols(const double* V, const double* D, const unsigned short* D16, int SD, const double* Rtp,
-                            const double* u, const double* alpha, int64_t N, int S, int n_c, int n_u, double* scratch,
-                            double* out, hipStream_t st);
+hipError_t launch_vdv_cols(const ProblemView& p, double* slab, double* out, hipStream_t st);
+hipError_t launch_cost_cols(const ProblemView& p, const double* u, const double* alpha, int n_u, double* scratch, double* out,
+                            hipStream_t st);
 
 // generic weighted Gram accumulation over the extended row vector x = (Rt, u, v)
-hipError_t launch_gram(const double* V, const double* D, const double* Rt, const double* u,
-                       int64_t N, int S, int n_c, int n_u, GramJobTable jobs,
-                       double* slab, int64_t slab_doubles, double* gb, const int* done_flag,
-                       hipStream_t st);
+hipError_t launch_gram(const ProblemView& p, const double* u, int n_u, GramJobTable jobs, double* slab, int64_t slab_doubles,
+                       double* gb, const int* done_flag, hipStream_t st);
 int64_t gram_slab_doubles(int64_t N, int S, int n_jobs);
 hipError_t launch_gram_reduce(const double* slab, int ny, int n_jobs, int S, const int* dst_row,
                               double* gb, const int* done_flag, hipStream_t st);
@@ -116,38 +165,27 @@ hipError_t launch_gram_reduce(const double* slab, int ny, int n_jobs, int S, con
 // Rtp = R_trunc with rows zero-padded to a multiple of 4 doubles (dmf_problem::Rtp).
 bool gram_u_supported(int n_c, int n_u);
 int64_t gram_u_slab_doubles(int64_t N, int S, int n_c, int n_u);
-hipError_t launch_gram_u(const double* V, const double* D, const double* Rtp, const double* u, int64_t N,
-                         int S, int n_c, int n_u, double* slab, const int* done_flag, int* ny_out,
+hipError_t launch_gram_u(const ProblemView& p, const double* u, int n_u, double* slab, const int* done_flag, int* ny_out,
                          hipStream_t st);
 
 // u phase, Gram form (n_u <= 8): all n_iter2 inner iterations in one launch
-hipError_t launch_u_phase_gram(const double* V, const double* D, const double* Rt,
-                               const double* alpha, double* u, double* u_prev,
-                               const SolverState* state, int64_t N, int S, int n_c, int n_u,
-                               int n_iter2, int mode, hipStream_t st);
+hipError_t launch_u_phase_gram(const ProblemView& p, const IterateView& it, int n_iter2, hipStream_t st);
 bool u_phase_gram_supported(int S, int n_c, int n_u);
-// u phase on the FP64 matrix cores (n_u <= 8, n_c <= 16, S <= 512); takes the padded Rtp as well
+// u phase on the FP64 matrix cores (n_u <= 8, n_c <= 16, S <= 512); reads the padded Rtp, and D16 where there is one
 bool u_phase_mfma_supported(int S, int n_c, int n_u);
-hipError_t launch_u_phase_mfma(const double* V, const double* D, const unsigned short* D16, int SD, const double* Rtp,
-                               const double* alpha, double* u, double* u_prev, const SolverState* state, int64_t N, int S,
-                               int n_c, int n_u, int n_iter2, int mode, hipStream_t st);
+hipError_t launch_u_phase_mfma(const ProblemView& p, const IterateView& it, int n_iter2, hipStream_t st);
 // fused row pass: u phase + u-dependent Gram slab + ||u||^2 / l_h in one read of V and D
 // (S % 4 == 0, S <= 256, n_c <= 16, n_u <= 8, accumulators <= 80, counts exact in f32);
-// grid_out = workgroups launched; the slab holds 2 rows per workgroup
+// grid_out = workgroups launched; the slab (scratch.slab, with scratch.u2_partials) holds 2 rows per workgroup
 bool rowpass_fused_supported(int S, int n_c, int n_u);
 int rowpass_fused_grid(int64_t N, int S);
 int64_t rowpass_fused_slab_doubles(int64_t N, int S, int n_c, int n_u);
-hipError_t launch_rowpass_fused(const double* V, const double* D, const double* Rtp, const double* alpha,
-                                double* u, double* u_prev, SolverState* state, int64_t N, int S, int n_c,
-                                int n_u, int n_iter2, int mode, double* slab, double* u2_partials,
+hipError_t launch_rowpass_fused(const ProblemView& p, const IterateView& it, int n_iter2, const UScratch& scratch,
                                 int* grid_out, hipStream_t st);
 // sum of the fused kernel's per-workgroup ||u||^2 shares -> state->u_norm2 and l_h (deconvolution.py:212)
 hipError_t launch_finish_u_norm(const double* u2_partials, int n, SolverState* state, hipStream_t st);
-// u phase, schedule-faithful fallback: ONE inner iteration (index t) per launch
-hipError_t launch_u_step_direct(const double* V, const double* D, const double* Rt,
-                                const double* alpha, const double* u_cur, const double* u_prev,
-                                double* u_next, const SolverState* state, int64_t N, int S,
-                                int n_c, int n_u, int t, int mode, hipStream_t st);
+// u phase, schedule-faithful fallback: ONE inner iteration (index t) per launch, from (it.u, it.u_prev) into u_next
+hipError_t launch_u_step_direct(const ProblemView& p, const IterateView& it, double* u_next, int t, hipStream_t st);
 bool u_step_direct_supported(int S, int n_c, int n_u);
 
 // alpha phase on the packed Gram buffer gb[(K+1)(K+2)/2][S]
@@ -168,42 +206,33 @@ hipError_t launch_init_state(SolverState* state, const double* consts, const dou
                              int S, int n_c, int n_u, hipStream_t st);
 
 // the same u phase in two launches for many inner steps: c_i / M_i per row to `cm`, then inner iterations with
-// every lane busy; cm holds u_phase_split_cm_doubles(N, n_u) doubles, beta n_iter2 doubles (<= 6144)
+// every lane busy; scratch.cm holds u_phase_split_cm_doubles(N, n_u) doubles, scratch.beta n_iter2 doubles
 int64_t u_phase_split_cm_doubles(int64_t N, int n_u);
-hipError_t launch_u_phase_split(const double* V, const double* D, const unsigned short* D16, int SD, const double* Rtp,
-                                const double* alpha, double* u, double* u_prev, const SolverState* state, int64_t N, int S,
-                                int n_c, int n_u, int n_iter2, int mode, double* cm, double* beta, hipStream_t st);
+hipError_t launch_u_phase_split(const ProblemView& p, const IterateView& it, int n_iter2, const UScratch& scratch,
+                                hipStream_t st);
 
 // split u phase whose producer runs M_i on the integer matrix cores (dmf_kernels_cm_i8.hip): n_u <= 16, 2 <= S <= 2048
-// (panels of 256 samples), u16 counts with ND digit planes, alpha in [0, 1]
-bool cm_i8_supported(const double* V, int S, int n_c, int n_u, int ND, int SD);
-hipError_t launch_cm_i8(const double* V, const unsigned short* D16, int SD, int ND, const double* Rtp, const double* alpha,
-                        const SolverState* state, int64_t N, int S, int n_c, int n_u, double* cm, hipStream_t st);
-hipError_t launch_u_phase_split_i8(const double* V, const unsigned short* D16, int SD, int ND, const double* Rtp,
-                                   const double* alpha, double* u, double* u_prev, const SolverState* state, int64_t N,
-                                   int S, int n_c, int n_u, int n_iter2, int mode, double* cm, double* beta,
+// (panels of 256 samples), u16 counts with ND digit planes, alpha in [0, 1]; v_align = ProblemView::v_align()
+bool cm_i8_supported(unsigned v_align, int S, int n_c, int n_u, int ND, int SD);
+hipError_t launch_cm_i8(const ProblemView& p, const IterateView& it, double* cm, hipStream_t st);
+hipError_t launch_u_phase_split_i8(const ProblemView& p, const IterateView& it, int n_iter2, const UScratch& scratch,
                                    hipStream_t st);
 
-// ... and with the inner iterations fused with the b_u stream of the integer Gram route (k_inner_bu): slab holds
-// u_inner_bu_grid(N, S) x n_u x S doubles, u2_partials one double per workgroup (their count comes back in grid_out)
-bool u_inner_bu_supported(const double* V, int S, int SD, int n_u, int n_iter2);
+// ... and with the inner iterations fused with the b_u stream of the integer Gram route (k_inner_bu): scratch.slab holds
+// u_inner_bu_grid(N, S) x n_u x S doubles, scratch.u2_partials one double per workgroup (their count comes back in grid_out)
+bool u_inner_bu_supported(unsigned v_align, int S, int SD, int n_u, int n_iter2);
 int u_inner_bu_grid(int64_t N, int S);
-hipError_t launch_u_phase_split_i8_bu(const double* V, const unsigned short* D16, int SD, int ND, const double* Rtp,
-                                      const double* alpha, double* u, double* u_prev, const SolverState* state, int64_t N,
-                                      int S, int n_c, int n_u, int n_iter2, int mode, double* cm, double* beta,
-                                      double* slab, double* u2_partials, int* grid_out, hipStream_t st);
+hipError_t launch_u_phase_split_i8_bu(const ProblemView& p, const IterateView& it, int n_iter2, const UScratch& scratch,
+                                      int* grid_out, hipStream_t st);
 
 // u phase for 9 <= n_u <= 26 unknown types on the matrix cores (dmf_kernels_rowpass_big.hip); Rtp = padded R_trunc
 bool u_phase_big_supported(int S, int n_c, int n_u, int n_iter2);
-hipError_t launch_u_phase_big(const double* V, const double* D, const double* Rtp, const double* alpha, double* u,
-                              double* u_prev, const SolverState* state, int64_t N, int S, int n_c, int n_u,
-                              int n_iter2, int mode, hipStream_t st);
+hipError_t launch_u_phase_big(const ProblemView& p, const IterateView& it, int n_iter2, hipStream_t st);
 
 // any-shape Gram accumulation on the matrix cores (dmf_kernels_gram_mfma.hip): jobs [0, n_dense) have l < K,
 // the rest are the "v" column; the slab ([ny][count][S]) is then summed by launch_gram_reduce
-hipError_t launch_gram_mfma(const double* V, const double* D, const double* Rt, const double* u, int64_t N, int S,
-                            int n_c, int n_u, GramJobTable jobs, int n_dense, double* slab, int64_t slab_doubles,
-                            const int* done_flag, int* ny_out, hipStream_t st);
+hipError_t launch_gram_mfma(const ProblemView& p, const double* u, int n_u, GramJobTable jobs, int n_dense, double* slab,
+                            int64_t slab_doubles, const int* done_flag, int* ny_out, hipStream_t st);
 int64_t gram_mfma_slab_doubles(int64_t N, int S, int n_jobs);
 
 // ---- second-generation row pass (dmf_kernels_rowpass2.hip) + integer-matrix-core Gram (dmf_kernels_gram_i8.hip)
@@ -237,13 +266,11 @@ hipError_t launch_mask_problem(const double* srcV, const double* srcD, const uns
 hipError_t launch_holdout_weights_f64(const unsigned char* bits, double* W, int64_t N, int S, hipStream_t st);
 bool rowpass_v2_supported(int S, int n_c, int n_u, int n_iter2);
 int rowpass_v2_grid(int64_t N, int S);
-// u phase + b_u slab ([grid][n_u][S] doubles) + per-workgroup ||u||^2 shares in one read of V (f64) and D16 -- or, when
-// X16 is not null, of X16 and D16 (V is not read).  pair: two blocks per phase B where the X16 form allows it
-// (rowpass_v2_pair_fits); the same results bit for bit.  *paired_out (may be null): whether the pair schedule was launched
-hipError_t launch_rowpass_v2(const double* V, const unsigned short* D16, const unsigned short* X16, int SD,
-                             const double* Rtp, const double* alpha, double* u, double* u_prev, SolverState* state, int64_t N,
-                             int S, int n_c, int n_u, int n_iter2, int mode, int nd, double* slab, double* u2_partials,
-                             int* grid_out, bool pair, bool* paired_out, hipStream_t st);
+// u phase + b_u slab (scratch.slab: [grid][n_u][S] doubles) + per-workgroup ||u||^2 shares in one read of V (f64) and
+// D16 -- or, when p.X16 is not null, of X16 and D16 (V is not read).  pair: two blocks per phase B where the X16 form allows
+// it (rowpass_v2_pair_fits); the same results bit for bit.  *paired_out (may be null): whether the pair schedule was launched
+hipError_t launch_rowpass_v2(const ProblemView& p, const IterateView& it, int n_iter2, const UScratch& scratch, int* grid_out,
+                             bool pair, bool* paired_out, hipStream_t st);
 // the X16 row pass can run two blocks per phase B at this shape: 2..4 waves, and the grid's workgroups per CU fit the LDS
 bool rowpass_v2_pair_fits(int S, int n_u, int n_iter2);
 bool gram_i8_supported(int n_c, int n_u, int ND, int64_t N, int SD);
@@ -256,13 +283,12 @@ int64_t gram_i8_acc_words_nf(int S, int nf, int n_bu);
 // exact cross / uu Gram entries: features p = (feat_a[p], feat_b[p]) over x = (Rt, u), i64 slab [ny][2][slots][SD];
 // Rtp = the padded R_trunc copy (rows of 4 ceil(n_c / 4) doubles); Rtp, u, Dt8 16-byte aligned, u allocated to a
 // multiple of 16 bytes
-hipError_t launch_gram_i8(const signed char* Dt8, int64_t plane_stride, int SD, int ND, const double* Rtp, const double* u,
-                          int64_t N, int n_c, int n_u, const short* feat_a, const short* feat_b, int NF, long long* slab,
-                          int64_t slab_words, const int* done_flag, int* ny_out, hipStream_t st);
+hipError_t launch_gram_i8(const ProblemView& p, const double* u, int n_u, const short* feat_a, const short* feat_b, int NF,
+                          long long* slab, int64_t slab_words, const int* done_flag, int* ny_out, hipStream_t st);
 // b_u alone (for u phases that are kernels of their own): slab [n_slabs][n_u][S] doubles, n_u <= 20
 int bu_cols_grid(int64_t N);
-hipError_t launch_bu_cols(const double* V, const unsigned short* D16, int SD, const double* u, int64_t N, int S, int n_u,
-                          double* slab, const int* done_flag, int* n_slabs_out, hipStream_t st, bool* with_vdv = nullptr);
+hipError_t launch_bu_cols(const ProblemView& p, const double* u, int n_u, double* slab, const int* done_flag,
+                          int* n_slabs_out, hipStream_t st, bool* with_vdv = nullptr);
 // gb rows of the u-dependent jobs from the i64 slab (jobs < NF) and the row pass's b_u slabs (jobs NF .. NF + n_u);
 // acc_words: gram_i8_acc_words() i64 words, all zero before the first call (the kernels leave them zero again);
 // u2_partials != null: the finish kernel also sums the row pass's ||u||^2 shares into state (u_norm2, l_h)

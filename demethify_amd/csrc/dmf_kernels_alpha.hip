@@ -6,6 +6,7 @@
 // are b_s = R^T (d_s * v_s), row tri(K,K) is v_s^T D_s v_s.  With them
 //     R^T (d_s * (v_s - R a)) = b_s - G_s a,      cost_s = vDv_s - 2 a.b_s + a^T G_s a.
 #include "dmf_device.h"
+#include "dmf_dispatch.h"
 #include "dmf_internal.h"
 
 namespace dmf {
@@ -314,8 +315,7 @@ static hipError_t launch_alpha_t(const double* gb, double* alpha, double* alpha_
     const size_t lds = (size_t)(K + 1) * (K + 2) / 2 * 64 * sizeof(double);
     const int in_lds = lds <= 150 * 1024;
     if (in_lds && lds > 48 * 1024) {
-        hipError_t e = hipFuncSetAttribute((const void*)k_alpha_phase<KMAX>,
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        const hipError_t e = raise_dynamic_lds<k_alpha_phase<KMAX>>(lds);
         if (e != hipSuccess) return e;
     }
     hipLaunchKernelGGL(k_alpha_phase<KMAX>, dim3(nb), dim3(64), in_lds ? lds : 0, st, gb, alpha,

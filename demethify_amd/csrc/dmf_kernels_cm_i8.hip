@@ -26,6 +26,7 @@
 
 #include "dmf_device.h"
 #include "dmf_fixedpoint.h"
+#include "dmf_dispatch.h"
 #include "dmf_internal.h"
 
 namespace dmf {
@@ -378,68 +379,20 @@ __global__ __launch_bounds__(512) void k_cm_i8(const double* __restrict__ V, con
 
 constexpr int kCmPanel = 256;  // samples per launch
 
-bool cm_i8_supported(const double* V, int S, int n_c, int n_u, int ND, int SD) {
+bool cm_i8_supported(unsigned v_align, int S, int n_c, int n_u, int ND, int SD) {
     if (n_u < 1 || n_u > 32 || n_c < 0 || n_c > 4 * kCmNkcWide || n_c + n_u > 64) return false;
     if (S < 2 || S > 2048 || (SD & 3) != 0 || SD < (S + 63) / 64 * 64) return false;
     if (ND != 1 && ND != 2) return false;
-    if ((reinterpret_cast<uintptr_t>(V) & 7) != 0) return false;
+    if ((v_align & 7) != 0) return false;
     return cm_layout(S < kCmPanel ? S : kCmPanel, n_c, n_u, 1).bytes <= 160 * 1024;  // (at least one pair tile per launch)
-}
-
-template <int NKC, int ND, int NCGX, bool S4>
-static hipError_t launch_cm_t(const double* V, const unsigned short* D16, int SD, const double* Rtp, const double* alpha,
-                              const SolverState* state, int64_t N, int S, int n_c, int n_u, double* cm, int col0, int Sp,
-                              int c_tile, int c_store, int mt0, int mt1, hipStream_t st) {
-    const size_t lds = cm_layout(Sp, n_c, n_u, mt1 - mt0).bytes;
-    static bool raised[64] = {};
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) dev = 0;
-    if (!raised[dev]) {
-        hipError_t e = hipFuncSetAttribute((const void*)k_cm_i8<NKC, ND, NCGX, S4>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                           160 * 1024);
-        if (e != hipSuccess) return e;
-        raised[dev] = true;
-    }
-    const int64_t nblk = (N + 31) / 32;
-    const int64_t want = (nblk + kCmWaves - 1) / kCmWaves;
-    // one workgroup (two waves per SIMD at ~200 registers) per CU, two where the tables leave room
-    int per_cu = lds <= 76 * 1024 ? 2 : 1;
-#ifdef DMF_EXPERIMENT  // (an experiment build only: DMF_EXPERIMENT=1 python -m demethify_amd._build)
-    if (const char* v = getenv("DMF_CM_PER_CU")) per_cu = atoi(v) > 0 ? atoi(v) : per_cu;  // (experiments)
-#endif
-    const int64_t cap = (int64_t)256 * per_cu;
-    const int64_t grid = want < cap ? want : cap;
-    hipLaunchKernelGGL((k_cm_i8<NKC, ND, NCGX, S4>), dim3((unsigned)grid), dim3(kCmWaves * 64), lds, st, V, D16, SD, Rtp, alpha,
-                       state, N, S, n_c, n_u, cm, col0, Sp, col0 > 0 ? 1 : 0, c_tile, c_store, mt0, mt1);
-    return hipGetLastError();
-}
-
-template <int NKC>
-static hipError_t launch_cm_nkc(const double* V, const unsigned short* D16, int SD, int ND, const double* Rtp,
-                                const double* alpha, const SolverState* state, int64_t N, int S, int n_c, int n_u,
-                                double* cm, int col0, int Sp, int c_tile, int c_store, int mt0, int mt1, hipStream_t st) {
-    const bool wide = Sp > 128;
-    const bool s4 = (Sp & 3) == 0 && (S & 1) == 0;  // (odd S: rows of V are 8-byte aligned only)
-#define DMF_CM(ND_, NCGX_)                                                                                                  \
-    return s4 ? launch_cm_t<NKC, ND_, NCGX_, true>(V, D16, SD, Rtp, alpha, state, N, S, n_c, n_u, cm, col0, Sp, c_tile,      \
-                                                   c_store, mt0, mt1, st)                                                   \
-              : launch_cm_t<NKC, ND_, NCGX_, false>(V, D16, SD, Rtp, alpha, state, N, S, n_c, n_u, cm, col0, Sp, c_tile,     \
-                                                    c_store, mt0, mt1, st)
-    if (ND == 1) {
-        if (wide) DMF_CM(1, 4);
-        DMF_CM(1, 2);
-    }
-    if (wide) DMF_CM(2, 4);
-    DMF_CM(2, 2);
-#undef DMF_CM
 }
 
 // cm: N x (n_u + n_u (n_u + 1) / 2) doubles.  Preconditions (cm_i8_supported + the caller): counts integral in
 // [0, 127] (ND = 1) or [0, 32639] (ND = 2) in D16 (row stride SD, zero padded to a multiple of 64 samples, rows to a
 // multiple of 16), alpha in [0, 1], Rtp = padded R_trunc (row stride 4 ceil(n_c / 4)).
-hipError_t launch_cm_i8(const double* V, const unsigned short* D16, int SD, int ND, const double* Rtp, const double* alpha,
-                        const SolverState* state, int64_t N, int S, int n_c, int n_u, double* cm, hipStream_t st) {
-    if (!cm_i8_supported(V, S, n_c, n_u, ND, SD) || cm == nullptr || D16 == nullptr) return hipErrorInvalidValue;
+hipError_t launch_cm_i8(const ProblemView& p, const IterateView& it, double* cm, hipStream_t st) {
+    const int S = p.S, n_c = p.n_c, n_u = it.n_u;
+    if (!cm_i8_supported(p.v_align(), S, n_c, n_u, p.ND, p.SD) || cm == nullptr || p.D16 == nullptr) return hipErrorInvalidValue;
     const int nmt = (n_u * (n_u + 1) / 2 + 15) / 16, n_ct = (n_u + 15) / 16;
     for (int col0 = 0; col0 < S; col0 += kCmPanel) {  // panels of 256 samples; the second and later ones add to cm
         const int Sp = S - col0 < kCmPanel ? S - col0 : kCmPanel;
@@ -449,20 +402,36 @@ hipError_t launch_cm_i8(const double* V, const unsigned short* D16, int SD, int 
         int n_launch = (nmt + tpl - 1) / tpl;
         if (n_launch < n_ct) n_launch = n_ct;
         tpl = (nmt + n_launch - 1) / n_launch;
+        const bool s4 = (Sp & 3) == 0 && (S & 1) == 0;  // (odd S: rows of V are 8-byte aligned only)
         for (int li = 0; li < n_launch; ++li) {
             const int mt0 = li * tpl < nmt ? li * tpl : nmt, mt1 = mt0 + tpl < nmt ? mt0 + tpl : nmt;
             const int c_tile = li < n_ct ? li : n_ct - 1, c_store = li < n_ct ? 1 : 0;
-            hipError_t e;
-            switch ((n_c + 3) / 4) {
-#define DMF_NKC(X_) e = launch_cm_nkc<X_>(V, D16, SD, ND, Rtp, alpha, state, N, S, n_c, n_u, cm, col0, Sp, c_tile, c_store, mt0, mt1, st)
-                case 0: DMF_NKC(0); break;
-                case 1: DMF_NKC(1); break;
-                case 2: DMF_NKC(2); break;
-                case 3: DMF_NKC(3); break;
-                case 4: DMF_NKC(4); break;
-                default: DMF_NKC(kCmNkcWide); break;
-#undef DMF_NKC
-            }
+            const size_t lds = cm_layout(Sp, n_c, n_u, mt1 - mt0).bytes;
+            const int64_t nblk = (p.N + 31) / 32;
+            const int64_t want = (nblk + kCmWaves - 1) / kCmWaves;
+            // one workgroup (two waves per SIMD at ~200 registers) per CU, two where the tables leave room
+            const int64_t cap = (int64_t)256 * per_cu_knob("DMF_CM_PER_CU", lds <= 76 * 1024 ? 2 : 1);
+            const int64_t grid = want < cap ? want : cap;
+            // template parameters: known-type chunks (beyond four: kCmNkcWide), digit planes, column groups (four on panels
+            // of more than 128 samples, else two), whole float4 columns
+            const auto launch = [&](auto nkc) {
+                return dispatch_int<1, 2>(p.ND, [&](auto nd) {
+                    return dispatch_bool(Sp > 128, [&](auto wide) {
+                        return dispatch_bool(s4, [&](auto s4_t) {
+                            constexpr auto kernel = k_cm_i8<decltype(nkc)::value, decltype(nd)::value,
+                                                            decltype(wide)::value ? 4 : 2, decltype(s4_t)::value>;
+                            const hipError_t e = raise_dynamic_lds<kernel>(160 * 1024);
+                            if (e != hipSuccess) return e;
+                            hipLaunchKernelGGL(kernel, dim3((unsigned)grid), dim3(kCmWaves * 64), lds, st, p.V, p.D16, p.SD, p.Rtp,
+                                               it.alpha, it.state, p.N, S, n_c, n_u, cm, col0, Sp, col0 > 0 ? 1 : 0, c_tile,
+                                               c_store, mt0, mt1);
+                            return hipGetLastError();
+                        });
+                    });
+                });
+            };
+            const int nkc = (n_c + 3) / 4;
+            const hipError_t e = nkc <= 4 ? dispatch_int<0, 4>(nkc, launch) : launch(std::integral_constant<int, kCmNkcWide>{});
             if (e != hipSuccess) return e;
         }
     }

@@ -19,6 +19,7 @@
 // the unfused kernels), S % 4 == 0, S <= 256, n_c <= 16, n_u <= 4, counts exactly representable in f32;
 // `Rtp` is the problem's zero-padded copy of R_trunc (row stride 4 NKC).
 #include "dmf_device.h"
+#include "dmf_dispatch.h"
 #include "dmf_internal.h"
 #include "dmf_phaseb.h"
 
@@ -572,68 +573,34 @@ int64_t rowpass_fused_slab_doubles(int64_t N, int S, int n_c, int n_u) {
     return (int64_t)2 * rowpass_fused_grid(N, S) * (n_c * n_u + n_u * (n_u + 1) / 2 + n_u) * S;
 }
 
-template <int NKC, int NU>
-static hipError_t launch_fused_t(const double* V, const double* D, const double* Rtp, const double* alpha,
-                                 double* u, double* u_prev, SolverState* state, int64_t N, int S, int n_c,
-                                 int n_iter2, int mode, double* slab, double* u2_partials, int* grid_out,
-                                 hipStream_t st) {
-    if constexpr (4 * NKC * NU + NU * (NU + 1) / 2 + NU > 80) {
-        return hipErrorInvalidValue;
-    } else {
-        const int NW = (S + 63) / 64;
-        const size_t lds = fused_lds_bytes(S, 4 * NKC, NU, n_iter2);
-        if (lds > 160 * 1024 || (N & 15) != 0 || N < 16) return hipErrorInvalidValue;
-        // raise the dynamic-LDS limit once per (instantiation, device): this launch sits in the per-iteration loop
-        static bool lds_limit_raised[64] = {};
-        int dev = 0;
-        if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) dev = 0;
-        if (lds > 48 * 1024 && !lds_limit_raised[dev]) {
-            hipError_t e = hipFuncSetAttribute((const void*)k_rowpass_fused<NKC, NU>,
-                                               hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-            if (e != hipSuccess) return e;
-            lds_limit_raised[dev] = true;
-        }
-        const int grid = rowpass_fused_grid(N, S);
-        *grid_out = grid;
-        hipLaunchKernelGGL((k_rowpass_fused<NKC, NU>), dim3(grid), dim3(DMF_WAVES_PER_WG(NW) * 64), lds, st, V, D, Rtp, alpha, u,
-                           u_prev, state, N, S, n_c, n_iter2, mode, slab, u2_partials
-#ifdef DMF_STAMPS
-                           , (unsigned long long*)nullptr
-#endif
-                           );
-        return hipGetLastError();
-    }
-}
-
-template <int NKC>
-static hipError_t launch_fused_nkc(int n_u, const double* V, const double* D, const double* Rtp,
-                                   const double* alpha, double* u, double* u_prev, SolverState* state,
-                                   int64_t N, int S, int n_c, int n_iter2, int mode, double* slab,
-                                   double* u2_partials, int* grid_out, hipStream_t st) {
-    switch (n_u) {
-#define DMF_CASE(NU_)                                                                                      \
-    case NU_:                                                                                              \
-        return launch_fused_t<NKC, NU_>(V, D, Rtp, alpha, u, u_prev, state, N, S, n_c, n_iter2, mode, slab, \
-                                        u2_partials, grid_out, st);
-        DMF_CASE(1) DMF_CASE(2) DMF_CASE(3) DMF_CASE(4)
-#undef DMF_CASE
-        default: return hipErrorInvalidValue;
-    }
-}
-
-hipError_t launch_rowpass_fused(const double* V, const double* D, const double* Rtp, const double* alpha,
-                                double* u, double* u_prev, SolverState* state, int64_t N, int S, int n_c,
-                                int n_u, int n_iter2, int mode, double* slab, double* u2_partials,
+hipError_t launch_rowpass_fused(const ProblemView& p, const IterateView& it, int n_iter2, const UScratch& scratch,
                                 int* grid_out, hipStream_t st) {
-    switch ((n_c + 3) / 4) {
-#define DMF_NKC(X)                                                                                          \
-    case X:                                                                                                 \
-        return launch_fused_nkc<X>(n_u, V, D, Rtp, alpha, u, u_prev, state, N, S, n_c, n_iter2, mode, slab, \
-                                   u2_partials, grid_out, st);
-        DMF_NKC(0) DMF_NKC(1) DMF_NKC(2) DMF_NKC(3) DMF_NKC(4)
-#undef DMF_NKC
-        default: return hipErrorInvalidValue;
-    }
+    return dispatch_int<0, 4>((p.n_c + 3) / 4, [&](auto nkc) {
+        return dispatch_int<1, 4>(it.n_u, [&](auto nu) {
+            constexpr int NKC = decltype(nkc)::value, NU = decltype(nu)::value;
+            if constexpr (4 * NKC * NU + NU * (NU + 1) / 2 + NU > 80) {
+                return hipErrorInvalidValue;
+            } else {
+                const int S = p.S, NW = (S + 63) / 64;
+                const size_t lds = fused_lds_bytes(S, 4 * NKC, NU, n_iter2);
+                if (lds > 160 * 1024 || (p.N & 15) != 0 || p.N < 16) return hipErrorInvalidValue;
+                if (lds > 48 * 1024) {
+                    const hipError_t e = raise_dynamic_lds<k_rowpass_fused<NKC, NU>>(160 * 1024);
+                    if (e != hipSuccess) return e;
+                }
+                const int grid = rowpass_fused_grid(p.N, S);
+                *grid_out = grid;
+                hipLaunchKernelGGL((k_rowpass_fused<NKC, NU>), dim3(grid), dim3(DMF_WAVES_PER_WG(NW) * 64), lds, st, p.V, p.D,
+                                   p.Rtp, it.alpha, it.u, it.u_prev, it.state, p.N, S, p.n_c, n_iter2, it.mode, scratch.slab,
+                                   scratch.u2_partials
+#ifdef DMF_STAMPS
+                                   , (unsigned long long*)nullptr
+#endif
+                                   );
+                return hipGetLastError();
+            }
+        });
+    });
 }
 
 }  // namespace dmf

@@ -9,6 +9,7 @@
 //     bu[j]       += d * v * u_ij            (NU)
 // Job order of the slab = the solver's job table (dmf_api_solver.hip: l = n_c..K, k <= l).
 #include "dmf_device.h"
+#include "dmf_dispatch.h"
 #include "dmf_internal.h"
 
 namespace dmf {
@@ -146,49 +147,24 @@ int64_t gram_u_slab_doubles(int64_t N, int S, int n_c, int n_u) {
     return (int64_t)ny * (n_c * n_u + n_u * (n_u + 1) / 2 + n_u) * S;
 }
 
-template <int NCT, int NU>
-static hipError_t launch_gram_u_t(const double* V, const double* D, const double* Rt, const double* u,
-                                  int64_t N, int S, int n_c, double* slab, const int* done_flag,
-                                  int* ny_out, hipStream_t st) {
-    int nsx, ny;
-    int64_t rpc;
-    gram_u_geometry(N, S, &nsx, &ny, &rpc);
-    *ny_out = ny;
-    hipLaunchKernelGGL((k_gram_u<NCT, NU>), dim3(nsx, ny), dim3(256), 0, st, V, D, Rt, u, N, S, n_c, rpc, slab,
-                       done_flag);
-    return hipGetLastError();
-}
-
-template <int NCT>
-static hipError_t launch_gram_u_nct(int n_u, const double* V, const double* D, const double* Rt,
-                                    const double* u, int64_t N, int S, int n_c, double* slab,
-                                    const int* done_flag, int* ny_out, hipStream_t st) {
-    switch (n_u) {
-#define DMF_CASE(NU_)                                                                       \
-    case NU_:                                                                               \
-        if constexpr (NCT * NU_ + NU_ * (NU_ + 1) / 2 + NU_ <= 112)                          \
-            return launch_gram_u_t<NCT, NU_>(V, D, Rt, u, N, S, n_c, slab, done_flag, ny_out, st); \
-        else                                                                                \
-            return hipErrorInvalidValue;
-        DMF_CASE(1) DMF_CASE(2) DMF_CASE(3) DMF_CASE(4) DMF_CASE(5) DMF_CASE(6) DMF_CASE(7) DMF_CASE(8)
-        DMF_CASE(9) DMF_CASE(10) DMF_CASE(11) DMF_CASE(12) DMF_CASE(13)
-#undef DMF_CASE
-        default: return hipErrorInvalidValue;
-    }
-}
-
-hipError_t launch_gram_u(const double* V, const double* D, const double* Rt, const double* u, int64_t N,
-                         int S, int n_c, int n_u, double* slab, const int* done_flag, int* ny_out,
+hipError_t launch_gram_u(const ProblemView& p, const double* u, int n_u, double* slab, const int* done_flag, int* ny_out,
                          hipStream_t st) {
-    const int nct = (n_c + 3) / 4 * 4;
-    switch (nct) {
-        case 0: return launch_gram_u_nct<0>(n_u, V, D, Rt, u, N, S, n_c, slab, done_flag, ny_out, st);
-        case 4: return launch_gram_u_nct<4>(n_u, V, D, Rt, u, N, S, n_c, slab, done_flag, ny_out, st);
-        case 8: return launch_gram_u_nct<8>(n_u, V, D, Rt, u, N, S, n_c, slab, done_flag, ny_out, st);
-        case 12: return launch_gram_u_nct<12>(n_u, V, D, Rt, u, N, S, n_c, slab, done_flag, ny_out, st);
-        case 16: return launch_gram_u_nct<16>(n_u, V, D, Rt, u, N, S, n_c, slab, done_flag, ny_out, st);
-        default: return hipErrorInvalidValue;
-    }
+    return dispatch_int<0, 4>((p.n_c + 3) / 4, [&](auto nkc) {
+        return dispatch_int<1, 13>(n_u, [&](auto nu) {
+            constexpr int NCT = 4 * decltype(nkc)::value, NU = decltype(nu)::value;
+            if constexpr (NCT * NU + NU * (NU + 1) / 2 + NU <= 112) {
+                int nsx, ny;
+                int64_t rpc;
+                gram_u_geometry(p.N, p.S, &nsx, &ny, &rpc);
+                *ny_out = ny;
+                hipLaunchKernelGGL((k_gram_u<NCT, NU>), dim3(nsx, ny), dim3(256), 0, st, p.V, p.D, p.Rtp, u, p.N, p.S, p.n_c, rpc,
+                                   slab, done_flag);
+                return hipGetLastError();
+            } else {
+                return hipErrorInvalidValue;
+            }
+        });
+    });
 }
 
 }  // namespace dmf

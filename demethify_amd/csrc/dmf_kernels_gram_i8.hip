@@ -25,6 +25,7 @@
 #include <cstdlib>
 
 #include "dmf_device.h"
+#include "dmf_dispatch.h"
 #include "dmf_internal.h"
 #include "dmf_fixedpoint.h"
 
@@ -721,37 +722,27 @@ int bu_cols_grid(int64_t N) {
 
 // with_vdv (may be null): in: the caller would like sum_i d v^2 as one more slab row per workgroup (slab rows n_u + 1);
 // out: whether the kernel chosen for this shape delivers it.
-hipError_t launch_bu_cols(const double* V, const unsigned short* D16, int SD, const double* u, int64_t N, int S, int n_u,
-                          double* slab, const int* done_flag, int* n_slabs_out, hipStream_t st, bool* with_vdv) {
-    const int nbx = bu_cols_grid(N);
+hipError_t launch_bu_cols(const ProblemView& p, const double* u, int n_u, double* slab, const int* done_flag,
+                          int* n_slabs_out, hipStream_t st, bool* with_vdv) {
+    const int S = p.S, nbx = bu_cols_grid(p.N);
     *n_slabs_out = nbx;
     const dim3 block(256);
-    const bool two = (SD & 1) == 0 && S >= 128 && n_u <= 16 && (reinterpret_cast<uintptr_t>(V) & 7) == 0;
+    const bool two = (p.SD & 1) == 0 && S >= 128 && n_u <= 16 && (p.v_align() & 7) == 0;
     const int vdv = (with_vdv != nullptr && *with_vdv && two) ? 1 : 0;
     if (with_vdv != nullptr) *with_vdv = vdv != 0;
-    if (two) {
+    if (two && n_u >= 1) {  // (LDS for the cross-wave sum: 3 x NU x 2 x 64 doubles = 48 KB at sixteen unknowns)
         const dim3 grid2(nbx, (S + 127) / 128);
-        switch (n_u) {  // (LDS for the cross-wave sum: 3 x NU x 2 x 64 doubles = 48 KB at sixteen unknowns)
-#define DMF_CASE2(NU_) \
-    case NU_: hipLaunchKernelGGL((k_bu_cols2<NU_>), grid2, block, 0, st, V, D16, SD, u, N, S, slab, done_flag, vdv); return hipGetLastError();
-            DMF_CASE2(1) DMF_CASE2(2) DMF_CASE2(3) DMF_CASE2(4) DMF_CASE2(5) DMF_CASE2(6) DMF_CASE2(7) DMF_CASE2(8) DMF_CASE2(9) DMF_CASE2(10)
-            DMF_CASE2(11) DMF_CASE2(12) DMF_CASE2(13) DMF_CASE2(14) DMF_CASE2(15) DMF_CASE2(16)
-#undef DMF_CASE2
-            default: break;
-        }
+        return dispatch_int<1, 16>(n_u, [&](auto nu) {
+            hipLaunchKernelGGL((k_bu_cols2<decltype(nu)::value>), grid2, block, 0, st, p.V, p.D16, p.SD, u, p.N, S, slab,
+                               done_flag, vdv);
+            return hipGetLastError();
+        });
     }
     const dim3 grid(nbx, (S + 63) / 64);
-    switch (n_u) {
-#define DMF_CASE(NU_) \
-    case NU_: hipLaunchKernelGGL((k_bu_cols<NU_>), grid, block, 0, st, V, D16, SD, u, N, S, slab, done_flag); break;
-        DMF_CASE(1) DMF_CASE(2) DMF_CASE(3) DMF_CASE(4) DMF_CASE(5) DMF_CASE(6) DMF_CASE(7) DMF_CASE(8) DMF_CASE(9) DMF_CASE(10)
-        DMF_CASE(11) DMF_CASE(12) DMF_CASE(13) DMF_CASE(14) DMF_CASE(15) DMF_CASE(16) DMF_CASE(17) DMF_CASE(18) DMF_CASE(19) DMF_CASE(20)
-        DMF_CASE(21) DMF_CASE(22) DMF_CASE(23) DMF_CASE(24) DMF_CASE(25) DMF_CASE(26) DMF_CASE(27) DMF_CASE(28) DMF_CASE(29) DMF_CASE(30)
-        DMF_CASE(31) DMF_CASE(32)
-#undef DMF_CASE
-        default: return hipErrorInvalidValue;
-    }
-    return hipGetLastError();
+    return dispatch_int<1, 32>(n_u, [&](auto nu) {
+        hipLaunchKernelGGL((k_bu_cols<decltype(nu)::value>), grid, block, 0, st, p.V, p.D16, p.SD, u, p.N, S, slab, done_flag);
+        return hipGetLastError();
+    });
 }
 
 // ------------------------------------------------------------------------------------------------ reduce
@@ -929,56 +920,39 @@ int64_t gram_i8_acc_words(int S, int n_c, int n_u) {
 
 size_t gram_i8_w8_lds_bytes(int xl, int nd, int ring) { return (size_t)ring * (4096 * nd + xl * 4096) + (size_t)3 * 2 * (kNSL * 64) * 16; }
 
-template <int XL, int ND, int RING = kRing>
-static hipError_t launch_gram_i8_w8_t(const signed char* Dt8, int64_t plane_stride, int SD, const double* Rtp, const double* u,
-                                      int64_t N, int n_c, int n_u, const short* fa, const short* fb, int NF, int p0, int MFtot,
-                                      long long* slab, const int* done_flag, hipStream_t st) {
+hipError_t launch_gram_i8(const ProblemView& p, const double* u, int n_u, const short* fa, const short* fb, int NF,
+                          long long* slab, int64_t slab_words, const int* done_flag, int* ny_out, hipStream_t st) {
+    const int SD = p.SD, n_c = p.n_c;
     int nsh, ny;
     int64_t rpw;
-    gram_i8_geometry(N, SD, &nsh, &ny, &rpw);
-    const size_t lds = gram_i8_w8_lds_bytes(XL, ND, RING);
-    static bool lds_limit_raised[64] = {};
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) dev = 0;
-    if (!lds_limit_raised[dev]) {
-        hipError_t e = hipFuncSetAttribute((const void*)k_gram_i8_w8<XL, ND, RING>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return e;
-        lds_limit_raised[dev] = true;
-    }
-    hipLaunchKernelGGL((k_gram_i8_w8<XL, ND, RING>), dim3(nsh * ny), dim3(512), lds, st, Dt8, plane_stride, SD / 32, Rtp,
-                       (n_c + 3) / 4 * 4, u, N, n_c, n_u, fa, fb, NF, p0, MFtot, rpw, slab, SD, done_flag
-#ifdef DMF_STAMPS
-                       , (unsigned long long*)nullptr
-#endif
-                       );
-    return hipGetLastError();
-}
-
-hipError_t launch_gram_i8(const signed char* Dt8, int64_t plane_stride, int SD, int ND, const double* Rtp, const double* u,
-                          int64_t N, int n_c, int n_u, const short* fa, const short* fb, int NF, long long* slab,
-                          int64_t slab_words, const int* done_flag, int* ny_out, hipStream_t st) {
-    int nsh, ny;
-    int64_t rpw;
-    gram_i8_geometry(N, SD, &nsh, &ny, &rpw);
+    gram_i8_geometry(p.N, SD, &nsh, &ny, &rpw);
     *ny_out = ny;
     const int MFtot = (NF + 31) / 32 * 32;
     // every workgroup (row range) writes its own [2][MFtot][SD] slab: the buffer must hold all of them
-    if ((int64_t)ny * 2 * MFtot * SD > slab_words || rpw * 128 * 128 * ND >= (int64_t)1 << 31) return hipErrorInvalidValue;
+    if ((int64_t)ny * 2 * MFtot * SD > slab_words || rpw * 128 * 128 * p.ND >= (int64_t)1 << 31) return hipErrorInvalidValue;
     // more than 64 features = more launches over the (small) 8-bit planes
     const int chunk = 64;  // features per launch (lane = feature slot of a 64-lane wave; two feature halves of 32)
     const bool wide = (n_c + 3) / 4 * 4 + n_u > 16;  // x image of a block beyond 4 KB: two DMA pieces per thread
     for (int p0 = 0; p0 < NF; p0 += chunk) {
         const int nf = NF - p0 < chunk ? NF - p0 : chunk;
-        hipError_t e;
-        if (ND == 1) {
-            if (wide) e = launch_gram_i8_w8_t<2, 1>(Dt8, plane_stride, SD, Rtp, u, N, n_c, n_u, fa, fb, nf, p0, MFtot, slab, done_flag, st);
-            else e = launch_gram_i8_w8_t<1, 1>(Dt8, plane_stride, SD, Rtp, u, N, n_c, n_u, fa, fb, nf, p0, MFtot, slab, done_flag, st);
-        } else {  // two count digits (some count above 127: what sequencing data looks like)
-            if (wide)  // (16-KB block slots: a ring of six is what the LDS holds beside the three A tiles)
-                e = launch_gram_i8_w8_t<2, 2, 6>(Dt8, plane_stride, SD, Rtp, u, N, n_c, n_u, fa, fb, nf, p0, MFtot, slab, done_flag, st);
-            else
-                e = launch_gram_i8_w8_t<1, 2>(Dt8, plane_stride, SD, Rtp, u, N, n_c, n_u, fa, fb, nf, p0, MFtot, slab, done_flag, st);
-        }
+        // one count digit, or two (some count above 127: what sequencing data looks like)
+        const hipError_t e = dispatch_bool(p.ND == 1, [&](auto one_digit) {
+            return dispatch_bool(wide, [&](auto wide_t) {
+                constexpr int XL = decltype(wide_t)::value ? 2 : 1, ND = decltype(one_digit)::value ? 1 : 2;
+                // (wide with two digits: 16-KB block slots: a ring of six is what the LDS holds beside the three A tiles)
+                constexpr int RING = XL == 2 && ND == 2 ? 6 : kRing;
+                const size_t lds = gram_i8_w8_lds_bytes(XL, ND, RING);
+                const hipError_t e_lds = raise_dynamic_lds<k_gram_i8_w8<XL, ND, RING>>(lds);
+                if (e_lds != hipSuccess) return e_lds;
+                hipLaunchKernelGGL((k_gram_i8_w8<XL, ND, RING>), dim3(nsh * ny), dim3(512), lds, st, p.Dt8, p.plane_stride, SD / 32,
+                                   p.Rtp, (n_c + 3) / 4 * 4, u, p.N, n_c, n_u, fa, fb, nf, p0, MFtot, rpw, slab, SD, done_flag
+#ifdef DMF_STAMPS
+                                   , (unsigned long long*)nullptr
+#endif
+                                   );
+                return hipGetLastError();
+            });
+        });
         if (e != hipSuccess) return e;
     }
     return hipSuccess;

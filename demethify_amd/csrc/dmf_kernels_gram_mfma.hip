@@ -16,6 +16,7 @@
 // Layouts (tools/mfma_probe.hip): A[i][k]: lane (i = l & 15, k = l >> 4); B[k][j]: lane (k = l >> 4, j = l & 15);
 // C register r of lane l = C[(l >> 4) + 4 r][l & 15].
 // Output: slab[y][job][s] per row chunk y, summed in fixed order by k_gram_reduce: deterministic.
+#include "dmf_dispatch.h"
 #include "dmf_internal.h"
 
 namespace dmf {
@@ -241,17 +242,17 @@ int64_t gram_mfma_slab_doubles(int64_t N, int S, int n_jobs) {
 }
 
 // jobs [0, n_dense) have B = D, jobs [n_dense, count) are the "v" column (B = D * V); ny_out = slab rows per job
-hipError_t launch_gram_mfma(const double* V, const double* D, const double* Rt, const double* u, int64_t N, int S,
-                            int n_c, int n_u, GramJobTable jobs, int n_dense, double* slab, int64_t slab_doubles,
-                            const int* done_flag, int* ny_out, hipStream_t st) {
-    if (jobs.count <= 0 || n_dense < 0 || n_dense > jobs.count || n_c + n_u > kMaxK) return hipErrorInvalidValue;
+hipError_t launch_gram_mfma(const ProblemView& p, const double* u, int n_u, GramJobTable jobs, int n_dense, double* slab,
+                            int64_t slab_doubles, const int* done_flag, int* ny_out, hipStream_t st) {
+    const int S = p.S;
+    if (jobs.count <= 0 || n_dense < 0 || n_dense > jobs.count || p.n_c + n_u > kMaxK) return hipErrorInvalidValue;
     int nsx, ny;
     int64_t rpc;
-    gram_mfma_geometry(N, S, &nsx, &ny, &rpc);
+    gram_mfma_geometry(p.N, S, &nsx, &ny, &rpc);
     if ((int64_t)ny * jobs.count * S > slab_doubles) return hipErrorInvalidValue;
     *ny_out = ny;
     const dim3 grid(nsx, ny), block(kGramMfmaWaves * 64);
-    const bool dma = (S & 1) == 0 && S >= 2 && ((uintptr_t)D & 15) == 0 && ((uintptr_t)V & 15) == 0;
+    const bool dma = (S & 1) == 0 && S >= 2 && ((uintptr_t)p.D & 15) == 0 && ((uintptr_t)p.V & 15) == 0;
     int d_begin = 0, v_begin = n_dense;
     while (d_begin < n_dense || v_begin < jobs.count) {
         const int tiles_d = (n_dense - d_begin + 15) / 16, tiles_v = (jobs.count - v_begin + 15) / 16;
@@ -267,23 +268,14 @@ hipError_t launch_gram_mfma(const double* V, const double* D, const double* Rt, 
         if (d_end > n_dense) d_end = n_dense;
         if (v_end > jobs.count) v_end = jobs.count;
         const int v_wave0 = kGramMfmaWaves - waves_v;
-#define DMF_CASE(M_)                                                                                          \
-    case M_:                                                                                                  \
-        if (dma)                                                                                              \
-            hipLaunchKernelGGL((k_gram_mfma<M_, true>), grid, block, 0, st, V, D, Rt, u, N, S, n_c, n_u,      \
-                               jobs.k_idx, jobs.l_idx, jobs.count, d_begin, d_end, v_begin, v_end, v_wave0, \
-                               rpc, slab, done_flag);                                                         \
-        else                                                                                                  \
-            hipLaunchKernelGGL((k_gram_mfma<M_, false>), grid, block, 0, st, V, D, Rt, u, N, S, n_c, n_u,     \
-                               jobs.k_idx, jobs.l_idx, jobs.count, d_begin, d_end, v_begin, v_end, v_wave0, \
-                               rpc, slab, done_flag);                                                         \
-        break;
-        switch (mtw) {
-            DMF_CASE(1) DMF_CASE(2) DMF_CASE(3) DMF_CASE(4)
-            default: return hipErrorInvalidValue;
-        }
-#undef DMF_CASE
-        hipError_t e = hipGetLastError();
+        const hipError_t e = dispatch_int<1, 4>(mtw, [&](auto m) {
+            return dispatch_bool(dma, [&](auto dma_t) {
+                hipLaunchKernelGGL((k_gram_mfma<decltype(m)::value, decltype(dma_t)::value>), grid, block, 0, st, p.V, p.D, p.Rt,
+                                   u, p.N, S, p.n_c, n_u, jobs.k_idx, jobs.l_idx, jobs.count, d_begin, d_end, v_begin, v_end,
+                                   v_wave0, rpc, slab, done_flag);
+                return hipGetLastError();
+            });
+        });
         if (e != hipSuccess) return e;
         d_begin = d_end;
         v_begin = v_end;

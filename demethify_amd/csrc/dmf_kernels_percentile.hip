@@ -10,6 +10,7 @@
 //                       counting (ties broken by replicate index, so each rank is taken exactly once).
 // The interpolation between the two neighbouring order statistics repeats numpy's _lerp operation by
 // operation (no fused multiply-add), so the results are bit-identical to numpy's.
+#include "dmf_dispatch.h"
 #include "dmf_internal.h"
 
 namespace dmf {
@@ -161,15 +162,10 @@ hipError_t launch_percentile_pair(const double* x, int64_t n, int64_t m, Percent
     int P = 8;
     while (P > 1 && (size_t)n * P * sizeof(double) > 152 * 1024) P >>= 1;
     const size_t lds = (size_t)n * P * sizeof(double);
-    static bool raised[64] = {};
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) dev = 0;
-    if (lds > 48 * 1024 && !raised[dev]) {
+    if (lds > 48 * 1024) {
         // (the kernel also has 256 B of static LDS: dynamic + static must stay within the CU's 160 KB)
-        hipError_t e = hipFuncSetAttribute((const void*)k_percentile_rank, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                           152 * 1024);
+        const hipError_t e = raise_dynamic_lds<k_percentile_rank>(152 * 1024);
         if (e != hipSuccess) return e;
-        raised[dev] = true;
     }
     const int64_t grid = (m + P - 1) / P;
     if (grid > 0x7fffffffLL) return hipErrorInvalidValue;

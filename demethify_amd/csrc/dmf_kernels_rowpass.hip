@@ -6,6 +6,7 @@
 //     M_i = alpha_unk diag(d_i) alpha_unk^T                        (n_u x n_u, symmetric)
 // One pass over V and D builds c_i, M_i; the n_iter2 inner iterations are then row-local.
 #include "dmf_device.h"
+#include "dmf_dispatch.h"
 #include "dmf_internal.h"
 
 namespace dmf {
@@ -127,31 +128,16 @@ bool u_phase_gram_supported(int S, int n_c, int n_u) {
     return n_u >= 1 && n_u <= 16;  // 9..16: c and M (up to 152 doubles) still fit the register file
 }
 
-template <int NU>
-static hipError_t launch_u_gram_t(const double* V, const double* D, const double* Rt,
-                                  const double* alpha, double* u, double* u_prev,
-                                  const SolverState* state, int64_t N, int S, int n_c, int n_iter2,
-                                  int mode, hipStream_t st) {
-    const size_t lds = (size_t)(n_c + NU) * S * sizeof(double);
-    const int in_lds = lds <= 36 * 1024;
-    const int64_t nb = (N + kRowsPerBlockU - 1) / kRowsPerBlockU;
-    hipLaunchKernelGGL(k_u_phase_gram<NU>, dim3((unsigned)nb), dim3(256), in_lds ? lds : 0, st, V, D,
-                       Rt, alpha, u, u_prev, state, N, S, n_c, n_iter2, mode, in_lds);
-    return hipGetLastError();
-}
-
-hipError_t launch_u_phase_gram(const double* V, const double* D, const double* Rt,
-                               const double* alpha, double* u, double* u_prev,
-                               const SolverState* state, int64_t N, int S, int n_c, int n_u,
-                               int n_iter2, int mode, hipStream_t st) {
-    switch (n_u) {
-#define DMF_CASE(NU_) \
-    case NU_: return launch_u_gram_t<NU_>(V, D, Rt, alpha, u, u_prev, state, N, S, n_c, n_iter2, mode, st);
-        DMF_CASE(1) DMF_CASE(2) DMF_CASE(3) DMF_CASE(4) DMF_CASE(5) DMF_CASE(6) DMF_CASE(7) DMF_CASE(8)
-        DMF_CASE(9) DMF_CASE(10) DMF_CASE(11) DMF_CASE(12) DMF_CASE(13) DMF_CASE(14) DMF_CASE(15) DMF_CASE(16)
-#undef DMF_CASE
-        default: return hipErrorInvalidValue;
-    }
+hipError_t launch_u_phase_gram(const ProblemView& p, const IterateView& it, int n_iter2, hipStream_t st) {
+    return dispatch_int<1, 16>(it.n_u, [&](auto nu) {
+        constexpr int NU = decltype(nu)::value;
+        const size_t lds = (size_t)(p.n_c + NU) * p.S * sizeof(double);
+        const int in_lds = lds <= 36 * 1024;
+        const int64_t nb = (p.N + kRowsPerBlockU - 1) / kRowsPerBlockU;
+        hipLaunchKernelGGL(k_u_phase_gram<NU>, dim3((unsigned)nb), dim3(256), in_lds ? lds : 0, st, p.V, p.D, p.Rt, it.alpha,
+                           it.u, it.u_prev, it.state, p.N, p.S, p.n_c, n_iter2, it.mode, in_lds);
+        return hipGetLastError();
+    });
 }
 
 // ---- schedule-faithful fallback: one inner iteration per launch, any n_u <= 64 ------------
@@ -206,15 +192,12 @@ bool u_step_direct_supported(int S, int n_c, int n_u) {
     return n_u >= 1 && n_u <= 64 && (size_t)4 * (S + 128) * sizeof(double) <= 60 * 1024;
 }
 
-hipError_t launch_u_step_direct(const double* V, const double* D, const double* Rt,
-                                const double* alpha, const double* u_cur, const double* u_prev,
-                                double* u_next, const SolverState* state, int64_t N, int S, int n_c,
-                                int n_u, int t, int mode, hipStream_t st) {
-    const size_t lds = (size_t)4 * (S + 128) * sizeof(double);
-    int64_t nb = (N + 3) / 4;
+hipError_t launch_u_step_direct(const ProblemView& p, const IterateView& it, double* u_next, int t, hipStream_t st) {
+    const size_t lds = (size_t)4 * (p.S + 128) * sizeof(double);
+    int64_t nb = (p.N + 3) / 4;
     if (nb > 4096) nb = 4096;
-    hipLaunchKernelGGL(k_u_step_direct, dim3((unsigned)nb), dim3(256), lds, st, V, D, Rt, alpha, u_cur,
-                       u_prev, u_next, state, N, S, n_c, n_u, t, mode);
+    hipLaunchKernelGGL(k_u_step_direct, dim3((unsigned)nb), dim3(256), lds, st, p.V, p.D, p.Rt, it.alpha, it.u,
+                       it.u_prev, u_next, it.state, p.N, p.S, p.n_c, it.n_u, t, it.mode);
     return hipGetLastError();
 }
 

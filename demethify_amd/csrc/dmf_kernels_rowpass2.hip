@@ -28,6 +28,7 @@
 // Preconditions (checked by the launcher / the solver): 2 <= S <= 256 (odd S: see the tile prefetch), n_c <= 16, n_u <= 4, counts integral and
 // <= 32639 (nd = 1: <= 127), alpha within [0, 1] (true of every iterate: columns on the simplex).
 #include "dmf_device.h"
+#include "dmf_dispatch.h"
 #include "dmf_internal.h"
 #include "dmf_phaseb.h"
 #include "dmf_fixedpoint.h"
@@ -716,11 +717,8 @@ bool rowpass_v2_supported(int S, int n_c, int n_u, int n_iter2) {
 
 // workgroups per CU the grid is sized for
 static int rowpass_v2_per_cu(int NW) {
-    int per_cu = NW > 4 ? 1 : 8 / NW;  // two waves per SIMD: NW = 5..8 -> 1, 4 -> 2, 3 -> 2, 2 -> 4, 1 -> 8 workgroups per CU
-#ifdef DMF_EXPERIMENT  // (an experiment build only: DMF_EXPERIMENT=1 python -m demethify_amd._build)
-    if (const char* v = getenv("DMF_V2_PER_CU")) per_cu = atoi(v) > 0 ? atoi(v) : per_cu;  // (experiments)
-#endif
-    return per_cu;
+    // two waves per SIMD: NW = 5..8 -> 1, 4 -> 2, 3 -> 2, 2 -> 4, 1 -> 8 workgroups per CU
+    return per_cu_knob("DMF_V2_PER_CU", NW > 4 ? 1 : 8 / NW);
 }
 
 // The pair schedule applies to the X16 form with two to four waves, when the grid's workgroups per CU still fit the CU's
@@ -739,83 +737,48 @@ int rowpass_v2_grid(int64_t N, int S) {
     return (int)(nblk < g ? nblk : g);
 }
 
-namespace {
-// one launch's arguments, as launch_rowpass_v2 receives them, handed down its dispatch on the template parameters
-struct V2Args {
-    const double* V;
-    const unsigned short *D16, *X16;
-    int SD;
-    const double *Rtp, *alpha;
-    double *u, *u_prev;
-    SolverState* state;
-    int64_t N;
-    int S, n_c, n_iter2, mode, nd;
-    double *slab, *u2_partials;
-    int* grid_out;
-    hipStream_t st;
-};
-}  // namespace
-
-template <int NKC, int NU, int MAXW, bool XS, bool PAIR = false>
-static hipError_t launch_v2_t(const V2Args& a) {
-    const int NW = (a.S + 63) / 64;
-    const size_t lds = rowpass_v2_lds_bytes(a.S, NU, a.n_iter2, XS, PAIR);
-    constexpr size_t kLdsCap = (size_t)(MAXW == 4 ? 80 : 160) * 1024;
-    if (NW > MAXW || (MAXW == 8 && NW <= 4) || (PAIR && NW < 2) || lds > kLdsCap || a.N < 1 || a.SD < NW * 64 || (a.SD & 7) != 0 ||
-        a.nd < 1 || a.nd > 2)
-        return hipErrorInvalidValue;
-    static bool lds_limit_raised[64] = {};
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) dev = 0;
-    if (lds > 48 * 1024 && !lds_limit_raised[dev]) {
-        hipError_t e = hipFuncSetAttribute((const void*)k_rowpass_v2<NKC, NU, MAXW, XS, PAIR>,
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsCap);
-        if (e != hipSuccess) return e;
-        lds_limit_raised[dev] = true;
-    }
-    const int grid = rowpass_v2_grid(a.N, a.S);
-    *a.grid_out = grid;
-    hipLaunchKernelGGL((k_rowpass_v2<NKC, NU, MAXW, XS, PAIR>), dim3(grid), dim3(NW * 64), lds, a.st, a.V, a.D16, a.X16, a.SD,
-                       a.Rtp, a.alpha, a.u, a.u_prev, a.state, a.N, a.S, a.n_c, a.n_iter2, a.mode, a.nd, a.slab, a.u2_partials
-#ifdef DMF_STAMPS
-                       , (unsigned long long*)nullptr
-#endif
-                       );
-    return hipGetLastError();
-}
-
-template <int NKC, bool XS>
-static hipError_t launch_v2_nkc(const V2Args& a, int n_u, bool pair, bool* paired_out) {
+hipError_t launch_rowpass_v2(const ProblemView& p, const IterateView& it, int n_iter2, const UScratch& scratch, int* grid_out,
+                             bool pair, bool* paired_out, hipStream_t st) {
+    const int S = p.S, NW = (S + 63) / 64;
     // the pair schedule where it applies (rowpass_v2_pair_fits), else one block per barrier cycle
-    pair = pair && XS && rowpass_v2_pair_fits(a.S, n_u, a.n_iter2);
+    pair = pair && p.X16 != nullptr && rowpass_v2_pair_fits(S, it.n_u, n_iter2);
     if (paired_out != nullptr) *paired_out = pair;
-    switch (n_u) {
-#define DMF_CASE(NU_)                                                                                                   \
-    case NU_:                                                                                                           \
-        if (a.S > 256) return launch_v2_t<NKC, NU_, 8, XS>(a);                                                          \
-        if constexpr (XS) {                                                                                             \
-            if (pair) return launch_v2_t<NKC, NU_, 4, XS, true>(a);                                                     \
-        }                                                                                                               \
-        return launch_v2_t<NKC, NU_, 4, XS>(a);
-        DMF_CASE(1) DMF_CASE(2) DMF_CASE(3) DMF_CASE(4)
-#undef DMF_CASE
-        default: return hipErrorInvalidValue;
-    }
-}
-
-hipError_t launch_rowpass_v2(const double* V, const unsigned short* D16, const unsigned short* X16, int SD,
-                             const double* Rtp, const double* alpha, double* u, double* u_prev, SolverState* state, int64_t N,
-                             int S, int n_c, int n_u, int n_iter2, int mode, int nd, double* slab, double* u2_partials,
-                             int* grid_out, bool pair, bool* paired_out, hipStream_t st) {
-    const V2Args a{V, D16, X16, SD, Rtp, alpha, u, u_prev, state, N, S, n_c, n_iter2, mode, nd, slab, u2_partials, grid_out, st};
-    switch ((n_c + 3) / 4) {
-#define DMF_NKC(X)                                                                                                    \
-    case X:                                                                                                           \
-        return X16 != nullptr ? launch_v2_nkc<X, true>(a, n_u, pair, paired_out) : launch_v2_nkc<X, false>(a, n_u, pair, paired_out);
-        DMF_NKC(0) DMF_NKC(1) DMF_NKC(2) DMF_NKC(3) DMF_NKC(4)
-#undef DMF_NKC
-        default: return hipErrorInvalidValue;
-    }
+    return dispatch_int<0, 4>((p.n_c + 3) / 4, [&](auto nkc) {
+        return dispatch_bool(p.X16 != nullptr, [&](auto xs) {
+            return dispatch_int<1, 4>(it.n_u, [&](auto nu) {
+                const auto launch = [&](auto maxw, auto pair_t) {
+                    constexpr int NU = decltype(nu)::value, MAXW = decltype(maxw)::value;
+                    constexpr bool XS = decltype(xs)::value, PAIR = decltype(pair_t)::value;
+                    constexpr auto kernel = k_rowpass_v2<decltype(nkc)::value, NU, MAXW, XS, PAIR>;
+                    const size_t lds = rowpass_v2_lds_bytes(S, NU, n_iter2, XS, PAIR);
+                    constexpr size_t kLdsCap = (size_t)(MAXW == 4 ? 80 : 160) * 1024;
+                    if (NW > MAXW || (MAXW == 8 && NW <= 4) || (PAIR && NW < 2) || lds > kLdsCap || p.N < 1 ||
+                        p.SD < NW * 64 || (p.SD & 7) != 0 || p.ND < 1 || p.ND > 2)
+                        return hipErrorInvalidValue;
+                    if (lds > 48 * 1024) {
+                        const hipError_t e = raise_dynamic_lds<kernel>(kLdsCap);
+                        if (e != hipSuccess) return e;
+                    }
+                    const int grid = rowpass_v2_grid(p.N, S);
+                    *grid_out = grid;
+                    hipLaunchKernelGGL(kernel, dim3(grid), dim3(NW * 64), lds, st, p.V, p.D16, p.X16, p.SD, p.Rtp, it.alpha,
+                                       it.u, it.u_prev, it.state, p.N, S, p.n_c, n_iter2, it.mode, p.ND, scratch.slab,
+                                       scratch.u2_partials
+#ifdef DMF_STAMPS
+                                       , (unsigned long long*)nullptr
+#endif
+                                       );
+                    return hipGetLastError();
+                };
+                // more than 256 samples: one workgroup of up to eight waves; the pair leg only on X16
+                if (S > 256) return launch(std::integral_constant<int, 8>{}, std::false_type{});
+                if constexpr (decltype(xs)::value) {
+                    if (pair) return launch(std::integral_constant<int, 4>{}, std::true_type{});
+                }
+                return launch(std::integral_constant<int, 4>{}, std::false_type{});
+            });
+        });
+    });
 }
 
 }  // namespace dmf

@@ -18,6 +18,7 @@
 #include <cstdlib>
 
 #include "dmf_device.h"
+#include "dmf_dispatch.h"
 #include "dmf_internal.h"
 
 namespace dmf {
@@ -272,46 +273,25 @@ bool u_phase_big_supported(int S, int n_c, int n_u, int n_iter2) {
     return (size_t)big_layout(S, n_c, n_u, n_iter2, GS).total * sizeof(double) <= 160 * 1024;
 }
 
-template <int NKC, int GS>
-static hipError_t launch_big_t(const double* V, const double* D, const double* Rtp, const double* alpha, double* u,
-                               double* u_prev, const SolverState* state, int64_t N, int S, int n_c, int n_u,
-                               int n_iter2, int mode, hipStream_t st) {
-    const size_t lds = (size_t)big_layout(S, n_c, n_u, n_iter2, GS).total * sizeof(double);
-    if (lds > 160 * 1024) return hipErrorInvalidValue;
-    static bool raised[64] = {};
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) dev = 0;
-    if (lds > 48 * 1024 && !raised[dev]) {
-        hipError_t e = hipFuncSetAttribute((const void*)k_u_phase_big<NKC, GS>,
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        if (e != hipSuccess) return e;
-        raised[dev] = true;
-    }
-    const int64_t nblk = (N + 15) / 16;
-    int per_cu = lds <= 78 * 1024 ? 2 : 1;
-#ifdef DMF_EXPERIMENT  // (an experiment build only: DMF_EXPERIMENT=1 python -m demethify_amd._build)
-    if (const char* v = getenv("DMF_UBIG_PER_CU")) per_cu = atoi(v) > 0 ? atoi(v) : per_cu;  // (experiments)
-#endif
-    const int64_t want = 256 * per_cu;
-    const int64_t grid = nblk < want ? nblk : want;
-    hipLaunchKernelGGL((k_u_phase_big<NKC, GS>), dim3((unsigned)grid), dim3(GS == 16 ? 256 : 512), lds, st, V, D, Rtp,
-                       alpha, u, u_prev, state, N, S, n_c, n_u, n_iter2, mode);
-    return hipGetLastError();
-}
-
-hipError_t launch_u_phase_big(const double* V, const double* D, const double* Rtp, const double* alpha, double* u,
-                              double* u_prev, const SolverState* state, int64_t N, int S, int n_c, int n_u,
-                              int n_iter2, int mode, hipStream_t st) {
-    const int gs = big_group_size(n_u);
-#define DMF_CASE(X)                                                                                              \
-    case X:                                                                                                      \
-        return gs == 16 ? launch_big_t<X, 16>(V, D, Rtp, alpha, u, u_prev, state, N, S, n_c, n_u, n_iter2, mode, st) \
-                        : launch_big_t<X, 32>(V, D, Rtp, alpha, u, u_prev, state, N, S, n_c, n_u, n_iter2, mode, st);
-    switch ((n_c + 3) / 4) {
-        DMF_CASE(0) DMF_CASE(1) DMF_CASE(2) DMF_CASE(3) DMF_CASE(4)
-        default: return hipErrorInvalidValue;
-    }
-#undef DMF_CASE
+hipError_t launch_u_phase_big(const ProblemView& p, const IterateView& it, int n_iter2, hipStream_t st) {
+    const int gs = big_group_size(it.n_u);
+    return dispatch_int<0, 4>((p.n_c + 3) / 4, [&](auto nkc) {
+        return dispatch_bool(gs == 16, [&](auto gs16) {
+            constexpr int NKC = decltype(nkc)::value, GS = decltype(gs16)::value ? 16 : 32;
+            const size_t lds = (size_t)big_layout(p.S, p.n_c, it.n_u, n_iter2, GS).total * sizeof(double);
+            if (lds > 160 * 1024) return hipErrorInvalidValue;
+            if (lds > 48 * 1024) {
+                const hipError_t e = raise_dynamic_lds<k_u_phase_big<NKC, GS>>(160 * 1024);
+                if (e != hipSuccess) return e;
+            }
+            const int64_t nblk = (p.N + 15) / 16;
+            const int64_t want = 256 * per_cu_knob("DMF_UBIG_PER_CU", lds <= 78 * 1024 ? 2 : 1);
+            const int64_t grid = nblk < want ? nblk : want;
+            hipLaunchKernelGGL((k_u_phase_big<NKC, GS>), dim3((unsigned)grid), dim3(GS == 16 ? 256 : 512), lds, st, p.V, p.D, p.Rtp,
+                               it.alpha, it.u, it.u_prev, it.state, p.N, p.S, p.n_c, it.n_u, n_iter2, it.mode);
+            return hipGetLastError();
+        });
+    });
 }
 
 }  // namespace dmf

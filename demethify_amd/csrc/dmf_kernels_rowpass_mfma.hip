@@ -18,6 +18,7 @@
 #include <type_traits>
 
 #include "dmf_device.h"
+#include "dmf_dispatch.h"
 #include "dmf_internal.h"
 #include "dmf_phaseb.h"
 
@@ -29,28 +30,10 @@ typedef double v2d __attribute__((ext_vector_type(2)));
 constexpr int kStripsPerWave = 4;  // 16-sample strips owned by one wave (64 samples)
 constexpr int kMfmaMaxWaves = 8;   // S <= 512 on this path
 
-// Broadcast of lane (group base + L)'s value inside aligned groups of NU lanes.  NU = 2 / 4 use a DPP
-// quad permute (no LDS traffic); other group sizes go through ds_bpermute.
-template <int CTRL>
-__device__ __forceinline__ double dpp_quad(double x) {
-    // (mov_dpp: every lane of a quad permute has a source, no "old" value to initialise)
-    const int lo = __builtin_amdgcn_mov_dpp(__double2loint(x), CTRL, 0xF, 0xF, false);
-    const int hi = __builtin_amdgcn_mov_dpp(__double2hiint(x), CTRL, 0xF, 0xF, false);
-    return __hiloint2double(hi, lo);
-}
-
-template <int NU, int L>
-__device__ __forceinline__ double group_bcast(double x, int lane0) {
-    if constexpr (NU == 1) return x;
-    else if constexpr (NU == 2) return dpp_quad<(L) | (L << 2) | ((2 + L) << 4) | ((2 + L) << 6)>(x);
-    else if constexpr (NU == 4) return dpp_quad<L | (L << 2) | (L << 4) | (L << 6)>(x);
-    else return __shfl(x, lane0 + L, 64);
-}
-
 template <int NU, int L = 0>
 __device__ __forceinline__ double grad_row(double g, double base, const double (&Mrow)[NU], int lane0) {
     if constexpr (L < NU) {
-        g = fma(-group_bcast<NU, L>(base, lane0), Mrow[L], g);
+        g = fma(-f_group_bcast<NU, L>(base, lane0), Mrow[L], g);
         return grad_row<NU, L + 1>(g, base, Mrow, lane0);
     } else {
         return g;
@@ -310,78 +293,44 @@ bool u_phase_mfma_supported(int S, int n_c, int n_u) {
     return n_u >= 1 && n_u <= 8 && n_c <= 16 && S <= 16 * kStripsPerWave * kMfmaMaxWaves;
 }
 
-template <int NKC, int NU>
-static hipError_t launch_u_mfma_t(const double* V, const double* D, const unsigned short* D16, int SD, const double* Rt,
-                                  const double* alpha, double* u, double* u_prev, const SolverState* state, int64_t N,
-                                  int S, int n_c, int n_iter2, int mode, double* cm_out, hipStream_t st) {
-    constexpr int NV = NU + NU * (NU + 1) / 2;
+// cm_out: null, or where the split mode leaves the per-row c_i / M_i (see the kernel)
+static hipError_t launch_u_phase_mfma_impl(const ProblemView& p, const IterateView& it, int n_iter2, double* cm_out,
+                                           hipStream_t st) {
+    const int S = p.S;
     const int nstrips = (S + 15) / 16;
     const int NW = (nstrips + kStripsPerWave - 1) / kStripsPerWave;
-    // (split mode keeps no momentum table in LDS)
-    const size_t lds = ((size_t)(cm_out ? 0 : ((n_iter2 + 1) & ~1)) + (size_t)2 * NW * NV * 16) * sizeof(double);
-    if (lds > 150 * 1024) return hipErrorInvalidValue;
     const bool vec = (S & 3) == 0;
-    const bool d16 = vec && D16 != nullptr && (SD & 3) == 0;
-    const void* fn = d16   ? (const void*)k_u_phase_mfma<NKC, NU, true, true>
-                     : vec ? (const void*)k_u_phase_mfma<NKC, NU, true, false>
-                           : (const void*)k_u_phase_mfma<NKC, NU, false, false>;
-    if (lds > 48 * 1024) {
-        hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return e;
-    }
-    const int64_t nblk = (N + 15) / 16;
+    const bool d16 = vec && p.D16 != nullptr && (p.SD & 3) == 0;
     // persistent workgroups: as many as fit two waves per SIMD (the kernel needs ~250 registers) -- 3 per CU at
     // NW = 2 left a quarter of the wave slots empty
-    int per_cu = NW >= 8 ? 1 : 8 / NW;
-#ifdef DMF_EXPERIMENT  // (an experiment build only: DMF_EXPERIMENT=1 python -m demethify_amd._build)
-    if (const char* v = getenv("DMF_UMFMA_PER_CU")) per_cu = atoi(v) > 0 ? atoi(v) : per_cu;  // (experiments)
-#endif
-    const int64_t cap = (int64_t)256 * per_cu;
+    const int per_cu = per_cu_knob("DMF_UMFMA_PER_CU", NW >= 8 ? 1 : 8 / NW);
+    const int64_t nblk = (p.N + 15) / 16, cap = (int64_t)256 * per_cu;
     const int64_t grid = nblk < cap ? nblk : cap;
-    if (d16)
-        hipLaunchKernelGGL((k_u_phase_mfma<NKC, NU, true, true>), dim3((unsigned)grid), dim3(NW * 64), lds, st, V, D, D16, SD,
-                           Rt, alpha, u, u_prev, state, N, S, n_c, n_iter2, mode, cm_out);
-    else if (vec)
-        hipLaunchKernelGGL((k_u_phase_mfma<NKC, NU, true, false>), dim3((unsigned)grid), dim3(NW * 64), lds, st, V, D, D16, SD,
-                           Rt, alpha, u, u_prev, state, N, S, n_c, n_iter2, mode, cm_out);
-    else
-        hipLaunchKernelGGL((k_u_phase_mfma<NKC, NU, false, false>), dim3((unsigned)grid), dim3(NW * 64), lds, st, V, D, D16,
-                           SD, Rt, alpha, u, u_prev, state, N, S, n_c, n_iter2, mode, cm_out);
-    return hipGetLastError();
+    return dispatch_int<0, 4>((p.n_c + 3) / 4, [&](auto nkc) {
+        return dispatch_int<1, 8>(it.n_u, [&](auto nu) {
+            constexpr int NKC = decltype(nkc)::value, NU = decltype(nu)::value, NV = NU + NU * (NU + 1) / 2;
+            // (split mode keeps no momentum table in LDS)
+            const size_t lds = ((size_t)(cm_out ? 0 : ((n_iter2 + 1) & ~1)) + (size_t)2 * NW * NV * 16) * sizeof(double);
+            if (lds > 150 * 1024) return hipErrorInvalidValue;
+            const auto launch = [&](auto vec_t, auto d16_t) {
+                constexpr auto kernel = k_u_phase_mfma<NKC, NU, decltype(vec_t)::value, decltype(d16_t)::value>;
+                if (lds > 48 * 1024) {
+                    const hipError_t e = raise_dynamic_lds<kernel>(lds);
+                    if (e != hipSuccess) return e;
+                }
+                hipLaunchKernelGGL(kernel, dim3((unsigned)grid), dim3(NW * 64), lds, st, p.V, p.D, p.D16, p.SD, p.Rtp, it.alpha,
+                                   it.u, it.u_prev, it.state, p.N, S, p.n_c, n_iter2, it.mode, cm_out);
+                return hipGetLastError();
+            };
+            if (d16) return launch(std::true_type{}, std::true_type{});
+            if (vec) return launch(std::true_type{}, std::false_type{});
+            return launch(std::false_type{}, std::false_type{});
+        });
+    });
 }
 
-template <int NKC>
-static hipError_t launch_u_mfma_nkc(int n_u, const double* V, const double* D, const unsigned short* D16, int SD,
-                                    const double* Rt, const double* alpha, double* u, double* u_prev,
-                                    const SolverState* state, int64_t N, int S, int n_c, int n_iter2, int mode,
-                                    double* cm_out, hipStream_t st) {
-    switch (n_u) {
-#define DMF_CASE(NU_) \
-    case NU_: return launch_u_mfma_t<NKC, NU_>(V, D, D16, SD, Rt, alpha, u, u_prev, state, N, S, n_c, n_iter2, mode, cm_out, st);
-        DMF_CASE(1) DMF_CASE(2) DMF_CASE(3) DMF_CASE(4) DMF_CASE(5) DMF_CASE(6) DMF_CASE(7) DMF_CASE(8)
-#undef DMF_CASE
-        default: return hipErrorInvalidValue;
-    }
-}
-
-static hipError_t launch_u_phase_mfma_impl(const double* V, const double* D, const unsigned short* D16, int SD,
-                                           const double* Rt, const double* alpha, double* u, double* u_prev,
-                                           const SolverState* state, int64_t N, int S, int n_c, int n_u, int n_iter2,
-                                           int mode, double* cm_out, hipStream_t st) {
-    switch ((n_c + 3) / 4) {
-        case 0: return launch_u_mfma_nkc<0>(n_u, V, D, D16, SD, Rt, alpha, u, u_prev, state, N, S, n_c, n_iter2, mode, cm_out, st);
-        case 1: return launch_u_mfma_nkc<1>(n_u, V, D, D16, SD, Rt, alpha, u, u_prev, state, N, S, n_c, n_iter2, mode, cm_out, st);
-        case 2: return launch_u_mfma_nkc<2>(n_u, V, D, D16, SD, Rt, alpha, u, u_prev, state, N, S, n_c, n_iter2, mode, cm_out, st);
-        case 3: return launch_u_mfma_nkc<3>(n_u, V, D, D16, SD, Rt, alpha, u, u_prev, state, N, S, n_c, n_iter2, mode, cm_out, st);
-        case 4: return launch_u_mfma_nkc<4>(n_u, V, D, D16, SD, Rt, alpha, u, u_prev, state, N, S, n_c, n_iter2, mode, cm_out, st);
-        default: return hipErrorInvalidValue;
-    }
-}
-
-hipError_t launch_u_phase_mfma(const double* V, const double* D, const unsigned short* D16, int SD, const double* Rt,
-                               const double* alpha, double* u, double* u_prev, const SolverState* state, int64_t N, int S,
-                               int n_c, int n_u, int n_iter2, int mode, hipStream_t st) {
-    return launch_u_phase_mfma_impl(V, D, D16, SD, Rt, alpha, u, u_prev, state, N, S, n_c, n_u, n_iter2, mode, nullptr, st);
+hipError_t launch_u_phase_mfma(const ProblemView& p, const IterateView& it, int n_iter2, hipStream_t st) {
+    return launch_u_phase_mfma_impl(p, it, n_iter2, nullptr, st);
 }
 
 // ---- split mode for many inner steps (the CLI default under --purity is 500): c_i / M_i per row through HBM
@@ -747,9 +696,8 @@ __global__ __launch_bounds__(256 * NSG) void k_inner_bu(const double* __restrict
     }
 }
 
-bool u_inner_bu_supported(const double* V, int S, int SD, int n_u, int n_iter2) {
-    return n_u >= 1 && n_u <= 16 && S >= 2 && S <= 256 && (SD & 1) == 0 && n_iter2 <= kInnerBuMaxSteps &&
-           (reinterpret_cast<uintptr_t>(V) & 7) == 0;
+bool u_inner_bu_supported(unsigned v_align, int S, int SD, int n_u, int n_iter2) {
+    return n_u >= 1 && n_u <= 16 && S >= 2 && S <= 256 && (SD & 1) == 0 && n_iter2 <= kInnerBuMaxSteps && (v_align & 7) == 0;
 }
 
 int u_inner_bu_grid(int64_t N, int S) {
@@ -759,114 +707,76 @@ int u_inner_bu_grid(int64_t N, int S) {
 }
 
 // cm + beta as launch_u_inner; slab: u_inner_bu_grid(N, S) x n_u x S doubles; u2_partials: one double per workgroup
-static hipError_t launch_u_inner_bu(const double* cm, double* beta, double* u, double* u_prev, const SolverState* state,
-                                    const double* V, const unsigned short* D16, int SD, int64_t N, int S, int n_u,
-                                    int n_iter2, int mode, double* slab, double* u2_partials, int* grid_out,
-                                    hipStream_t st) {
-    if (!u_inner_bu_supported(V, S, SD, n_u, n_iter2)) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(k_beta_table, dim3(1), dim3(1), 0, st, state, n_iter2, beta);
-    const int grid = u_inner_bu_grid(N, S);
+static hipError_t launch_u_inner_bu(const ProblemView& p, const IterateView& it, int n_iter2, const UScratch& scratch,
+                                    int* grid_out, hipStream_t st) {
+    const int S = p.S, n_u = it.n_u;
+    if (!u_inner_bu_supported(p.v_align(), S, p.SD, n_u, n_iter2)) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_beta_table, dim3(1), dim3(1), 0, st, it.state, n_iter2, scratch.beta);
+    const int grid = u_inner_bu_grid(p.N, S);
     *grid_out = grid;
     const int nsg = S <= 128 ? 1 : 2;
     const int us = n_u + (n_u & 1);
     const size_t lds = ((size_t)((n_iter2 + 1) & ~1) + (size_t)2 * 16 * nsg * us + (size_t)nsg * n_u * 2 * 64) * sizeof(double);
-#define DMF_LAUNCH(NU_, NSG_, ODD_)                                                                                      \
-    hipLaunchKernelGGL((k_inner_bu<NU_, NSG_, ODD_>), dim3((unsigned)grid), dim3(256 * NSG_), lds, st, cm, beta, u, u_prev, \
-                       state, V, D16, SD, N, S, n_iter2, mode, slab, u2_partials)
-#define DMF_CASE(NU_)                                     \
-    case NU_:                                             \
-        if (nsg == 1) {                                   \
-            if (S & 1) DMF_LAUNCH(NU_, 1, true);          \
-            else DMF_LAUNCH(NU_, 1, false);               \
-        } else {                                          \
-            if (S & 1) DMF_LAUNCH(NU_, 2, true);          \
-            else DMF_LAUNCH(NU_, 2, false);               \
-        }                                                 \
-        break;
-    switch (n_u) {
-        DMF_CASE(1) DMF_CASE(2) DMF_CASE(3) DMF_CASE(4)  // (narrow row groups behind the producer: more than 16 known types)
-        DMF_CASE(5) DMF_CASE(6) DMF_CASE(7) DMF_CASE(8) DMF_CASE(9) DMF_CASE(10) DMF_CASE(11) DMF_CASE(12) DMF_CASE(13)
-        DMF_CASE(14) DMF_CASE(15) DMF_CASE(16)
-        default: return hipErrorInvalidValue;
-    }
-#undef DMF_CASE
-#undef DMF_LAUNCH
-    return hipGetLastError();
+    // (1..4: narrow row groups behind the producer: more than 16 known types)
+    return dispatch_int<1, 16>(n_u, [&](auto nu) {
+        return dispatch_int<1, 2>(nsg, [&](auto nsg_t) {
+            return dispatch_bool((S & 1) != 0, [&](auto odd) {
+                constexpr int NSG = decltype(nsg_t)::value;
+                hipLaunchKernelGGL((k_inner_bu<decltype(nu)::value, NSG, decltype(odd)::value>), dim3((unsigned)grid),
+                                   dim3(256 * NSG), lds, st, scratch.cm, scratch.beta, it.u, it.u_prev, it.state, p.V, p.D16,
+                                   p.SD, p.N, S, n_iter2, it.mode, scratch.slab, scratch.u2_partials);
+                return hipGetLastError();
+            });
+        });
+    });
 }
 
 int64_t u_phase_split_cm_doubles(int64_t N, int n_u) { return N * (n_u + (int64_t)n_u * (n_u + 1) / 2); }
 
-// the inner iterations from cm (N x (n_u + NP) doubles); beta: n_iter2 doubles of device scratch
-static hipError_t launch_u_inner(const double* cm, double* beta, double* u, double* u_prev, const SolverState* state,
-                                 int64_t N, int n_u, int n_iter2, int mode, hipStream_t st) {
-    hipLaunchKernelGGL(k_beta_table, dim3(1), dim3(1), 0, st, state, n_iter2, beta);
+// the inner iterations from scratch.cm (N x (n_u + NP) doubles); scratch.beta: n_iter2 doubles of device scratch
+static hipError_t launch_u_inner(int64_t N, const IterateView& it, int n_iter2, const UScratch& scratch, hipStream_t st) {
+    hipLaunchKernelGGL(k_beta_table, dim3(1), dim3(1), 0, st, it.state, n_iter2, scratch.beta);
     const size_t lds = (size_t)(n_iter2 < kBetaChunk ? n_iter2 : kBetaChunk) * sizeof(double);
-#define DMF_CASE(NU_)                                                                                          \
-    case NU_: {                                                                                                \
-        const int64_t rows_per_block = 4 * (64 / NU_);                                                         \
-        const int64_t grid = (N + rows_per_block - 1) / rows_per_block;                                        \
-        hipLaunchKernelGGL((k_u_inner_rows<NU_>), dim3((unsigned)grid), dim3(256), lds, st, cm, beta, u, u_prev, \
-                           state, N, n_iter2, mode);                                                           \
-        break;                                                                                                 \
-    }
-#define DMF_CASE16(NU_)                                                                                          \
-    case NU_: {                                                                                                  \
-        const int64_t grid = (N + 15) / 16; /* 4 waves x 4 rows */                                               \
-        hipLaunchKernelGGL((k_u_inner_rows16<NU_>), dim3((unsigned)grid), dim3(256), lds, st, cm, beta, u, u_prev, \
-                           state, N, n_iter2, mode);                                                             \
-        break;                                                                                                   \
-    }
-    switch (n_u) {
-        DMF_CASE(1) DMF_CASE(2) DMF_CASE(3) DMF_CASE(4) DMF_CASE16(5) DMF_CASE16(6) DMF_CASE16(7) DMF_CASE16(8)
-        DMF_CASE16(9) DMF_CASE16(10) DMF_CASE16(11) DMF_CASE16(12) DMF_CASE16(13) DMF_CASE16(14) DMF_CASE16(15) DMF_CASE16(16)
-#define DMF_CASE32(NU_)                                                                                          \
-    case NU_: {                                                                                                  \
-        const int64_t grid = (N + 7) / 8; /* 4 waves x 2 rows */                                                 \
-        hipLaunchKernelGGL((k_u_inner_rows32<NU_>), dim3((unsigned)grid), dim3(256), lds, st, cm, beta, u, u_prev, \
-                           state, N, n_iter2, mode);                                                             \
-        break;                                                                                                   \
-    }
-        DMF_CASE32(17) DMF_CASE32(18) DMF_CASE32(19) DMF_CASE32(20) DMF_CASE32(21) DMF_CASE32(22) DMF_CASE32(23) DMF_CASE32(24)
-        DMF_CASE32(25) DMF_CASE32(26) DMF_CASE32(27) DMF_CASE32(28) DMF_CASE32(29) DMF_CASE32(30) DMF_CASE32(31) DMF_CASE32(32)
-#undef DMF_CASE32
-        default: return hipErrorInvalidValue;
-    }
-#undef DMF_CASE
-#undef DMF_CASE16
-    return hipGetLastError();
+    // rows per workgroup of 4 waves: 4 x (64 / n_u) up to four unknowns, 4 x 4 up to sixteen, 4 x 2 beyond
+    const auto launch = [&](auto kernel, int64_t rows_per_block) {
+        const int64_t grid = (N + rows_per_block - 1) / rows_per_block;
+        hipLaunchKernelGGL(kernel, dim3((unsigned)grid), dim3(256), lds, st, scratch.cm, scratch.beta, it.u, it.u_prev,
+                           it.state, N, n_iter2, it.mode);
+        return hipGetLastError();
+    };
+    if (it.n_u <= 4)
+        return dispatch_int<1, 4>(it.n_u, [&](auto nu) { return launch(k_u_inner_rows<nu.value>, 4 * (64 / nu.value)); });
+    if (it.n_u <= 16) return dispatch_int<5, 16>(it.n_u, [&](auto nu) { return launch(k_u_inner_rows16<nu.value>, 16); });
+    return dispatch_int<17, 32>(it.n_u, [&](auto nu) { return launch(k_u_inner_rows32<nu.value>, 8); });
 }
 
-// cm: N x (n_u + NP) doubles, beta: n_iter2 doubles (both device scratch owned by the caller)
-hipError_t launch_u_phase_split(const double* V, const double* D, const unsigned short* D16, int SD, const double* Rt,
-                                const double* alpha, double* u, double* u_prev, const SolverState* state, int64_t N, int S,
-                                int n_c, int n_u, int n_iter2, int mode, double* cm, double* beta, hipStream_t st) {
-    if (cm == nullptr || beta == nullptr) return hipErrorInvalidValue;
-    hipError_t e = launch_u_phase_mfma_impl(V, D, D16, SD, Rt, alpha, u, u_prev, state, N, S, n_c, n_u, n_iter2, mode, cm, st);
+// scratch.cm: N x (n_u + NP) doubles, scratch.beta: n_iter2 doubles (both device scratch owned by the caller)
+hipError_t launch_u_phase_split(const ProblemView& p, const IterateView& it, int n_iter2, const UScratch& scratch,
+                                hipStream_t st) {
+    if (scratch.cm == nullptr || scratch.beta == nullptr) return hipErrorInvalidValue;
+    hipError_t e = launch_u_phase_mfma_impl(p, it, n_iter2, scratch.cm, st);
     if (e != hipSuccess) return e;
-    return launch_u_inner(cm, beta, u, u_prev, state, N, n_u, n_iter2, mode, st);
+    return launch_u_inner(p.N, it, n_iter2, scratch, st);
 }
 
 // the same with the integer-matrix-core producer of dmf_kernels_cm_i8.hip (n_u <= 16; its preconditions are the caller's)
-hipError_t launch_u_phase_split_i8(const double* V, const unsigned short* D16, int SD, int ND, const double* Rt,
-                                   const double* alpha, double* u, double* u_prev, const SolverState* state, int64_t N,
-                                   int S, int n_c, int n_u, int n_iter2, int mode, double* cm, double* beta,
+hipError_t launch_u_phase_split_i8(const ProblemView& p, const IterateView& it, int n_iter2, const UScratch& scratch,
                                    hipStream_t st) {
-    if (cm == nullptr || beta == nullptr) return hipErrorInvalidValue;
-    hipError_t e = launch_cm_i8(V, D16, SD, ND, Rt, alpha, state, N, S, n_c, n_u, cm, st);
+    if (scratch.cm == nullptr || scratch.beta == nullptr) return hipErrorInvalidValue;
+    hipError_t e = launch_cm_i8(p, it, scratch.cm, st);
     if (e != hipSuccess) return e;
-    return launch_u_inner(cm, beta, u, u_prev, state, N, n_u, n_iter2, mode, st);
+    return launch_u_inner(p.N, it, n_iter2, scratch, st);
 }
 
 // producer of dmf_kernels_cm_i8.hip, then the inner iterations fused with the b_u stream (k_inner_bu): the whole u phase
 // plus b_u and ||u||^2 of the integer Gram route in two launches (+ the momentum table)
-hipError_t launch_u_phase_split_i8_bu(const double* V, const unsigned short* D16, int SD, int ND, const double* Rt,
-                                      const double* alpha, double* u, double* u_prev, const SolverState* state, int64_t N,
-                                      int S, int n_c, int n_u, int n_iter2, int mode, double* cm, double* beta,
-                                      double* slab, double* u2_partials, int* grid_out, hipStream_t st) {
-    if (cm == nullptr || beta == nullptr || slab == nullptr || u2_partials == nullptr) return hipErrorInvalidValue;
-    hipError_t e = launch_cm_i8(V, D16, SD, ND, Rt, alpha, state, N, S, n_c, n_u, cm, st);
+hipError_t launch_u_phase_split_i8_bu(const ProblemView& p, const IterateView& it, int n_iter2, const UScratch& scratch,
+                                      int* grid_out, hipStream_t st) {
+    if (scratch.cm == nullptr || scratch.beta == nullptr || scratch.slab == nullptr || scratch.u2_partials == nullptr)
+        return hipErrorInvalidValue;
+    hipError_t e = launch_cm_i8(p, it, scratch.cm, st);
     if (e != hipSuccess) return e;
-    return launch_u_inner_bu(cm, beta, u, u_prev, state, V, D16, SD, N, S, n_u, n_iter2, mode, slab, u2_partials, grid_out, st);
+    return launch_u_inner_bu(p, it, n_iter2, scratch, grid_out, st);
 }
 
 }  // namespace dmf

@@ -2,6 +2,7 @@
 // (demethify/deconvolution.py:15-17) and the generic per-sample weighted Gram accumulation
 // that feeds the alpha phase (G_s = R^T diag(d_s) R, b_s = R^T (d_s * v_s)).
 #include "dmf_device.h"
+#include "dmf_dispatch.h"
 #include "dmf_internal.h"
 
 namespace dmf {
@@ -422,140 +423,87 @@ int vdv_cols_grid(int64_t N) {
 }
 
 // slab: vdv_cols_grid(N) * S doubles
-hipError_t launch_vdv_cols(const double* V, const double* D, const unsigned short* D16, int SD, int64_t N, int S, double* slab,
-                           double* out, hipStream_t st) {
-    const int nbx = vdv_cols_grid(N);
+hipError_t launch_vdv_cols(const ProblemView& p, double* slab, double* out, hipStream_t st) {
+    const int S = p.S, nbx = vdv_cols_grid(p.N);
     const dim3 grid(nbx, (S + 63) / 64);
-    if (D16 != nullptr) hipLaunchKernelGGL((k_vdv_cols<true>), grid, dim3(256), 0, st, V, (const void*)D16, SD, N, S, slab);
-    else hipLaunchKernelGGL((k_vdv_cols<false>), grid, dim3(256), 0, st, V, (const void*)D, S, N, S, slab);
+    if (p.D16 != nullptr) hipLaunchKernelGGL((k_vdv_cols<true>), grid, dim3(256), 0, st, p.V, (const void*)p.D16, p.SD, p.N, S, slab);
+    else hipLaunchKernelGGL((k_vdv_cols<false>), grid, dim3(256), 0, st, p.V, (const void*)p.D, S, p.N, S, slab);
     hipLaunchKernelGGL(k_vdv_finish, dim3((S + 63) / 64), dim3(64), 0, st, slab, nbx, S, out);
     return hipGetLastError();
 }
 
 bool cost_cols_supported(int S, int n_c, int n_u) { return n_c <= 16 && n_u >= 0 && n_u <= 4 && n_c + n_u >= 1; }
 
+// the two-samples-per-lane form (u16 counts, V aligned to 8 bytes, an even SD) and the sum of its partials
 template <int NKC, int NU>
-static hipError_t launch_cost_cols_t(const double* V, const double* D, const unsigned short* D16, int SD, const double* Rtp,
-                                     const double* u, const double* alpha, int64_t N, int S, int n_c, double* scratch,
-                                     double* out, hipStream_t st) {
-    const int ny = (S + 63) / 64;
-    int64_t want = (N + 4 * 8 - 1) / (4 * 8);
-    int nbx = (int)(want < 1 ? 1 : want);
-    const int cap = 1024 / ny;  // scratch: 1024 partials
-    if (nbx > cap) nbx = cap;
-    if (D16 != nullptr && S >= 128 && SD % 2 == 0 && (reinterpret_cast<uintptr_t>(V) & 7) == 0) {
-        const int ny2 = (S + 127) / 128;
-        nbx = (int)(want < 1 ? 1 : want);
-        if (nbx > 1024 / ny2) nbx = 1024 / ny2;
-        if (S & 1)
-            hipLaunchKernelGGL((k_cost_cols2<NKC, NU, true>), dim3(nbx, ny2), dim3(256), 0, st, V, D16, SD, Rtp, u, alpha, N, S,
-                               n_c, scratch);
-        else
-            hipLaunchKernelGGL((k_cost_cols2<NKC, NU, false>), dim3(nbx, ny2), dim3(256), 0, st, V, D16, SD, Rtp, u, alpha, N, S,
-                               n_c, scratch);
-        hipLaunchKernelGGL(k_reduce_final<1>, dim3(1), dim3(256), 0, st, scratch, nbx * ny2, out, (const int*)nullptr);
-        return hipGetLastError();
-    }
-    if (D16 != nullptr)
-        hipLaunchKernelGGL((k_cost_cols<NKC, NU, true>), dim3(nbx, ny), dim3(256), 0, st, V, (const void*)D16, SD, Rtp, u,
-                           alpha, N, S, n_c, scratch);
-    else
-        hipLaunchKernelGGL((k_cost_cols<NKC, NU, false>), dim3(nbx, ny), dim3(256), 0, st, V, (const void*)D, S, Rtp, u, alpha,
-                           N, S, n_c, scratch);
-    hipLaunchKernelGGL(k_reduce_final<1>, dim3(1), dim3(256), 0, st, scratch, nbx * ny, out, (const int*)nullptr);
-    return hipGetLastError();
-}
-
-template <int NKC>
-static hipError_t launch_cost_cols_nkc(int n_u, const double* V, const double* D, const unsigned short* D16, int SD,
-                                       const double* Rtp, const double* u, const double* alpha, int64_t N, int S, int n_c,
-                                       double* scratch, double* out, hipStream_t st) {
-    switch (n_u) {
-#define DMF_CASE(NU_) \
-    case NU_: return launch_cost_cols_t<NKC, NU_>(V, D, D16, SD, Rtp, u, alpha, N, S, n_c, scratch, out, st);
-        DMF_CASE(0) DMF_CASE(1) DMF_CASE(2) DMF_CASE(3) DMF_CASE(4)
-#undef DMF_CASE
-        default: return hipErrorInvalidValue;
-    }
-}
-
-hipError_t launch_cost_cols(const double* V, const double* D, const unsigned short* D16, int SD, const double* Rtp,
-                            const double* u, const double* alpha, int64_t N, int S, int n_c, int n_u, double* scratch,
-                            double* out, hipStream_t st) {
-    switch ((n_c + 3) / 4) {
-#define DMF_NKC(X) \
-    case X: return launch_cost_cols_nkc<X>(n_u, V, D, D16, SD, Rtp, u, alpha, N, S, n_c, scratch, out, st);
-        DMF_NKC(0) DMF_NKC(1) DMF_NKC(2) DMF_NKC(3) DMF_NKC(4)
-#undef DMF_NKC
-        default: return hipErrorInvalidValue;
-    }
-}
-
-// Wide row groups (5..16 unknowns): the two-samples-per-lane form only (u16 counts, S even and >= 128, 16-B aligned V);
-// other shapes of that width stay on the generic k_cost.
-bool cost_cols2_wide_supported(const double* V, const unsigned short* D16, int S, int SD, int n_c, int n_u) {
-    // (below 128 samples part of the lanes idle; what competes is the any-shape k_cost, slower from ~32 samples on)
-    return D16 != nullptr && n_c <= 16 && n_u >= 5 && n_u <= 16 && S >= 32 && SD % 2 == 0 &&
-           (reinterpret_cast<uintptr_t>(V) & 7) == 0;
-}
-
-template <int NKC, int NU>
-static hipError_t launch_cost_cols2_wide_t(const double* V, const unsigned short* D16, int SD, const double* Rtp,
-                                           const double* u, const double* alpha, int64_t N, int S, int n_c, double* scratch,
-                                           double* out, hipStream_t st) {
-    const int ny2 = (S + 127) / 128;
-    const int64_t want = (N + 4 * 8 - 1) / (4 * 8);
+static hipError_t launch_cost_cols2_t(const ProblemView& p, const double* u, const double* alpha, double* scratch, double* out,
+                                      hipStream_t st) {
+    const int S = p.S, ny2 = (S + 127) / 128;
+    const int64_t want = (p.N + 4 * 8 - 1) / (4 * 8);
     int nbx = (int)(want < 1 ? 1 : want);
     if (nbx > 1024 / ny2) nbx = 1024 / ny2;  // scratch: 1024 partials
     if (S & 1)
-        hipLaunchKernelGGL((k_cost_cols2<NKC, NU, true>), dim3(nbx, ny2), dim3(256), 0, st, V, D16, SD, Rtp, u, alpha, N, S, n_c,
-                           scratch);
+        hipLaunchKernelGGL((k_cost_cols2<NKC, NU, true>), dim3(nbx, ny2), dim3(256), 0, st, p.V, p.D16, p.SD, p.Rtp, u, alpha,
+                           p.N, S, p.n_c, scratch);
     else
-        hipLaunchKernelGGL((k_cost_cols2<NKC, NU, false>), dim3(nbx, ny2), dim3(256), 0, st, V, D16, SD, Rtp, u, alpha, N, S, n_c,
-                           scratch);
+        hipLaunchKernelGGL((k_cost_cols2<NKC, NU, false>), dim3(nbx, ny2), dim3(256), 0, st, p.V, p.D16, p.SD, p.Rtp, u, alpha,
+                           p.N, S, p.n_c, scratch);
     hipLaunchKernelGGL(k_reduce_final<1>, dim3(1), dim3(256), 0, st, scratch, nbx * ny2, out, (const int*)nullptr);
     return hipGetLastError();
 }
 
-template <int NKC>
-static hipError_t launch_cost_cols2_wide_nkc(int n_u, const double* V, const unsigned short* D16, int SD, const double* Rtp,
-                                             const double* u, const double* alpha, int64_t N, int S, int n_c,
-                                             double* scratch, double* out, hipStream_t st) {
-    switch (n_u) {
-#define DMF_CASE(NU_) \
-    case NU_: return launch_cost_cols2_wide_t<NKC, NU_>(V, D16, SD, Rtp, u, alpha, N, S, n_c, scratch, out, st);
-        DMF_CASE(5) DMF_CASE(6) DMF_CASE(7) DMF_CASE(8) DMF_CASE(9) DMF_CASE(10) DMF_CASE(11) DMF_CASE(12) DMF_CASE(13)
-        DMF_CASE(14) DMF_CASE(15) DMF_CASE(16)
-#undef DMF_CASE
-        default: return hipErrorInvalidValue;
-    }
+hipError_t launch_cost_cols(const ProblemView& p, const double* u, const double* alpha, int n_u, double* scratch, double* out,
+                            hipStream_t st) {
+    return dispatch_int<0, 4>((p.n_c + 3) / 4, [&](auto nkc) {
+        return dispatch_int<0, 4>(n_u, [&](auto nu) {
+            constexpr int NKC = decltype(nkc)::value, NU = decltype(nu)::value;
+            const int S = p.S, ny = (S + 63) / 64;
+            if (p.D16 != nullptr && S >= 128 && p.SD % 2 == 0 && (p.v_align() & 7) == 0)
+                return launch_cost_cols2_t<NKC, NU>(p, u, alpha, scratch, out, st);
+            const int64_t want = (p.N + 4 * 8 - 1) / (4 * 8);
+            int nbx = (int)(want < 1 ? 1 : want);
+            const int cap = 1024 / ny;  // scratch: 1024 partials
+            if (nbx > cap) nbx = cap;
+            if (p.D16 != nullptr)
+                hipLaunchKernelGGL((k_cost_cols<NKC, NU, true>), dim3(nbx, ny), dim3(256), 0, st, p.V, (const void*)p.D16, p.SD,
+                                   p.Rtp, u, alpha, p.N, S, p.n_c, scratch);
+            else
+                hipLaunchKernelGGL((k_cost_cols<NKC, NU, false>), dim3(nbx, ny), dim3(256), 0, st, p.V, (const void*)p.D, S,
+                                   p.Rtp, u, alpha, p.N, S, p.n_c, scratch);
+            hipLaunchKernelGGL(k_reduce_final<1>, dim3(1), dim3(256), 0, st, scratch, nbx * ny, out, (const int*)nullptr);
+            return hipGetLastError();
+        });
+    });
 }
 
-hipError_t launch_cost_cols2_wide(const double* V, const unsigned short* D16, int SD, const double* Rtp, const double* u,
-                                  const double* alpha, int64_t N, int S, int n_c, int n_u, double* scratch, double* out,
-                                  hipStream_t st) {
-    if (!cost_cols2_wide_supported(V, D16, S, SD, n_c, n_u)) return hipErrorInvalidValue;
-    switch ((n_c + 3) / 4) {
-#define DMF_NKC(X) \
-    case X: return launch_cost_cols2_wide_nkc<X>(n_u, V, D16, SD, Rtp, u, alpha, N, S, n_c, scratch, out, st);
-        DMF_NKC(0) DMF_NKC(1) DMF_NKC(2) DMF_NKC(3) DMF_NKC(4)
-#undef DMF_NKC
-        default: return hipErrorInvalidValue;
-    }
+// Wide row groups (5..16 unknowns): the two-samples-per-lane form only (u16 counts, S even and >= 128, 16-B aligned V);
+// other shapes of that width stay on the generic k_cost.
+bool cost_cols2_wide_supported(const ProblemView& p, int n_u) {
+    // (below 128 samples part of the lanes idle; what competes is the any-shape k_cost, slower from ~32 samples on)
+    return p.D16 != nullptr && p.n_c <= 16 && n_u >= 5 && n_u <= 16 && p.S >= 32 && p.SD % 2 == 0 && (p.v_align() & 7) == 0;
 }
 
-hipError_t launch_cost(const double* V, const double* D, const double* Rt, const double* u,
-                       const double* alpha, int64_t N, int S, int n_c, int n_u,
-                       double* scratch, double* out, hipStream_t st) {
-    const int K = n_c + n_u;
+hipError_t launch_cost_cols2_wide(const ProblemView& p, const double* u, const double* alpha, int n_u, double* scratch,
+                                  double* out, hipStream_t st) {
+    if (!cost_cols2_wide_supported(p, n_u)) return hipErrorInvalidValue;
+    return dispatch_int<0, 4>((p.n_c + 3) / 4, [&](auto nkc) {
+        return dispatch_int<5, 16>(n_u, [&](auto nu) {
+            return launch_cost_cols2_t<decltype(nkc)::value, decltype(nu)::value>(p, u, alpha, scratch, out, st);
+        });
+    });
+}
+
+hipError_t launch_cost(const ProblemView& p, const double* u, const double* alpha, int n_u, double* scratch, double* out,
+                       hipStream_t st) {
+    const int S = p.S, K = p.n_c + n_u;
     const int tpr = S < 256 ? S : 256;
     const int rows_per_tile = 256 / tpr;
-    int64_t tiles = (N + rows_per_tile - 1) / rows_per_tile;
+    int64_t tiles = (p.N + rows_per_tile - 1) / rows_per_tile;
     const int nb = (int)(tiles < 1024 ? (tiles < 1 ? 1 : tiles) : 1024);
     const size_t lds = (size_t)K * S * sizeof(double);
     const int in_lds = lds <= 48 * 1024;
-    hipLaunchKernelGGL(k_cost, dim3(nb), dim3(256), in_lds ? lds : 0, st, V, D, Rt, u, alpha, N, S,
-                       n_c, n_u, in_lds, scratch);
+    hipLaunchKernelGGL(k_cost, dim3(nb), dim3(256), in_lds ? lds : 0, st, p.V, p.D, p.Rt, u, alpha, p.N, S, p.n_c, n_u, in_lds,
+                       scratch);
     hipLaunchKernelGGL(k_reduce_final<1>, dim3(1), dim3(256), 0, st, scratch, nb, out,
                        (const int*)nullptr);
     return hipGetLastError();
@@ -687,15 +635,15 @@ hipError_t launch_gram_reduce(const double* slab, int ny, int n_jobs, int S, con
     return hipGetLastError();
 }
 
-hipError_t launch_gram(const double* V, const double* D, const double* Rt, const double* u,
-                       int64_t N, int S, int n_c, int n_u, GramJobTable jobs, double* slab,
-                       int64_t slab_doubles, double* gb, const int* done_flag, hipStream_t st) {
+hipError_t launch_gram(const ProblemView& p, const double* u, int n_u, GramJobTable jobs, double* slab, int64_t slab_doubles,
+                       double* gb, const int* done_flag, hipStream_t st) {
     if (jobs.count <= 0) return hipSuccess;
+    const int S = p.S;
     int nsx, nz, ny;
     int64_t rpc;
-    gram_geometry(N, S, jobs.count, &nsx, &nz, &ny, &rpc);
+    gram_geometry(p.N, S, jobs.count, &nsx, &nz, &ny, &rpc);
     if ((int64_t)ny * jobs.count * S > slab_doubles) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(k_gram, dim3(nsx, ny, nz), dim3(256), 0, st, V, D, Rt, u, N, S, n_c, n_u,
+    hipLaunchKernelGGL(k_gram, dim3(nsx, ny, nz), dim3(256), 0, st, p.V, p.D, p.Rt, u, p.N, S, p.n_c, n_u,
                        jobs.k_idx, jobs.l_idx, jobs.count, rpc, slab, done_flag);
     hipLaunchKernelGGL(k_gram_reduce, dim3((S + 31) / 32, jobs.count), dim3(256), 0, st, slab, ny,
                        jobs.count, S, jobs.dst_row, gb, done_flag);

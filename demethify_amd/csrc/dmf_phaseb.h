@@ -22,33 +22,6 @@ __device__ __forceinline__ double f_group_bcast(double x, int lane0) {
     else return __shfl(x, lane0 + L, 64);
 }
 
-// sum_l base_l * Ms[l] over the NU lanes of a row group, as a balanced tree: phase B is one dependent
-// chain on the workgroup's critical path, so its depth (not its instruction count) is what costs
-template <int NU, int L0, int L1>
-__device__ __forceinline__ double f_dot_tree(double base, const double (&Ms)[NU], int lane0) {
-    if constexpr (L1 - L0 == 1) {
-        return f_group_bcast<NU, L0>(base, lane0) * Ms[L0];
-    } else {
-        constexpr int MID = (L0 + L1) / 2;
-        return f_dot_tree<NU, L0, MID>(base, Ms, lane0) + f_dot_tree<NU, MID, L1>(base, Ms, lane0);
-    }
-}
-
-// clip(a - b, 0, 1) in one instruction: the VOP3 clamp modifier clamps an FP result to [0, 1]
-// (np.clip(x, 0, 1) of deconvolution.py:88; a NaN would come out as 0 instead of NaN)
-__device__ __forceinline__ double f_sub_clamp01(double a, double b) {
-    double r;
-    asm("v_add_f64 %0, %1, -%2 clamp" : "=v"(r) : "v"(a), "v"(b));
-    return r;
-}
-
-// clip(a + b, 0, 1) in one instruction (VOP3 clamp modifier; a NaN would come out as 0 instead of NaN)
-__device__ __forceinline__ double f_add_clamp01(double a, double b) {
-    double r;
-    asm("v_add_f64 %0, %1, %2 clamp" : "=v"(r) : "v"(a), "v"(b));
-    return r;
-}
-
 // clip(a * b + c, 0, 1) in one instruction: the VOP3 clamp modifier clamps an FP result to [0, 1]
 // (np.clip(x, 0, 1) of deconvolution.py:88; a NaN would come out as 0 instead of NaN)
 __device__ __forceinline__ double f_fma_clamp01(double a, double b, double c) {

@@ -1,36 +1,16 @@
 // Kernel selection (dmf_select.h): the one place where shape rules live.  Host code only.
 #include "dmf_select.h"
+#include "dmf_dispatch.h"
 #include "dmf_internal.h"
 #include <cstdio>
-#include <cstdlib>
 
 namespace dmf {
-
-namespace {
-
-// A threshold: a named constant in the product.  Only a -DDMF_EXPERIMENT build (DMF_EXPERIMENT=1 python -m
-// demethify_amd._build, what tools/wide_nu_sweep.py and tools/gram_i8_vs_fp64.py use for their before / after columns) lets
-// the environment move it.
-int knob(const char* name, int value) {
-#ifdef DMF_EXPERIMENT
-    if (const char* v = getenv(name)) return atoi(v);
-#else
-    (void)name;
-#endif
-    return value;
-}
-
-// (the support predicates of the stream kernels test the alignment of V through its address)
-const double* aligned_like(unsigned align) { return reinterpret_cast<const double*>((uintptr_t)0x10000 + align); }
-
-}  // namespace
 
 PathSpec select_path(const ShapeKey& k) {
     PathSpec s;
     const int S = k.S, n_c = k.n_c, n_u = k.n_u;
     const bool fast = k.level == 0 || k.level == 3 || k.level == 4;
     const bool ints = k.nd > 0;  // the problem carries u16 / 8-bit-plane copies of its counts
-    const double* v_like = aligned_like(k.v_align);
 
     // ---- fall-back u phase and FP64 Gram kernels (every level)
     if (fast && u_phase_mfma_supported(S, n_c, n_u)) s.u_path = 0;
@@ -49,7 +29,7 @@ PathSpec select_path(const ShapeKey& k) {
     // phase with the integer-matrix-core producer.  Measured at 5e5 x 128 against what ran before: DESIGN.md section 5.
     const int cm_min_nu = knob("DMF_CM_I8_MIN_NU", kCmI8MinNu);
     s.use_cm_i8 = k.level == 0 && !s.use_v2 && ints && (n_u >= cm_min_nu || S > 512 || n_c > 16) && n_u <= 32 &&
-                  (n_c == 0 || (k.rtp_present && (k.rtp_align & 7) == 0)) && cm_i8_supported(v_like, S, n_c, n_u, k.nd, k.SD);
+                  (n_c == 0 || (k.rtp_present && (k.rtp_align & 7) == 0)) && cm_i8_supported(k.v_align, S, n_c, n_u, k.nd, k.SD);
 
     // ---- integer Gram route behind a u phase that is a kernel of its own.  What it competes with is k_gram_u, whose time
     // grows with its accumulator count (padded known types x unknowns + pairs + b_u) while the integer route is flat
@@ -58,7 +38,7 @@ PathSpec select_path(const ShapeKey& k) {
     // 8 unknowns (36 pairs) on.  Behind k_cm_i8 the b_u stream rides along with the inner iterations (k_inner_bu) and the
     // integer route is all that is left of the Gram pass: it then wins at every width.
     const int fp64_acc = (n_c + 3) / 4 * 4 * n_u + n_u * (n_u + 1) / 2 + n_u;
-    const bool fused_bu = s.use_cm_i8 && u_inner_bu_supported(v_like, S, k.SD, n_u, 20);
+    const bool fused_bu = s.use_cm_i8 && u_inner_bu_supported(k.v_align, S, k.SD, n_u, 20);
     const bool known_ok = n_c > 0 ? (k.rtp_present && k.rtp_align == 0) : true;
     const bool wide_enough = n_c > 0 ? fp64_acc >= knob("DMF_GRAM_I8_MIN", kGramI8MinFp64Acc)
                                      : n_u * (n_u + 1) / 2 >= knob("DMF_GRAM_I8_MIN_NC0", kGramI8MinPairsNoKnown);
@@ -83,14 +63,13 @@ PathSpec select_path(const ShapeKey& k) {
 IterationPlan plan_iteration(const ShapeKey& k, const PathSpec& s, int n_iter2, bool purity) {
     IterationPlan plan;
     const int S = k.S, n_c = k.n_c, n_u = k.n_u, K = n_c + n_u;
-    const double* v_like = aligned_like(k.v_align);
     // The fixed-point features of the integer Gram need u inside [0, 1]: the u phase's clip puts it there -- after at
     // least one inner step.  With none, u is still the caller's array and the FP64 kernels run.
     const bool clipped = n_iter2 >= 1;
     if (s.use_v2 && clipped && n_iter2 <= kSplitInnerSteps && rowpass_v2_supported(S, n_c, n_u, n_iter2)) {
         plan.row = RowKind::RowpassV2;
         plan.gram = GramKind::I8;
-    } else if (s.use_cm_i8 && s.use_gram_i8 && clipped && u_inner_bu_supported(v_like, S, k.SD, n_u, n_iter2)) {
+    } else if (s.use_cm_i8 && s.use_gram_i8 && clipped && u_inner_bu_supported(k.v_align, S, k.SD, n_u, n_iter2)) {
         plan.row = RowKind::CmI8InnerBu;
         plan.gram = GramKind::I8;
     } else if (s.use_fused && n_iter2 <= kSplitInnerSteps) {
