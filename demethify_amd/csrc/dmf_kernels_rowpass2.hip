@@ -69,6 +69,8 @@ __device__ __forceinline__ unsigned long long dmf2_stamp() {
 #define DMF2_SUB(i)
 #endif
 
+// Diagnostic switches (tools/rowpass2_probe.hip times the kernel without either from this source): DMF_CHAIN_NO_UNROLL
+// (the written-out step loop at kUnrolledSteps), DMF_CHAIN_NO_I32 (M digit pairs joined in i32 before the conversion).
 #ifndef DMF_V2_STAGGER
 #define DMF_V2_STAGGER 12  // x 64 cycles: how long the waves that do not run phase B hold back their prefetch
 #endif
@@ -125,6 +127,23 @@ __device__ __forceinline__ void inner_steps(double& uu, double& up, double cj, c
         const double tmp = uu;
         uu = up;
         up = tmp;
+    }
+}
+
+// The CLI's default n_iter2 has its step loop written out: beta_t then comes from a CONSTANT lane, so the v_readlane pair
+// of a step waits for no scalar add (a lane select written by the scalar unit costs wait states before v_readlane may
+// use it) and stands off the dependent chain, and the loop's counter, compare and branch are gone.  Same values, same
+// arithmetic, same order.  (An even count: (u, u_) swap roles every step.)
+constexpr int kUnrolledSteps = 20;
+
+template <int NU, bool AT_PREV>
+__device__ __forceinline__ void inner_steps_unrolled(double& uu, double& up, double cj, const double (&Ms)[NU], int b_lo, int b_hi,
+                                                     int lane0) {
+    static_assert(kUnrolledSteps % 2 == 0 && kUnrolledSteps <= 64, "pairs of steps; beta_t in lane t of one register pair");
+#pragma unroll
+    for (int t2 = 0; t2 < kUnrolledSteps; t2 += 2) {
+        inner_step<NU, AT_PREV>(uu, up, cj, Ms, b_lo, b_hi, t2, lane0);
+        inner_step<NU, AT_PREV>(up, uu, cj, Ms, b_lo, b_hi, t2 + 1, lane0);
     }
 }
 
@@ -495,7 +514,9 @@ __global__ __launch_bounds__(64 * MAXW, MAXW == 4 ? 2 : 1) void k_rowpass_v2(
         }
 #endif
         // lane (pair m16, q) holds rows 4 q + reg: the exact integer sum_w 256^w mw[w] in two halves that fit a double
-        // without rounding (|mw| < 2^21 per digit product sum), one rounding when they are joined
+        // without rounding (|mw| < 2^21 per digit product sum), one rounding when they are joined.  The digit pairs
+        // mw[2k] + 256 mw[2k+1] (< 2^30) are joined in i32 first: four conversions and three FMAs per value on the FP64
+        // pipe instead of eight and seven, every intermediate exact either way.
         double mrow[4];
 #ifdef DMF_ABLATE_M
 #pragma unroll
@@ -503,8 +524,13 @@ __global__ __launch_bounds__(64 * MAXW, MAXW == 4 ? 2 : 1) void k_rowpass_v2(
 #else
 #pragma unroll
         for (int rr = 0; rr < 4; ++rr) {
+#ifndef DMF_CHAIN_NO_I32
+            const double lo = fma((double)(mw[3][rr] * 256 + mw[2][rr]), 65536.0, (double)(mw[1][rr] * 256 + mw[0][rr]));
+            const double hi = fma((double)(mw[7][rr] * 256 + mw[6][rr]), 65536.0, (double)(mw[5][rr] * 256 + mw[4][rr]));
+#else
             const double lo = fma(fma(fma((double)mw[3][rr], 256.0, (double)mw[2][rr]), 256.0, (double)mw[1][rr]), 256.0, (double)mw[0][rr]);
             const double hi = fma(fma(fma((double)mw[7][rr], 256.0, (double)mw[6][rr]), 256.0, (double)mw[5][rr]), 256.0, (double)mw[4][rr]);
+#endif
             mrow[rr] = fma(hi, 0x1p32, lo) * m_scale;
         }
 #endif
@@ -557,8 +583,20 @@ __global__ __launch_bounds__(64 * MAXW, MAXW == 4 ? 2 : 1) void k_rowpass_v2(
         }
         double uu = uu0, up = up0;
         DMF2_SUB(8)
-        // The momentum coefficients ride in a VGPR (lane t holds beta_t) and reach the loop through
+        // The momentum coefficients ride in a VGPR (lane t holds beta_t) and reach the steps through
         // v_readlane: an LDS read here would sit on the dependent chain every step.
+#ifndef DMF_CHAIN_NO_UNROLL
+        if (XS && MAXW == 4 && n_iter2 == kUnrolledSteps) {  // (X16 form, up to four waves: the written-out loop at its step count)
+            const double bvec = beta_tab[lane < kUnrolledSteps ? lane : kUnrolledSteps - 1];  // (as below)
+            const int b_lo = __double2loint(bvec), b_hi = __double2hiint(bvec);
+            if (mode == 1) {
+                inner_steps_unrolled<NU, true>(uu, up, cj, Ms, b_lo, b_hi, lane0);
+            } else {
+                Ms[0] += 1.0;
+                inner_steps_unrolled<NU, false>(uu, up, cj, Ms, b_lo, b_hi, lane0);
+            }
+        } else
+#endif
         for (int t0 = 0; t0 < n_iter2; t0 += 64) {
             const int tl = t0 + lane < n_iter2 ? t0 + lane : n_iter2 - 1;
             const double bvec = beta_tab[tl];  // (lane t: beta_t; the first read goes out with the partial-sum reads)

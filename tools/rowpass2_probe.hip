@@ -3,6 +3,9 @@
 //   -DPROBE_NO_STAMPS: the kernel as it ships (launch times only); -DPROBE_KERNEL_SRC="\"file\"": another version of the source
 //   -DPROBE_X16: the form on the methylated read counts (X16 + D16, V not read)
 //   -DPROBE_PAIR (with -DPROBE_X16): the pair schedule, two blocks per phase B; cycles then also per pair of blocks
+//   -DDMF_CHAIN_NO_UNROLL: the inner steps as a loop at every step count (T2 = 20 otherwise runs them written out)
+//   -DDMF_CHAIN_NO_I32: the M combine with eight conversions per value instead of digit pairs joined in i32
+//   both together: the kernel before either, from this source
 #ifndef PROBE_NO_STAMPS
 #define DMF_STAMPS 1
 #endif
