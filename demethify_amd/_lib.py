@@ -16,6 +16,7 @@ DMF_INIT_IN_UNIT_RANGE = 4
 DMF_SELECT_COUNTS_F32_EXACT, DMF_SELECT_PURITY, DMF_SELECT_ALPHA_OUTSIDE_UNIT, DMF_SELECT_V_UNALIGNED = 1, 2, 4, 8
 DMF_SELECT_X16 = 16
 DMF_COUNTS_F64 = 2
+DMF_WLS_TARGET_V, DMF_WLS_TARGET_DV = 0, 1
 DMF_MODE_PARTIAL = 0
 DMF_MODE_UNSUPERVISED = 1
 MAX_K = 64  # dmf::kMaxK: largest n_c + n_u the kernels are built for (DMF_ERR_UNSUPPORTED beyond)
@@ -52,6 +53,7 @@ SIGNATURES = {
     "dmf_project_simplex": (C.c_int, [_p, _p, _i64, _i64, C.c_double, C.c_int, _p]),
     "dmf_update_u": (C.c_int, [_p, _p, _p, _p, _p, _i64, _i64, C.c_int, C.c_int, _dbl_p, _p, _p]),
     "dmf_update_alpha": (C.c_int, [_p, _p, _p, _i64, _p, _p, _i64, C.c_int, _dbl_p, _p, _p]),
+    "dmf_wls_intercept": (C.c_int, [_p, _p, _p, _i64, C.c_int, C.c_int, _p, C.POINTER(C.c_int)]),
     "dmf_percentile_axis0": (C.c_int, [_p, _p, _i64, _i64, _p, _i64, C.c_int, _p]),
     "dmf_solver_create": (C.c_int, [_p, _p, _p, _p, _i64, C.c_int, C.c_int, C.POINTER(_p)]),
     "dmf_solver_set_purity": (C.c_int, [_p, _p, C.c_int]),

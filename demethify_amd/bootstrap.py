@@ -16,7 +16,7 @@ import numpy as np
 import pandas as pd
 
 from . import _lib as L
-from . import shard
+from . import init_func, shard
 from .deconvolution import init_BSSMF_md, init_BSSMF_md_p, solve_problem
 from .device import Problem, Solver, get_context
 from .init_func import wls_intercept
@@ -73,7 +73,19 @@ def bt_ci(confidence_level, n_bootstrap, n_u, meth_f, counts, ref, init_option, 
     rank, world, _ = shard.dist_state()
     seeds = bootstrap_seed_sequence(seed, n_bootstrap)
     local = []
-    if supervised:
+    if supervised and init_func.device_wls(n_rows, n_samples, n_ct):
+        # one resident problem; a replicate is a row gather on the device and one regression launch for all its samples
+        # (samples the device declines are solved on the host, from indexed copies made for that replicate only)
+        from .staging import indices_to_device
+
+        ctx = get_context()
+        with Problem(ctx, meth_f, counts, ref) as full:
+            for i in shard.my_items(n_bootstrap, rank, world):
+                idx = bootstrap_row_indices(seeds[i], n_rows)
+                with full.gather(indices_to_device(idx, ctx)) as resampled:
+                    props = resampled.wls_intercept(None, "dv", host_arrays=lambda: (meth_f[idx], counts[idx], ref[idx]))
+                local.append((i, (None, props)))
+    elif supervised:
         for i in shard.my_items(n_bootstrap, rank, world):
             idx = bootstrap_row_indices(seeds[i], n_rows)
             mf, ct, rf = meth_f[idx], counts[idx], ref[idx]

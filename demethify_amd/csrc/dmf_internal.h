@@ -301,4 +301,15 @@ hipError_t launch_percentile_pair(const double* x, int64_t n, int64_t m, Percent
                                   double* out0, double* out1, hipStream_t st);
 int64_t percentile_max_replicates();
 
+// wls_intercept for every sample at once (dmf_kernels_wls.hip).  launch_wls_moments: one pass over the rows for the first
+// moments of R = [Rt | u] under the weights d and the target t = v (target_dv 0) or d v (1), read from (X16, D16) where the
+// problem carries them, else from V and D; mom[2 K + 2][S] = { m_k, r_k, sw, st }, summed over wls_moments_grid(N) slabs in
+// fixed order; slab holds wls_slab_doubles(N, S, K) doubles.  launch_nnls_intercept: Lawson-Hanson per sample on the dense
+// part of a packed Gram gb and mom; out[K][S] for the samples with status 0 (1: not solved here, 2: weights sum to zero).
+int wls_moments_grid(int64_t N);
+int64_t wls_slab_doubles(int64_t N, int S, int K);
+hipError_t launch_wls_moments(const ProblemView& p, const double* u, int n_u, int target_dv, double* slab, double* mom,
+                              hipStream_t st);
+hipError_t launch_nnls_intercept(const double* gb, const double* mom, int K, int S, double* out, int* status, hipStream_t st);
+
 }  // namespace dmf

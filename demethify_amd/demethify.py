@@ -162,7 +162,8 @@ def main(argv=None):
     from . import _lib as L
     from . import shard, staging
     from .bootstrap import bt_ci
-    from .deconvolution import _init_unsupervised, init_BSSMF_md, init_BSSMF_md_p
+    from . import init_func
+    from .deconvolution import _init_guard, _init_unsupervised, init_BSSMF_md, init_BSSMF_md_p, rd, set_seed
     from .device import Problem, Solver, get_context
     from .ic import evaluate_best_ic
     from .init_func import wls_intercept
@@ -193,10 +194,20 @@ def main(argv=None):
             if args.restart > 1:
                 staging.reserve(((meth_f.shape[0], n_u), (K, meth_f.shape[1])), count=2)
 
+            # --init uniform on a large problem: u0 is drawn on the host as init_BSSMF_md / init_BSSMF_md_p draw it (set_seed,
+            # then rd.uniform: the same stream), alpha0 = wls_intercept per sample comes from the device, where the problem
+            # already is (solve_one: the context is not to be used from the worker thread)
+            device_init = (not unsupervised and args.init == "uniform" and n_u <= meth_f.shape[1]
+                           and init_func.device_wls(meth_f.shape[0], meth_f.shape[1], K))
+
             def prepare(k):
                 # the restart's initialisation (legacy-numpy draws, NNLS), drawn and uploaded one restart ahead of the
                 # GPU by a worker thread (staging.Prefetcher)
                 seed_k = shard.restart_seed(args.seed, k)
+                if device_init:
+                    set_seed(seed_k)
+                    u0 = rd.uniform(size=(meth_f.shape[0], n_u))
+                    return staging.to_device((u0,), problem.ctx)[0], u0
                 if unsupervised:
                     u0, a0 = _init_unsupervised(args.init, meth_f, n_u, seed_k)
                 elif purity is not None:
@@ -210,6 +221,12 @@ def main(argv=None):
 
             def solve_one(k, best_cost, prepared):
                 u0, a0 = prepared
+                if device_init:
+                    u0_host = a0
+                    a0 = problem.wls_intercept(u0, "v", host_arrays=lambda: (meth_f, counts, np.c_[ref, u0_host]))
+                    if purity is None:  # (init_BSSMF_md_p returns without the guard)
+                        a0 = _init_guard(a0, n_u)
+                    a0, = staging.to_device((a0,), problem.ctx)
                 mode = L.DMF_MODE_UNSUPERVISED if unsupervised else L.DMF_MODE_PARTIAL
                 s = Solver(problem, u0, a0, mode)
                 try:
@@ -236,9 +253,13 @@ def main(argv=None):
         header = unknown_header if unsupervised else header + unknown_header
     elif n_u == 0 and meth_f.shape[1] >= 1:
         ref_estimate = None
-        proportions = np.concatenate(
-            [wls_intercept(counts[:, k:k + 1] * meth_f[:, k:k + 1], counts[:, k:k + 1], ref)
-             for k in range(meth_f.shape[1])], axis=1)
+        if init_func.device_wls(meth_f.shape[0], meth_f.shape[1], ref.shape[1]):
+            with Problem(get_context(), meth_f, counts, ref) as problem:
+                proportions = problem.wls_intercept(None, "dv", host_arrays=(meth_f, counts, ref))
+        else:
+            proportions = np.concatenate(
+                [wls_intercept(counts[:, k:k + 1] * meth_f[:, k:k + 1], counts[:, k:k + 1], ref)
+                 for k in range(meth_f.shape[1])], axis=1)
     else:
         sys.exit(f'Invalid number of unknown value! : "{args.nbunknown}" ')
 

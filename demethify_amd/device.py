@@ -302,6 +302,63 @@ class Problem:
                                    C.byref(out)), "dmf_cost")
         return out.value
 
+    def wls_intercept(self, u=None, target="v", host_arrays=None):
+        """``wls_intercept`` (init_func.py:8-14) of every sample at once on the device (dmf_wls_intercept), with
+        R_full = [R_trunc | u], the sample's counts as weights and the target meth_frequency (``target="v"``, what the
+        initialisers pass) or counts * meth_frequency (``"dv"``, what the reference-based run passes).  ``u``: None, a host
+        array or a float64 device array (staging.DeviceArray / CUDA tensor) of N x n_u.  Returns the K x S proportions.
+
+        Samples the device declines (status 1: normal matrix rank-deficient to K eps, or the iteration cap) are solved by
+        the host ``init_func.wls_intercept`` from ``host_arrays`` = (meth_f, counts, R_full), or a callable returning that
+        tuple (it is only called when needed); without it they raise.  A sample whose counts sum to zero raises
+        ZeroDivisionError, as the reference does.  ``self.wls_status`` keeps the per-sample status of the last call."""
+        try:
+            tg = {"v": L.DMF_WLS_TARGET_V, "dv": L.DMF_WLS_TARGET_DV}[target]
+        except KeyError:
+            raise ValueError(f'target must be "v" or "dv", got {target!r}') from None
+        flags, n_u = 0, 0
+        if u is not None:
+            if getattr(u, "is_cuda", False):
+                from .staging import DeviceArray
+
+                if isinstance(u, DeviceArray):
+                    ok = u.ctx is self.ctx
+                else:
+                    ok = (_is_torch(u) and u.is_contiguous() and u.element_size() == 8 and u.is_floating_point()
+                          and u.device.index == self.ctx.device)
+                    if ok:
+                        import torch
+
+                        torch.cuda.current_stream(u.device).synchronize()
+                if not ok:
+                    raise ValueError("a device u must be a float64 staging.DeviceArray / contiguous CUDA tensor on the "
+                                     "context's GPU")
+                u = u.reshape(self.N, -1)
+                flags = L.DMF_PTR_DEVICE
+            else:
+                u = _host_f64(u, "u").reshape(self.N, -1)
+            n_u = int(u.shape[1])
+        K = self.n_c + n_u
+        out = np.zeros((K, self.S), dtype=np.float64)
+        status = np.full(self.S, -1, dtype=np.intc)
+        L.check(self._lib.dmf_wls_intercept(self.ctx._h, self._h, _ptr(u) if n_u else None, n_u, tg, flags, _ptr(out),
+                                            status.ctypes.data_as(C.POINTER(C.c_int))), "dmf_wls_intercept")
+        self.wls_status = status
+        if (status == 2).any():
+            raise ZeroDivisionError("Weights sum to zero, can't be normalized")
+        redo = np.flatnonzero(status != 0)
+        if redo.size:
+            if host_arrays is None:
+                raise RuntimeError(f"wls_intercept: the device did not solve samples {redo.tolist()} (rank-deficient "
+                                   "profiles or iteration cap) and no host_arrays were given to solve them on the host")
+            from .init_func import wls_intercept as host_wls
+
+            meth_f, counts, R_full = host_arrays() if callable(host_arrays) else host_arrays
+            for k in redo:
+                x = counts[:, k:k + 1] * meth_f[:, k:k + 1] if target == "dv" else meth_f[:, k:k + 1]
+                out[:, k:k + 1] = host_wls(x, counts[:, k:k + 1], R_full)
+        return out
+
     def update_u(self, u, u_prev, alpha, n_iter2, a1, l_w_prev, l_w, mode=L.DMF_MODE_PARTIAL):
         u = np.ascontiguousarray(u, dtype=np.float64).reshape(self.N, -1)
         u_prev = np.ascontiguousarray(u_prev, dtype=np.float64).reshape(u.shape)

@@ -162,6 +162,19 @@ int dmf_update_alpha(dmf_context* ctx, const dmf_problem* p, const double* u, in
                      const double* alpha, const double* alpha_prev, int64_t n_iter2, int flags,
                      double* scalars_io, double* out_alpha, double* out_alpha_prev);
 
+/* wls_intercept(x, d_x, R_full), init_func.py:8-14 -- weighted non-negative least squares with intercept, renormalised to
+ * proportions -- for every sample at once, with R_full = [Rt | u] (u may be NULL with n_u = 0), weights d_s and the target
+ * v_s (DMF_WLS_TARGET_V: what the initialisers pass) or d_s v_s (DMF_WLS_TARGET_DV: what the reference-based run passes,
+ * demethify.py:212).  Solved per sample from the centred normal equations G - m m^T / sw, r - m st / sw by Lawson-Hanson
+ * with scipy's entry rule and cap of 3 K solves.  DMF_PTR_DEVICE in flags: u is a device array; out_alpha (K x S doubles)
+ * and out_status (S ints) are host arrays, like dmf_cost's out_cost.  out_status: 0 ok, 1 not solved here (the sample's
+ * K x K normal matrix is rank-deficient to K eps, or the cap was reached: solve that sample on the host), 2 the sample's
+ * weights sum to zero (the reference raises ZeroDivisionError there); columns of out_alpha with a non-zero status are left
+ * untouched.  K > 64: DMF_ERR_UNSUPPORTED. */
+enum { DMF_WLS_TARGET_V = 0, DMF_WLS_TARGET_DV = 1 };
+int dmf_wls_intercept(dmf_context* ctx, const dmf_problem* p, const double* u, int64_t n_u, int target,
+                      int flags, double* out_alpha, int* out_status);
+
 /* Bootstrap post-processing (bootstrap.py:51-54 proportions, :75-78 profile estimates):
  * np.percentile(x, q, axis=0) with numpy's default "linear" method, for x = [n replicates][m positions]
  * (C order), q = n_q percentiles in [0, 100]; out = [n_q][m].  Bit-identical to numpy for finite inputs
