@@ -17,9 +17,19 @@ DMF_SELECT_COUNTS_F32_EXACT, DMF_SELECT_PURITY, DMF_SELECT_ALPHA_OUTSIDE_UNIT, D
 DMF_SELECT_X16 = 16
 DMF_COUNTS_F64 = 2
 DMF_WLS_TARGET_V, DMF_WLS_TARGET_DV = 0, 1
+DMF_WLS_F64_ARRAYS = 8
+DMF_ERR_BAD_ARG, DMF_ERR_NONFINITE, DMF_ERR_UNSUPPORTED = 1, 4, 5
 DMF_MODE_PARTIAL = 0
 DMF_MODE_UNSUPERVISED = 1
 MAX_K = 64  # dmf::kMaxK: largest n_c + n_u the kernels are built for (DMF_ERR_UNSUPPORTED beyond)
+SVD_MAX_S, SVD_MAX_NC, SVD_MAX_RANK, SVD_MAX_LDS = 512, 64, 64, 160 * 1024  # dmf::kSvdMax*: what the SVD initialiser's kernels take
+
+
+def svd_project_lds_bytes(n_samples, rank):
+    """dmf::svd_project_lds_bytes: the LDS of k_svd_project (E / sigma columns, an 8-row tile, the partial norms)."""
+    return 8 * (n_samples * rank + 8 * ((n_samples + 63) // 64 * 64 + 16) + 512)
+
+
 KERNEL_ROWPASS, KERNEL_GRAM, KERNEL_ALPHA, KERNEL_COST = 0, 1, 2, 3
 KERNEL_FAMILIES = ("rowpass", "gram", "alpha", "cost")
 
@@ -54,6 +64,9 @@ SIGNATURES = {
     "dmf_update_u": (C.c_int, [_p, _p, _p, _p, _p, _i64, _i64, C.c_int, C.c_int, _dbl_p, _p, _p]),
     "dmf_update_alpha": (C.c_int, [_p, _p, _p, _i64, _p, _p, _i64, C.c_int, _dbl_p, _p, _p]),
     "dmf_wls_intercept": (C.c_int, [_p, _p, _p, _i64, C.c_int, C.c_int, _p, C.POINTER(C.c_int)]),
+    "dmf_svd_gram": (C.c_int, [_p, _p, _p, C.c_int, _p, C.POINTER(_i64)]),
+    "dmf_svd_factor": (C.c_int, [_p, _p, _p, _p, _i64, C.c_int, _p, C.POINTER(_p)]),
+    "dmf_svd_finish": (C.c_int, [_p, _p, _i64, _i64, _p, _p, C.c_int, _p]),
     "dmf_percentile_axis0": (C.c_int, [_p, _p, _i64, _i64, _p, _i64, C.c_int, _p]),
     "dmf_solver_create": (C.c_int, [_p, _p, _p, _p, _i64, C.c_int, C.c_int, C.POINTER(_p)]),
     "dmf_solver_set_purity": (C.c_int, [_p, _p, C.c_int]),

@@ -17,7 +17,7 @@ import pandas as pd
 
 from . import _lib as L
 from . import init_func, shard
-from .deconvolution import init_BSSMF_md, init_BSSMF_md_p, solve_problem
+from .deconvolution import _init_guard, init_BSSMF_md, init_BSSMF_md_p, solve_problem, svd_factors
 from .device import Problem, Solver, get_context
 from .init_func import wls_intercept
 
@@ -105,7 +105,21 @@ def bt_ci(confidence_level, n_bootstrap, n_u, meth_f, counts, ref, init_option, 
         reserve(((n_rows, n_u), (n_ct + n_u, n_samples), (n_rows,)), count=2)
 
         mine = shard.my_items(n_bootstrap, rank, world)
-        needs_data = init_option == "uniform"
+        # "SVD" reads the data too, and above its gate it does so on the device: on the replicate's gathered problem, by the
+        # solving thread (a context is not thread-safe), with u0 staying in HBM; the worker threads then only draw the rows
+        svd_on_device = (init_option == "SVD" and n_u <= n_samples
+                         and init_func.device_svd(n_rows, n_samples, n_ct, n_u))
+        needs_data = init_option in ("uniform", "SVD") and not svd_on_device
+
+        def svd_init(resampled, idx):
+            u0, H = svd_factors(lambda: (meth_f[idx], counts[idx], ref[idx]), None, None, n_u, problem=resampled,
+                                keep_on_device=True)
+            if purity_frac is not None:  # deconvolution.py:262, as coded
+                a0 = np.vstack((purity_frac * init_func.project_simplex_columns(H[:-n_u]),
+                                init_func.project_simplex_columns(H[-n_u:])))
+            else:
+                a0 = _init_guard(init_func.project_simplex_columns(H), n_u)
+            return (u0,) + tuple(to_device((a0,), ctx))
 
         def draw_init(i, idx=None):
             mf = meth_f[idx] if needs_data else np.broadcast_to(meth_f[:1], meth_f.shape)
@@ -128,6 +142,8 @@ def bt_ci(confidence_level, n_bootstrap, n_u, meth_f, counts, ref, init_option, 
 
         if needs_data:
             feeds = (Prefetcher(mine, draw_both, depth=2, workers=1),)
+        elif svd_on_device:
+            feeds = (Prefetcher(mine, draw_rows, depth=2, workers=1),)
         else:
             feeds = (Prefetcher(mine, draw_rows, depth=2, workers=1), Prefetcher(mine, draw_init, depth=2, workers=1))
         u_stack = _device_stack(len(mine), n_rows * n_u)  # replicate profiles stay in HBM when torch is there
@@ -136,10 +152,15 @@ def bt_ci(confidence_level, n_bootstrap, n_u, meth_f, counts, ref, init_option, 
                 for j, parts in enumerate(zip(*feeds)):
                     if needs_data:
                         (i, (idx, idx_dev, u0, a0)), = parts
+                    elif svd_on_device:
+                        (i, (idx, idx_dev)), = parts
+                        u0 = a0 = None
                     else:
                         (i, (idx, idx_dev)), (i2, (u0, a0)) = parts
                         assert i == i2
-                    with full.gather(idx_dev) as resampled, Solver(resampled, u0, a0, L.DMF_MODE_PARTIAL) as s:
+                    with full.gather(idx_dev) as resampled, \
+                            Solver(resampled, *(svd_init(resampled, idx) if svd_on_device else (u0, a0)),
+                                   L.DMF_MODE_PARTIAL) as s:
                         if purity_frac is not None:
                             s.set_purity(purity_frac)
                         s.step(n_iter1, n_iter2, tol)

@@ -46,7 +46,11 @@ int dmf_wls_intercept(dmf_context* ctx, const dmf_problem* p, const double* u, i
     HIP_TRY(mom.alloc(ctx, (size_t)(2 * K + 2) * S));
     HIP_TRY(d_alpha.alloc(ctx, (size_t)K * S));
     HIP_TRY(d_status.alloc(ctx, (size_t)S));
-    HIP_TRY(dmf::launch_wls_moments(p->view(), du, (int)n_u, target == DMF_WLS_TARGET_DV, slab, mom, ctx->stream));
+    // DMF_WLS_F64_ARRAYS: weights and target from V and the f64 counts even where the problem carries (X16, D16), so that
+    // the result does not depend on whether it does (the SVD initialiser, whose residual is formed from the f64 V)
+    dmf::ProblemView pv = p->view();
+    if (flags & DMF_WLS_F64_ARRAYS) pv.X16 = nullptr, pv.D16 = nullptr;
+    HIP_TRY(dmf::launch_wls_moments(pv, du, (int)n_u, target == DMF_WLS_TARGET_DV, slab, mom, ctx->stream));
     HIP_TRY(dmf::launch_nnls_intercept(gb, mom, (int)K, (int)S, d_alpha, d_status, ctx->stream));
     std::vector<double> h_alpha((size_t)K * S);
     HIP_TRY(hipMemcpyAsync(out_status, d_status, (size_t)S * sizeof(int), hipMemcpyDeviceToHost, ctx->stream));

@@ -312,4 +312,26 @@ hipError_t launch_wls_moments(const ProblemView& p, const double* u, int n_u, in
                               hipStream_t st);
 hipError_t launch_nnls_intercept(const double* gb, const double* mom, int K, int S, double* out, int* status, hipStream_t st);
 
+// The SVD initialiser (dmf_kernels_svd.hip; constrained_nndsvd / nndsvd_initialize, init_func.py:17-82) by the Gram route.
+// Yres = max(V - Rt H1, 1e-8) (n_c = 0: V as it is) is formed on the fly from the f64 V, Rt and the device array H1[n_c][S].
+// launch_svd_gram: C[S][S] = Yres^T Yres, exactly symmetric; slab holds svd_gram_slab_doubles(N, S) doubles, flags
+// 2 svd_gram_grid(N, S) ints (per workgroup: negative, non-finite entries of V).  launch_svd_project: T[N][rank] = Yres Es
+// with Es[S][rank] = the e_j / sigma_j columns, norms[2][rank] = per column sum max(t, 0)^2, sum max(-t, 0)^2; slab holds
+// svd_project_slab_doubles(N, rank) doubles.  launch_svd_finish: T <- clip(cut(scale_j |t| or scale_j max(sign_j t, 0))),
+// in place (sign 0: the absolute value).  Every result depends on the data and (N, S, rank) alone.
+constexpr int kSvdMaxS = 512, kSvdMaxNc = 64, kSvdMaxRank = 64;
+constexpr size_t kSvdMaxLds = 160 * 1024;  // k_svd_project's E / sigma columns, row tile and partial norms must fit a CU's LDS
+size_t svd_project_lds_bytes(int S, int rank);
+struct SvdColumns {
+    double sign[kSvdMaxRank], scale[kSvdMaxRank];
+};
+bool svd_supported(int S, int n_c, int rank);
+int svd_gram_grid(int64_t N, int S);
+int64_t svd_gram_slab_doubles(int64_t N, int S);
+hipError_t launch_svd_gram(const ProblemView& p, const double* H1, double* slab, int* flags, double* C, hipStream_t st);
+int64_t svd_project_slab_doubles(int64_t N, int rank);
+hipError_t launch_svd_project(const ProblemView& p, const double* H1, const double* Es, int rank, double* T, double* slab,
+                              double* norms, hipStream_t st);
+hipError_t launch_svd_finish(double* T, int64_t N, int rank, const SvdColumns& cols, hipStream_t st);
+
 }  // namespace dmf

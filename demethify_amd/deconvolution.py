@@ -16,15 +16,19 @@ import numpy.random as rd
 
 from . import _lib as L
 from .device import Problem, Solver, get_context
+from . import init_func
 from .init_func import wls_intercept
 
 __all__ = [
     "set_seed", "cost_f_w", "projection_simplex_sort_2d", "init_BSSMF_md", "update_u", "update_alpha",
     "unsupervised_deconv", "mdwbssmf_deconv", "wls_intercept", "solve_problem", "init_BSSMF_md_p",
-    "mdwbssmf_deconv_p",
+    "mdwbssmf_deconv_p", "svd_factors",
 ]
 
-_OUT_OF_SCOPE_INITS = ("ICA", "SVD")
+_OUT_OF_SCOPE_INITS = ("ICA",)
+_ICA_REFUSAL = ("--init ICA (demethify/init_func.py:99-168) is not part of this build: its whitening step takes "
+                "np.cov(X, rowvar=True) of the N x S matrix (init_func.py:120), an N x N covariance that cannot exist at the "
+                "numbers of CpG rows this build is for; use SVD, the deterministic initialiser, or a random one")
 
 
 def set_seed(seed=None):
@@ -52,19 +56,44 @@ def _init_guard(alpha, n_u):
     return alpha
 
 
-def init_BSSMF_md(init_option, meth_frequency, d_x, R_trunc, n_u, seed=None, rb_alg=wls_intercept, _stack=True):
+def svd_factors(meth_frequency, d_x, R_trunc, n_u, problem=None, keep_on_device=False, host_only=False):
+    """The SVD initialiser's factors -> (u0, H), H = [H1; H2] before its projection: constrained_nndsvd (R_trunc given,
+    init_func.py:17-37) or nndsvd_initialize with u clipped to [0, 1] (R_trunc None, deconvolution.py:135-136).
+    The device route (Problem.nndsvd) runs on ``problem`` -- the resident upload of these very arrays -- when one is given,
+    else on an upload made for the call when init_func.device_svd says so; the host route otherwise, and always with
+    ``host_only`` (bi-cross-validation folds: their masked data are host arrays).  The three arrays may also be ONE
+    callable returning them, passed as ``meth_frequency`` with a ``problem``: it is called only if the host is needed."""
+    if callable(meth_frequency):
+        arrays = meth_frequency
+    else:
+        arrays = (meth_frequency, d_x, R_trunc)
+    if problem is not None and not host_only:
+        return problem.nndsvd(n_u, keep_on_device=keep_on_device, host_arrays=arrays)
+    n_rows, nb = meth_frequency.shape
+    n_c = 0 if R_trunc is None else R_trunc.shape[1]
+    if not host_only and init_func.device_svd(n_rows, nb, n_c, n_u):
+        with Problem(get_context(), meth_frequency, d_x, R_trunc) as p:
+            return p.nndsvd(n_u, keep_on_device=keep_on_device, host_arrays=arrays)
+    if R_trunc is None:
+        W, H = init_func.nndsvd_initialize(meth_frequency, n_u)
+        return W.clip(0, 1), H
+    W, H = init_func.constrained_nndsvd(meth_frequency, R_trunc, d_x, rank=n_u, flag=0)
+    return W[:, n_c:], H
+
+
+def init_BSSMF_md(init_option, meth_frequency, d_x, R_trunc, n_u, seed=None, rb_alg=wls_intercept, _stack=True,
+                  problem=None, _svd_host=False):
     """deconvolution.py:40-78 -> (u, R, alpha).  Host-side (RNG stream parity).  ``_stack=False`` (the restart, bootstrap
     and model-selection loops of this package, which only need u and alpha) returns R = None instead of copying
-    N x (n_c + n_u) doubles per call -- 25 ms at 1e6 rows, more than the draws themselves."""
+    N x (n_c + n_u) doubles per call -- 25 ms at 1e6 rows, more than the draws themselves.  ``problem``: the resident
+    upload of (meth_frequency, d_x, R_trunc), which "SVD" then runs on (see svd_factors)."""
     set_seed(seed)
     nb = meth_frequency.shape[1]
     n_rows, n_c = R_trunc.shape
     if init_option != "uniform_" and n_u > nb:
         init_option = "uniform_"
     if init_option in _OUT_OF_SCOPE_INITS:
-        raise NotImplementedError(
-            f"--init {init_option} (one-shot LAPACK initialiser, demethify/init_func.py) is not part of "
-            "this build; use uniform_, uniform or beta")
+        raise NotImplementedError(_ICA_REFUSAL)
     if init_option == "uniform":
         u = rd.uniform(size=(n_rows, n_u))
         stacked = np.c_[R_trunc, u]
@@ -77,6 +106,9 @@ def init_BSSMF_md(init_option, meth_frequency, d_x, R_trunc, n_u, seed=None, rb_
         shape = np.ones((n_rows, n_u)) * 0.5
         u = rd.beta(shape, shape)
         alpha = rd.dirichlet(np.ones(n_c + n_u), nb).T
+    elif init_option == "SVD":
+        u, H = svd_factors(meth_frequency, d_x, R_trunc, n_u, problem=problem, host_only=_svd_host)
+        alpha = init_func.project_simplex_columns(H)  # (on the host: this branch also runs on worker threads)
     else:
         raise UnboundLocalError(f"unknown init option {init_option!r}")  # upstream: u is never bound
     R = np.c_[R_trunc, u] if _stack else None
@@ -124,11 +156,11 @@ def mdwbssmf_deconv(u, R, alpha, meth_frequency, d_x, R_trunc, n_u, n_iter1=1000
                              tol)
 
 
-def init_BSSMF_md_p(init_option, meth_frequency, d_x, R_trunc, n_u, purity, rb_alg=wls_intercept, seed=None, _stack=True):
+def init_BSSMF_md_p(init_option, meth_frequency, d_x, R_trunc, n_u, purity, rb_alg=wls_intercept, seed=None, _stack=True,
+                    problem=None):
     """deconvolution.py:228-267 -> (u, R, alpha): as init_BSSMF_md but without the zero guard on the first
-    unknown row (the function returns right after building R); ``purity`` only matters to the SVD / ICA
-    initialisers, which are outside this build."""
-    del purity
+    unknown row (the function returns right after building R); ``purity`` only matters to the SVD initialiser, which
+    scales the projected known block by it and -- as coded upstream (:262) -- leaves the unknown block at mass 1."""
     set_seed(seed)
     nb = meth_frequency.shape[1]
     n_rows, n_c = R_trunc.shape
@@ -138,9 +170,7 @@ def init_BSSMF_md_p(init_option, meth_frequency, d_x, R_trunc, n_u, purity, rb_a
     if init_option != "uniform_" and n_u > nb:
         init_option = "uniform_"
     if init_option in _OUT_OF_SCOPE_INITS:
-        raise NotImplementedError(
-            f"--init {init_option} (one-shot LAPACK initialiser, demethify/init_func.py) is not part of "
-            "this build; use uniform_, uniform or beta")
+        raise NotImplementedError(_ICA_REFUSAL)
     if init_option == "uniform":
         u = rd.uniform(size=(n_rows, n_u))
         stacked = np.c_[R_trunc, u]
@@ -153,6 +183,9 @@ def init_BSSMF_md_p(init_option, meth_frequency, d_x, R_trunc, n_u, purity, rb_a
         shape = np.ones((n_rows, n_u)) * 0.5
         u = rd.beta(shape, shape)
         alpha = rd.dirichlet(np.ones(n_c + n_u), nb).T
+    elif init_option == "SVD":
+        u, H = svd_factors(meth_frequency, d_x, R_trunc, n_u, problem=problem)
+        alpha = np.vstack((purity * init_func.project_simplex_columns(H[:-n_u]), init_func.project_simplex_columns(H[-n_u:])))
     else:
         raise UnboundLocalError(f"unknown init option {init_option!r}")
     return u, (np.c_[R_trunc, u] if _stack else None), alpha
@@ -167,8 +200,9 @@ def mdwbssmf_deconv_p(u, R, alpha, meth_frequency, d_x, R_trunc, n_u, purity, n_
                              tol, purity=purity)
 
 
-def _init_unsupervised(init_option, meth_frequency, n_u, seed):
-    """deconvolution.py:108-137 (host RNG)."""
+def _init_unsupervised(init_option, meth_frequency, n_u, seed, d_x=None, problem=None, _svd_host=False):
+    """deconvolution.py:108-137 (host RNG).  "SVD" on the device needs a problem: ``problem``, the resident upload of
+    (meth_frequency, d_x), or one made for the call from ``d_x``; without either it runs the host route."""
     set_seed(seed)
     n_rows, nb = meth_frequency.shape
     if init_option != "uniform_" and n_u > nb:
@@ -177,9 +211,7 @@ def _init_unsupervised(init_option, meth_frequency, n_u, seed):
         # upstream references an undefined name here (deconvolution.py:117); kept, not "fixed"
         raise NameError("name 'R_trunc' is not defined")
     if init_option in _OUT_OF_SCOPE_INITS:
-        raise NotImplementedError(
-            f"--init {init_option} (one-shot LAPACK initialiser, demethify/init_func.py) is not part of "
-            "this build; use uniform_ or beta")
+        raise NotImplementedError(_ICA_REFUSAL)
     if init_option == "uniform_":
         u = rd.uniform(size=(n_rows, n_u))
         alpha = rd.dirichlet(np.ones(n_u), nb).T
@@ -187,6 +219,10 @@ def _init_unsupervised(init_option, meth_frequency, n_u, seed):
         shape = np.ones((n_rows, n_u)) * 0.5
         u = rd.beta(shape, shape)
         alpha = rd.dirichlet(np.ones(n_u), nb).T
+    elif init_option == "SVD":
+        u, H = svd_factors(meth_frequency, d_x, None, n_u, problem=problem,
+                           host_only=_svd_host or (problem is None and d_x is None))
+        alpha = init_func.project_simplex_columns(H)
     else:
         raise UnboundLocalError(f"unknown init option {init_option!r}")
     return u, alpha
@@ -194,6 +230,10 @@ def _init_unsupervised(init_option, meth_frequency, n_u, seed):
 
 def unsupervised_deconv(meth_frequency, n_u, d_x, init_option, n_iter1=100000, n_iter2=20, tol=1e-3, seed=None):
     """deconvolution.py:107-184 -> (u, alpha)."""
-    u, alpha = _init_unsupervised(init_option, meth_frequency, n_u, seed)
+    svd_on_device = init_option == "SVD" and init_func.device_svd(*meth_frequency.shape, 0, n_u)
+    if not svd_on_device:
+        u, alpha = _init_unsupervised(init_option, meth_frequency, n_u, seed)
     with Problem(get_context(), meth_frequency, d_x, None) as p:
+        if svd_on_device:  # (on the problem the solve runs on: one upload)
+            u, alpha = _init_unsupervised(init_option, meth_frequency, n_u, seed, problem=p)
         return solve_problem(p, u, alpha, L.DMF_MODE_UNSUPERVISED, n_iter1, n_iter2, tol)

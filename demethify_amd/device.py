@@ -302,7 +302,7 @@ class Problem:
                                    C.byref(out)), "dmf_cost")
         return out.value
 
-    def wls_intercept(self, u=None, target="v", host_arrays=None):
+    def wls_intercept(self, u=None, target="v", host_arrays=None, f64_arrays=False):
         """``wls_intercept`` (init_func.py:8-14) of every sample at once on the device (dmf_wls_intercept), with
         R_full = [R_trunc | u], the sample's counts as weights and the target meth_frequency (``target="v"``, what the
         initialisers pass) or counts * meth_frequency (``"dv"``, what the reference-based run passes).  ``u``: None, a host
@@ -311,7 +311,9 @@ class Problem:
         Samples the device declines (status 1: normal matrix rank-deficient to K eps, or the iteration cap) are solved by
         the host ``init_func.wls_intercept`` from ``host_arrays`` = (meth_f, counts, R_full), or a callable returning that
         tuple (it is only called when needed); without it they raise.  A sample whose counts sum to zero raises
-        ZeroDivisionError, as the reference does.  ``self.wls_status`` keeps the per-sample status of the last call."""
+        ZeroDivisionError, as the reference does.  ``self.wls_status`` keeps the per-sample status of the last call.
+        ``f64_arrays``: take weights and target from the f64 arrays even where the problem carries X16 (DMF_WLS_F64_ARRAYS):
+        the same result bit for bit with X16 on and off."""
         try:
             tg = {"v": L.DMF_WLS_TARGET_V, "dv": L.DMF_WLS_TARGET_DV}[target]
         except KeyError:
@@ -338,6 +340,8 @@ class Problem:
             else:
                 u = _host_f64(u, "u").reshape(self.N, -1)
             n_u = int(u.shape[1])
+        if f64_arrays:
+            flags |= L.DMF_WLS_F64_ARRAYS
         K = self.n_c + n_u
         out = np.zeros((K, self.S), dtype=np.float64)
         status = np.full(self.S, -1, dtype=np.intc)
@@ -358,6 +362,118 @@ class Problem:
                 x = counts[:, k:k + 1] * meth_f[:, k:k + 1] if target == "dv" else meth_f[:, k:k + 1]
                 out[:, k:k + 1] = host_wls(x, counts[:, k:k + 1], R_full)
         return out
+
+    def svd_gram(self, H1=None):
+        """``Yres.T @ Yres`` (S x S) of Yres = max(meth_frequency - R_trunc @ H1, 1e-8) -- meth_frequency itself without
+        known types -- on the device (dmf_svd_gram) -> (C, negative entries of meth_frequency, non-finite ones)."""
+        if self.n_c:
+            H1 = _host_f64(H1, "H1")
+            if H1.shape != (self.n_c, self.S):
+                raise ValueError(f"H1 shape {H1.shape} != {(self.n_c, self.S)}")
+        else:
+            H1 = None
+        out = np.empty((self.S, self.S), dtype=np.float64)
+        counts = (C.c_int64 * 2)()
+        L.check(self._lib.dmf_svd_gram(self.ctx._h, self._h, _ptr(H1), 0, _ptr(out), counts), "dmf_svd_gram")
+        return out, int(counts[0]), int(counts[1])
+
+    def nndsvd(self, rank, keep_on_device=False, host_arrays=None):
+        """The SVD initialiser's factors (init_func.py:17-82) on the device -> (u0, H): u0 = the N x rank unknown profiles,
+        cut at 1e-11 and clipped to [0, 1] (a host array, or with ``keep_on_device`` a staging.DeviceArray for ``Solver``),
+        H = the (n_c + rank) x S factor [H1; H2] before its projection onto the simplex.
+
+        H1 is ``wls_intercept(None, "v", f64_arrays=True)``; the S x S Gram of the residual comes from dmf_svd_gram, its eigendecomposition
+        from numpy.linalg.eigh here, the left factors from dmf_svd_factor / dmf_svd_finish.  ``host_arrays`` =
+        (meth_f, counts, R_trunc or None), or a callable returning that tuple (called only when needed), serves the samples
+        the device regression declines and the whole computation where the kernels do not take the shape, or where the
+        Gram route is not the SVD route to working precision (a used eigenvalue below 1e-10 of the largest): the host route
+        of init_func.  Without known types a negative entry raises the reference's ValueError."""
+        from .init_func import constrained_nndsvd, nndsvd_from_eig, nndsvd_initialize
+
+        rank = int(rank)
+        if rank < 1:
+            raise ValueError(f"rank must be at least 1, got {rank}")
+
+        def host_route():
+            if host_arrays is None:
+                raise RuntimeError("nndsvd: the device route does not take this problem and no host_arrays were given")
+            meth_f, counts, R_trunc = host_arrays() if callable(host_arrays) else host_arrays
+            if self.n_c:
+                W, H = constrained_nndsvd(meth_f, R_trunc, counts, rank)
+                u0 = W[:, self.n_c:]
+            else:
+                W, H = nndsvd_initialize(meth_f, rank)
+                u0 = np.clip(W, 0, 1)
+            u0 = np.ascontiguousarray(u0)
+            if keep_on_device:
+                from .staging import to_device
+
+                u0, = to_device((u0,), self.ctx)
+            return u0, H
+
+        if rank > self.S:
+            raise ValueError(f"rank {rank} exceeds the {self.S} samples")
+        # (from the f64 arrays, like the residual: u0 and H are then the same bit for bit with X16 on and off)
+        H1 = self.wls_intercept(None, "v", host_arrays=host_arrays, f64_arrays=True) if self.n_c else None
+        try:
+            gram, negatives, _ = self.svd_gram(H1)
+        except L.DemethifyHipError as e:
+            if e.status != L.DMF_ERR_UNSUPPORTED:
+                raise
+            return host_route()
+        if not self.n_c and negatives:
+            raise ValueError("The input matrix contains negative elements.")
+        lam, vec = np.linalg.eigh(gram)
+        lam, vec = lam[::-1][:rank], np.ascontiguousarray(vec[:, ::-1][:, :rank])
+        if not lam[-1] > 1e-10 * lam[0]:
+            return host_route()
+        sigma = np.sqrt(lam)
+        try:
+            u_dev, norms = self.svd_factor(H1, vec / sigma)
+        except L.DemethifyHipError as e:
+            if e.status != L.DMF_ERR_UNSUPPORTED:
+                raise
+            return host_route()
+        sign, scale, H2 = nndsvd_from_eig(sigma, vec, norms)
+        u0 = self.svd_finish(u_dev, sign, scale, keep_on_device)
+        return u0, (np.vstack([H1, H2]) if self.n_c else H2)
+
+    def svd_factor(self, H1, e_over_sigma):
+        """``Yres @ e_over_sigma`` (N x rank; Yres as in svd_gram, e_over_sigma S x rank) left on the device, and the sums of
+        max(t, 0)**2 and max(-t, 0)**2 of its columns (dmf_svd_factor) -> (staging.DeviceArray, 2 x rank array)."""
+        from .staging import DeviceArray
+
+        H1 = _host_f64(H1, "H1") if self.n_c else None
+        e_over_sigma = _host_f64(e_over_sigma, "e_over_sigma")
+        if e_over_sigma.ndim != 2 or e_over_sigma.shape[0] != self.S:
+            raise ValueError(f"e_over_sigma shape {e_over_sigma.shape} does not match {self.S} samples")
+        rank = int(e_over_sigma.shape[1])
+        norms = np.empty((2, rank), dtype=np.float64)
+        t = C.c_void_p()
+        L.check(self._lib.dmf_svd_factor(self.ctx._h, self._h, _ptr(H1), _ptr(e_over_sigma), rank, 0, _ptr(norms),
+                                         C.byref(t)), "dmf_svd_factor")
+        return DeviceArray(self.ctx, t.value, (self.N, rank)), norms
+
+    def svd_finish(self, t_dev, sign, scale, keep_on_device=False):
+        """u0 from svd_factor's array, in place (dmf_svd_finish): column j becomes scale_j |t| (sign_j = 0) or
+        scale_j max(sign_j t, 0), cut at 1e-11 and clipped to [0, 1] -> the array itself, or a host copy (the device array
+        is then released)."""
+        n, rank = t_dev.shape
+        sign = np.ascontiguousarray(sign, dtype=np.float64)
+        scale = np.ascontiguousarray(scale, dtype=np.float64)
+        if sign.shape != (rank,) or scale.shape != (rank,):
+            raise ValueError(f"sign and scale need {rank} values each")
+        if keep_on_device:
+            L.check(self._lib.dmf_svd_finish(self.ctx._h, _ptr(t_dev), n, rank, _ptr(sign), _ptr(scale), L.DMF_PTR_DEVICE,
+                                             None), "dmf_svd_finish")
+            return t_dev
+        u0 = np.empty((n, rank), dtype=np.float64)
+        try:
+            L.check(self._lib.dmf_svd_finish(self.ctx._h, _ptr(t_dev), n, rank, _ptr(sign), _ptr(scale), 0, _ptr(u0)),
+                    "dmf_svd_finish")
+        finally:
+            t_dev.close()
+        return u0
 
     def update_u(self, u, u_prev, alpha, n_iter2, a1, l_w_prev, l_w, mode=L.DMF_MODE_PARTIAL):
         u = np.ascontiguousarray(u, dtype=np.float64).reshape(self.N, -1)

@@ -14,6 +14,7 @@ import numpy as np
 
 from . import _lib as L
 from . import shard
+from . import init_func
 from .deconvolution import _init_unsupervised, cost_f_w, init_BSSMF_md, solve_problem
 from .device import Problem, Solver, get_context
 from .staging import Prefetcher
@@ -58,13 +59,23 @@ def compute_ccc(alpha_runs):
     return ccc
 
 
-def _solve(problem, meth_f, counts, ref, n_u, init_option, seed, iter1, iter2, tol):
+def _init_on(problem, meth_f, counts, ref, n_u, init_option, seed):
+    """(u0, alpha0) of one candidate.  ``problem``: the resident upload of (meth_f, counts, ref), which the "SVD"
+    initialiser runs on above its gate -- on the calling thread, which must then be the one that drives the context."""
+    n_ct = ref.shape[1] if ref is not None else 0
+    on_device = problem if (init_option == "SVD" and problem is not None
+                            and init_func.device_svd(meth_f.shape[0], meth_f.shape[1], n_ct, n_u)) else None
     if ref is not None:
-        u0, _, a0 = init_BSSMF_md(init_option, meth_f, counts, ref, n_u, seed=seed, rb_alg=wls_intercept, _stack=False)
-        mode = L.DMF_MODE_PARTIAL
+        u0, _, a0 = init_BSSMF_md(init_option, meth_f, counts, ref, n_u, seed=seed, rb_alg=wls_intercept, _stack=False,
+                                  problem=on_device, _svd_host=on_device is None)
     else:
-        u0, a0 = _init_unsupervised(init_option, meth_f, n_u, seed)
-        mode = L.DMF_MODE_UNSUPERVISED
+        u0, a0 = _init_unsupervised(init_option, meth_f, n_u, seed, problem=on_device, _svd_host=on_device is None)
+    return u0, a0
+
+
+def _solve(problem, meth_f, counts, ref, n_u, init_option, seed, iter1, iter2, tol):
+    u0, a0 = _init_on(problem, meth_f, counts, ref, n_u, init_option, seed)
+    mode = L.DMF_MODE_PARTIAL if ref is not None else L.DMF_MODE_UNSUPERVISED
     return solve_problem(problem, u0, a0, mode, iter1, iter2, tol)
 
 
@@ -91,15 +102,14 @@ def _bcv_draw_fold(meth_f, counts, ref, n_u, init_option, seed, fraction, stage=
     n_train = int(np.sum(train_mask))
     if n_train == train_mask.size or n_train == 0:
         return None
-    if init_option == "uniform":
-        # the one initialiser in scope that reads the data (rb_alg on every sample column): it sees the masked arrays
+    if init_option in ("uniform", "SVD"):
+        # the initialisers in scope that read the data (rb_alg on every sample column; the SVD of the residual): they see
+        # the masked arrays, and "SVD" stays on the host route whatever the size (a masked problem never takes the device
+        # regression or the device Gram: DESIGN section 7a / 7b)
         init_f, init_c = meth_f * train_mask, counts * train_mask
     else:
         init_f, init_c = meth_f, counts  # (uniform_ / beta take the shapes only)
-    if ref is not None:
-        u0, _, a0 = init_BSSMF_md(init_option, init_f, init_c, ref, n_u, seed=seed, rb_alg=wls_intercept, _stack=False)
-    else:
-        u0, a0 = _init_unsupervised(init_option, init_f, n_u, seed)
+    u0, a0 = _init_on(None, init_f, init_c, ref, n_u, init_option, seed)
     return train_mask, u0, a0, stage(train_mask) if stage is not None else None
 
 
@@ -236,22 +246,23 @@ def evaluate_best_ic(meth_f, ref, counts, init_option, ic, seed, iter1, iter2, t
     formula = compute_bic if ic == "BIC" else compute_aic
     local, keep = [], None  # keep = this rank's best candidate only (the reference keeps the running best, ic.py:212)
 
+    def on_device(n_u):  # the "SVD" initialiser of this candidate runs on the sweep's resident problem
+        return init_option == "SVD" and n_u <= n_samples and init_func.device_svd(n_cpg, n_samples, n_ct, n_u)
+
     def draw(i):
         # the candidate's initialisation (numpy's global generator: ONE worker thread), drawn while the GPU solves the
-        # candidate before it
+        # candidate before it -- except where it runs on the device: that is the solving thread's work (a context is not
+        # thread-safe)
         n_u = n_u_values[i]
-        if ref is not None:
-            u0, _, a0 = init_BSSMF_md(init_option, meth_f, counts, ref, n_u, seed=seed, rb_alg=wls_intercept, _stack=False)
-        else:
-            u0, a0 = _init_unsupervised(init_option, meth_f, n_u, seed)
-        return u0, a0
+        return None if on_device(n_u) else _init_on(None, meth_f, counts, ref, n_u, init_option, seed)
 
     mode = L.DMF_MODE_PARTIAL if ref is not None else L.DMF_MODE_UNSUPERVISED
     with Problem(get_context(), meth_f, counts, ref) as problem:
         feed = Prefetcher(mine, draw, depth=1, workers=1)
         try:
-            for i, (u0, a0) in feed:
+            for i, drawn in feed:
                 n_u = n_u_values[i]
+                u0, a0 = drawn if drawn is not None else _init_on(problem, meth_f, counts, ref, n_u, init_option, seed)
                 with Solver(problem, u0, a0, mode) as s:
                     s.step(iter1, iter2, tol)
                     cost = s.direct_cost()  # cost_f_w(meth_f, R, alpha, counts), ic.py:206, where the iterate lives

@@ -170,10 +170,44 @@ int dmf_update_alpha(dmf_context* ctx, const dmf_problem* p, const double* u, in
  * and out_status (S ints) are host arrays, like dmf_cost's out_cost.  out_status: 0 ok, 1 not solved here (the sample's
  * K x K normal matrix is rank-deficient to K eps, or the cap was reached: solve that sample on the host), 2 the sample's
  * weights sum to zero (the reference raises ZeroDivisionError there); columns of out_alpha with a non-zero status are left
- * untouched.  K > 64: DMF_ERR_UNSUPPORTED. */
+ * untouched.  K > 64: DMF_ERR_UNSUPPORTED.  DMF_WLS_F64_ARRAYS in flags: the first moments are taken from V and the f64 counts
+ * even where the problem carries the u16 copies (x = v d as an exact integer), so that the result is the same bit for bit
+ * with and without them: what the SVD initialiser asks for, whose residual is formed from the f64 V as well. */
 enum { DMF_WLS_TARGET_V = 0, DMF_WLS_TARGET_DV = 1 };
+enum { DMF_WLS_F64_ARRAYS = 8 };
 int dmf_wls_intercept(dmf_context* ctx, const dmf_problem* p, const double* u, int64_t n_u, int target,
                       int flags, double* out_alpha, int* out_status);
+
+/* The SVD initialiser -- constrained_nndsvd, init_func.py:17-37, and nndsvd_initialize, :40-82, reached from
+ * deconvolution.py:68-71, :134-137 and :260-263 -- without an SVD of the N x S matrix.  With Yres = max(V - Rt H1, 1e-8)
+ * (init_func.py:27; n_c = 0: V as it is, :135) the three calls below and a symmetric S x S eigendecomposition between the
+ * first two, which stays with the caller (this library links no LAPACK), replace svd(Yres) of :44 and the loops of :47-71:
+ * with C = Yres^T Yres = E diag(lambda) E^T, sigma_j = sqrt(lambda_j) and u_j = Yres e_j / sigma_j; the construction does not
+ * depend on the joint sign of (u_j, e_j).  H1: the n_c x S regression coefficients of :21-23 (dmf_wls_intercept, target v),
+ * a host array, or a device array with DMF_PTR_DEVICE in flags; NULL when n_c = 0.  Yres is formed on the fly from the
+ * problem's f64 V and Rt, never stored.
+ * Shapes: any N, S <= 512, n_c <= 64, rank <= 64 and 8 (S rank + 8 (64 ceil(S / 64) + 16) + 512) <= 163840 bytes (the projection
+ * keeps the e_j / sigma_j columns in LDS: every rank up to S = 256, rank 30 at S = 512); beyond: DMF_ERR_UNSUPPORTED (take the
+ * host route).
+ * A masked problem (its held-out elements are zeros in V) is refused with DMF_ERR_BAD_ARG.
+ *
+ * dmf_svd_gram: out_C (S x S host doubles) <- Yres^T Yres, on the FP64 matrix cores, equal to its transpose bit for bit
+ * and a function of the data and (N, S) alone; out_flags[2] <- the number of negative and of non-finite entries of V (what
+ * :41-42 raises on, for the caller to raise).  A non-finite C: DMF_ERR_NONFINITE.  With profiling on, the two launches are
+ * clocked under DMF_KERNEL_GRAM. */
+int dmf_svd_gram(dmf_context* ctx, const dmf_problem* p, const double* H1, int flags, double* out_C, int64_t* out_flags);
+/* dmf_svd_factor: E_over_sigma (S x rank host doubles, column j = e_j / sigma_j) -> *out_T, a device array of N x rank
+ * doubles holding t_ij = u_ij (U of :44, columns 0 .. rank - 1), which belongs to the caller and is released with
+ * dmf_stage_free; out_norms (2 x rank host doubles) <- per column the sums of max(t, 0)^2 and of max(-t, 0)^2: the squares
+ * of n_uup and n_uun of :58-59 (summed in an order that depends on (N, S, rank) alone). */
+int dmf_svd_factor(dmf_context* ctx, const dmf_problem* p, const double* H1, const double* E_over_sigma, int64_t rank,
+                   int flags, double* out_norms, void** out_T);
+/* dmf_svd_finish: T (N x rank, from dmf_svd_factor) <- u0, in place: x = scale_j |t| where sign_j = 0 (:50, component 0),
+ * else scale_j max(sign_j t, 0) (:64 / :67, sign_j = +1 or -1 and scale_j = sqrt(sigma_j term) / norm as the caller chose
+ * them at :63); x < 1e-11 -> 0 (:70); clipped to [0, 1] (:31, deconvolution.py:136).  out_u: N x rank host doubles; with
+ * DMF_PTR_DEVICE in flags NULL or T itself (u0 stays in T for dmf_solver_create) or another device array. */
+int dmf_svd_finish(dmf_context* ctx, void* T, int64_t N, int64_t rank, const double* sign, const double* scale, int flags,
+                   double* out_u);
 
 /* Bootstrap post-processing (bootstrap.py:51-54 proportions, :75-78 profile estimates):
  * np.percentile(x, q, axis=0) with numpy's default "linear" method, for x = [n replicates][m positions]
