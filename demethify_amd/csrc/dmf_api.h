@@ -248,6 +248,12 @@ struct dmf_solver {
         it.n_u = (int)n_u, it.mode = mode;
         return it;
     }
+    dmf::AlphaView alpha_view() const {
+        dmf::AlphaView a;
+        a.gb = gb, a.alpha = alpha, a.alpha_prev = alpha_prev, a.purity = purity, a.state = state, a.partials = partials;
+        a.S = (int)p->S, a.n_c = (int)p->n_c, a.n_u = (int)n_u;
+        return a;
+    }
     dmf::UScratch scratch() const {
         dmf::UScratch sc;
         sc.cm = cm, sc.beta = beta_tab, sc.slab = slab, sc.u2_partials = u2_partials;
@@ -325,7 +331,7 @@ int enqueue_u_phase(dmf_solver* s, int n_iter2, dmf::RowKind row);
 dmf::RowKind standalone_row_kind(const dmf_solver* s, int n_iter2);
 int enqueue_gram(dmf_solver* s, dmf::GramKind kind);
 dmf::GramKind fp64_gram_kind(const dmf_solver* s);
-int enqueue_alpha_phase(dmf_solver* s, int n_iter2);
+int enqueue_alpha_phase(dmf_solver* s, dmf::AlphaKind kind, int n_iter2);  // kind: plan_iteration(...).alpha
 int fetch_state(dmf_solver* s);
 int push_state(dmf_solver* s);
 

@@ -166,7 +166,8 @@ int dmf_update_alpha(dmf_context* ctx, const dmf_problem* p, const double* u, in
     s->h_state->l_h = scalars_io[2];
     DMF_TRY(push_state(raw));
     DMF_TRY(enqueue_gram(raw, fp64_gram_kind(raw)));  // (the caller's u: FP64 kernels)
-    DMF_TRY(enqueue_alpha_phase(raw, (int)n_iter2));
+    const dmf::AlphaKind kind = dmf::plan_iteration(raw->key, raw->spec, (int)n_iter2, raw->purity != nullptr).alpha;
+    DMF_TRY(enqueue_alpha_phase(raw, kind, (int)n_iter2));
     DMF_TRY(export_array(ctx, s->alpha, an, flags, out_alpha));
     DMF_TRY(export_array(ctx, s->alpha_prev, an, flags, out_alpha_prev));
     scalars_io[0] = advance_momentum(scalars_io[0], n_iter2);

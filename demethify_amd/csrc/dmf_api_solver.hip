@@ -109,28 +109,19 @@ dmf::GramKind fp64_gram_kind(const dmf_solver* s) {
     return s->spec.use_gram_spec ? dmf::GramKind::GramU : s->spec.use_gram_mfma ? dmf::GramKind::GramMfma : dmf::GramKind::Gram;
 }
 
-int enqueue_alpha_phase(dmf_solver* s, int n_iter2) {
-    dmf_context* ctx = s->ctx;
-    const dmf_problem* p = s->p;
-    FamilyScope scope(ctx, DMF_KERNEL_ALPHA);
-    if (s->purity != nullptr) {
-        HIP_TRY(dmf::launch_alpha_frank_wolfe(s->gb, s->alpha, s->purity, s->state, (int)p->S, (int)p->n_c,
-                                              (int)s->n_u, n_iter2, s->partials, ctx->stream));
-        return DMF_OK;
-    }
-    const bool thread_per_sample = ctx->generic_level == 1 || ctx->generic_level == 2;
-    HIP_TRY(dmf::launch_alpha_phase(s->gb, s->alpha, s->alpha_prev, s->state, (int)p->S, (int)p->n_c,
-                                    (int)s->n_u, n_iter2, s->partials, thread_per_sample, ctx->stream));
+int enqueue_alpha_phase(dmf_solver* s, dmf::AlphaKind kind, int n_iter2) {
+    FamilyScope scope(s->ctx, DMF_KERNEL_ALPHA);
+    HIP_TRY(dmf::launch_alpha(kind, s->alpha_view(), n_iter2, s->ctx->stream));
     return DMF_OK;
 }
 
 // what follows a row kernel that left `grid` b_u slabs and ||u||^2 shares: the integer Gram, its reduce, the alpha phase
-static int enqueue_gram_i8_tail(dmf_solver* s, int n_iter2, int grid) {
+static int enqueue_gram_i8_tail(dmf_solver* s, dmf::AlphaKind alpha, int n_iter2, int grid) {
     {
         FamilyScope scope(s->ctx, DMF_KERNEL_GRAM);
         DMF_TRY(gram_i8_and_reduce(s, grid, s->u2_partials, grid));
     }
-    return enqueue_alpha_phase(s, n_iter2);
+    return enqueue_alpha_phase(s, alpha, n_iter2);
 }
 
 static int enqueue_outer_iteration(dmf_solver* s, int n_iter2) {
@@ -155,7 +146,7 @@ static int enqueue_outer_iteration(dmf_solver* s, int n_iter2) {
             ++s->n_rowpass;
             s->n_rowpass_pair += paired ? 1 : 0;
         }
-        return enqueue_gram_i8_tail(s, n_iter2, grid);
+        return enqueue_gram_i8_tail(s, plan.alpha, n_iter2, grid);
     }
     if (plan.row == dmf::RowKind::CmI8InnerBu) {
         // Wide row groups on u16 counts: c_i / M_i (M_i on the integer matrix cores), then the inner iterations fused with
@@ -166,7 +157,7 @@ static int enqueue_outer_iteration(dmf_solver* s, int n_iter2) {
             FamilyScope scope(ctx, DMF_KERNEL_ROWPASS);
             HIP_TRY(dmf::launch_u_phase_split_i8_bu(p->view(), s->iterate(), n_iter2, s->scratch(), &grid, ctx->stream));
         }
-        return enqueue_gram_i8_tail(s, n_iter2, grid);
+        return enqueue_gram_i8_tail(s, plan.alpha, n_iter2, grid);
     }
     if (plan.row == dmf::RowKind::RowpassFused) {
         // The fused kernel takes whole 16-row blocks; a ragged tail (< 16 rows) goes through the unfused
@@ -193,14 +184,14 @@ static int enqueue_outer_iteration(dmf_solver* s, int n_iter2) {
             HIP_TRY(dmf::launch_gram_reduce(s->slab, 2 * grid + ny_tail, s->jobs.n, S, s->jobs.dst, s->gb,
                                             &s->state->done, ctx->stream));
         }
-        return enqueue_alpha_phase(s, n_iter2);
+        return enqueue_alpha_phase(s, plan.alpha, n_iter2);
     }
     DMF_TRY(enqueue_u_phase(s, n_iter2, plan.row));
     HIP_TRY(dmf::launch_sumsq_f64(s->u, p->N * s->n_u, ctx->scratch, &s->state->u_norm2, &s->state->done,
                                   ctx->stream));
     HIP_TRY(dmf::launch_set_lh(s->state, ctx->stream));
     DMF_TRY(enqueue_gram(s, plan.gram));
-    return enqueue_alpha_phase(s, n_iter2);
+    return enqueue_alpha_phase(s, plan.alpha, n_iter2);
 }
 
 int fetch_state(dmf_solver* s) {

@@ -4,6 +4,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "dmf_select.h"
+
 namespace dmf {
 
 // Device-resident scalar state of one solve (demethify/deconvolution.py:192-204 and the
@@ -109,6 +111,19 @@ struct IterateView {
     }
 };
 
+// What the alpha phase of a solver works on (dmf_solver::alpha_view()): the packed Gram buffer gb[(K+1)(K+2)/2][S], the
+// iterate, the per-sample known-block masses of a purity-constrained solve (null otherwise) and `partials`, which holds
+// 2 * (ceil(S / 64) + S) doubles.
+struct AlphaView {
+    const double* gb = nullptr;
+    double* alpha = nullptr;
+    double* alpha_prev = nullptr;
+    const double* purity = nullptr;
+    SolverState* state = nullptr;
+    double* partials = nullptr;
+    int S = 0, n_c = 0, n_u = 0;
+};
+
 // Per-solver scratch that some u phases write: c_i / M_i per row and the momentum coefficients of the split u phase, the
 // b_u slab and the per-workgroup ||u||^2 shares of the one-launch row passes.
 struct UScratch {
@@ -188,16 +203,10 @@ hipError_t launch_finish_u_norm(const double* u2_partials, int n, SolverState* s
 hipError_t launch_u_step_direct(const ProblemView& p, const IterateView& it, double* u_next, int t, hipStream_t st);
 bool u_step_direct_supported(int S, int n_c, int n_u);
 
-// alpha phase on the packed Gram buffer gb[(K+1)(K+2)/2][S]
-// thread_per_sample selects the one-thread-per-sample kernels (test levels 1 and 2) instead of the
-// lane-parallel one (G lanes per sample); partials must hold 2 * (ceil(S / 64) + S) doubles
-hipError_t launch_alpha_phase(const double* gb, double* alpha, double* alpha_prev,
-                              SolverState* state, int S, int n_c, int n_u, int n_iter2,
-                              double* partials, bool thread_per_sample, hipStream_t st);
+// alpha phase: the n_iter2 inner steps (Frank-Wolfe steps for the two purity kinds) with the kernel the plan names
+// (dmf_select.h), then the close of the outer iteration; hipErrorInvalidValue where `kind` does not take K = n_c + n_u
+hipError_t launch_alpha(AlphaKind kind, const AlphaView& a, int n_iter2, hipStream_t st);
 hipError_t launch_set_lh(SolverState* state, hipStream_t st);
-// purity-constrained alpha phase (Frank-Wolfe, deconvolution.py:280-302) on the same packed Gram buffer
-hipError_t launch_alpha_frank_wolfe(const double* gb, double* alpha, const double* purity, SolverState* state,
-                                    int S, int n_c, int n_u, int max_iter, double* partials, hipStream_t st);
 hipError_t launch_project_simplex(const double* X, double* out, int K, int S, double z,
                                   hipStream_t st);
 hipError_t launch_scatter_known_block(const double* gb_known, double* gb, int n_c, int K, int S,

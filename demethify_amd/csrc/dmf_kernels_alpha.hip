@@ -33,6 +33,9 @@ __device__ __forceinline__ void sort_desc(double (&x)[KMAX]) {
 }
 
 // projection_simplex_sort_2d for one column held in registers (deconvolution.py:25-35).
+// THE TWO PROJECTIONS STAY TWO: this one tests fma(srt_j, j + 1, -shifted) > 0 and divides once, project_column_dyn below
+// divides inside the scan (srt_j - shifted / (j + 1) > 0).  At a near tie between t_rho and t_(rho+1) the two tests can
+// pick a different rho, so merging them would change results of one of the kernel families.
 template <int KMAX>
 __device__ __forceinline__ void project_column(double (&x)[KMAX], int K, double z) {
     double srt[KMAX];
@@ -61,6 +64,48 @@ __device__ __forceinline__ void project_column(double (&x)[KMAX], int K, double 
     for (int k = 0; k < KMAX; ++k) x[k] = k < K ? fmax(x[k] - theta, 0.0) : 0.0;
 }
 
+__device__ __noinline__ void project_column_dyn(double* x, int K, double z) {
+    double srt[kMaxK];
+    for (int k = 0; k < K; ++k) {  // insertion sort, descending
+        const double v = x[k];
+        int j = k;
+        while (j > 0 && srt[j - 1] < v) {
+            srt[j] = srt[j - 1];
+            --j;
+        }
+        srt[j] = v;
+    }
+    double run = 0.0, theta = 0.0, last_shift = 0.0;
+    bool any = false;
+    for (int j = 0; j < K; ++j) {
+        run += srt[j];
+        const double shifted = run - z;
+        if (srt[j] - shifted / (double)(j + 1) > 0.0) {
+            theta = shifted / (double)(j + 1);
+            any = true;
+        }
+        last_shift = shifted;
+    }
+    if (!any) theta = last_shift / 0.0;
+    for (int k = 0; k < K; ++k) x[k] = fmax(x[k] - theta, 0.0);
+}
+
+// ---- one thread per sample (test levels 1 and 2, and the Frank-Wolfe kernel beyond 16 types) ------------------------
+// k_alpha_phase<KMAX>, k_alpha_phase_dyn and k_alpha_frank_wolfe each write out their gradient loop over the packed
+// triangle and their cost epilogue.  With these in shared __forceinline__ functions hipcc scheduled all five kernels
+// differently (other register counts, 2 SGPR spills at KMAX = 16) and they ran 1.5 % to 30 % slower: section 6 of
+// profiles/r12_alpha_refactor.txt.  As written they compile to the instruction streams they had before.
+
+// the block's share of the cost and of ||alpha_unknown||^2, for k_finish_iteration
+__device__ __forceinline__ void store_partials(double* partials, double cost, double n2) {
+    if (threadIdx.x == 0) {
+        partials[2 * blockIdx.x] = cost;
+        partials[2 * blockIdx.x + 1] = n2;
+    }
+}
+
+// KMAX = 4, 8, 16 >= K: every loop unrolled over KMAX slots and guarded by K, the per-thread arrays in registers.
+// gb_in_lds: the block's 64 packed Gram columns are staged in dynamic LDS first (the launcher's choice for small K).
 template <int KMAX>
 __global__ __launch_bounds__(64) void k_alpha_phase(const double* __restrict__ gb,
                                                     double* __restrict__ alpha,
@@ -134,42 +179,11 @@ __global__ __launch_bounds__(64) void k_alpha_phase(const double* __restrict__ g
         }
         cost = cost - 2.0 * lin + quad;
     }
-    cost = wave_sum(cost);
-    n2 = wave_sum(n2);
-    if (tid == 0) {
-        partials[2 * blockIdx.x] = cost;
-        partials[2 * blockIdx.x + 1] = n2;
-    }
+    store_partials(partials, wave_sum(cost), wave_sum(n2));
 }
 
-// ---- runtime-K variants (16 < K <= 64): per-thread arrays live in scratch, loops are not unrolled.
-// Rare path (model-selection sweeps with many unknown types); kept small to keep the build short.
-__device__ __noinline__ void project_column_dyn(double* x, int K, double z) {
-    double srt[kMaxK];
-    for (int k = 0; k < K; ++k) {  // insertion sort, descending
-        const double v = x[k];
-        int j = k;
-        while (j > 0 && srt[j - 1] < v) {
-            srt[j] = srt[j - 1];
-            --j;
-        }
-        srt[j] = v;
-    }
-    double run = 0.0, theta = 0.0, last_shift = 0.0;
-    bool any = false;
-    for (int j = 0; j < K; ++j) {
-        run += srt[j];
-        const double shifted = run - z;
-        if (srt[j] - shifted / (double)(j + 1) > 0.0) {
-            theta = shifted / (double)(j + 1);
-            any = true;
-        }
-        last_shift = shifted;
-    }
-    if (!any) theta = last_shift / 0.0;
-    for (int k = 0; k < K; ++k) x[k] = fmax(x[k] - theta, 0.0);
-}
-
+// the run-time-K instance (16 < K <= kMaxK): run-time loop bounds, arrays in scratch, no unrolling, the Gram buffer read
+// in place.  Rare path (model-selection sweeps with many unknown types); kept small to keep the build short.
 __global__ __launch_bounds__(64) void k_alpha_phase_dyn(const double* __restrict__ gb,
                                                         double* __restrict__ alpha,
                                                         double* __restrict__ alpha_prev,
@@ -223,12 +237,7 @@ __global__ __launch_bounds__(64) void k_alpha_phase_dyn(const double* __restrict
         }
         cost = cost - 2.0 * lin + quad;
     }
-    cost = wave_sum(cost);
-    n2 = wave_sum(n2);
-    if (tid == 0) {
-        partials[2 * blockIdx.x] = cost;
-        partials[2 * blockIdx.x + 1] = n2;
-    }
+    store_partials(partials, wave_sum(cost), wave_sum(n2));
 }
 
 __global__ __launch_bounds__(64) void k_project_dyn(const double* __restrict__ X, double* __restrict__ out,
@@ -307,24 +316,12 @@ hipError_t launch_set_lh(SolverState* state, hipStream_t st) {
     return hipGetLastError();
 }
 
-template <int KMAX>
-static hipError_t launch_alpha_t(const double* gb, double* alpha, double* alpha_prev,
-                                 SolverState* state, int S, int K, int n_u, int n_iter2,
-                                 double* partials, hipStream_t st) {
-    const int nb = (S + 63) / 64;
-    const size_t lds = (size_t)(K + 1) * (K + 2) / 2 * 64 * sizeof(double);
-    const int in_lds = lds <= 150 * 1024;
-    if (in_lds && lds > 48 * 1024) {
-        const hipError_t e = raise_dynamic_lds<k_alpha_phase<KMAX>>(lds);
-        if (e != hipSuccess) return e;
-    }
-    hipLaunchKernelGGL(k_alpha_phase<KMAX>, dim3(nb), dim3(64), in_lds ? lds : 0, st, gb, alpha,
-                       alpha_prev, state, S, K, n_u, n_iter2, in_lds, partials);
+static hipError_t launch_finish_iteration(const double* partials, int nb, SolverState* state, int n_iter2, hipStream_t st) {
     hipLaunchKernelGGL(k_finish_iteration, dim3(1), dim3(64), 0, st, partials, nb, state, n_iter2);
     return hipGetLastError();
 }
 
-// ---- lane-parallel alpha phase: G lanes per sample column (G = 4, 8, 16, 32, 64 >= K) --------------
+// ---- lane-parallel alpha phase: G lanes per sample column ----------------------------------------------------------
 // Lane k of a group owns row k of the sample's packed Gram matrix (registers), the extrapolated point
 // is exchanged with group broadcasts, the simplex projection sorts across the group's lanes (bitonic
 // network) and takes a parallel prefix sum.  ~10x shorter critical path than one thread per sample:
@@ -334,6 +331,37 @@ __device__ __forceinline__ double group_get(double x, int src_lane) {
     return __shfl(x, src_lane, 64);
 }
 
+// Lane k's row of the sample's packed Gram matrix, row[l] = G_s[k][l] (NEGATE: -G_s[k][l]) for l < G, and b_k (returned):
+// rows and columns beyond K are clamped for the load and masked to 0.
+template <int G, bool NEGATE>
+__device__ __forceinline__ double load_gram_row(const double* gb, int S, int K, int k, int sc, double (&row)[G]) {
+    const bool row_ok = k < K;
+    const int kc = row_ok ? k : K - 1;
+#pragma unroll
+    for (int l = 0; l < G; ++l) {
+        const int lc = l < K ? l : K - 1;
+        const int lo = kc < lc ? kc : lc, hi = kc < lc ? lc : kc;
+        const double v = gb[(int64_t)tri(lo, hi) * S + sc];
+        const bool ok = row_ok && l < K;
+        const double sv = NEGATE ? -v : v;
+        row[l] = ok ? sv : 0.0;
+    }
+    return row_ok ? gb[(int64_t)tri(kc, K) * S + sc] : 0.0;
+}
+
+// The wave's share of cost = sum_s vDv - 2 a.b + a^T G a (part) and of ||alpha_unknown||^2 (n2) from lane k's a_k,
+// (G_s a)_k and b_k; `in_n2`: lane k holds an unknown type of a sample that exists.
+__device__ __forceinline__ void lane_cost(const double* gb, int S, int K, int k, int sc, bool col_ok, bool in_n2,
+                                          double a, double ga, double bk, double& part, double& n2) {
+    part = col_ok ? fma(a, ga, -2.0 * a * bk) : 0.0;
+    if (col_ok && k == 0) part += gb[(int64_t)tri(K, K) * S + sc];
+    n2 = in_n2 ? a * a : 0.0;
+    part = wave_sum(part);
+    n2 = wave_sum(n2);
+}
+
+// Built for G = 32 (K = 17..32, two columns per wave) and G = 64 (K = 33..64, a wave per sample: the one-thread-per-sample
+// kernel took 8.3 ms at 128 samples and K = 41); K <= 16 is k_alpha_phase_row16's.
 template <int G>
 __global__ __launch_bounds__(64) void k_alpha_phase_lanes(const double* __restrict__ gb,
                                                           double* __restrict__ alpha,
@@ -341,6 +369,7 @@ __global__ __launch_bounds__(64) void k_alpha_phase_lanes(const double* __restri
                                                           const SolverState* __restrict__ state, int S,
                                                           int K, int n_u, int n_iter2,
                                                           double* __restrict__ partials) {
+    static_assert(G == 32 || G == 64, "k_alpha_phase_lanes is built for G = 32 and 64");
     if (state->done) return;
     constexpr int CPW = 64 / G;  // sample columns per wave
     const int lane = threadIdx.x;
@@ -352,14 +381,7 @@ __global__ __launch_bounds__(64) void k_alpha_phase_lanes(const double* __restri
     const int kc = row_ok ? k : K - 1;
 
     double Grow[G];
-#pragma unroll
-    for (int l = 0; l < G; ++l) {
-        const int lc = l < K ? l : K - 1;
-        const int lo = kc < lc ? kc : lc, hi = kc < lc ? lc : kc;
-        const double v = gb[(int64_t)tri(lo, hi) * S + sc];
-        Grow[l] = (row_ok && l < K) ? v : 0.0;
-    }
-    const double bk = row_ok ? gb[(int64_t)tri(kc, K) * S + sc] : 0.0;
+    const double bk = load_gram_row<G, false>(gb, S, K, k, sc, Grow);
     double a = row_ok ? alpha[(int64_t)kc * S + sc] : 0.0;
     double ap = row_ok ? alpha_prev[(int64_t)kc * S + sc] : 0.0;
 
@@ -413,47 +435,45 @@ __global__ __launch_bounds__(64) void k_alpha_phase_lanes(const double* __restri
         alpha[(int64_t)k * S + s] = a;
         alpha_prev[(int64_t)k * S + s] = ap;
     }
-    // cost_s = vDv - 2 a.b + a^T G a ; ||alpha_unknown||^2
-    double ga = 0.0;
+    double ga = 0.0, part, n2;  // (G_s a)_k, summed in column order
 #pragma unroll
     for (int l = 0; l < G; ++l) ga = fma(Grow[l], group_get<G>(a, base + l), ga);
-    double part = col_ok ? fma(a, ga, -2.0 * a * bk) : 0.0;
-    if (col_ok && k == 0) part += gb[(int64_t)tri(K, K) * S + sc];
-    double n2 = (col_ok && row_ok && k >= K - n_u) ? a * a : 0.0;
-    part = wave_sum(part);
-    n2 = wave_sum(n2);
-    if (lane == 0) {
-        partials[2 * blockIdx.x] = part;
-        partials[2 * blockIdx.x + 1] = n2;
-    }
+    lane_cost(gb, S, K, k, sc, col_ok, col_ok && row_ok && k >= K - n_u, a, ga, bk, part, n2);
+    store_partials(partials, part, n2);
 }
 
 // ---- K <= 16: one sample per 16-lane DPP row, every cross-lane step on DPP (no LDS round trips) ------------
-// Same arithmetic as k_alpha_phase_lanes<16> except the summation order of G a (four interleaved chains).
+// Same arithmetic as k_alpha_phase_lanes with 16 lanes per sample except the summation order of G a (four interleaved
+// chains).
 // The inner iteration of this kernel is one long dependent chain run by 64 waves at the headline size, i.e.
 // pure latency: a ds_bpermute round trip per shuffle (16 for the product, 10 sort stages, 4 scan steps) is what
 // the older kernel spends most of its 2.2 us per inner iteration on.
-template <int CTRL, bool ZERO_OOB>
-__device__ __forceinline__ double dpp16(double x) {
-    if constexpr (ZERO_OOB) {  // lanes without a source must read 0: needs the "old" operand
-        const int lo = __builtin_amdgcn_update_dpp(0, __double2loint(x), CTRL, 0xF, 0xF, true);
-        const int hi = __builtin_amdgcn_update_dpp(0, __double2hiint(x), CTRL, 0xF, 0xF, true);
-        return __hiloint2double(hi, lo);
-    } else {  // permutations / values that are masked afterwards: no destination to initialise
-        const int lo = __builtin_amdgcn_mov_dpp(__double2loint(x), CTRL, 0xF, 0xF, false);
-        const int hi = __builtin_amdgcn_mov_dpp(__double2hiint(x), CTRL, 0xF, 0xF, false);
-        return __hiloint2double(hi, lo);
-    }
+template <int CTRL>
+__device__ __forceinline__ int row_mov(int x) {  // permutations, or values masked afterwards: no destination to initialise
+    return __builtin_amdgcn_mov_dpp(x, CTRL, 0xF, 0xF, false);
+}
+template <int CTRL>
+__device__ __forceinline__ double row_mov(double x) {
+    const int lo = row_mov<CTRL>(__double2loint(x)), hi = row_mov<CTRL>(__double2hiint(x));
+    return __hiloint2double(hi, lo);
 }
 
-// value of lane (k ^ J) of the 16-lane row
-template <int J>
-__device__ __forceinline__ double row_xor(double x, int k) {
-    if constexpr (J == 1) return dpp16<0xB1, false>(x);       // quad_perm [1, 0, 3, 2]
-    else if constexpr (J == 2) return dpp16<0x4E, false>(x);  // quad_perm [2, 3, 0, 1]
-    else if constexpr (J == 8) return dpp16<0x128, false>(x); // row_ror:8
-    else {                                                    // J == 4: row_shl:4 for the lower half of an octet
-        const double from_above = dpp16<0x104, false>(x), from_below = dpp16<0x114, false>(x);
+// row_shr and the like: lanes without a source must read 0, which needs the "old" operand
+template <int CTRL>
+__device__ __forceinline__ double row_mov_or_zero(double x) {
+    const int lo = __builtin_amdgcn_update_dpp(0, __double2loint(x), CTRL, 0xF, 0xF, true);
+    const int hi = __builtin_amdgcn_update_dpp(0, __double2hiint(x), CTRL, 0xF, 0xF, true);
+    return __hiloint2double(hi, lo);
+}
+
+// value of lane (k ^ J) of the 16-lane row, for a double or an int
+template <int J, class T>
+__device__ __forceinline__ T row_xor(T x, int k) {
+    if constexpr (J == 1) return row_mov<0xB1>(x);       // quad_perm [1, 0, 3, 2]
+    else if constexpr (J == 2) return row_mov<0x4E>(x);  // quad_perm [2, 3, 0, 1]
+    else if constexpr (J == 8) return row_mov<0x128>(x); // row_ror:8
+    else {                                               // J == 4: row_shl:4 for the lower half of an octet
+        const T from_above = row_mov<0x104>(x), from_below = row_mov<0x114>(x);
         return (k & 4) ? from_below : from_above;
     }
 }
@@ -470,6 +490,16 @@ __device__ __forceinline__ void fmac_rowbcast(double& acc, double x, double m) {
         asm volatile("v_fmac_f64_dpp %0, %1, %2 row_newbcast:%3 row_mask:0xf bank_mask:0xf" : "+v"(acc) : "v"(x), "v"(m), "n"(L));
 }
 
+// acc[i % CHAINS] += x[lane L0 + i of the row] * m[L0 + i] for i = 0 .. N - 1, in this order.  FIRST / REST: the FIRST flag
+// of term 0 / of the terms behind it.
+template <int L0, int N, bool FIRST, bool REST, int CHAINS, int I = 0>
+__device__ __forceinline__ void fmac_rowbcast_seq(double (&acc)[CHAINS], double x, const double (&m)[16]) {
+    if constexpr (I < N) {
+        fmac_rowbcast<L0 + I, I == 0 ? FIRST : REST>(acc[I % CHAINS], x, m[L0 + I]);
+        fmac_rowbcast_seq<L0, N, FIRST, REST, CHAINS, I + 1>(acc, x, m);
+    }
+}
+
 template <int J>
 __device__ __forceinline__ void bitonic_step(double& srt, int k, int k2) {
     const double other = row_xor<J>(srt, k);
@@ -483,7 +513,7 @@ __global__ __launch_bounds__(64) void k_alpha_phase_row16(const double* __restri
                                                           int n_u, int n_iter2, double* __restrict__ partials) {
     if (state->done) return;
     const int lane = threadIdx.x;
-    const int k = lane & 15, grp = lane >> 4, base = grp * 16;
+    const int k = lane & 15, grp = lane >> 4;
     const int s = blockIdx.x * 4 + grp;
     const bool col_ok = s < S;
     const int sc = col_ok ? s : S - 1;
@@ -491,14 +521,7 @@ __global__ __launch_bounds__(64) void k_alpha_phase_row16(const double* __restri
     const int kc = row_ok ? k : K - 1;
 
     double Gneg[16];  // -G_s[k][l]
-#pragma unroll
-    for (int l = 0; l < 16; ++l) {
-        const int lc = l < K ? l : K - 1;
-        const int lo = kc < lc ? kc : lc, hi = kc < lc ? lc : kc;
-        const double v = gb[(int64_t)tri(lo, hi) * S + sc];
-        Gneg[l] = (row_ok && l < K) ? -v : 0.0;
-    }
-    const double bk = row_ok ? gb[(int64_t)tri(kc, K) * S + sc] : 0.0;
+    const double bk = load_gram_row<16, true>(gb, S, K, k, sc, Gneg);
     double a = row_ok ? alpha[(int64_t)kc * S + sc] : 0.0;
     double ap = row_ok ? alpha_prev[(int64_t)kc * S + sc] : 0.0;
 
@@ -523,22 +546,12 @@ __global__ __launch_bounds__(64) void k_alpha_phase_row16(const double* __restri
         const double at = a + beta * (a - ap);
         ap = a;
         // b - G at, four interleaved chains; the columns beyond K are zero and skipped in fours (K is wave-uniform)
-        double g0 = bk, g1 = 0.0, g2 = 0.0, g3 = 0.0;
-        fmac_rowbcast<0>(g0, at, Gneg[0]);          fmac_rowbcast<1, false>(g1, at, Gneg[1]);
-        fmac_rowbcast<2, false>(g2, at, Gneg[2]);   fmac_rowbcast<3, false>(g3, at, Gneg[3]);
-        if (K > 4) {
-            fmac_rowbcast<4, false>(g0, at, Gneg[4]);   fmac_rowbcast<5, false>(g1, at, Gneg[5]);
-            fmac_rowbcast<6, false>(g2, at, Gneg[6]);   fmac_rowbcast<7, false>(g3, at, Gneg[7]);
-        }
-        if (K > 8) {
-            fmac_rowbcast<8, false>(g0, at, Gneg[8]);   fmac_rowbcast<9, false>(g1, at, Gneg[9]);
-            fmac_rowbcast<10, false>(g2, at, Gneg[10]); fmac_rowbcast<11, false>(g3, at, Gneg[11]);
-        }
-        if (K > 12) {
-            fmac_rowbcast<12, false>(g0, at, Gneg[12]); fmac_rowbcast<13, false>(g1, at, Gneg[13]);
-            fmac_rowbcast<14, false>(g2, at, Gneg[14]); fmac_rowbcast<15, false>(g3, at, Gneg[15]);
-        }
-        const double g = (g0 + g1) + (g2 + g3);
+        double g4[4] = {bk, 0.0, 0.0, 0.0};
+        fmac_rowbcast_seq<0, 4, true, false>(g4, at, Gneg);
+        if (K > 4) fmac_rowbcast_seq<4, 4, false, false>(g4, at, Gneg);
+        if (K > 8) fmac_rowbcast_seq<8, 4, false, false>(g4, at, Gneg);
+        if (K > 12) fmac_rowbcast_seq<12, 4, false, false>(g4, at, Gneg);
+        const double g = (g4[0] + g4[1]) + (g4[2] + g4[3]);
         const double x = at + g / lh;  // deconvolution.py:100: alpha_temp + (...) / l_h
         // ---- projection onto the simplex (deconvolution.py:25-35): bitonic sort of the row, descending.  The lanes
         // beyond K hold -inf: with K <= 8 (4, 2) only the first 8 (4, 2) lanes need sorting -- the last stage then runs
@@ -561,10 +574,10 @@ __global__ __launch_bounds__(64) void k_alpha_phase_row16(const double* __restri
             bitonic_step<1>(srt, k, 16);
         }
         double cum = row_ok ? srt : 0.0;  // padded lanes sort to the end (-inf) and add nothing
-        cum += dpp16<0x111, true>(cum);   // row_shr:1 .. 8, lanes without a source read 0: inclusive scan
-        cum += dpp16<0x112, true>(cum);
-        if (K > 4) cum += dpp16<0x114, true>(cum);
-        if (K > 8) cum += dpp16<0x118, true>(cum);
+        cum += row_mov_or_zero<0x111>(cum);   // row_shr:1 .. 8, lanes without a source read 0: inclusive scan
+        cum += row_mov_or_zero<0x112>(cum);
+        if (K > 4) cum += row_mov_or_zero<0x114>(cum);
+        if (K > 8) cum += row_mov_or_zero<0x118>(cum);
         // theta = (cumsum_rho - 1) / (rho + 1) with rho the LAST position where u_rho - (cumsum_rho - 1) / (rho + 1) > 0
         // (:28-33).  t_j = (cumsum_j - 1) / (j + 1) grows exactly while that condition holds -- t_(j+1) - t_j =
         // (u_(j+1) - t_j) / (j + 2), and u_(j+1) > t_(j+1) <=> u_(j+1) > t_j -- and never again behind rho (u keeps falling,
@@ -586,21 +599,10 @@ __global__ __launch_bounds__(64) void k_alpha_phase_row16(const double* __restri
     }
     // cost_s = vDv - 2 a.b + a^T G a ; ||alpha_unknown||^2.  (G a as one chain of DPP row broadcasts in column order: the
     // same sum, term by term, as sixteen ds_bpermute round trips gave -- fma(-x, y, -z) = -fma(x, y, z).)
-    double nga = 0.0;
-    fmac_rowbcast<0>(nga, a, Gneg[0]);          fmac_rowbcast<1, false>(nga, a, Gneg[1]);
-    fmac_rowbcast<2, false>(nga, a, Gneg[2]);   fmac_rowbcast<3, false>(nga, a, Gneg[3]);
-    fmac_rowbcast<4, false>(nga, a, Gneg[4]);   fmac_rowbcast<5, false>(nga, a, Gneg[5]);
-    fmac_rowbcast<6, false>(nga, a, Gneg[6]);   fmac_rowbcast<7, false>(nga, a, Gneg[7]);
-    fmac_rowbcast<8, false>(nga, a, Gneg[8]);   fmac_rowbcast<9, false>(nga, a, Gneg[9]);
-    fmac_rowbcast<10, false>(nga, a, Gneg[10]); fmac_rowbcast<11, false>(nga, a, Gneg[11]);
-    fmac_rowbcast<12, false>(nga, a, Gneg[12]); fmac_rowbcast<13, false>(nga, a, Gneg[13]);
-    fmac_rowbcast<14, false>(nga, a, Gneg[14]); fmac_rowbcast<15, false>(nga, a, Gneg[15]);
-    const double ga = -nga;
-    double part = col_ok ? fma(a, ga, -2.0 * a * bk) : 0.0;
-    if (col_ok && k == 0) part += gb[(int64_t)tri(K, K) * S + sc];
-    double n2 = (col_ok && row_ok && k >= K - n_u) ? a * a : 0.0;
-    part = wave_sum(part);
-    n2 = wave_sum(n2);
+    double nga[1] = {0.0};
+    fmac_rowbcast_seq<0, 16, true, false>(nga, a, Gneg);
+    double part, n2;
+    lane_cost(gb, S, K, k, sc, col_ok, col_ok && row_ok && k >= K - n_u, a, -nga[0], bk, part, n2);
     int last = 0;
     if (lane == 0) {
         // handed to the closing workgroup as returning atomic exchanges (see k_gram_v2_reduce: all atomics on an address
@@ -616,51 +618,6 @@ __global__ __launch_bounds__(64) void k_alpha_phase_row16(const double* __restri
     // counter, so advancing the state here races with nobody.  Same summation order as k_finish_iteration.
     last = __shfl(last, 0, 64);
     if (last) finish_iteration_body<true>(partials, (int)gridDim.x, state, n_iter2);
-}
-
-static hipError_t launch_alpha_row16(const double* gb, double* alpha, double* alpha_prev, SolverState* state, int S,
-                                     int K, int n_u, int n_iter2, double* partials, hipStream_t st) {
-    const int nb = (S + 3) / 4;
-    hipLaunchKernelGGL(k_alpha_phase_row16, dim3(nb), dim3(64), 0, st, gb, alpha, alpha_prev, state, S, K, n_u,
-                       n_iter2, partials);  // (closes the outer iteration itself)
-    return hipGetLastError();
-}
-
-template <int G>
-static hipError_t launch_alpha_lanes_t(const double* gb, double* alpha, double* alpha_prev, SolverState* state,
-                                       int S, int K, int n_u, int n_iter2, double* partials, hipStream_t st) {
-    const int nb = (S * G + 63) / 64;
-    hipLaunchKernelGGL(k_alpha_phase_lanes<G>, dim3(nb), dim3(64), 0, st, gb, alpha, alpha_prev, state, S, K, n_u,
-                       n_iter2, partials);
-    hipLaunchKernelGGL(k_finish_iteration, dim3(1), dim3(64), 0, st, partials, nb, state, n_iter2);
-    return hipGetLastError();
-}
-
-hipError_t launch_alpha_phase(const double* gb, double* alpha, double* alpha_prev,
-                              SolverState* state, int S, int n_c, int n_u, int n_iter2,
-                              double* partials, bool thread_per_sample, hipStream_t st) {
-    const int K = n_c + n_u;
-    if (!thread_per_sample) {
-        if (K <= 16) return launch_alpha_row16(gb, alpha, alpha_prev, state, S, K, n_u, n_iter2, partials, st);
-        if (K <= 4) return launch_alpha_lanes_t<4>(gb, alpha, alpha_prev, state, S, K, n_u, n_iter2, partials, st);
-        if (K <= 8) return launch_alpha_lanes_t<8>(gb, alpha, alpha_prev, state, S, K, n_u, n_iter2, partials, st);
-        if (K <= 16) return launch_alpha_lanes_t<16>(gb, alpha, alpha_prev, state, S, K, n_u, n_iter2, partials, st);
-        if (K <= 32) return launch_alpha_lanes_t<32>(gb, alpha, alpha_prev, state, S, K, n_u, n_iter2, partials, st);
-        // (a wave per sample: the one-thread-per-sample kernel below took 8.3 ms at 128 samples and K = 41)
-        if (K <= 64) return launch_alpha_lanes_t<64>(gb, alpha, alpha_prev, state, S, K, n_u, n_iter2, partials, st);
-    } else {
-        if (K <= 4) return launch_alpha_t<4>(gb, alpha, alpha_prev, state, S, K, n_u, n_iter2, partials, st);
-        if (K <= 8) return launch_alpha_t<8>(gb, alpha, alpha_prev, state, S, K, n_u, n_iter2, partials, st);
-        if (K <= 16) return launch_alpha_t<16>(gb, alpha, alpha_prev, state, S, K, n_u, n_iter2, partials, st);
-    }
-    if (K <= kMaxK) {
-        const int nb = (S + 63) / 64;
-        hipLaunchKernelGGL(k_alpha_phase_dyn, dim3(nb), dim3(64), 0, st, gb, alpha, alpha_prev, state, S, K,
-                           n_u, n_iter2, partials);
-        hipLaunchKernelGGL(k_finish_iteration, dim3(1), dim3(64), 0, st, partials, nb, state, n_iter2);
-        return hipGetLastError();
-    }
-    return hipErrorInvalidValue;
 }
 
 // ---- purity-constrained alpha phase: Frank-Wolfe on the packed Gram data ----------------------------
@@ -719,30 +676,19 @@ __global__ __launch_bounds__(64) void k_alpha_frank_wolfe(const double* __restri
         }
         cost = cost - 2.0 * lin + quad;
     }
-    cost = wave_sum(cost);
-    n2 = wave_sum(n2);
-    if (threadIdx.x == 0) {
-        partials[2 * blockIdx.x] = cost;
-        partials[2 * blockIdx.x + 1] = n2;
-    }
+    store_partials(partials, wave_sum(cost), wave_sum(n2));
 }
 
 // K <= 16: one sample per 16-lane DPP row, as k_alpha_phase_row16 (the thread-per-sample kernel above keeps a[]
 // and grad[] in scratch and needs ~40 us per Frank-Wolfe iteration; the CLI default with --purity is 500 of them
 // per outer iteration).  Lane k owns row k of G_s; both block-wise argmins are butterfly reductions on DPP
-// moves, lowest index first among equal minima (np.argmin).
+// moves, lowest index first among equal minima (np.argmin).  The row load and the cost epilogue are written out here:
+// through load_gram_row / lane_cost the kernel took 60 instead of 62 VGPRs and another instruction stream, with no gain in
+// time (profiles/r12_alpha_refactor.txt, section 6); as written it compiles to the stream it had before.
 template <int J>
 __device__ __forceinline__ void argmin_step(double& v, int& idx, int k) {
     const double ov = row_xor<J>(v, k);
-    int oi;
-    if constexpr (J == 1) oi = __builtin_amdgcn_mov_dpp(idx, 0xB1, 0xF, 0xF, false);
-    else if constexpr (J == 2) oi = __builtin_amdgcn_mov_dpp(idx, 0x4E, 0xF, 0xF, false);
-    else if constexpr (J == 8) oi = __builtin_amdgcn_mov_dpp(idx, 0x128, 0xF, 0xF, false);
-    else {
-        const int up = __builtin_amdgcn_mov_dpp(idx, 0x104, 0xF, 0xF, false);
-        const int dn = __builtin_amdgcn_mov_dpp(idx, 0x114, 0xF, 0xF, false);
-        oi = (k & 4) ? dn : up;
-    }
+    const int oi = row_xor<J>(idx, k);
     const bool take = ov < v || (ov == v && oi < idx);
     v = take ? ov : v;
     idx = take ? oi : idx;
@@ -778,16 +724,9 @@ __global__ __launch_bounds__(64) void k_alpha_frank_wolfe_row16(const double* __
     double a = row_ok ? alpha[(int64_t)kc * S + sc] : 0.0;
 
     for (int it = 0; it < max_iter; ++it) {
-        double g0 = -bk, g1 = 0.0, g2 = 0.0, g3 = 0.0;  // grad = G a - b (= -R^T (d * (v - R a)))
-        fmac_rowbcast<0>(g0, a, Grow[0]);   fmac_rowbcast<1>(g1, a, Grow[1]);
-        fmac_rowbcast<2>(g2, a, Grow[2]);   fmac_rowbcast<3>(g3, a, Grow[3]);
-        fmac_rowbcast<4>(g0, a, Grow[4]);   fmac_rowbcast<5>(g1, a, Grow[5]);
-        fmac_rowbcast<6>(g2, a, Grow[6]);   fmac_rowbcast<7>(g3, a, Grow[7]);
-        fmac_rowbcast<8>(g0, a, Grow[8]);   fmac_rowbcast<9>(g1, a, Grow[9]);
-        fmac_rowbcast<10>(g2, a, Grow[10]); fmac_rowbcast<11>(g3, a, Grow[11]);
-        fmac_rowbcast<12>(g0, a, Grow[12]); fmac_rowbcast<13>(g1, a, Grow[13]);
-        fmac_rowbcast<14>(g2, a, Grow[14]); fmac_rowbcast<15>(g3, a, Grow[15]);
-        const double grad = (g0 + g1) + (g2 + g3);
+        double g4[4] = {-bk, 0.0, 0.0, 0.0};  // grad = G a - b (= -R^T (d * (v - R a)))
+        fmac_rowbcast_seq<0, 16, true, true>(g4, a, Grow);  // (FIRST on every term: DESIGN.md section 8)
+        const double grad = (g4[0] + g4[1]) + (g4[2] + g4[3]);
         double v1 = known ? grad : INFINITY, v2 = unknown ? grad : INFINITY;
         int i1 = k, i2 = k;
         argmin_step<1>(v1, i1, k); argmin_step<2>(v1, i1, k); argmin_step<4>(v1, i1, k); argmin_step<8>(v1, i1, k);
@@ -798,37 +737,81 @@ __global__ __launch_bounds__(64) void k_alpha_frank_wolfe_row16(const double* __
         a = (1.0 - gamma) * a + gamma * vertex;
     }
     if (col_ok && row_ok) alpha[(int64_t)k * S + s] = a;
-    // cost_s = vDv - 2 a.b + a^T G a ; ||alpha_unknown||^2
     double ga = 0.0;
 #pragma unroll
     for (int l = 0; l < 16; ++l) ga = fma(Grow[l], __shfl(a, base + l, 64), ga);
     double part = col_ok ? fma(a, ga, -2.0 * a * bk) : 0.0;
     if (col_ok && k == 0) part += gb[(int64_t)tri(K, K) * S + sc];
-    double n2 = (col_ok && unknown) ? a * a : 0.0;
-    part = wave_sum(part);
-    n2 = wave_sum(n2);
-    if (lane == 0) {
-        partials[2 * blockIdx.x] = part;
-        partials[2 * blockIdx.x + 1] = n2;
-    }
+    const double n2 = (col_ok && unknown) ? a * a : 0.0;
+    store_partials(partials, wave_sum(part), wave_sum(n2));
 }
 
-hipError_t launch_alpha_frank_wolfe(const double* gb, double* alpha, const double* purity, SolverState* state,
-                                    int S, int n_c, int n_u, int max_iter, double* partials, hipStream_t st) {
-    const int K = n_c + n_u;
-    if (K > kMaxK) return hipErrorInvalidValue;
-    if (K <= 16 && n_c >= 1) {
-        const int nb4 = (S + 3) / 4;
-        hipLaunchKernelGGL(k_alpha_frank_wolfe_row16, dim3(nb4), dim3(64), 0, st, gb, alpha, purity, state, S, K, n_u,
-                           max_iter, partials);
-        hipLaunchKernelGGL(k_finish_iteration, dim3(1), dim3(64), 0, st, partials, nb4, state, max_iter);
-        return hipGetLastError();
+// ---- the launcher ----------------------------------------------------------------------------------------------------
+// K -> KMAX of the thread-per-sample instances: f(std::integral_constant<int, 4, 8 or 16>), 0 (run-time K) beyond 16
+template <class F>
+static hipError_t dispatch_kmax(int K, F&& f) {
+    if (K > 16) return f(std::integral_constant<int, 0>{});
+    if (K > 8) return f(std::integral_constant<int, 16>{});
+    return K > 4 ? f(std::integral_constant<int, 8>{}) : f(std::integral_constant<int, 4>{});
+}
+
+template <int KMAX>
+static hipError_t launch_alpha_thread(const AlphaView& a, int n_iter2, hipStream_t st) {
+    const int K = a.n_c + a.n_u, nb = (a.S + 63) / 64;
+    if constexpr (KMAX > 0) {
+        const size_t lds = (size_t)(K + 1) * (K + 2) / 2 * 64 * sizeof(double);
+        const int in_lds = lds <= 150 * 1024;
+        if (in_lds && lds > 48 * 1024) {
+            const hipError_t e = raise_dynamic_lds<k_alpha_phase<KMAX>>(lds);
+            if (e != hipSuccess) return e;
+        }
+        hipLaunchKernelGGL(k_alpha_phase<KMAX>, dim3(nb), dim3(64), in_lds ? lds : 0, st, a.gb, a.alpha, a.alpha_prev, a.state,
+                           a.S, K, a.n_u, n_iter2, in_lds, a.partials);
+    } else {
+        hipLaunchKernelGGL(k_alpha_phase_dyn, dim3(nb), dim3(64), 0, st, a.gb, a.alpha, a.alpha_prev, a.state, a.S, K, a.n_u,
+                           n_iter2, a.partials);
     }
-    const int nb = (S + 63) / 64;
-    hipLaunchKernelGGL(k_alpha_frank_wolfe, dim3(nb), dim3(64), 0, st, gb, alpha, purity, state, S, K, n_u, max_iter,
-                       partials);
-    hipLaunchKernelGGL(k_finish_iteration, dim3(1), dim3(64), 0, st, partials, nb, state, max_iter);
-    return hipGetLastError();
+    return launch_finish_iteration(a.partials, nb, a.state, n_iter2, st);
+}
+
+template <int G>
+static hipError_t launch_alpha_lanes(const AlphaView& a, int n_iter2, hipStream_t st) {
+    const int nb = (a.S * G + 63) / 64;
+    hipLaunchKernelGGL(k_alpha_phase_lanes<G>, dim3(nb), dim3(64), 0, st, a.gb, a.alpha, a.alpha_prev, a.state, a.S,
+                       a.n_c + a.n_u, a.n_u, n_iter2, a.partials);
+    return launch_finish_iteration(a.partials, nb, a.state, n_iter2, st);
+}
+
+hipError_t launch_alpha(AlphaKind kind, const AlphaView& a, int n_iter2, hipStream_t st) {
+    const int S = a.S, K = a.n_c + a.n_u, nb4 = (S + 3) / 4, nb64 = (S + 63) / 64;
+    if (K < 1 || K > kMaxK) return hipErrorInvalidValue;
+    switch (kind) {
+        case AlphaKind::PhaseRow16:  // (closes the outer iteration itself)
+            if (K > 16) break;
+            hipLaunchKernelGGL(k_alpha_phase_row16, dim3(nb4), dim3(64), 0, st, a.gb, a.alpha, a.alpha_prev, a.state, S, K, a.n_u,
+                               n_iter2, a.partials);
+            return hipGetLastError();
+        case AlphaKind::PhaseLanes:
+            if (K <= 16) break;
+            return K <= 32 ? launch_alpha_lanes<32>(a, n_iter2, st) : launch_alpha_lanes<64>(a, n_iter2, st);
+        case AlphaKind::Phase:
+            if (K > 16) break;
+            return dispatch_kmax(K, [&](auto kmax) { return launch_alpha_thread<kmax>(a, n_iter2, st); });
+        case AlphaKind::PhaseDyn:
+            if (K <= 16) break;
+            return launch_alpha_thread<0>(a, n_iter2, st);
+        case AlphaKind::FrankWolfeRow16:
+            if (K > 16 || a.n_c < 1 || a.purity == nullptr) break;
+            hipLaunchKernelGGL(k_alpha_frank_wolfe_row16, dim3(nb4), dim3(64), 0, st, a.gb, a.alpha, a.purity, a.state, S, K,
+                               a.n_u, n_iter2, a.partials);
+            return launch_finish_iteration(a.partials, nb4, a.state, n_iter2, st);
+        case AlphaKind::FrankWolfe:
+            if (a.purity == nullptr) break;
+            hipLaunchKernelGGL(k_alpha_frank_wolfe, dim3(nb64), dim3(64), 0, st, a.gb, a.alpha, a.purity, a.state, S, K, a.n_u,
+                               n_iter2, a.partials);
+            return launch_finish_iteration(a.partials, nb64, a.state, n_iter2, st);
+    }
+    return hipErrorInvalidValue;  // the kind does not take this shape
 }
 
 // ---- standalone projection (KAT entry point) ----------------------------------------------
@@ -849,12 +832,12 @@ __global__ __launch_bounds__(64) void k_project(const double* __restrict__ X, do
 hipError_t launch_project_simplex(const double* X, double* out, int K, int S, double z,
                                   hipStream_t st) {
     const dim3 grid((S + 63) / 64), block(64);
-    if (K <= 4) hipLaunchKernelGGL(k_project<4>, grid, block, 0, st, X, out, K, S, z);
-    else if (K <= 8) hipLaunchKernelGGL(k_project<8>, grid, block, 0, st, X, out, K, S, z);
-    else if (K <= 16) hipLaunchKernelGGL(k_project<16>, grid, block, 0, st, X, out, K, S, z);
-    else if (K <= kMaxK) hipLaunchKernelGGL(k_project_dyn, grid, block, 0, st, X, out, K, S, z);
-    else return hipErrorInvalidValue;
-    return hipGetLastError();
+    if (K < 1 || K > kMaxK) return hipErrorInvalidValue;
+    return dispatch_kmax(K, [&](auto kmax) {
+        if constexpr (kmax > 0) hipLaunchKernelGGL(k_project<kmax>, grid, block, 0, st, X, out, K, S, z);
+        else hipLaunchKernelGGL(k_project_dyn, grid, block, 0, st, X, out, K, S, z);
+        return hipGetLastError();
+    });
 }
 
 // ---- solver set-up helpers -------------------------------------------------------------------

@@ -1,7 +1,9 @@
 // Kernel selection as ONE table: which kernels a (shape, counts, level) gets for the u phase, the u-dependent Gram entries
 // and the alpha phase of an outer iteration (deconvolution.py:206-221).  Pure host functions of the key -- no pointers, no
-// context -- so that dmf_solver_create / enqueue_outer_iteration / dmf_solver_describe read the same answer and a CPU test
-// can enumerate a grid of keys against a checked-in table (tests/golden/kernel_selection.tsv, dmf_select_describe).
+// context -- so that dmf_solver_create / enqueue_outer_iteration / dmf_update_alpha / dmf_solver_describe read the same answer
+// (every launch of an outer iteration, the alpha kernel included, is the one the plan names: launch_alpha() takes the
+// AlphaKind) and a CPU test can enumerate a grid of keys against a checked-in table (tests/golden/kernel_selection.tsv,
+// dmf_select_describe).  The key is frozen when the solver is created: a later dmf_context_set_generic does not reach it.
 #pragma once
 #include <cstddef>
 #include <cstdint>

@@ -114,9 +114,34 @@ def test_update_u_unsupervised_gradient_point(ctx):
         assert np.abs(got[1] - uo_prev).max() < 1e-11
 
 
-@pytest.mark.parametrize("N,S,n_c,n_u", SHAPES + [(500, 20, 10, 10), (400, 6, 5, 25)])
-def test_update_alpha_matches_oracle(ctx, N, S, n_c, n_u):
-    from demethify_amd.device import Problem
+def _alpha_cases():
+    """(N, S, n_c, n_u, generic) of test_update_alpha_matches_oracle with the alpha kernel each must run.  The small shapes
+    put K = n_c + n_u on both sides of every branch of the alpha kernels -- 2..16: the shortened sort, scan and product of
+    k_alpha_phase_row16 and k_alpha_phase<4 / 8 / 16>; 17, 32: k_alpha_phase_lanes<32>; 33, 64: k_alpha_phase_lanes<64>;
+    17..64: k_alpha_phase_dyn -- each with and without known types, at sample counts ragged against the columns of a wave
+    (4 for row16, 2 for lanes<32>, 64 for the thread-per-sample kernels of level 1)."""
+    cases = []
+    for generic in (0, 1):
+        tag = "" if generic == 0 else "-level1"
+        for N, S, n_c, n_u in SHAPES + [(500, 20, 10, 10), (400, 6, 5, 25)]:
+            cases.append(pytest.param(N, S, n_c, n_u, generic, id=f"{N}-{S}-{n_c}-{n_u}{tag}"))
+        for K in (2, 3, 4, 5, 8, 9, 12, 13, 16, 17, 32, 33, 64):
+            sizes = (3, 66) if generic == 1 else (3, 5) if K <= 16 else (5,) if K <= 32 else (3,)
+            for S in sizes:
+                for n_c in (0, K // 2):
+                    cases.append(pytest.param(300, S, n_c, K - n_c, generic, id=f"300-{S}-{n_c}-{K - n_c}{tag}"))
+    return cases
+
+
+def _alpha_kernel(K, generic):
+    if generic == 1:
+        return "k_alpha_phase" if K <= 16 else "k_alpha_phase_dyn"
+    return "k_alpha_phase_row16" if K <= 16 else "k_alpha_phase_lanes"
+
+
+@pytest.mark.parametrize("N,S,n_c,n_u,generic", _alpha_cases())
+def test_update_alpha_matches_oracle(ctx, N, S, n_c, n_u, generic):
+    from demethify_amd.device import Problem, Solver
 
     V, D, Rt, u, alpha, rs = _problem(N, S, n_c, n_u, 5)
     alpha_prev = rs.dirichlet(np.ones(n_c + n_u), S).T
@@ -125,8 +150,17 @@ def test_update_alpha_matches_oracle(ctx, N, S, n_c, n_u):
     l_h = np.linalg.norm(R) ** 2 * d
     a2, l_h_prev = 3.1, 1.1 * l_h
     want = osol.alpha_phase(4, alpha, a2, l_h_prev, l_h, alpha_prev, R, D, V)
-    with Problem(ctx, V, D, Rt if n_c else None) as p:
-        got = p.update_alpha(u, alpha, alpha_prev, 4, a2, l_h_prev, l_h)
+    ctx.set_generic(generic)
+    try:
+        with Problem(ctx, V, D, Rt if n_c else None) as p:
+            got = p.update_alpha(u, alpha, alpha_prev, 4, a2, l_h_prev, l_h)
+            with Solver(p, u, alpha) as s:
+                path = s.describe(4)
+    finally:
+        ctx.set_generic(0)
+    print(f"max |alpha - oracle| = {np.abs(got[0] - want[0]).max():.3e}, "
+          f"max |alpha_prev - oracle| = {np.abs(got[1] - want[1]).max():.3e}  ({path})")
+    assert path.endswith("alpha=" + _alpha_kernel(n_c + n_u, generic))
     assert np.abs(got[0] - want[0]).max() < 1e-10
     assert np.abs(got[1] - want[1]).max() < 1e-10
     assert got[2] == pytest.approx(want[2], rel=1e-15) and got[3] == want[3]
