@@ -88,6 +88,9 @@ SIGNATURES = {
     "dmf_write_interval_csv": (C.c_int, [C.c_char_p, C.c_char_p, _p, _p, _i64, C.c_int, C.c_int, C.c_int]),
     "dmf_stage_upload": (C.c_int, [_p, _p, C.c_size_t, C.POINTER(C.c_void_p)]),
     "dmf_stage_free": (C.c_int, [_p, _p]),
+    "dmf_stage_download": (C.c_int, [_p, _p, C.c_size_t, _p]),
+    "dmf_mask_draw": (C.c_int, [_p, _p, C.POINTER(C.c_int), _i64, _i64, C.c_uint64, C.POINTER(C.c_void_p),
+                                C.POINTER(_i64)]),
     "dmf_solve": (C.c_int, [_p, _p, _p, _p, _i64, C.c_int, _i64, _i64, C.c_double, C.c_int, _p, _p,
                             _dbl_p, C.POINTER(_i64)]),
 }

@@ -76,19 +76,26 @@ namespace dmf_api {
 // The context's pool (dmf_api_context.hip).  pool_free is for the pool code, DevBuf and dmf_stage_free alone.
 hipError_t pool_alloc(dmf_context* ctx, void** p, size_t bytes);
 void pool_free(dmf_context* ctx, void* p);
+// A block for the staging calls, which run on worker threads: from the pool on the given stream, past the kept lists (they
+// belong to the thread that drives `stream`), and its release before anybody else has seen the block.
+hipError_t stage_alloc(dmf_context* ctx, hipStream_t st, void** p, size_t bytes);
+void stage_release(dmf_context* ctx, hipStream_t st, void* p);
 
 // Owner of one device array.  Either the array came from pool_alloc and goes back through pool_free when the owner dies
 // (or is reset), or it is somebody else's (a caller's DMF_PTR_DEVICE array, another handle's buffer) and is left alone.
+// A staging call's block (alloc_staged) lives on that call's stream instead, until it is released to the caller.
 // Reads like the pointer it holds.
 template <class T>
 class DevBuf {
   public:
     DevBuf() = default;
-    DevBuf(DevBuf&& o) noexcept : ctx_(o.ctx_), ptr_(o.ptr_), owned_(o.owned_) { o.ptr_ = nullptr, o.owned_ = false; }
+    DevBuf(DevBuf&& o) noexcept : ctx_(o.ctx_), ptr_(o.ptr_), owned_(o.owned_), stage_(o.stage_) {
+        o.ptr_ = nullptr, o.owned_ = false;
+    }
     DevBuf& operator=(DevBuf&& o) noexcept {
         if (this != &o) {
             reset();
-            ctx_ = o.ctx_, ptr_ = o.ptr_, owned_ = o.owned_;
+            ctx_ = o.ctx_, ptr_ = o.ptr_, owned_ = o.owned_, stage_ = o.stage_;
             o.ptr_ = nullptr, o.owned_ = false;
         }
         return *this;
@@ -98,12 +105,25 @@ class DevBuf {
         reset();
         const hipError_t e = pool_alloc(ctx, (void**)&ptr_, count * sizeof(T));
         if (e != hipSuccess) ptr_ = nullptr;
-        ctx_ = ctx, owned_ = e == hipSuccess;
+        ctx_ = ctx, owned_ = e == hipSuccess, stage_ = nullptr;
         return e;
+    }
+    hipError_t alloc_staged(dmf_context* ctx, size_t count, hipStream_t st) {  // stage_alloc on `st`, uninitialised
+        reset();
+        const hipError_t e = stage_alloc(ctx, st, (void**)&ptr_, count * sizeof(T));
+        if (e != hipSuccess) ptr_ = nullptr;
+        ctx_ = ctx, owned_ = e == hipSuccess, stage_ = st;
+        return e;
+    }
+    T* release() {  // the array becomes the caller's (who frees it with dmf_stage_free)
+        T* p = ptr_;
+        ptr_ = nullptr, owned_ = false;
+        return p;
     }
     void borrow(const T* p) { reset(), ptr_ = const_cast<T*>(p); }
     void reset() {
-        if (owned_) pool_free(ctx_, ptr_);
+        if (owned_ && stage_ != nullptr) stage_release(ctx_, stage_, ptr_);
+        else if (owned_) pool_free(ctx_, ptr_);
         ptr_ = nullptr, owned_ = false;
     }
     T* get() const { return ptr_; }
@@ -114,6 +134,7 @@ class DevBuf {
     dmf_context* ctx_ = nullptr;
     T* ptr_ = nullptr;
     bool owned_ = false;
+    hipStream_t stage_ = nullptr;  // alloc_staged: the stream the block was allocated on
 };
 
 // the problem's constants: indices into dmf_problem::h_consts and into the device array `consts` that the kernels read

@@ -89,13 +89,14 @@ void pool_free(dmf_context* ctx, void* p) {
     (void)hipFreeAsync(p, ctx->stream);
 }
 
-// A block for the upload staging: from the pool on the given stream, past the kept lists (which belong to the thread that
-// drives `stream`; dmf_stage_upload runs on worker threads), and its release before anybody else has seen the block.
-static hipError_t stage_alloc(dmf_context* ctx, hipStream_t st, void** p, size_t bytes) {
+// A block for the staging calls: from the pool on the given stream, past the kept lists (which belong to the thread that
+// drives `stream`; dmf_stage_upload and dmf_mask_draw run on worker threads), and its release before anybody else has seen
+// the block.
+hipError_t stage_alloc(dmf_context* ctx, hipStream_t st, void** p, size_t bytes) {
     if (!pool_enabled() || ctx->pool == nullptr) return hipMalloc(p, bytes);
     return hipMallocFromPoolAsync(p, bytes, ctx->pool, st);
 }
-static void stage_release(dmf_context* ctx, hipStream_t st, void* p) {
+void stage_release(dmf_context* ctx, hipStream_t st, void* p) {
     if (!pool_enabled() || ctx->pool == nullptr) (void)hipFree(p);
     else (void)hipFreeAsync(p, st);
 }
@@ -233,6 +234,50 @@ int dmf_stage_upload(dmf_context* ctx, const void* host, size_t bytes, void** ou
         return hip_fail(e, "dmf_stage_upload", __FILE_NAME__, __LINE__);
     }
     *out_dev = d;
+    return DMF_OK;
+}
+
+int dmf_stage_download(dmf_context* ctx, const void* dev, size_t bytes, void* host) {
+    if (ctx == nullptr || dev == nullptr || host == nullptr || bytes == 0) return DMF_ERR_BAD_ARG;
+    HIP_TRY(hipSetDevice(ctx->device));
+    std::lock_guard<std::mutex> lock(ctx->copy_mutex);
+    if (ctx->copy_stream == nullptr) HIP_TRY(hipStreamCreateWithFlags(&ctx->copy_stream, hipStreamNonBlocking));
+    HIP_TRY(hipMemcpyAsync(host, dev, bytes, hipMemcpyDeviceToHost, ctx->copy_stream));
+    HIP_TRY(hipStreamSynchronize(ctx->copy_stream));
+    return DMF_OK;
+}
+
+/* The hold-out mask of a bi-cross-validation fold (ic.py:68, `np.random.rand(*meth_f.shape) < fraction`) drawn where it
+ * is used: numpy's MT19937 stream is continued by one persistent workgroup (dmf_kernels_rng.hip) on the copy stream, under
+ * dmf_stage_upload's threading contract.  No kernel-family clock: a FamilyScope records on `stream`, which another thread
+ * drives. */
+int dmf_mask_draw(dmf_context* ctx, uint32_t key[624], int* pos, int64_t N, int64_t S, uint64_t threshold, void** out_bits,
+                  int64_t* n_kept) {
+    if (ctx == nullptr || key == nullptr || pos == nullptr || out_bits == nullptr || n_kept == nullptr) return DMF_ERR_BAD_ARG;
+    *out_bits = nullptr;
+    if (*pos < 0 || *pos > 624 || N < 1 || S < 1 || threshold > ((uint64_t)1 << 53)) return DMF_ERR_BAD_ARG;
+    if (S > dmf::kMaskDrawMaxS || N > dmf::kMaskDrawMaxElements / S) return DMF_ERR_UNSUPPORTED;
+    HIP_TRY(hipSetDevice(ctx->device));  // (the current device is per thread)
+    std::lock_guard<std::mutex> lock(ctx->copy_mutex);
+    if (ctx->copy_stream == nullptr) HIP_TRY(hipStreamCreateWithFlags(&ctx->copy_stream, hipStreamNonBlocking));
+    const hipStream_t st = ctx->copy_stream;
+    constexpr size_t kStateWords = 624 + 4;  // the key, then { ones, position } as two u64 (8-byte aligned: 624 is even)
+    DevBuf<unsigned char> bits;
+    DevBuf<uint32_t> state;
+    HIP_TRY(bits.alloc_staged(ctx, (size_t)N * (size_t)((S + 7) / 8), st));
+    HIP_TRY(state.alloc_staged(ctx, kStateWords, st));
+    uint32_t h_state[kStateWords] = {};
+    std::memcpy(h_state, key, 624 * sizeof(uint32_t));
+    HIP_TRY(hipMemcpyAsync(state, h_state, sizeof(h_state), hipMemcpyHostToDevice, st));
+    HIP_TRY(dmf::launch_mask_draw(state, *pos, N, S, threshold, bits, reinterpret_cast<unsigned long long*>(state + 624), st));
+    HIP_TRY(hipMemcpyAsync(h_state, state, sizeof(h_state), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    unsigned long long result[2];
+    std::memcpy(result, h_state + 624, sizeof(result));
+    std::memcpy(key, h_state, 624 * sizeof(uint32_t));
+    *pos = (int)result[1];
+    *n_kept = (int64_t)result[0];
+    *out_bits = bits.release();
     return DMF_OK;
 }
 

@@ -273,6 +273,13 @@ hipError_t launch_mask_problem(const double* srcV, const double* srcD, const uns
                                int SD, unsigned long long* stats, hipStream_t st);
 // W[N][S] <- 1.0 where held out, 0.0 where kept
 hipError_t launch_holdout_weights_f64(const unsigned char* bits, double* W, int64_t N, int S, hipStream_t st);
+// the mask draw (dmf_kernels_rng.hip): bits <- `np.random.rand(N, S) < fraction` of the MT19937 state (key_io, pos), packed as
+// above with every byte written and the padding bits zero; threshold = ceil(fraction 2^53) (0 .. 2^53).  key_io[624] (device)
+// <- the key as of the last regeneration; result[2] <- { number of ones, position after the last word used }.  pos in
+// [0, 624], 624 = regenerate first.  One persistent workgroup.
+constexpr int64_t kMaskDrawMaxS = ((int64_t)1 << 31) - 1, kMaskDrawMaxElements = (int64_t)1 << 60;
+hipError_t launch_mask_draw(unsigned int* key_io, int pos, int64_t N, int64_t S, unsigned long long threshold,
+                            unsigned char* bits, unsigned long long* result, hipStream_t st);
 bool rowpass_v2_supported(int S, int n_c, int n_u, int n_iter2);
 int rowpass_v2_grid(int64_t N, int S);
 // u phase + b_u slab (scratch.slab: [grid][n_u][S] doubles) + per-workgroup ||u||^2 shares in one read of V (f64) and

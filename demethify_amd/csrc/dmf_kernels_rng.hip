@@ -1,0 +1,183 @@
+// Hold-out mask draw (dmf_mask_draw): `np.random.rand(N, S) < fraction` of numpy's legacy global generator (ic.py:68), bit for
+// bit, written straight into the packed form dmf_problem_mask reads -- so that a bi-cross-validation fold's mask never
+// exists on the host.
+//
+// The generator is MT19937.  One regeneration of its 624-word key is three groups of mutually independent words
+//     tw(a, b) = (y >> 1) ^ (y & 1 ? 0x9908b0df : 0),  y = (a & 0x80000000) | (b & 0x7fffffff)
+//     i in [0, 227):    new[i] = old[i + 397] ^ tw(old[i], old[i + 1])
+//     i in [227, 454):  new[i] = new[i - 227] ^ tw(old[i], old[i + 1])
+//     i in [454, 623):  new[i] = new[i - 227] ^ tw(old[i], old[i + 1]);  new[623] = new[396] ^ tw(old[623], new[0])
+// which is as far as the recurrence parallelises without a jump-ahead: ONE workgroup of 256 threads walks the stream, the
+// key ping-ponging between two LDS arrays (old is read while new is written), a barrier after each group.  random_sample
+// makes a double from two consecutive tempered words, k / 2^53 with k = (a >> 5) 2^26 + (b >> 6), so `x < fraction` is the
+// integer compare k < T with the host's T = ceil(fraction 2^53): no floating point here.
+//
+// A "stretch" is the part of the stream one key serves: stretch 0 the key as given from position p (or, for position 624,
+// its first regeneration), every later one 624 words = 312 doubles.  With p odd a double straddles two stretches: its `a`
+// is word 623 of the previous key, still intact in the other LDS array.  Element j of the row-major N x S matrix is double
+// j of the stream; thread by thread the compare bits of a stretch are gathered per wave (__ballot) into a ring of 2048
+// bits indexed by j mod 2048, in 64-bit slots aligned in j -- the one slot a stretch shares with its predecessor is
+// merged by the lane that writes it.  A byte of the output holds at most 8 consecutive j (sample s = bit (s & 7) of byte
+// (s >> 3), ceil(S / 8) bytes per row, padding bits zero), so the bytes that a stretch completes are cut out of the ring and
+// stored by consecutive lanes; a byte that a stretch leaves partly filled waits in the ring for the next.  The emission of
+// stretch t runs between the first two barriers of regeneration t + 1, which saves it a barrier of its own.
+#include <cstdint>
+
+#include "dmf_internal.h"
+
+namespace dmf {
+
+namespace {
+
+constexpr int kMtN = 624, kMtM = 397, kRingSlots = 32;  // (ring: 32 x 64 bits >= 7 waiting + 313 new + 63 of alignment)
+
+__device__ __forceinline__ unsigned int mt_twist(unsigned int a, unsigned int b) {
+    const unsigned int y = (a & 0x80000000u) | (b & 0x7fffffffu);
+    return (y >> 1) ^ ((y & 1u) ? 0x9908b0dfu : 0u);
+}
+
+__device__ __forceinline__ unsigned int mt_temper(unsigned int y) {
+    y ^= y >> 11;
+    y ^= (y << 7) & 0x9d2c5680u;
+    y ^= (y << 15) & 0xefc60000u;
+    y ^= y >> 18;
+    return y;
+}
+
+// What has been emitted so far (uniform over the workgroup): the next byte is byte `col` of row `row`.
+struct Emitted {
+    unsigned long long row = 0;
+    unsigned int col = 0;
+};
+
+// Stores every byte that lies wholly below element (row_c, s_c) -- the first element not drawn yet -- and is not out yet.
+__device__ __forceinline__ void emit_bytes(const unsigned long long* ring, unsigned char* __restrict__ bits,
+                                           unsigned long long S, unsigned int nb, unsigned long long row_c,
+                                           unsigned int s_c, Emitted& done, unsigned long long& kept) {
+    const unsigned int count = (unsigned int)((row_c - done.row) * nb) + (s_c >> 3) - done.col;  // (<= 320)
+    for (unsigned int i = threadIdx.x; i < count; i += blockDim.x) {
+        // byte done.col + i counted on from row done.row: a handful of rows at most where a row has 8 bytes or more (a
+        // stretch completes 39 + 312 / S bytes), so no division there
+        unsigned int cb = done.col + i, up = 0;
+        if (nb >= 8) {
+            while (cb >= nb) cb -= nb, ++up;
+        } else {
+            up = cb / nb;
+            cb -= up * nb;
+        }
+        const unsigned long long r = done.row + up;
+        const unsigned long long j0 = r * S + 8ull * cb, left = S - 8ull * cb;
+        const unsigned int n = left >= 8 ? 8u : (unsigned int)left;
+        const unsigned int at = (unsigned int)j0 & (64 * kRingSlots - 1), slot = at >> 6, sh = at & 63;
+        unsigned long long v = ring[slot] >> sh;
+        if (sh > 56) v |= ring[(slot + 1) & (kRingSlots - 1)] << (64 - sh);
+        const unsigned int b = (unsigned int)v & ((1u << n) - 1u);
+        bits[r * nb + cb] = (unsigned char)b;
+        kept += __popc(b);
+    }
+    done.row = row_c, done.col = s_c >> 3;
+}
+
+}  // namespace
+
+// key_io[624]: the generator's key, in and out (the key as of the last regeneration); p = position % 624 of the first word
+// to use, regen_first: the position was 624.  bits <- the packed N x S mask (every byte written), result[0] <- number of
+// ones, result[1] <- the position after the last word used (1..624).  Launched as ONE workgroup of 256 threads.
+__global__ __launch_bounds__(256) void k_mask_draw(unsigned int* __restrict__ key_io, int p, int regen_first,
+                                                   unsigned long long N, unsigned long long S, unsigned long long T,
+                                                   unsigned char* __restrict__ bits,
+                                                   unsigned long long* __restrict__ result) {
+    __shared__ unsigned int key[2][kMtN];
+    __shared__ unsigned long long ring[kRingSlots];
+    __shared__ unsigned long long wave_kept[4];
+    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+    const unsigned long long M = N * S, last_word = (unsigned long long)p + 2 * M - 1, t_last = last_word / kMtN;
+    const unsigned int nb = (unsigned int)((S + 7) / 8);
+    for (int i = tid; i < kMtN; i += 256) key[0][i] = key_io[i];
+    if (tid < kRingSlots) ring[tid] = 0;
+    __syncthreads();
+
+    int cur = 0;  // the LDS array that holds the key of the stretch in hand
+    unsigned long long kept = 0;
+    unsigned long long row_c = 0;  // (row_c, s_c): the first element not drawn yet
+    unsigned int s_c = 0;
+    unsigned long long jb = 0;  // = row_c S + s_c
+    Emitted done;
+    for (unsigned long long t = 0; t <= t_last; ++t) {
+        if (t > 0 || regen_first) {
+            const unsigned int* __restrict__ o = key[cur];
+            unsigned int* __restrict__ n = key[cur ^ 1];
+            if (tid < 227) n[tid] = o[tid + kMtM] ^ mt_twist(o[tid], o[tid + 1]);
+            __syncthreads();
+            // (the bits of the stretch before are in the ring since the barrier above; the next to write it is this
+            // stretch's compare, behind two more barriers)
+            emit_bytes(ring, bits, S, nb, row_c, s_c, done, kept);
+            if (tid < 227) n[tid + 227] = n[tid] ^ mt_twist(o[tid + 227], o[tid + 228]);
+            __syncthreads();
+            if (tid < 169) n[tid + 454] = n[tid + 227] ^ mt_twist(o[tid + 454], o[tid + 455]);
+            if (tid == 169) n[623] = n[396] ^ mt_twist(o[623], n[0]);
+            __syncthreads();
+            cur ^= 1;
+        }
+        // the doubles this stretch completes: [ja, jb_new), double j from the words p + 2 j and p + 2 j + 1 of the stream
+        const unsigned long long first = t * kMtN, ja = jb;
+        unsigned long long jb_new = ((t + 1) * kMtN - (unsigned long long)p) / 2;
+        jb_new = jb_new < M ? jb_new : M;
+        const int rel0 = (int)((long long)((unsigned long long)p + 2 * ja) - (long long)first);  // `a` of double ja: -1 = straddles
+        const unsigned long long base = ja & ~63ull;
+        const unsigned int* __restrict__ k_cur = key[cur];
+        const unsigned int* __restrict__ k_prev = key[cur ^ 1];
+        for (int pass = 0; pass < 2; ++pass) {
+            const unsigned long long chunk = base + 64ull * (pass * 4 + wave);  // (wave-uniform)
+            if (chunk >= jb_new) continue;
+            const unsigned long long j = chunk + lane;
+            bool bit = false;
+            if (j >= ja && j < jb_new) {
+                const int rel = rel0 + 2 * (int)(j - ja);
+                const unsigned int wa = rel >= 0 ? k_cur[rel] : k_prev[kMtN - 1];
+                const unsigned long long a = mt_temper(wa) >> 5, b = mt_temper(k_cur[rel + 1]) >> 6;
+                bit = ((a << 26) + b) < T;
+            }
+            const unsigned long long votes = __ballot(bit);
+            if (lane == 0) {
+                const unsigned int slot = (unsigned int)(chunk >> 6) & (kRingSlots - 1);
+                ring[slot] = (chunk < ja ? ring[slot] : 0ull) | votes;  // (bits below ja: the stretch before wrote them)
+            }
+        }
+        // advance (row_c, s_c) by the doubles drawn: at most 313, i.e. five rows from 64 samples on; a 32-bit division below
+        unsigned long long s_new = s_c + (jb_new - ja);
+        if (S >= 64) {
+            while (s_new >= S) s_new -= S, ++row_c;
+        } else {
+            const unsigned int q = (unsigned int)s_new / (unsigned int)S;
+            row_c += q;
+            s_new -= (unsigned long long)q * S;
+        }
+        s_c = (unsigned int)s_new;
+        jb = jb_new;
+    }
+    __syncthreads();
+    emit_bytes(ring, bits, S, nb, row_c, s_c, done, kept);  // (jb = M: row_c = N, s_c = 0 -- every byte is out)
+
+    for (int i = tid; i < kMtN; i += 256) key_io[i] = key[cur][i];
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) kept += __shfl_xor(kept, off, 64);
+    if (lane == 0) wave_kept[wave] = kept;
+    __syncthreads();
+    if (tid == 0) {
+        result[0] = wave_kept[0] + wave_kept[1] + wave_kept[2] + wave_kept[3];
+        result[1] = last_word % kMtN + 1;
+    }
+}
+
+hipError_t launch_mask_draw(unsigned int* key_io, int pos, int64_t N, int64_t S, unsigned long long threshold,
+                            unsigned char* bits, unsigned long long* result, hipStream_t st) {
+    if (key_io == nullptr || bits == nullptr || result == nullptr || pos < 0 || pos > kMtN || N < 1 || S < 1 ||
+        S > kMaskDrawMaxS || N > kMaskDrawMaxElements / S)
+        return hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_mask_draw, dim3(1), dim3(256), 0, st, key_io, pos % kMtN, pos == kMtN ? 1 : 0,
+                       (unsigned long long)N, (unsigned long long)S, threshold, bits, result);
+    return hipGetLastError();
+}
+
+}  // namespace dmf

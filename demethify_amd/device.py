@@ -45,6 +45,20 @@ def pack_mask(mask) -> np.ndarray:
     return np.packbits(m.astype(bool, copy=False), axis=1, bitorder="little")
 
 
+def mask_threshold(fraction) -> int:
+    """``x < fraction`` for a double x = k / 2**53 of numpy's legacy generator (k an integer below 2**53) as the integer
+    compare ``k < T`` that dmf_mask_draw runs: T = 0 for fraction <= 0 or NaN, 2**53 for fraction >= 1, else
+    ceil(fraction * 2**53) -- the product is a scaling by a power of two, hence exact."""
+    import math
+
+    f = float(fraction)
+    if not f > 0.0:
+        return 0
+    if f >= 1.0:
+        return 1 << 53
+    return math.ceil(f * 9007199254740992.0)
+
+
 class Context:
     """dmf_context: a GPU, a HIP stream and the kernel-family clocks."""
 

@@ -6,7 +6,8 @@ expression that is not the textbook one.  The sweep over candidate n_u (ic.py:16
 dealt to the ranks longest-first and only the per-candidate scores and the winner's factors are
 exchanged.  CCC and BCV sweeps run on one rank from one resident upload; a bi-cross-validation fold
 (ic.py:58-89) is derived from it on the device (Problem.masked) and its hold-out error taken there
-(Solver.holdout_error), while the mask draws stay on the host, in the reference's order.
+(Solver.holdout_error); from DEVICE_MASK_MIN_ELEMENTS elements on the mask itself is drawn there too (staging.draw_mask: numpy's
+stream continued on the GPU, bit for bit), for the initialisers that do not read the masked data.
 """
 from __future__ import annotations
 
@@ -93,11 +94,37 @@ def run_deconvolution(meth_f, counts, ref, n_u, init_option, seed, iter1, iter2,
     return u, R, alpha
 
 
-def _bcv_draw_fold(meth_f, counts, ref, n_u, init_option, seed, fraction, stage=None):
+# The number of elements N x S from which a fold's mask is drawn on the device (staging.draw_mask) instead of on the host:
+# the smallest measured size from which the device leg is the faster one at every larger measured size.  Measured
+# (profiles/r13_mask_draw.txt: 350 x 10 to 1e6 x 256) it is the faster one at none -- 0.940 s against 0.881 s at 1e6 x 256 --
+# so the gate sits above them all and the host draws.
+DEVICE_MASK_MIN_ELEMENTS = 1 << 62
+
+
+def _bcv_draw_fold(meth_f, counts, ref, n_u, init_option, seed, fraction, stage=None, draw=None):
     """The host half of one bi-cross-validation fold, in the reference's draw order (ic.py:68-75): the train mask from
     numpy's global generator, then the initialiser -- which reseeds -- on the masked data.  Returns None for a fold the
     reference skips (empty train or test set: nothing further is drawn), else (train_mask, u0, alpha0, staged) with
-    ``staged = stage(train_mask)``: the device driver packs and uploads the mask here, on the drawing thread."""
+    ``staged = stage(train_mask)``: the device driver packs and uploads the mask here, on the drawing thread.
+
+    ``draw(shape, fraction) -> (packed bits, number of ones)``, when one is offered, makes the same mask from the same
+    generator and leaves the generator where ``rand`` would have: it is used from DEVICE_MASK_MIN_ELEMENTS elements on when
+    the initialiser does not read the data ("uniform_" and "beta", and whatever option the initialisers silently replace
+    by "uniform_" because n_u exceeds the samples); the fold is then (None, u0, alpha0, packed bits)."""
+    shapes_only = init_option in ("uniform_", "beta") or n_u > meth_f.shape[1]
+    if draw is not None and shapes_only and meth_f.size >= DEVICE_MASK_MIN_ELEMENTS:
+        bits, n_train = draw(meth_f.shape, fraction)
+        if n_train == meth_f.size or n_train == 0:
+            if hasattr(bits, "close"):
+                bits.close()
+            return None
+        try:
+            u0, a0 = _init_on(None, meth_f, counts, ref, n_u, init_option, seed)
+        except BaseException:
+            if hasattr(bits, "close"):
+                bits.close()
+            raise
+        return None, u0, a0, bits
     train_mask = np.random.rand(*meth_f.shape) < fraction
     n_train = int(np.sum(train_mask))
     if n_train == train_mask.size or n_train == 0:
@@ -128,6 +155,11 @@ class _DeviceFolds:
 
         return mask_to_device(pack_mask(train_mask), self.problem.ctx)
 
+    def draw(self, shape, fraction):
+        from .staging import draw_mask
+
+        return draw_mask(shape, fraction, self.problem.ctx)
+
     def __call__(self, fold, best):
         _, u0, a0, bits = fold
         try:
@@ -151,8 +183,10 @@ def bicross_validation(meth_f, n_u, counts, iter1, iter2, tol, n_folds=10, seed=
     The data are uploaded once (``problem``: a resident upload of (meth_f, counts, ref) to reuse; created here when
     none is given); each fold derives its masked problem on the device and takes its error there.  The draws stay on the
     host and in the reference's order -- seed once, then per fold the mask and the (reseeding) initialiser -- on ONE worker
-    thread (numpy's global generator), one fold ahead of the GPU.  ``_fold_solver(fold, best) -> (test_error, (u, alpha)
-    or None)`` replaces the device half (tests drive the draw order through it without a GPU)."""
+    thread (numpy's global generator), one fold ahead of the GPU; above the gate of _bcv_draw_fold that thread has the
+    device continue the generator's stream for the mask (``solve.draw``) and takes the generator up behind it.
+    ``_fold_solver(fold, best) -> (test_error, (u, alpha) or None)`` replaces the device half (tests drive the draw order
+    through it without a GPU); its ``stage`` and ``draw`` attributes, where it has them, are picked up like _DeviceFolds'."""
     np.random.seed(seed)
     total_press, best_u, best_alpha, min_error = 0, None, None, float("inf")
     own = problem is None and _fold_solver is None
@@ -161,10 +195,10 @@ def bicross_validation(meth_f, n_u, counts, iter1, iter2, tol, n_folds=10, seed=
     feed = None
     try:
         solve = _fold_solver if _fold_solver is not None else _DeviceFolds(problem, ref is None, iter1, iter2, tol)
-        stage = getattr(solve, "stage", None)
+        stage, draw_mask = getattr(solve, "stage", None), getattr(solve, "draw", None)
 
         def draw(_):
-            return _bcv_draw_fold(meth_f, counts, ref, n_u, init_option, seed, fraction, stage)
+            return _bcv_draw_fold(meth_f, counts, ref, n_u, init_option, seed, fraction, stage, draw_mask)
 
         feed = Prefetcher(range(n_folds), draw, depth=1, workers=1)
         for _, fold in feed:

@@ -92,6 +92,18 @@ class DeviceArray:
         view.in_unit_range = self.in_unit_range
         return view
 
+    def to_host(self, dtype=np.float64):
+        """A host copy of the array's bytes as ``dtype`` (dmf_stage_download): the bits of a packed mask with uint8."""
+        import ctypes as C
+
+        from . import _lib as L
+
+        out = np.empty(self.shape, dtype=dtype)
+        if out.nbytes:
+            L.check(self.ctx._lib.dmf_stage_download(self.ctx._h, C.c_void_p(self._ptr), out.nbytes,
+                                                     out.ctypes.data_as(C.c_void_p)), "dmf_stage_download")
+        return out
+
     def close(self):
         if self._fin is not None:
             self._fin()
@@ -166,6 +178,29 @@ def mask_to_device(bits, ctx):
     out = DeviceArray(ctx, dev.value, bits.shape)
     out.packed_mask = tuple(bits.shape)
     return out
+
+
+def draw_mask(shape, fraction, ctx):
+    """``pack_mask(np.random.rand(*shape) < fraction)`` of numpy's global generator, drawn on the context's GPU
+    (dmf_mask_draw) and left there: the generator's key and position go to the device, the stream is continued by the
+    kernel, and the advanced key and position are put back -- the Gaussian cache fields as they were -- so that whatever
+    draws next sees the stream exactly where the host draw would have left it.  Returns (DeviceArray carrying
+    ``packed_mask``, number of ones).  Meant for the ONE thread that owns the global generator (see ic.bicross_validation)."""
+    import ctypes as C
+
+    from . import _lib as L
+    from .device import mask_threshold
+
+    n, s = (int(x) for x in shape)
+    name, key, pos, has_gauss, cached = np.random.get_state()
+    key = np.ascontiguousarray(key, dtype=np.uint32).copy()
+    pos_io, dev, kept = C.c_int(int(pos)), C.c_void_p(), C.c_int64()
+    L.check(ctx._lib.dmf_mask_draw(ctx._h, key.ctypes.data_as(C.c_void_p), C.byref(pos_io), n, s,
+                                   mask_threshold(fraction), C.byref(dev), C.byref(kept)), "dmf_mask_draw")
+    out = DeviceArray(ctx, dev.value, (n, (s + 7) // 8))
+    out.packed_mask = out.shape
+    np.random.set_state((name, key, pos_io.value, has_gauss, cached))
+    return out, kept.value
 
 
 def reserve(shapes, count: int = 1):

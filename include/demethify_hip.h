@@ -307,6 +307,26 @@ int dmf_write_interval_csv(const char* path, const char* header_line, const doub
  * the context's stream). */
 int dmf_stage_upload(dmf_context* ctx, const void* host, size_t bytes, void** out_dev);
 int dmf_stage_free(dmf_context* ctx, void* dev);
+/* The way back, for a buffer the staging calls made (dmf_stage_upload, dmf_mask_draw): `bytes` bytes from `dev` to the host
+ * array, on the copy stream, under dmf_stage_upload's threading contract; returns when the copy is complete. */
+int dmf_stage_download(dmf_context* ctx, const void* dev, size_t bytes, void* host);
+
+/* ---- hold-out mask draw.  A bi-cross-validation fold's train mask is `np.random.rand(*meth_f.shape) < fraction` of numpy's
+ * legacy global generator (ic.py:68): MT19937, whose doubles are integer arithmetic on pairs of its words.  dmf_mask_draw
+ * continues that stream on the device and writes the mask straight into the packed form dmf_problem_mask reads, the same
+ * bit for bit as the host draw from the same state.  key / *pos: the generator's 624 words and position (0..624; 624 =
+ * regenerate first, the state right after seed()), i.e. np.random.get_state()[1:3]; both are updated in place to the state
+ * after rand(N, S) -- the key as of the last regeneration, the position behind the last word used -- for set_state.
+ * threshold: x < fraction as an integer compare on x 2^53: 0 for fraction <= 0 or NaN, 2^53 for fraction >= 1, else
+ * ceil(fraction 2^53) (the product is exact).  *out_bits: a new device buffer of N ceil(S / 8) bytes, every byte written,
+ * padding bits zero -- what dmf_problem_mask takes with DMF_PTR_DEVICE -- released with dmf_stage_free; *n_kept: the number of
+ * ones.  One persistent workgroup walks the stream (the recurrence allows no more without a jump-ahead).
+ * Threading as dmf_stage_upload: it runs on the context's copy stream, may be called from a worker thread while the
+ * context's stream iterates, and returns when the mask and the three results are complete.  DMF_ERR_BAD_ARG: a position
+ * outside [0, 624], N or S below 1, a threshold above 2^53, a null pointer; DMF_ERR_UNSUPPORTED: S >= 2^31 or more than 2^60
+ * elements.  After an error nothing stays allocated and key / *pos are untouched. */
+int dmf_mask_draw(dmf_context* ctx, uint32_t key[624], int* pos, int64_t N, int64_t S,
+                  uint64_t threshold, void** out_bits, int64_t* n_kept);
 
 #ifdef __cplusplus
 }
