@@ -19,6 +19,7 @@ DMF_COUNTS_F64 = 2
 DMF_WLS_TARGET_V, DMF_WLS_TARGET_DV = 0, 1
 DMF_WLS_F64_ARRAYS = 8
 DMF_ERR_BAD_ARG, DMF_ERR_NONFINITE, DMF_ERR_UNSUPPORTED = 1, 4, 5
+DMF_ERR_BAD_SHAPE = 2
 DMF_MODE_PARTIAL = 0
 DMF_MODE_UNSUPERVISED = 1
 MAX_K = 64  # dmf::kMaxK: largest n_c + n_u the kernels are built for (DMF_ERR_UNSUPPORTED beyond)
@@ -72,6 +73,8 @@ SIGNATURES = {
     "dmf_solver_set_purity": (C.c_int, [_p, _p, C.c_int]),
     "dmf_solver_step": (C.c_int, [_p, _i64, _i64, C.c_double, C.POINTER(_i64), C.POINTER(C.c_int)]),
     "dmf_solver_get": (C.c_int, [_p, C.c_int, _p, _p, _dbl_p, C.POINTER(_i64)]),
+    "dmf_solver_match_components": (C.c_int, [_p, _p, _i64, _p, _p]),
+    "dmf_solver_get_u_permuted": (C.c_int, [_p, C.POINTER(C.c_int32), _p]),
     "dmf_solver_cost": (C.c_int, [_p, _dbl_p]),
     "dmf_solver_cost_begin": (C.c_int, [_p]),
     "dmf_solver_cost_end": (C.c_int, [_p, _dbl_p]),

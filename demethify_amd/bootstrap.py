@@ -17,11 +17,12 @@ import pandas as pd
 
 from . import _lib as L
 from . import init_func, shard
-from .deconvolution import _init_guard, init_BSSMF_md, init_BSSMF_md_p, solve_problem, svd_factors
+from .deconvolution import (_ICA_REFUSAL, _OUT_OF_SCOPE_INITS, _init_guard, _init_unsupervised, init_BSSMF_md,
+                            init_BSSMF_md_p, solve_problem, svd_factors)
 from .device import Problem, Solver, get_context
 from .init_func import wls_intercept
 
-__all__ = ["bt_ci", "bootstrap_seed_sequence", "bootstrap_row_indices"]
+__all__ = ["bt_ci", "bootstrap_seed_sequence", "bootstrap_row_indices", "match_components"]
 
 
 def bootstrap_seed_sequence(seed, n_bootstrap):
@@ -39,6 +40,23 @@ def bootstrap_row_indices(seed, n_rows):
     return np.random.RandomState(seed).randint(0, n_rows, size=(n_rows,))
 
 
+def match_components(P):
+    """The assignment of a replicate's unknown components to the anchor's: ``perm[a]`` is the anchor component that
+    replicate component ``a`` is named after, the permutation that maximises ``sum_a P[a, perm[a]]`` for
+    ``P = u_rep.T @ u_anchor[idx]`` (Solver.match_components).  With the column norms fixed this is the assignment of
+    least total squared distance between the profiles.  Aligned profiles are ``u[:, argsort(perm)]``, aligned
+    proportions permute the last n_u rows of alpha the same way."""
+    from scipy.optimize import linear_sum_assignment
+
+    P = np.asarray(P, dtype=np.float64)
+    if P.ndim != 2 or P.shape[0] != P.shape[1]:
+        raise ValueError(f"P must be square, got shape {P.shape}")
+    rows, cols = linear_sum_assignment(P, maximize=True)
+    perm = np.empty(P.shape[0], dtype=np.int64)
+    perm[rows] = cols
+    return perm
+
+
 def _device_stack(n_local, width):
     """(n_local, width) float64 buffer on this process's GPU for the replicate profiles (B x N x n_u doubles: 16 GB at
     500 x 1e6 x 4, held in HBM instead of travelling to the host and back for the percentiles), or None when PyTorch
@@ -53,11 +71,37 @@ def _device_stack(n_local, width):
 
 
 def bt_ci(confidence_level, n_bootstrap, n_u, meth_f, counts, ref, init_option, n_iter1, n_iter2, tol, header,
-          outdir, samples, purity, seed, materialize=True, _observe=None):
+          outdir, samples, purity, seed, materialize=True, _observe=None, anchor=None, align_unknown=None):
     """bootstrap.py:10-93 -> [proportions CI DataFrame, (profile CI DataFrame)]; writes the two CSVs.
     materialize=False (the CLI, which ignores the return value) skips building the N-row DataFrame of tuples for the
     profile intervals: the CSV is written by the library and the second result is the (lower, upper) array pair.
-    _observe(i, seed_i, row_indices, solver) is called after replicate i's solve (tests look at the replicate through it)."""
+    _observe(i, seed_i, row_indices, solver) is called after replicate i's solve (tests look at the replicate through it;
+    ``solver.component_perm`` is the replicate's assignment, None where it was not aligned).
+
+    ``ref=None`` (no reference panel; upstream's bt_ci fails at ``ref.shape`` there): every replicate is an unsupervised
+    solve of the resampled data from ``_init_unsupervised(init_option, ..., seeds[i])``, ``header`` is [] and the rows of
+    the proportions table are the unknown_cell_i.  ``purity`` has no meaning without a reference (ValueError).
+
+    ``align_unknown``: name the unknown components of every replicate after those of one solve, the anchor, before the
+    percentiles are taken: P = u_rep.T @ u_anchor[idx] on the device, ``match_components(P)``, and
+    the replicate's profile columns / proportion rows are stored in the anchor's order.  None = True without a reference
+    and False with one (upstream's unaligned percentiles, every existing call as before); skipped for n_u == 1.
+    ``anchor`` = (u, alpha) of the solve the components are named after (the CLI passes its point estimate); absent, it is
+    solved here on every rank from the unresampled data, ``seed`` and the same initialiser."""
+    if ref is None:
+        if n_u < 1:
+            raise ValueError("a bootstrap without a reference needs at least one unknown cell type")
+        if purity:
+            raise ValueError("--purity without a reference has no meaning: there is no known block to hold at that mass")
+        # deconvolution.py:108-117, before any device work
+        option = "uniform_" if (init_option != "uniform_" and n_u > meth_f.shape[1]) else init_option
+        if option == "uniform":
+            raise NameError("name 'R_trunc' is not defined")  # upstream's undefined name (deconvolution.py:117), kept
+        if option in _OUT_OF_SCOPE_INITS:
+            raise NotImplementedError(_ICA_REFUSAL)
+    if align_unknown is None:
+        align_unknown = ref is None
+    align = bool(align_unknown) and n_u >= 2
     purity_frac = None
     if purity:
         # upstream quirk kept: bt_ci takes the raw percentages and uses p / 100 (bootstrap.py:18) while main()
@@ -68,7 +112,8 @@ def bt_ci(confidence_level, n_bootstrap, n_u, meth_f, counts, ref, init_option, 
     lower_percentile = 100 * (a / 2)
     upper_percentile = 100 * (1 - (a / 2))
     n_rows, n_samples = meth_f.shape
-    n_ct = ref.shape[1]
+    n_ct = 0 if ref is None else ref.shape[1]
+    mode = L.DMF_MODE_UNSUPERVISED if ref is None else L.DMF_MODE_PARTIAL
 
     rank, world, _ = shard.dist_state()
     seeds = bootstrap_seed_sequence(seed, n_bootstrap)
@@ -112,9 +157,11 @@ def bt_ci(confidence_level, n_bootstrap, n_u, meth_f, counts, ref, init_option, 
         needs_data = init_option in ("uniform", "SVD") and not svd_on_device
 
         def svd_init(resampled, idx):
-            u0, H = svd_factors(lambda: (meth_f[idx], counts[idx], ref[idx]), None, None, n_u, problem=resampled,
-                                keep_on_device=True)
-            if purity_frac is not None:  # deconvolution.py:262, as coded
+            u0, H = svd_factors(lambda: (meth_f[idx], counts[idx], None if ref is None else ref[idx]), None, None, n_u,
+                                problem=resampled, keep_on_device=True)
+            if ref is None:  # deconvolution.py:135-137: no guard on the unsupervised path
+                a0 = init_func.project_simplex_columns(H)
+            elif purity_frac is not None:  # deconvolution.py:262, as coded
                 a0 = np.vstack((purity_frac * init_func.project_simplex_columns(H[:-n_u]),
                                 init_func.project_simplex_columns(H[-n_u:])))
             else:
@@ -123,6 +170,8 @@ def bt_ci(confidence_level, n_bootstrap, n_u, meth_f, counts, ref, init_option, 
 
         def draw_init(i, idx=None):
             mf = meth_f[idx] if needs_data else np.broadcast_to(meth_f[:1], meth_f.shape)
+            if ref is None:  # (below the device gate "SVD" takes the host route on the resampled rows)
+                return to_device(_init_unsupervised(init_option, mf, n_u, seeds[i]), ctx)
             ct = counts[idx] if needs_data else np.broadcast_to(counts[:1], counts.shape)
             rf = ref[idx] if needs_data else np.broadcast_to(ref[:1], ref.shape)
             if purity_frac is not None:
@@ -140,15 +189,39 @@ def bt_ci(confidence_level, n_bootstrap, n_u, meth_f, counts, ref, init_option, 
             idx, idx_dev = draw_rows(i)
             return (idx, idx_dev) + tuple(draw_init(i, idx))
 
-        if needs_data:
-            feeds = (Prefetcher(mine, draw_both, depth=2, workers=1),)
-        elif svd_on_device:
-            feeds = (Prefetcher(mine, draw_rows, depth=2, workers=1),)
-        else:
-            feeds = (Prefetcher(mine, draw_rows, depth=2, workers=1), Prefetcher(mine, draw_init, depth=2, workers=1))
+        def start_feeds():
+            if needs_data:
+                return (Prefetcher(mine, draw_both, depth=2, workers=1),)
+            if svd_on_device:
+                return (Prefetcher(mine, draw_rows, depth=2, workers=1),)
+            return (Prefetcher(mine, draw_rows, depth=2, workers=1), Prefetcher(mine, draw_init, depth=2, workers=1))
+
+        def solve_anchor(full):
+            # the solve the components are named after: the unresampled data, `seed`, the replicates' initialiser
+            if ref is None:
+                u0, a0 = _init_unsupervised(init_option, meth_f, n_u, seed, problem=full)
+            elif purity_frac is not None:
+                u0, _, a0 = init_BSSMF_md_p(init_option, meth_f, counts, ref, n_u, purity_frac, seed=seed, rb_alg=wls_intercept,
+                                            _stack=False, problem=full)
+            else:
+                u0, _, a0 = init_BSSMF_md(init_option, meth_f, counts, ref, n_u, rb_alg=wls_intercept, seed=seed, _stack=False,
+                                          problem=full)
+            return solve_problem(full, u0, a0, mode, n_iter1, n_iter2, tol, purity=purity_frac)
+
+        # (an anchor solved here draws from numpy's global generator: the worker threads start after it)
+        feeds = start_feeds() if not (align and anchor is None) else ()
         u_stack = _device_stack(len(mine), n_rows * n_u)  # replicate profiles stay in HBM when torch is there
+        anchor_dev = None
         try:
             with Problem(ctx, meth_f, counts, ref) as full:
+                if align:
+                    if anchor is None:
+                        anchor = solve_anchor(full)
+                        feeds = start_feeds()
+                    anchor_u = np.ascontiguousarray(anchor[0], dtype=np.float64).reshape(n_rows, -1)
+                    if anchor_u.shape[1] != n_u:
+                        raise ValueError(f"anchor profiles have shape {np.shape(anchor[0])}, expected {(n_rows, n_u)}")
+                    anchor_dev, = to_device((anchor_u,), ctx)  # resident for every replicate's comparison
                 for j, parts in enumerate(zip(*feeds)):
                     if needs_data:
                         (i, (idx, idx_dev, u0, a0)), = parts
@@ -159,19 +232,26 @@ def bt_ci(confidence_level, n_bootstrap, n_u, meth_f, counts, ref, init_option, 
                         (i, (idx, idx_dev)), (i2, (u0, a0)) = parts
                         assert i == i2
                     with full.gather(idx_dev) as resampled, \
-                            Solver(resampled, *(svd_init(resampled, idx) if svd_on_device else (u0, a0)),
-                                   L.DMF_MODE_PARTIAL) as s:
+                            Solver(resampled, *(svd_init(resampled, idx) if svd_on_device else (u0, a0)), mode) as s:
                         if purity_frac is not None:
                             s.set_purity(purity_frac)
                         s.step(n_iter1, n_iter2, tol)
+                        # which anchor component each of the replicate's is: n_u x n_u inner products taken where the
+                        # profiles live, the assignment on the host; `order` renames columns / rows on the way out
+                        s.component_perm = match_components(s.match_components(anchor_dev, idx_dev)) if align else None
+                        order = np.argsort(s.component_perm) if align else None
                         if _observe is not None:
                             _observe(i, seeds[i], idx, s)
                         if u_stack is not None:
-                            s.copy_u_to(u_stack[j])
-                            local.append((i, (None, s.get_alpha())))
+                            s.copy_u_to(u_stack[j], columns=order)
+                            u, alpha = None, s.get_alpha()
                         else:
                             u, alpha, _, _ = s.get()
-                            local.append((i, (u, alpha)))
+                            if align:
+                                u = np.ascontiguousarray(u[:, order])
+                        if align:
+                            alpha[n_ct:] = alpha[n_ct:][order]
+                        local.append((i, (u, alpha)))
         finally:
             for f in feeds:
                 f.close()

@@ -350,4 +350,19 @@ hipError_t launch_svd_project(const ProblemView& p, const double* H1, const doub
                               double* norms, hipStream_t st);
 hipError_t launch_svd_finish(double* T, int64_t N, int rank, const SvdColumns& cols, hipStream_t st);
 
+// Component matching (dmf_kernels_match.hip).  launch_match_gram: P[n_u][n_u] (device) = sum_j u[j][a] anchor[idx[j]][b] over
+// the N rows of u, anchor n_anchor_rows x n_u, idx N int64 row indices or null (the identity); slab holds
+// match_gram_slab_doubles(N, n_u) doubles, flags match_gram_grid(N, n_u) ints (per workgroup: indices outside
+// [0, n_anchor_rows), which are not dereferenced -- P is then to be discarded).  P depends on the data and (N, n_u) alone.
+// launch_copy_cols_permuted: dst[i][b] = u[i][cols.src[b]] (dst != u).  1 <= n_u <= kMaxK.
+struct MatchColumns {
+    int src[kMaxK];
+};
+int match_gram_grid(int64_t N, int n_u);
+int64_t match_gram_slab_doubles(int64_t N, int n_u);
+hipError_t launch_match_gram(const double* u, const double* anchor, const long long* idx, int64_t N, int64_t n_anchor_rows,
+                             int n_u, double* slab, int* flags, double* P, hipStream_t st);
+hipError_t launch_copy_cols_permuted(const double* u, double* dst, int64_t N, int n_u, const MatchColumns& cols,
+                                     hipStream_t st);
+
 }  // namespace dmf

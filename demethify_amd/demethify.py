@@ -10,6 +10,9 @@ Deliberate differences from upstream, all flagged at run time:
   * ``--restart r``: upstream re-runs the SAME seed r times; here restart k > 0 uses seed + k
     (restart 0 is bit-compatible), SURVEY.md section 8b.
   * ``--plot`` is ignored with a note and ``--init SVD|ICA`` exits with a message (outside this build's scope).
+  * ``--confidence`` without ``--ref`` (upstream's bootstrap fails at ``ref.shape``): needs ``--nbunknown >= 1``; the point
+    estimate runs first and every replicate's unknown types are matched to its profiles before the percentiles are taken
+    (DESIGN.md section 6).  With ``--ref`` the intervals are upstream's, unaligned.
   * ``--ic NAME [n [lo hi]]``: upstream sweeps the hard-coded range 1..25 (ic.py:171); two more values after the
     restart count restrict the sweep to lo..hi unknown types (``--ic BIC 5 2 12``).  Without them: 1..25, as upstream.
 """
@@ -172,10 +175,15 @@ def main(argv=None):
     n_u = args.nbunknown[0]
     ic_n_u = None
 
-    if args.confidence:
+    def bootstrap(anchor=None):
         bt_ci(args.confidence[0], args.confidence[1], n_u, meth_f, counts, ref, args.init, args.iterations[0],
-              args.iterations[1], args.termination, header, outdir, args.methfreq, args.purity, args.seed,
-              materialize=False)
+              args.iterations[1], args.termination, header if args.ref else [], outdir, args.methfreq, args.purity,
+              args.seed, materialize=False, anchor=anchor)
+
+    if args.confidence and args.ref:
+        bootstrap()
+    elif args.confidence and n_u < 1:
+        sys.exit(f'Invalid number of unknown value! : "{args.nbunknown}" ')
 
     if args.ic:
         ref_estimate, proportions, ic_n_u, _scores = evaluate_best_ic(
@@ -262,6 +270,11 @@ def main(argv=None):
                  for k in range(meth_f.shape[1])], axis=1)
     else:
         sys.exit(f'Invalid number of unknown value! : "{args.nbunknown}" ')
+
+    if args.confidence and not args.ref:
+        # no reference: the point estimate ran first and names the components -- the replicates' unknown types are matched
+        # to ITS profiles, so the intervals speak about the rows celltypes_proportions.csv reports (and no solve runs twice)
+        bootstrap(anchor=(ref_estimate, proportions))
 
     time_tot = time() - time_start
 

@@ -632,12 +632,62 @@ class Solver:
         L.check(self._lib.dmf_solver_get(self._h, 0, None, _ptr(alpha), None, None), "dmf_solver_get")
         return alpha
 
-    def copy_u_to(self, tensor):
+    def match_components(self, anchor, idx=None):
+        """P (n_u x n_u host array), P[a, b] = sum_j u[j, a] * anchor[idx[j], b]: the inner products of this solver's profile
+        columns with the anchor's, computed where both live (dmf_solver_match_components).  ``anchor``: the n_rows x n_u
+        profiles the components are named after, a staging.DeviceArray or a contiguous float64 CUDA tensor on the context's
+        GPU; ``idx``: the int64 row indices this solver's problem was gathered with, as staging.indices_to_device returns
+        them (or an int64 CUDA tensor); None = the identity (the anchor then has this problem's N rows).  An index outside
+        the anchor's rows raises (DMF_ERR_BAD_ARG).  ``bootstrap.match_components(P)`` turns P into the assignment."""
+        from .staging import DeviceArray
+
+        ctx = self.problem.ctx
+
+        def on_device(t, floating):
+            if isinstance(t, DeviceArray):
+                return t.ctx is ctx
+            ok = (_is_torch(t) and t.is_cuda and t.is_contiguous() and t.element_size() == 8
+                  and t.is_floating_point() == floating and t.device.index == ctx.device)
+            if ok and not floating:
+                import torch
+
+                ok = t.dtype == torch.int64
+            if ok:
+                import torch
+
+                torch.cuda.current_stream(t.device).synchronize()  # (produced on torch's stream, read on ours)
+            return ok
+
+        if not on_device(anchor, True):
+            raise ValueError("anchor must be a float64 staging.DeviceArray / contiguous CUDA tensor on the context's GPU")
+        n_el = int(np.prod(tuple(anchor.shape)))
+        if n_el == 0 or n_el % self.n_u:
+            raise ValueError(f"anchor shape {tuple(anchor.shape)} does not hold rows of {self.n_u} profiles")
+        n_rows = n_el // self.n_u
+        if idx is not None:
+            if not on_device(idx, False):
+                raise ValueError("idx must be the int64 row indices in HBM (staging.indices_to_device) on the context's GPU")
+            if int(np.prod(tuple(idx.shape))) != self.problem.N:
+                raise ValueError(f"idx holds {int(np.prod(tuple(idx.shape)))} indices, the problem has {self.problem.N} rows")
+        P = np.empty((self.n_u, self.n_u), dtype=np.float64)
+        L.check(self._lib.dmf_solver_match_components(self._h, _ptr(anchor), n_rows, _ptr(idx), _ptr(P)),
+                "dmf_solver_match_components")
+        return P
+
+    def copy_u_to(self, tensor, columns=None):
         """Copy the current profile estimate u (N x n_u, C order) into a float64 CUDA torch tensor of N * n_u elements
-        on the context's GPU (device to device): the bootstrap keeps its replicate stack in HBM."""
+        on the context's GPU (device to device): the bootstrap keeps its replicate stack in HBM.  ``columns``: a permutation
+        of 0 .. n_u - 1; the tensor then receives ``u[:, columns]`` (dmf_solver_get_u_permuted)."""
         if not (_is_torch(tensor) and tensor.is_cuda and tensor.is_contiguous() and tensor.numel() == self.problem.N * self.n_u
                 and tensor.element_size() == 8 and tensor.device.index == self.problem.ctx.device):
             raise ValueError("copy_u_to needs a contiguous float64 CUDA tensor of N * n_u elements on the context's GPU")
+        if columns is not None:
+            cols = np.ascontiguousarray(columns, dtype=np.int32).ravel()
+            if cols.size != self.n_u or not np.array_equal(np.sort(cols), np.arange(self.n_u)):
+                raise ValueError(f"columns must be a permutation of 0..{self.n_u - 1}, got {list(np.ravel(columns))}")
+            L.check(self._lib.dmf_solver_get_u_permuted(self._h, cols.ctypes.data_as(C.POINTER(C.c_int32)), _ptr(tensor)),
+                    "dmf_solver_get_u_permuted")
+            return
         L.check(self._lib.dmf_solver_get(self._h, L.DMF_PTR_DEVICE, _ptr(tensor), None, None, None), "dmf_solver_get")
 
     def get_cost(self):

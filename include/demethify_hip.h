@@ -231,6 +231,22 @@ int dmf_solver_step(dmf_solver* s, int64_t n_outer, int64_t n_iter2, double tol,
                     int64_t* iters_done_total, int* converged);
 int dmf_solver_get(dmf_solver* s, int flags, double* out_u, double* out_alpha,
                    double* out_cost, int64_t* out_iters);
+/* Component matching, for the bootstrap (bootstrap.py:26-46 runs every replicate from a random draw of its own, so the
+ * unknown types of two replicates come out in arbitrary order; upstream takes its percentiles over them as they come).
+ * dmf_solver_match_components: out_P (n_u x n_u host doubles) <- P[a][b] = sum_j u[j][a] anchor[idx[j]][b] over the N rows
+ * of the solver's current u, where anchor_dev is a device array of n_anchor_rows x n_u doubles (the profiles the components
+ * are named after) and idx_dev the N int64 row indices in HBM that dmf_problem_gather_device was given for this solver's
+ * problem; idx_dev NULL = the identity, which needs n_anchor_rows = N (DMF_ERR_BAD_SHAPE otherwise).  One pass over u and the
+ * gathered anchor rows, plain FP64, every sum in an order fixed by (N, n_u): two calls give the same bits.  An index outside
+ * [0, n_anchor_rows) is never dereferenced: the call returns DMF_ERR_BAD_ARG and leaves out_P untouched.  The assignment
+ * that maximises sum_a P[a][perm[a]] stays with the caller.
+ * dmf_solver_get_u_permuted: dst_dev (N x n_u device doubles, not the solver's own u) <- u[:, src_col], i.e.
+ * dst[i][b] = u[i][src_col[b]]; src_col: n_u host ints, a permutation of 0 .. n_u - 1 (DMF_ERR_BAD_ARG otherwise).  Complete
+ * when the call returns, like dmf_solver_get with DMF_PTR_DEVICE.
+ * With profiling on, the launches of both are clocked under DMF_KERNEL_GRAM. */
+int dmf_solver_match_components(dmf_solver* s, const void* anchor_dev, int64_t n_anchor_rows, const int64_t* idx_dev,
+                                double* out_P);
+int dmf_solver_get_u_permuted(dmf_solver* s, const int32_t* src_col, void* dst_dev);
 /* cost_f_w(meth_f, [Rt | u], alpha, counts) of the solver's CURRENT iterate by the streaming formula
  * (deconvolution.py:15-17), without moving u / alpha to the host: what the restart and model-selection loops
  * recompute after every solve (demethify.py:169,199; ic.py:206).  out_cost: host double. */
