@@ -61,6 +61,8 @@ SIGNATURES = {
     "dmf_problem_destroy": (C.c_int, [_p]),
     "dmf_problem_shape": (C.c_int, [_p, C.POINTER(_i64), C.POINTER(_i64), C.POINTER(_i64)]),
     "dmf_cost": (C.c_int, [_p, _p, _p, _i64, _p, C.c_int, _dbl_p]),
+    "dmf_cost_describe": (C.c_int, [_i64, _i64, _i64, C.c_int, _i64, C.c_int, C.c_int, C.c_int, C.c_char_p, _i64]),
+    "dmf_problem_cost_describe": (C.c_int, [_p, _p, _i64, C.c_char_p, _i64]),
     "dmf_project_simplex": (C.c_int, [_p, _p, _i64, _i64, C.c_double, C.c_int, _p]),
     "dmf_update_u": (C.c_int, [_p, _p, _p, _p, _p, _i64, _i64, C.c_int, C.c_int, _dbl_p, _p, _p]),
     "dmf_update_alpha": (C.c_int, [_p, _p, _p, _i64, _p, _p, _i64, C.c_int, _dbl_p, _p, _p]),

@@ -72,6 +72,24 @@ int dmf_select_describe(int64_t N, int64_t S, int64_t n_c, int64_t n_u, int nd, 
     return DMF_OK;
 }
 
+int dmf_cost_describe(int64_t S, int64_t n_c, int64_t n_u, int has_u16, int64_t SD, int v_align, int rtp_present, int level,
+                      char* buf, int64_t cap) {
+    if (buf == nullptr || cap < 1 || S < 1 || S > (1 << 24) || n_c < 0 || n_u < 0 || n_c + n_u < 1 || n_c + n_u > dmf::kMaxK ||
+        SD < 0 || SD > (1 << 24) || (has_u16 && SD < S) || v_align < 0 || v_align > 15 || level < 0 || level > 4)
+        return DMF_ERR_BAD_ARG;
+    dmf::CostKey key;
+    key.S = (int)S;
+    key.n_c = (int)n_c;
+    key.n_u = (int)n_u;
+    key.d16 = has_u16 != 0;
+    key.SD = (int)SD;
+    key.v_align = (unsigned)v_align;
+    key.rtp_present = rtp_present != 0;
+    key.level = level;
+    dmf::describe_cost_plan(dmf::cost_plan(key), buf, (size_t)cap);
+    return DMF_OK;
+}
+
 int dmf_cost(dmf_context* ctx, const dmf_problem* p, const double* u, int64_t n_u, const double* alpha,
              int flags, double* out_cost) {
     DMF_TRY(check_ctx(ctx));

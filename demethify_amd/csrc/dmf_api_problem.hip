@@ -152,32 +152,18 @@ static int problem_finalize(dmf_problem* p, bool counts_done = false) {
     return DMF_OK;
 }
 
-enum class CostKind { Cols, Cols2Wide, Generic };
-
-// which kernel computes cost_f_w on this problem's data: the column-resident ones when the shape allows, else the generic
-static CostKind cost_kind(dmf_context* ctx, const dmf::ProblemView& p, int n_u) {
-    const bool rtp_ok = p.n_c == 0 || p.Rtp != nullptr;
-    if ((ctx->generic_level == 0 || ctx->generic_level == 3 || ctx->generic_level == 4) && rtp_ok &&
-        dmf::cost_cols_supported(p.S, p.n_c, n_u))
-        return CostKind::Cols;
-    if (ctx->generic_level == 0 && rtp_ok && dmf::cost_cols2_wide_supported(p, n_u)) return CostKind::Cols2Wide;
-    return CostKind::Generic;
+// which kernel computes cost_f_w on this problem's data: the plan (dmf_kernels_stream.hip) of its key at the context's level
+static dmf::CostPlan cost_plan_of(dmf_context* ctx, const dmf::ProblemView& p, int n_u) {
+    return dmf::cost_plan(dmf::cost_key(p, n_u, ctx->generic_level));
 }
 
 hipError_t enqueue_cost(dmf_context* ctx, const dmf::ProblemView& p, const double* u, const double* alpha, int n_u,
                         double* scratch, double* out) {
-    switch (cost_kind(ctx, p, n_u)) {
-        case CostKind::Cols: return dmf::launch_cost_cols(p, u, alpha, n_u, scratch, out, ctx->stream);
-        case CostKind::Cols2Wide: return dmf::launch_cost_cols2_wide(p, u, alpha, n_u, scratch, out, ctx->stream);
-        default: return dmf::launch_cost(p, u, alpha, n_u, scratch, out, ctx->stream);
-    }
+    return dmf::launch_cost_plan(cost_plan_of(ctx, p, n_u), p, u, alpha, n_u, scratch, out, ctx->stream);
 }
 
 // Does enqueue_cost read the counts of this problem from D16 alone (never from the f64 D)?
-// (k_cost_cols / k_cost_cols2 take D16 wherever there is one)
-bool cost_reads_u16_only(dmf_context* ctx, const dmf::ProblemView& p, int n_u) {
-    return p.D16 != nullptr && cost_kind(ctx, p, n_u) != CostKind::Generic;
-}
+bool cost_reads_u16_only(dmf_context* ctx, const dmf::ProblemView& p, int n_u) { return cost_plan_of(ctx, p, n_u).d16; }
 
 // The streaming cost (deconvolution.py:15-17) of (u, alpha) on the problem's data into a host slot; without `wait` the
 // copy is only enqueued (a page-locked slot, and the caller's event behind it).
@@ -368,6 +354,13 @@ int dmf_problem_destroy(dmf_problem* p) {
     if (p == nullptr) return DMF_OK;
     hipSetDevice(p->ctx->device);
     delete p;
+    return DMF_OK;
+}
+
+int dmf_problem_cost_describe(dmf_context* ctx, const dmf_problem* p, int64_t n_u, char* buf, int64_t cap) {
+    if (ctx == nullptr || p == nullptr || buf == nullptr || cap < 1 || n_u < 0 || p->ctx != ctx) return DMF_ERR_BAD_ARG;
+    if (p->n_c + n_u < 1 || p->n_c + n_u > dmf::kMaxK) return DMF_ERR_BAD_ARG;
+    dmf::describe_cost_plan(cost_plan_of(ctx, p->view(), (int)n_u), buf, (size_t)cap);
     return DMF_OK;
 }
 

@@ -155,20 +155,24 @@ hipError_t launch_index_range_check(const long long* idx, int64_t n_idx, int64_t
 hipError_t launch_gather_rows(const double* src, double* dst, const long long* idx, int64_t n_idx,
                               int64_t width, hipStream_t st);
 
-// direct weighted cost: *out = sum d (v - [Rt|u] alpha)^2
-hipError_t launch_cost(const ProblemView& p, const double* u, const double* alpha, int n_u, double* scratch, double* out,
-                       hipStream_t st);
-
-// the same cost for n_c <= 16, n_u <= 4 with the lane's alpha column in registers: Rtp = padded R_trunc copy,
-// D16 (u16 counts, row stride SD) is read instead of D when it is not null
-bool cost_cols_supported(int S, int n_c, int n_u);
-bool cost_cols2_wide_supported(const ProblemView& p, int n_u);
-hipError_t launch_cost_cols2_wide(const ProblemView& p, const double* u, const double* alpha, int n_u, double* scratch,
-                                  double* out, hipStream_t st);
+// direct weighted cost: *out = sum d (v - [Rt|u] alpha)^2 by the kernel that `plan` names (dmf_select.h; the plan of
+// cost_key(p, n_u, level), or hipErrorInvalidValue comes back); scratch: kCostPartials doubles.  The column-resident
+// kernels keep the lane's alpha column in registers and read Rtp (the padded R_trunc copy) and, where the plan says so,
+// D16 (u16 counts, row stride SD) instead of D.
+inline CostKey cost_key(const ProblemView& p, int n_u, int level) {
+    CostKey k;
+    k.S = p.S, k.n_c = p.n_c, k.n_u = n_u;
+    k.d16 = p.D16 != nullptr;
+    k.SD = p.SD;
+    k.v_align = p.v_align();
+    k.rtp_present = p.Rtp != nullptr;
+    k.level = level;
+    return k;
+}
+hipError_t launch_cost_plan(const CostPlan& plan, const ProblemView& p, const double* u, const double* alpha, int n_u,
+                            double* scratch, double* out, hipStream_t st);
 int vdv_cols_grid(int64_t N);
 hipError_t launch_vdv_cols(const ProblemView& p, double* slab, double* out, hipStream_t st);
-hipError_t launch_cost_cols(const ProblemView& p, const double* u, const double* alpha, int n_u, double* scratch, double* out,
-                            hipStream_t st);
 
 // generic weighted Gram accumulation over the extended row vector x = (Rt, u, v)
 hipError_t launch_gram(const ProblemView& p, const double* u, int n_u, GramJobTable jobs, double* slab, int64_t slab_doubles,

@@ -1,6 +1,8 @@
 // Streaming kernels: count conversion, reductions, row gather, the direct weighted cost
 // (demethify/deconvolution.py:15-17) and the generic per-sample weighted Gram accumulation
 // that feeds the alpha phase (G_s = R^T diag(d_s) R, b_s = R^T (d_s * v_s)).
+#include <cstdio>
+
 #include "dmf_device.h"
 #include "dmf_dispatch.h"
 #include "dmf_internal.h"
@@ -432,17 +434,73 @@ hipError_t launch_vdv_cols(const ProblemView& p, double* slab, double* out, hipS
     return hipGetLastError();
 }
 
-bool cost_cols_supported(int S, int n_c, int n_u) { return n_c <= 16 && n_u >= 0 && n_u <= 4 && n_c + n_u >= 1; }
+// ------------------------------------------------------------------ which cost kernel: the plan
+// The whole decision, a pure function of the key (dmf_select.h).
+//   levels 1, 2 (the any-shape kernels) and problems without the padded R_trunc copy: k_cost;
+//   n_c <= 16, n_u <= 4 at levels 0, 3, 4: the column-resident kernels -- two samples per lane on u16 counts from 128
+//     samples on (an even SD, V aligned to 8 bytes), else one sample per lane on whichever counts there are;
+//   n_c <= 16, 5 <= n_u <= 16 at level 0: the two-samples-per-lane form alone, on u16 counts, from 32 samples on (below
+//     128 samples part of the lanes idle; what competes is the any-shape k_cost, slower from ~32 samples on);
+//   a column-resident kernel writes ceil(S / 64) (two samples per lane: ceil(S / 128)) partials per row block, and its
+//     launcher caps the row blocks so that they fit the kCostPartials of the scratch: beyond 1024 partial columns not one
+//     row block fits, and the shape goes to k_cost;
+//   everything else: k_cost, alpha staged in LDS while K S doubles fit 48 KiB.
+CostPlan cost_plan(const CostKey& k) {
+    CostPlan plan;
+    const int S = k.S, K = k.n_c + k.n_u;
+    const bool rtp_ok = k.n_c == 0 || k.rtp_present;
+    const bool pair_ok = k.d16 && k.SD % 2 == 0 && (k.v_align & 7) == 0 && (S + 127) / 128 <= kCostPartials;
+    plan.nkc = (k.n_c + 3) / 4;
+    plan.nu = k.n_u;
+    plan.odd = (S & 1) != 0;
+    if ((k.level == 0 || k.level == 3 || k.level == 4) && rtp_ok && k.n_c <= 16 && k.n_u >= 0 && k.n_u <= 4 && K >= 1) {
+        if (pair_ok && S >= 128) {
+            plan.kind = CostKind::Cols2;
+            plan.d16 = true;
+            return plan;
+        }
+        if ((S + 63) / 64 <= kCostPartials) {
+            plan.kind = CostKind::Cols;
+            plan.d16 = k.d16;
+            plan.odd = false;
+            return plan;
+        }
+    } else if (k.level == 0 && rtp_ok && k.n_c <= 16 && k.n_u >= 5 && k.n_u <= 16 && pair_ok && S >= 32) {
+        plan.kind = CostKind::Cols2Wide;
+        plan.d16 = true;
+        return plan;
+    }
+    plan = CostPlan{};
+    plan.alpha_in_lds = (size_t)K * S * sizeof(double) <= 48 * 1024;
+    return plan;
+}
+
+int describe_cost_plan(const CostPlan& plan, char* buf, size_t cap) {
+    switch (plan.kind) {
+        case CostKind::Cols:
+            return snprintf(buf, cap, "cost=k_cost_cols<%d,%d,%s>", plan.nkc, plan.nu, plan.d16 ? "u16" : "f64");
+        case CostKind::Cols2:
+        case CostKind::Cols2Wide:
+            return snprintf(buf, cap, "cost=k_cost_cols2<%d,%d,%s>", plan.nkc, plan.nu, plan.odd ? "odd" : "even");
+        default: return snprintf(buf, cap, "cost=k_cost alpha=%s", plan.alpha_in_lds ? "lds" : "global");
+    }
+}
+
+// row blocks of a column-resident cost kernel: one per 32 rows, as many as fit the scratch beside `ny` partial columns
+static int cost_cols_row_blocks(int64_t N, int ny) {
+    const int64_t want = (N + 4 * 8 - 1) / (4 * 8);
+    int nbx = (int)(want < 1 ? 1 : want);
+    if (nbx > kCostPartials / ny) nbx = kCostPartials / ny;
+    return nbx;
+}
 
 // the two-samples-per-lane form (u16 counts, V aligned to 8 bytes, an even SD) and the sum of its partials
 template <int NKC, int NU>
-static hipError_t launch_cost_cols2_t(const ProblemView& p, const double* u, const double* alpha, double* scratch, double* out,
-                                      hipStream_t st) {
+static hipError_t launch_cost_cols2_t(bool odd, const ProblemView& p, const double* u, const double* alpha, double* scratch,
+                                      double* out, hipStream_t st) {
     const int S = p.S, ny2 = (S + 127) / 128;
-    const int64_t want = (p.N + 4 * 8 - 1) / (4 * 8);
-    int nbx = (int)(want < 1 ? 1 : want);
-    if (nbx > 1024 / ny2) nbx = 1024 / ny2;  // scratch: 1024 partials
-    if (S & 1)
+    const int nbx = cost_cols_row_blocks(p.N, ny2);
+    if (odd)
         hipLaunchKernelGGL((k_cost_cols2<NKC, NU, true>), dim3(nbx, ny2), dim3(256), 0, st, p.V, p.D16, p.SD, p.Rtp, u, alpha,
                            p.N, S, p.n_c, scratch);
     else
@@ -452,61 +510,65 @@ static hipError_t launch_cost_cols2_t(const ProblemView& p, const double* u, con
     return hipGetLastError();
 }
 
-hipError_t launch_cost_cols(const ProblemView& p, const double* u, const double* alpha, int n_u, double* scratch, double* out,
-                            hipStream_t st) {
-    return dispatch_int<0, 4>((p.n_c + 3) / 4, [&](auto nkc) {
-        return dispatch_int<0, 4>(n_u, [&](auto nu) {
-            constexpr int NKC = decltype(nkc)::value, NU = decltype(nu)::value;
-            const int S = p.S, ny = (S + 63) / 64;
-            if (p.D16 != nullptr && S >= 128 && p.SD % 2 == 0 && (p.v_align() & 7) == 0)
-                return launch_cost_cols2_t<NKC, NU>(p, u, alpha, scratch, out, st);
-            const int64_t want = (p.N + 4 * 8 - 1) / (4 * 8);
-            int nbx = (int)(want < 1 ? 1 : want);
-            const int cap = 1024 / ny;  // scratch: 1024 partials
-            if (nbx > cap) nbx = cap;
-            if (p.D16 != nullptr)
-                hipLaunchKernelGGL((k_cost_cols<NKC, NU, true>), dim3(nbx, ny), dim3(256), 0, st, p.V, (const void*)p.D16, p.SD,
-                                   p.Rtp, u, alpha, p.N, S, p.n_c, scratch);
-            else
-                hipLaunchKernelGGL((k_cost_cols<NKC, NU, false>), dim3(nbx, ny), dim3(256), 0, st, p.V, (const void*)p.D, S,
-                                   p.Rtp, u, alpha, p.N, S, p.n_c, scratch);
-            hipLaunchKernelGGL(k_reduce_final<1>, dim3(1), dim3(256), 0, st, scratch, nbx * ny, out, (const int*)nullptr);
-            return hipGetLastError();
-        });
-    });
+template <int NKC, int NU>
+static hipError_t launch_cost_cols_t(bool d16, const ProblemView& p, const double* u, const double* alpha, double* scratch,
+                                     double* out, hipStream_t st) {
+    const int S = p.S, ny = (S + 63) / 64;
+    const int nbx = cost_cols_row_blocks(p.N, ny);
+    if (d16)
+        hipLaunchKernelGGL((k_cost_cols<NKC, NU, true>), dim3(nbx, ny), dim3(256), 0, st, p.V, (const void*)p.D16, p.SD, p.Rtp, u,
+                           alpha, p.N, S, p.n_c, scratch);
+    else
+        hipLaunchKernelGGL((k_cost_cols<NKC, NU, false>), dim3(nbx, ny), dim3(256), 0, st, p.V, (const void*)p.D, S, p.Rtp, u,
+                           alpha, p.N, S, p.n_c, scratch);
+    hipLaunchKernelGGL(k_reduce_final<1>, dim3(1), dim3(256), 0, st, scratch, nbx * ny, out, (const int*)nullptr);
+    return hipGetLastError();
 }
 
-// Wide row groups (5..16 unknowns): the two-samples-per-lane form only (u16 counts, S even and >= 128, 16-B aligned V);
-// other shapes of that width stay on the generic k_cost.
-bool cost_cols2_wide_supported(const ProblemView& p, int n_u) {
-    // (below 128 samples part of the lanes idle; what competes is the any-shape k_cost, slower from ~32 samples on)
-    return p.D16 != nullptr && p.n_c <= 16 && n_u >= 5 && n_u <= 16 && p.S >= 32 && p.SD % 2 == 0 && (p.v_align() & 7) == 0;
-}
-
-hipError_t launch_cost_cols2_wide(const ProblemView& p, const double* u, const double* alpha, int n_u, double* scratch,
-                                  double* out, hipStream_t st) {
-    if (!cost_cols2_wide_supported(p, n_u)) return hipErrorInvalidValue;
-    return dispatch_int<0, 4>((p.n_c + 3) / 4, [&](auto nkc) {
-        return dispatch_int<5, 16>(n_u, [&](auto nu) {
-            return launch_cost_cols2_t<decltype(nkc)::value, decltype(nu)::value>(p, u, alpha, scratch, out, st);
-        });
-    });
-}
-
-hipError_t launch_cost(const ProblemView& p, const double* u, const double* alpha, int n_u, double* scratch, double* out,
-                       hipStream_t st) {
+static hipError_t launch_cost(bool in_lds, const ProblemView& p, const double* u, const double* alpha, int n_u, double* scratch,
+                              double* out, hipStream_t st) {
     const int S = p.S, K = p.n_c + n_u;
     const int tpr = S < 256 ? S : 256;
     const int rows_per_tile = 256 / tpr;
     int64_t tiles = (p.N + rows_per_tile - 1) / rows_per_tile;
-    const int nb = (int)(tiles < 1024 ? (tiles < 1 ? 1 : tiles) : 1024);
+    const int nb = (int)(tiles < kCostPartials ? (tiles < 1 ? 1 : tiles) : kCostPartials);
     const size_t lds = (size_t)K * S * sizeof(double);
-    const int in_lds = lds <= 48 * 1024;
-    hipLaunchKernelGGL(k_cost, dim3(nb), dim3(256), in_lds ? lds : 0, st, p.V, p.D, p.Rt, u, alpha, p.N, S, p.n_c, n_u, in_lds,
-                       scratch);
+    hipLaunchKernelGGL(k_cost, dim3(nb), dim3(256), in_lds ? lds : 0, st, p.V, p.D, p.Rt, u, alpha, p.N, S, p.n_c, n_u,
+                       in_lds ? 1 : 0, scratch);
     hipLaunchKernelGGL(k_reduce_final<1>, dim3(1), dim3(256), 0, st, scratch, nb, out,
                        (const int*)nullptr);
     return hipGetLastError();
+}
+
+// The launch of what the plan names.  A plan that is not this problem's own (another shape, counts it does not carry) is
+// refused: a kernel's template arguments are never taken from anywhere else.
+hipError_t launch_cost_plan(const CostPlan& plan, const ProblemView& p, const double* u, const double* alpha, int n_u,
+                            double* scratch, double* out, hipStream_t st) {
+    if (plan.kind != CostKind::Generic &&
+        (plan.nkc != (p.n_c + 3) / 4 || plan.nu != n_u || (plan.d16 && p.D16 == nullptr) || (!plan.d16 && p.D == nullptr) ||
+         (p.n_c > 0 && p.Rtp == nullptr)))
+        return hipErrorInvalidValue;
+    if (plan.kind == CostKind::Generic && p.D == nullptr) return hipErrorInvalidValue;
+    switch (plan.kind) {
+        case CostKind::Cols:
+        case CostKind::Cols2:
+            return dispatch_int<0, 4>(plan.nkc, [&](auto nkc) {
+                return dispatch_int<0, 4>(plan.nu, [&](auto nu) {
+                    constexpr int NKC = decltype(nkc)::value, NU = decltype(nu)::value;
+                    if (plan.kind == CostKind::Cols2)
+                        return launch_cost_cols2_t<NKC, NU>(plan.odd, p, u, alpha, scratch, out, st);
+                    return launch_cost_cols_t<NKC, NU>(plan.d16, p, u, alpha, scratch, out, st);
+                });
+            });
+        case CostKind::Cols2Wide:
+            return dispatch_int<0, 4>(plan.nkc, [&](auto nkc) {
+                return dispatch_int<5, 16>(plan.nu, [&](auto nu) {
+                    return launch_cost_cols2_t<decltype(nkc)::value, decltype(nu)::value>(plan.odd, p, u, alpha, scratch, out,
+                                                                                         st);
+                });
+            });
+        default: return launch_cost(plan.alpha_in_lds, p, u, alpha, n_u, scratch, out, st);
+    }
 }
 
 // ------------------------------------------------------------------ generic weighted Gram

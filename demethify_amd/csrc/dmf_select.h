@@ -67,4 +67,33 @@ IterationPlan plan_iteration(const ShapeKey& k, const PathSpec& s, int n_iter2, 
 // "rowpass=... gram=... alpha=..." (what dmf_solver_describe reports and the parity tests assert)
 int describe_plan(const ShapeKey& k, const IterationPlan& plan, char* buf, size_t cap);
 
+// ---- the streaming cost (cost_f_w, deconvolution.py:15-17; the kernels and the plan: dmf_kernels_stream.hip).  Like the
+// table above a pure function of a key, read by the launch (launch_cost_plan), by what the hold-out error asks about it
+// and by the describe string (dmf_cost_describe, dmf_problem_cost_describe), so the three cannot drift apart.
+struct CostKey {
+    int S = 0, n_c = 0, n_u = 0;
+    bool d16 = false;         // a u16 copy of the counts (or of the hold-out weights) is there to be read
+    int SD = 0;               // its padded row length
+    unsigned v_align = 0;     // address of V modulo 16
+    bool rtp_present = true;  // the padded copy of R_trunc exists (n_c > 0)
+    int level = 0;            // kernel selection level (dmf_context_set_generic)
+};
+enum class CostKind {
+    Cols,       // k_cost_cols<NKC,NU,D16>: one sample per lane
+    Cols2,      // k_cost_cols2<NKC,NU,ODD>, NU 0..4: two samples per lane
+    Cols2Wide,  // k_cost_cols2<NKC,NU,ODD>, NU 5..16
+    Generic     // k_cost: any shape
+};
+struct CostPlan {
+    CostKind kind = CostKind::Generic;
+    int nkc = 0, nu = 0;        // template arguments of the column-resident kernels
+    bool d16 = false;           // the kernel reads the u16 counts (never the f64 copy)
+    bool odd = false;           // k_cost_cols2: S is odd (the lone lane)
+    bool alpha_in_lds = false;  // k_cost: alpha staged in LDS
+};
+constexpr int kCostPartials = 1024;  // scratch of the cost kernels: one partial per workgroup
+CostPlan cost_plan(const CostKey& k);
+// "cost=k_cost_cols2<3,4,odd>", "cost=k_cost_cols<2,1,u16>", "cost=k_cost alpha=lds"
+int describe_cost_plan(const CostPlan& plan, char* buf, size_t cap);
+
 }  // namespace dmf

@@ -316,6 +316,14 @@ class Problem:
                                    C.byref(out)), "dmf_cost")
         return out.value
 
+    def cost_describe(self, n_u: int) -> str:
+        """Which kernel ``cost`` -- and a solver's direct_cost / cost_begin -- runs on this problem with n_u unknown types
+        at the context's current level, e.g. "cost=k_cost_cols2<3,4,odd>" (dmf_problem_cost_describe)."""
+        buf = C.create_string_buffer(128)
+        L.check(self._lib.dmf_problem_cost_describe(self.ctx._h, self._h, int(n_u), buf, len(buf)),
+                "dmf_problem_cost_describe")
+        return buf.value.decode()
+
     def wls_intercept(self, u=None, target="v", host_arrays=None, f64_arrays=False):
         """``wls_intercept`` (init_func.py:8-14) of every sample at once on the device (dmf_wls_intercept), with
         R_full = [R_trunc | u], the sample's counts as weights and the target meth_frequency (``target="v"``, what the

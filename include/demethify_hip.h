@@ -146,6 +146,19 @@ int dmf_problem_shape(const dmf_problem* p, int64_t* N, int64_t* S, int64_t* n_c
 /* cost_f_w(y, R, alpha, d_x), deconvolution.py:15-17, with R = [Rt | u]. */
 int dmf_cost(dmf_context* ctx, const dmf_problem* p, const double* u, int64_t n_u,
              const double* alpha, int flags, double* out_cost);
+/* Which kernel dmf_cost, dmf_solver_cost / _cost_begin and dmf_solver_holdout_error run for a key, as text naming the kernel
+ * and its template arguments: "cost=k_cost_cols2<3,4,odd>" (two samples per lane; NKC = ceil(n_c / 4), NU = n_u, parity of
+ * S), "cost=k_cost_cols<2,1,u16>" / "cost=k_cost_cols<0,4,f64>" (one sample per lane, on the u16 or the f64 counts),
+ * "cost=k_cost alpha=lds" / "cost=k_cost alpha=global" (any shape).  The launch dispatches on the same plan
+ * (csrc/dmf_kernels_stream.hip), so the text cannot say anything else than what runs.
+ * dmf_cost_describe: a pure function of the key, no GPU is touched -- has_u16: the problem carries the u16 copy of its
+ * counts (integers up to 32639, 2 <= S <= 2048, n_c <= 48, R_trunc in [0, 1], created at level 0), SD its padded row
+ * length (S rounded up to 64), v_align the address of meth_frequency modulo 16, rtp_present the padded copy of R_trunc
+ * (1 <= n_c <= 48), level the kernel selection level.  dmf_problem_cost_describe: the same for a resident problem at the
+ * context's current level.  DMF_ERR_BAD_ARG for n_c + n_u outside [1, 64] and fields out of range. */
+int dmf_cost_describe(int64_t S, int64_t n_c, int64_t n_u, int has_u16, int64_t SD, int v_align, int rtp_present, int level,
+                      char* buf, int64_t cap);
+int dmf_problem_cost_describe(dmf_context* ctx, const dmf_problem* p, int64_t n_u, char* buf, int64_t cap);
 /* projection_simplex_sort_2d(v, z), deconvolution.py:21-37; X and out are K x S. */
 int dmf_project_simplex(dmf_context* ctx, const double* X, int64_t K, int64_t S, double z,
                         int flags, double* out);

@@ -12,6 +12,11 @@ pytestmark = pytest.mark.gpu
 SHAPES = [  # (N, S, n_c, n_u)
     (257, 7, 6, 1), (1000, 64, 6, 2), (513, 100, 0, 4), (300, 10, 5, 3), (2048, 130, 12, 4), (129, 33, 3, 8),
 ]
+# ... and for the cost alone, real-valued data on each two-samples-per-lane form and on the any-shape kernel
+COST_SHAPES = SHAPES + [(200, 129, 3, 2), (150, 64, 2, 7), (60, 20, 17, 1)]
+COST_KERNELS = ["k_cost_cols<2,1,u16>", "k_cost_cols<2,2,u16>", "k_cost_cols<0,4,u16>", "k_cost_cols<2,3,u16>",
+                "k_cost_cols2<3,4,even>", "k_cost_cols2<1,8,odd>", "k_cost_cols2<1,2,odd>", "k_cost_cols2<1,7,even>",
+                "k_cost alpha=lds"]
 
 
 def _problem(N, S, n_c, n_u, seed):
@@ -22,14 +27,21 @@ def _problem(N, S, n_c, n_u, seed):
     return V, D, Rt, u, alpha, rs
 
 
-@pytest.mark.parametrize("N,S,n_c,n_u", SHAPES)
+@pytest.mark.parametrize("N,S,n_c,n_u", COST_SHAPES)
 def test_cost_matches_oracle(ctx, N, S, n_c, n_u):
+    """cost_f_w on real-valued data against sum d e e in extended precision (no sqrt(d), which oracle.solver.weighted_cost
+    goes through), on the kernel the shape is listed for."""
     from demethify_amd.device import Problem
 
+    kernel = COST_KERNELS[COST_SHAPES.index((N, S, n_c, n_u))]
     V, D, Rt, u, alpha, _ = _problem(N, S, n_c, n_u, 1)
-    want = osol.weighted_cost(V, np.c_[Rt, u], alpha, D)
+    ld = np.longdouble
+    e = V.astype(ld) - np.c_[Rt, u].astype(ld) @ alpha.astype(ld)
+    want = float((D.astype(ld) * e * e).sum())
     with Problem(ctx, V, D, Rt if n_c else None) as p:
+        assert p.cost_describe(n_u) == "cost=" + kernel
         got = p.cost(u, alpha)
+    print(f"{kernel}: rel {abs(got - want) / abs(want):.2e}")
     assert abs(got - want) <= 1e-11 * abs(want)
 
 
