@@ -193,6 +193,8 @@ bool u_phase_gram_supported(int S, int n_c, int n_u);
 // u phase on the FP64 matrix cores (n_u <= 8, n_c <= 16, S <= 512); reads the padded Rtp, and D16 where there is one
 bool u_phase_mfma_supported(int S, int n_c, int n_u);
 hipError_t launch_u_phase_mfma(const ProblemView& p, const IterateView& it, int n_iter2, hipStream_t st);
+// the same kernel; cm_out: null, or where its split mode leaves the per-row c_i / M_i instead of running the inner steps
+hipError_t launch_u_phase_mfma_impl(const ProblemView& p, const IterateView& it, int n_iter2, double* cm_out, hipStream_t st);
 // fused row pass: u phase + u-dependent Gram slab + ||u||^2 / l_h in one read of V and D
 // (S % 4 == 0, S <= 256, n_c <= 16, n_u <= 8, accumulators <= 80, counts exact in f32);
 // grid_out = workgroups launched; the slab (scratch.slab, with scratch.u2_partials) holds 2 rows per workgroup

@@ -17,7 +17,7 @@
 //     the 16 bytes of an i8 MFMA A operand (k <-> (q, strip, r)), no LDS round trip.
 // Then, per 16-pair tile: 7 (or 14) integer MFMAs per column group and row half against the P digits (B operands,
 // built once per workgroup in LDS in the same k order), the exact combine of dmf_kernels_rowpass2.hip, and the
-// row's M values go to HBM.  k_u_inner_rows16 runs the inner iterations from there.
+// row's M values go to HBM.  k_u_inner_rows (or k_inner_bu) runs the inner iterations from there.
 //
 // Layout facts used (tools/mfma_probe.hip): FP64 A[i][k]: lane (i = l & 15, k = l >> 4); B[k][j]: lane (k = l >> 4,
 // j = l & 15); C register r of lane l = C[(l >> 4) + 4 r][l & 15].  i8 16x16x64: A lane (row l & 15), B lane (column

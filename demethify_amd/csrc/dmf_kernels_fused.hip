@@ -21,7 +21,7 @@
 #include "dmf_device.h"
 #include "dmf_dispatch.h"
 #include "dmf_internal.h"
-#include "dmf_phaseb.h"
+#include "dmf_ustep.h"
 
 namespace dmf {
 
@@ -117,16 +117,7 @@ __global__ __launch_bounds__(768) void k_rowpass_fused(
     auto tile_of = [&](int buf) { return tiles + (size_t)(buf * NW + cg) * kTileBytes; };
     constexpr int ZROW = NCT + NU;  // index of the all-zero row of alds
 
-    if (threadIdx.x == 0) {
-        double a1 = state->a1, lw_prev = state->l_w_prev;
-        const double lw = state->l_w;
-        for (int t2 = 0; t2 < n_iter2; ++t2) {
-            double beta;
-            momentum_step(a1, lw_prev, lw, beta);
-            beta_tab[t2] = beta;
-            lw_prev = lw;
-        }
-    }
+    if (threadIdx.x == 0) fill_momentum_table(state, n_iter2, beta_tab);
     for (int i = threadIdx.x; i < (NCT + NU + 1) * AS; i += blockDim.x) {
         const int r = i / AS, c = i - r * AS;
         double val = 0.0;

@@ -30,7 +30,7 @@
 #include "dmf_device.h"
 #include "dmf_dispatch.h"
 #include "dmf_internal.h"
-#include "dmf_phaseb.h"
+#include "dmf_ustep.h"
 #include "dmf_fixedpoint.h"
 #include <cstdlib>
 #include <type_traits>
@@ -83,36 +83,6 @@ constexpr int kTileDBytes2 = 16 * kRowD * 2;
 constexpr int kTileBytes2 = kTileVBytes2 + kTileDBytes2;  // one column group: V (f64), counts (u16, as they arrive)
 constexpr int kTileBytesX = 2 * kTileDBytes2;               // X16 form: counts and methylated counts, both u16
 }  // namespace
-
-// One accelerated projected-gradient step of a row group (deconvolution.py:83-88): (cur, prev) = (u, u_) in,
-// prev = the new u out (cur is then u_).  AT_PREV: gradient at the previous iterate (deconvolution.py:163) instead
-// of the extrapolated point (:88).  c and M arrive pre-scaled by 1 / l_w (M negated).
-// Ms: this lane's row of -M / l_w in ROTATED order -- Ms[r] = -M[j][(j + r) % NU] / l_w -- with the step's own "+ ut"
-// folded into Ms[0] at the extrapolated point (deconvolution.py:88; not at :163, where the gradient point differs).
-// A wave alone on its SIMD issues an FP64 instruction every 8 cycles and a 32-bit one every 4 (tools/rowpass2_probe:
-// 145 cycles per step for 11 FP64 + 10 other instructions, with or without a second workgroup on the CU), so phase B
-// costs what it issues: NU - 1 quad rotations (instead of NU broadcasts) and one FMA chain whose last link clamps --
-// 6 FP64 + 8 other instructions per step at NU = 4.
-template <int NU, bool AT_PREV>
-__device__ __forceinline__ void inner_step(double cur, double& prev, double cj, const double (&Ms)[NU], int b_lo, int b_hi,
-                                           int t2, int lane0) {
-    const double beta = __hiloint2double(__builtin_amdgcn_readlane(b_hi, t2), __builtin_amdgcn_readlane(b_lo, t2));
-    const double ut = fma(beta, cur - prev, cur);
-    const double x = AT_PREV ? cur : ut;
-    if constexpr (NU == 3) {  // (three lanes per row do not tile a quad: shuffles, in the same rotated order)
-        const int jb = (threadIdx.x & 63) - lane0;
-        double acc = fma(Ms[0], x, AT_PREV ? ut + cj : cj);
-        acc = fma(Ms[1], __shfl(x, lane0 + (jb + 1) % 3, 64), acc);
-        prev = f_fma_clamp01(Ms[2], __shfl(x, lane0 + (jb + 2) % 3, 64), acc);
-    } else if constexpr (NU == 1) {
-        prev = f_fma_clamp01(Ms[0], x, AT_PREV ? ut + cj : cj);
-    } else {
-        double acc = fma(Ms[0], x, AT_PREV ? ut + cj : cj);
-#pragma unroll
-        for (int r = 1; r < NU - 1; ++r) acc = fma(Ms[r], r == 1 ? f_group_rot<NU, 1>(x) : f_group_rot<NU, 2>(x), acc);
-        prev = f_fma_clamp01(Ms[NU - 1], NU == 2 ? f_group_rot<NU, 1>(x) : f_group_rot<NU, 3>(x), acc);
-    }
-}
 
 template <int NU, bool AT_PREV>
 __device__ __forceinline__ void inner_steps(double& uu, double& up, double cj, const double (&Ms)[NU], int b_lo, int b_hi,
@@ -212,14 +182,7 @@ __global__ __launch_bounds__(64 * MAXW, MAXW == 4 ? 2 : 1) void k_rowpass_v2(
         for (int t2 = threadIdx.x; t2 < n_iter2; t2 += blockDim.x)
             beta_tab[t2] = fmin(mrow[2 + t2], t2 == 0 ? 0.9999 * sqrt(lw_prev / lw) : 0.9999);  // l_w_ = l_w behind step 0 (:89)
     } else if (threadIdx.x == 0) {
-        double a1 = state->a1, lw_prev = state->l_w_prev;
-        const double lw = state->l_w;
-        for (int t2 = 0; t2 < n_iter2; ++t2) {
-            double beta;
-            momentum_step(a1, lw_prev, lw, beta);
-            beta_tab[t2] = beta;
-            lw_prev = lw;
-        }
+        fill_momentum_table(state, n_iter2, beta_tab);
     }
     // the partial-sum slots of column groups this workgroup does not have stay zero (phase B adds all MAXW of them,
     // unrolled, so that its LDS reads go out in one batch)

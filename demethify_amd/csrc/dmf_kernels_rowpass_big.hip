@@ -20,6 +20,7 @@
 #include "dmf_device.h"
 #include "dmf_dispatch.h"
 #include "dmf_internal.h"
+#include "dmf_ustep.h"
 
 namespace dmf {
 
@@ -72,16 +73,7 @@ __global__ __launch_bounds__(GS == 16 ? 256 : 512) void k_u_phase_big(
     const int lane = threadIdx.x & 63;
     const int m16 = lane & 15, q = lane >> 4;
 
-    if (threadIdx.x == 0) {  // momentum coefficients of the n_iter2 inner steps (deconvolution.py:83-85)
-        double a1 = state->a1, lw_prev = state->l_w_prev;
-        const double lw = state->l_w;
-        for (int t2 = 0; t2 < n_iter2; ++t2) {
-            double beta;
-            momentum_step(a1, lw_prev, lw, beta);
-            beta_tab[t2] = beta;
-            lw_prev = lw;
-        }
-    }
+    if (threadIdx.x == 0) fill_momentum_table(state, n_iter2, beta_tab);  // (deconvolution.py:83-85)
     for (int i = threadIdx.x; i < K * AS; i += NWV * 64) {
         const int r = i / AS, c = i - r * AS;
         double val = 0.0;
