@@ -20,6 +20,7 @@ DMF_WLS_TARGET_V, DMF_WLS_TARGET_DV = 0, 1
 DMF_WLS_F64_ARRAYS = 8
 DMF_ERR_BAD_ARG, DMF_ERR_NONFINITE, DMF_ERR_UNSUPPORTED = 1, 4, 5
 DMF_ERR_BAD_SHAPE = 2
+DMF_GRAM_INTEGER, DMF_GRAM_FP64 = 0, 1
 DMF_MODE_PARTIAL = 0
 DMF_MODE_UNSUPERVISED = 1
 MAX_K = 64  # dmf::kMaxK: largest n_c + n_u the kernels are built for (DMF_ERR_UNSUPPORTED beyond)
@@ -60,6 +61,9 @@ SIGNATURES = {
     "dmf_solver_holdout_error": (C.c_int, [_p, _p, _dbl_p, C.POINTER(_i64)]),
     "dmf_problem_destroy": (C.c_int, [_p]),
     "dmf_problem_shape": (C.c_int, [_p, C.POINTER(_i64), C.POINTER(_i64), C.POINTER(_i64)]),
+    "dmf_problem_gram_known": (C.c_int, [_p, _p, C.c_char_p, _i64]),
+    "dmf_gram_i8_describe": (C.c_int, [_i64, _i64, _i64, _i64, C.c_int, C.c_char_p, _i64]),
+    "dmf_solver_gram": (C.c_int, [_p, C.c_int, _p, C.c_char_p, _i64]),
     "dmf_cost": (C.c_int, [_p, _p, _p, _i64, _p, C.c_int, _dbl_p]),
     "dmf_cost_describe": (C.c_int, [_i64, _i64, _i64, C.c_int, _i64, C.c_int, C.c_int, C.c_int, C.c_char_p, _i64]),
     "dmf_problem_cost_describe": (C.c_int, [_p, _p, _i64, C.c_char_p, _i64]),

@@ -195,6 +195,7 @@ struct dmf_problem {
     double x16_dev = 0.0, x16_sum = 0.0;
     bool d_f32_exact = false;    // every count survives a round trip through f32 (the fused tile stores D as f32)
     dmf_api::DevBuf<double> gb_known;  // [(n_c+1)(n_c+2)/2][S]
+    dmf::GramRan known_ran;            // which route problem_finalize took for it, as text (dmf_problem_gram_known)
     // a masked problem (dmf_problem_mask) keeps what dmf_solver_holdout_error needs: the train mask as it came (bit-packed,
     // ceil(S / 8) bytes per row, 1 = kept), the number of held-out elements, and -- with integer count copies -- the
     // hold-out weights (1 where held out) as u16 in D16's padded layout, which the u16 cost kernels read in D16's place
@@ -350,7 +351,8 @@ int cost_to_host(dmf_context* ctx, const dmf::ProblemView& p, const double* u, c
 // dmf_api_solver.hip: the phases of an outer iteration, for the single-function entry points
 int enqueue_u_phase(dmf_solver* s, int n_iter2, dmf::RowKind row);
 dmf::RowKind standalone_row_kind(const dmf_solver* s, int n_iter2);
-int enqueue_gram(dmf_solver* s, dmf::GramKind kind);
+// heed_done false: the kernels compute on a converged solver too (dmf_solver_gram); ran: what the launcher ran, as text
+int enqueue_gram(dmf_solver* s, dmf::GramKind kind, bool heed_done = true, dmf::GramRan* ran = nullptr);
 dmf::GramKind fp64_gram_kind(const dmf_solver* s);
 int enqueue_alpha_phase(dmf_solver* s, dmf::AlphaKind kind, int n_iter2);  // kind: plan_iteration(...).alpha
 int fetch_state(dmf_solver* s);

@@ -90,6 +90,16 @@ int dmf_cost_describe(int64_t S, int64_t n_c, int64_t n_u, int has_u16, int64_t 
     return DMF_OK;
 }
 
+int dmf_gram_i8_describe(int64_t N, int64_t S, int64_t n_c, int64_t n_u, int nd, char* buf, int64_t cap) {
+    if (buf == nullptr || cap < 1 || N < 1 || S < 1 || S > (1 << 24) || n_c < 0 || n_u < 0 || n_c + n_u < 1 ||
+        n_c + n_u > dmf::kMaxK)
+        return DMF_ERR_BAD_ARG;
+    const dmf::GramI8Plan g = dmf::gram_i8_plan(N, (int)((S + 63) / 64 * 64), (int)n_c, (int)n_u, nd);
+    if (!g.supported) return DMF_ERR_UNSUPPORTED;
+    dmf::describe_gram_i8_plan(g, buf, (size_t)cap);
+    return DMF_OK;
+}
+
 int dmf_cost(dmf_context* ctx, const dmf_problem* p, const double* u, int64_t n_u, const double* alpha,
              int flags, double* out_cost) {
     DMF_TRY(check_ctx(ctx));

@@ -20,6 +20,14 @@ static int alloc_count_copies(dmf_problem* p, int ND, bool x16, bool w16) {
     return DMF_OK;
 }
 
+// one more piece of dmf_problem::known_ran, the text of dmf_problem_gram_known: "int_known" / "fp64" (without either: fp64),
+// then every launcher that contributed rows, in launch order, separated by blanks
+static void known_route(dmf_problem* p, const char* piece) {
+    char* t = p->known_ran.text;
+    const size_t have = std::strlen(t), cap = sizeof(p->known_ran.text);
+    snprintf(t + have, cap - have, "%s%s", have > 0 ? " " : "", piece);
+}
+
 // Builds the per-problem constants: max(D)^2, ||Rt||_F^2 and the known block of the packed Gram.
 // `counts_done`: a copy of a resident problem (dmf_problem_gather, dmf_problem_mask) whose integer count copies are
 // already written from the source's and whose count constants -- max(D) in kDmax and kIntCountMax, the exactness flags
@@ -126,16 +134,23 @@ static int problem_finalize(dmf_problem* p, bool counts_done = false) {
         HIP_TRY(slab_bu.alloc(ctx, (size_t)dmf::bu_cols_grid(N) * (n_c + 1) * S));
         HIP_TRY(hipMemsetAsync(acc, 0, (size_t)acc_words * sizeof(long long), ctx->stream));
         int ny = 0, n_slabs = 0;
-        HIP_TRY(dmf::launch_gram_i8(pv, nullptr, 0, jobs.k, jobs.l, n_dense, slab_i8, slab_words, nullptr, &ny, ctx->stream));
+        dmf::GramRan ran;
+        HIP_TRY(dmf::launch_gram_i8(pv, nullptr, 0, jobs.k, jobs.l, n_dense, slab_i8, slab_words, nullptr, &ny, ctx->stream, &ran));
+        known_route(p, "int_known");
+        known_route(p, ran.text);
         // (v^T D v rides along where the two-samples-per-lane form of the stream kernel runs)
         HIP_TRY(dmf::launch_bu_cols(pv, p->Rt, (int)n_c, slab_bu, nullptr, &n_slabs, ctx->stream, &vdv_done));
+        known_route(p, vdv_done ? "+ k_bu_cols2 with vDv" : "+ k_bu_cols");
         // (dst lists the dense pairs first, then the n_c right-hand sides, then (v, v): the order of the reduce's jobs)
         HIP_TRY(dmf::launch_gram_v2_reduce(slab_i8, ny, n_dense, p->SD, slab_bu, n_slabs, (int)n_c + (vdv_done ? 1 : 0), (int)S,
                                            acc, jobs.dst, p->gb_known, nullptr, nullptr, 0, nullptr, ctx->stream));
     } else if (mfma) {
         dmf::GramJobTable fast{jobs.k, jobs.l, jobs.dst, n_fast};
         int ny = 0;
-        HIP_TRY(dmf::launch_gram_mfma(pv, nullptr, 0, fast, n_dense, slab, slab_doubles, nullptr, &ny, ctx->stream));
+        dmf::GramRan ran;
+        HIP_TRY(dmf::launch_gram_mfma(pv, nullptr, 0, fast, n_dense, slab, slab_doubles, nullptr, &ny, ctx->stream, &ran));
+        known_route(p, "fp64");
+        known_route(p, ran.text);
         HIP_TRY(dmf::launch_gram_reduce(slab, ny, n_fast, (int)S, jobs.dst, p->gb_known, nullptr, ctx->stream));
     }
     if (int_known && vdv_done) {
@@ -144,9 +159,14 @@ static int problem_finalize(dmf_problem* p, bool counts_done = false) {
                (int64_t)dmf::vdv_cols_grid(N) * S <= slab_doubles) {
         // what is left is v^T D v alone: a stream kernel of its own (the generic kernel took 2.7 ms for it at 1e6 x 256)
         HIP_TRY(dmf::launch_vdv_cols(pv, slab, p->gb_known + (int64_t)jobs.h_dst[n_jobs - 1] * S, ctx->stream));
+        known_route(p, p->known_ran.text[0] == 0 ? "fp64 k_vdv_cols" : "+ k_vdv_cols");
     } else {
         dmf::GramJobTable rest{jobs.k + n_fast, jobs.l + n_fast, jobs.dst + n_fast, n_jobs - n_fast};
-        HIP_TRY(dmf::launch_gram(pv, nullptr, 0, rest, slab, slab_doubles, p->gb_known, nullptr, ctx->stream));
+        dmf::GramRan ran;
+        if (p->known_ran.text[0] == 0) known_route(p, "fp64");
+        else known_route(p, "+");
+        HIP_TRY(dmf::launch_gram(pv, nullptr, 0, rest, slab, slab_doubles, p->gb_known, nullptr, ctx->stream, &ran));
+        known_route(p, ran.text);
     }
     HIP_TRY(hipStreamSynchronize(ctx->stream));  // (the uploads of the job table read host memory of this frame)
     return DMF_OK;
@@ -361,6 +381,17 @@ int dmf_problem_cost_describe(dmf_context* ctx, const dmf_problem* p, int64_t n_
     if (ctx == nullptr || p == nullptr || buf == nullptr || cap < 1 || n_u < 0 || p->ctx != ctx) return DMF_ERR_BAD_ARG;
     if (p->n_c + n_u < 1 || p->n_c + n_u > dmf::kMaxK) return DMF_ERR_BAD_ARG;
     dmf::describe_cost_plan(cost_plan_of(ctx, p->view(), (int)n_u), buf, (size_t)cap);
+    return DMF_OK;
+}
+
+int dmf_problem_gram_known(const dmf_problem* p, double* out, char* out_text, int64_t cap) {
+    if (p == nullptr || out == nullptr || (out_text != nullptr && cap < 1)) return DMF_ERR_BAD_ARG;
+    dmf_context* ctx = p->ctx;
+    DMF_TRY(check_ctx(ctx));
+    const size_t n = (size_t)(p->n_c + 1) * (p->n_c + 2) / 2 * p->S;
+    HIP_TRY(hipMemcpyAsync(out, p->gb_known, n * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    if (out_text != nullptr) snprintf(out_text, (size_t)cap, "%s", p->known_ran.text);
     return DMF_OK;
 }
 

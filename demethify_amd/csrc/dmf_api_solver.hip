@@ -61,47 +61,73 @@ dmf::RowKind standalone_row_kind(const dmf_solver* s, int n_iter2) {
     return dmf::plan_iteration(s->key, spec, n_iter2, false).row;
 }
 
+// What the integer Gram route of a solver writes and works in: the solver's own buffers in the loop, temporaries of the
+// same sizes for dmf_solver_gram on a solver whose path never allocated them.
+struct GramI8Buffers {
+    double* slab_bu = nullptr;     // b_u slabs: bu_cols_grid(N) x n_u x S doubles (or what the row kernel left there)
+    long long* slab_i8 = nullptr;  // gram_i8_slab_words() i64 words
+    int64_t slab_i8_words = 0;
+    long long* acc = nullptr;      // gram_i8_acc_words() i64 words, zero (the kernels leave them zero again)
+    double* gb = nullptr;          // the packed Gram the rows go to
+    const int* done = nullptr;     // the solver's done flag, or null: compute whatever the flag says
+};
+
+static GramI8Buffers solver_i8_buffers(dmf_solver* s) {
+    GramI8Buffers b;
+    b.slab_bu = s->slab, b.slab_i8 = s->slab_i8, b.slab_i8_words = s->slab_i8_words, b.acc = s->acc_i8, b.gb = s->gb;
+    b.done = &s->state->done;
+    return b;
+}
+
 // The integer Gram of the u-dependent entries on the 8-bit count planes and its reduce, which also folds in the b_u
-// slabs (`n_slabs` of them in s->slab) and, where the row kernel left them, `n_u2` shares of ||u||^2.
-static int gram_i8_and_reduce(dmf_solver* s, int n_slabs, const double* u2_partials, int n_u2) {
+// slabs (`n_slabs` of them in b.slab_bu) and, where the row kernel left them, `n_u2` shares of ||u||^2.
+static int gram_i8_and_reduce(dmf_solver* s, const GramI8Buffers& b, int n_slabs, const double* u2_partials, int n_u2,
+                              dmf::GramRan* ran = nullptr) {
     dmf_context* ctx = s->ctx;
     const dmf_problem* p = s->p;
     const int S = (int)p->S, n_c = (int)p->n_c, n_u = (int)s->n_u, nf = n_c * n_u + n_u * (n_u + 1) / 2;
     int ny = 0;
-    HIP_TRY(dmf::launch_gram_i8(p->view(), s->u, n_u, s->jobs.k, s->jobs.l, nf, s->slab_i8, s->slab_i8_words, &s->state->done,
-                                &ny, ctx->stream));
-    HIP_TRY(dmf::launch_gram_v2_reduce(s->slab_i8, ny, nf, p->SD, s->slab, n_slabs, n_u, S, s->acc_i8, s->jobs.dst, s->gb,
-                                       &s->state->done, u2_partials, n_u2, s->state, ctx->stream));
+    HIP_TRY(dmf::launch_gram_i8(p->view(), s->u, n_u, s->jobs.k, s->jobs.l, nf, b.slab_i8, b.slab_i8_words, b.done, &ny,
+                                ctx->stream, ran));
+    HIP_TRY(dmf::launch_gram_v2_reduce(b.slab_i8, ny, nf, p->SD, b.slab_bu, n_slabs, n_u, S, b.acc, s->jobs.dst, b.gb, b.done,
+                                       u2_partials, n_u2, s->state, ctx->stream));
     return DMF_OK;
+}
+
+// b_u by the stream kernel, then the integer Gram and its reduce: GramKind::BuColsI8
+static int gram_bu_cols_i8(dmf_solver* s, const GramI8Buffers& b, dmf::GramRan* ran = nullptr) {
+    int n_slabs = 0;
+    HIP_TRY(dmf::launch_bu_cols(s->p->view(), s->u, (int)s->n_u, b.slab_bu, b.done, &n_slabs, s->ctx->stream));
+    return gram_i8_and_reduce(s, b, n_slabs, nullptr, 0, ran);
 }
 
 // kind: GramKind::BuColsI8 only behind a u phase with at least one inner step (its clip puts u inside [0, 1], which the
 // fixed-point features need); the dmf_update_alpha entry point hands over the caller's u and passes an FP64 kind
-int enqueue_gram(dmf_solver* s, dmf::GramKind kind) {
+int enqueue_gram(dmf_solver* s, dmf::GramKind kind, bool heed_done, dmf::GramRan* ran) {
     dmf_context* ctx = s->ctx;
     const dmf::ProblemView pv = s->p->view();
     const int S = pv.S, n_u = (int)s->n_u;
-    const int* done = &s->state->done;
+    const int* done = heed_done ? &s->state->done : nullptr;
     FamilyScope scope(ctx, DMF_KERNEL_GRAM);
     if (kind == dmf::GramKind::BuColsI8) {
-        int n_slabs = 0;
-        HIP_TRY(dmf::launch_bu_cols(pv, s->u, n_u, s->slab, done, &n_slabs, ctx->stream));
-        return gram_i8_and_reduce(s, n_slabs, nullptr, 0);
+        GramI8Buffers b = solver_i8_buffers(s);
+        b.done = done;
+        return gram_bu_cols_i8(s, b, ran);
     }
     if (kind == dmf::GramKind::GramU) {
         int ny = 0;
-        HIP_TRY(dmf::launch_gram_u(pv, s->u, n_u, s->slab, done, &ny, ctx->stream));
+        HIP_TRY(dmf::launch_gram_u(pv, s->u, n_u, s->slab, done, &ny, ctx->stream, ran));
         HIP_TRY(dmf::launch_gram_reduce(s->slab, ny, s->jobs.n, S, s->jobs.dst, s->gb, done, ctx->stream));
         return DMF_OK;
     }
     dmf::GramJobTable jobs{s->jobs.k, s->jobs.l, s->jobs.dst, s->jobs.n};
     if (kind == dmf::GramKind::GramMfma) {
         int ny = 0;
-        HIP_TRY(dmf::launch_gram_mfma(pv, s->u, n_u, jobs, s->jobs.n - n_u, s->slab, s->slab_doubles, done, &ny, ctx->stream));
+        HIP_TRY(dmf::launch_gram_mfma(pv, s->u, n_u, jobs, s->jobs.n - n_u, s->slab, s->slab_doubles, done, &ny, ctx->stream, ran));
         HIP_TRY(dmf::launch_gram_reduce(s->slab, ny, s->jobs.n, S, s->jobs.dst, s->gb, done, ctx->stream));
         return DMF_OK;
     }
-    HIP_TRY(dmf::launch_gram(pv, s->u, n_u, jobs, s->slab, s->slab_doubles, s->gb, done, ctx->stream));
+    HIP_TRY(dmf::launch_gram(pv, s->u, n_u, jobs, s->slab, s->slab_doubles, s->gb, done, ctx->stream, ran));
     return DMF_OK;
 }
 
@@ -119,7 +145,7 @@ int enqueue_alpha_phase(dmf_solver* s, dmf::AlphaKind kind, int n_iter2) {
 static int enqueue_gram_i8_tail(dmf_solver* s, dmf::AlphaKind alpha, int n_iter2, int grid) {
     {
         FamilyScope scope(s->ctx, DMF_KERNEL_GRAM);
-        DMF_TRY(gram_i8_and_reduce(s, grid, s->u2_partials, grid));
+        DMF_TRY(gram_i8_and_reduce(s, solver_i8_buffers(s), grid, s->u2_partials, grid));
     }
     return enqueue_alpha_phase(s, alpha, n_iter2);
 }
@@ -591,6 +617,56 @@ int dmf_solver_holdout_error(dmf_solver* s, const dmf_problem* full, double* sum
         pv.D = weights, pv.D16 = nullptr, pv.SD = 0;
     }
     return cost_to_host(ctx, pv, s->u, s->alpha, (int)s->n_u, sum_sq, true);
+}
+
+// dmf_solver_gram once its arguments are checked: the work on the stream.  Whatever it returns, the caller waits for the
+// stream before the temporaries of this frame have gone back to the pool for long and clears in_flight.
+static int solver_gram_enqueue(dmf_solver* s, int kind, double* out_gb, dmf::GramRan* ran) {
+    dmf_context* ctx = s->ctx;
+    const dmf_problem* p = s->p;
+    const int64_t N = p->N, S = p->S, n_c = p->n_c, n_u = s->n_u, K = n_c + n_u;
+    const size_t gbn = (size_t)(K + 1) * (K + 2) / 2 * S;
+    DevBuf<double> slab_bu;  // (the temporaries of the integer kind live until the wait at the bottom)
+    DevBuf<long long> slab_i8, acc;
+    if (kind == DMF_GRAM_FP64) {
+        DMF_TRY(enqueue_gram(s, fp64_gram_kind(s), false, ran));
+    } else {
+        // whatever select_path chose for the solver: temporaries of the sizes problem_finalize / solver_setup allocate
+        GramI8Buffers b;
+        b.slab_i8_words = dmf::gram_i8_slab_words(N, p->SD, (int)n_c, (int)n_u);
+        const size_t acc_words = (size_t)dmf::gram_i8_acc_words((int)S, (int)n_c, (int)n_u);
+        HIP_TRY(slab_bu.alloc(ctx, (size_t)dmf::bu_cols_grid(N) * n_u * S));
+        HIP_TRY(slab_i8.alloc(ctx, (size_t)b.slab_i8_words));
+        HIP_TRY(acc.alloc(ctx, acc_words));
+        HIP_TRY(hipMemsetAsync(acc, 0, acc_words * sizeof(long long), ctx->stream));
+        b.slab_bu = slab_bu, b.slab_i8 = slab_i8, b.acc = acc, b.gb = s->gb;
+        FamilyScope scope(ctx, DMF_KERNEL_GRAM);
+        DMF_TRY(gram_bu_cols_i8(s, b, ran));
+    }
+    HIP_TRY(hipMemcpyAsync(out_gb, s->gb, gbn * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    return DMF_OK;
+}
+
+int dmf_solver_gram(dmf_solver* s, int kind, double* out_gb, char* out_text, int64_t cap) {
+    if (s == nullptr || out_gb == nullptr || (kind != DMF_GRAM_INTEGER && kind != DMF_GRAM_FP64)) return DMF_ERR_BAD_ARG;
+    if (out_text != nullptr && cap < 1) return DMF_ERR_BAD_ARG;
+    dmf_context* ctx = s->ctx;
+    DMF_TRY(check_ctx(ctx));
+    const dmf_problem* p = s->p;
+    if (kind == DMF_GRAM_INTEGER &&
+        (p->ND < 1 || p->D16 == nullptr || p->Dt8 == nullptr || (p->n_c > 0 && p->Rtp == nullptr) ||
+         (reinterpret_cast<uintptr_t>(p->Rtp.get()) & 15) != 0 ||
+         !dmf::gram_i8_supported((int)p->n_c, (int)s->n_u, p->ND, p->N, p->SD)))
+        return DMF_ERR_UNSUPPORTED;
+    dmf::GramRan ran;
+    s->in_flight = true;
+    const int status = solver_gram_enqueue(s, kind, out_gb, &ran);
+    // on an error path too: nothing of this call stays on the stream behind its temporaries, and the flag is cleared
+    if (status != DMF_OK) (void)hipStreamSynchronize(ctx->stream);
+    s->in_flight = false;
+    if (status == DMF_OK && out_text != nullptr) snprintf(out_text, (size_t)cap, "%s", ran.text);
+    return status;
 }
 
 int dmf_solver_destroy(dmf_solver* s) {

@@ -174,9 +174,15 @@ hipError_t launch_cost_plan(const CostPlan& plan, const ProblemView& p, const do
 int vdv_cols_grid(int64_t N);
 hipError_t launch_vdv_cols(const ProblemView& p, double* slab, double* out, hipStream_t st);
 
+// What a Gram launcher ran, as text: the kernel, its template arguments and the number of launches (dmf_solver_gram
+// reports it).  Written by the launcher itself, next to the launch.
+struct GramRan {
+    char text[192] = "";
+};
+
 // generic weighted Gram accumulation over the extended row vector x = (Rt, u, v)
 hipError_t launch_gram(const ProblemView& p, const double* u, int n_u, GramJobTable jobs, double* slab, int64_t slab_doubles,
-                       double* gb, const int* done_flag, hipStream_t st);
+                       double* gb, const int* done_flag, hipStream_t st, GramRan* ran = nullptr);
 int64_t gram_slab_doubles(int64_t N, int S, int n_jobs);
 hipError_t launch_gram_reduce(const double* slab, int ny, int n_jobs, int S, const int* dst_row,
                               double* gb, const int* done_flag, hipStream_t st);
@@ -185,7 +191,7 @@ hipError_t launch_gram_reduce(const double* slab, int ny, int n_jobs, int S, con
 bool gram_u_supported(int n_c, int n_u);
 int64_t gram_u_slab_doubles(int64_t N, int S, int n_c, int n_u);
 hipError_t launch_gram_u(const ProblemView& p, const double* u, int n_u, double* slab, const int* done_flag, int* ny_out,
-                         hipStream_t st);
+                         hipStream_t st, GramRan* ran = nullptr);
 
 // u phase, Gram form (n_u <= 8): all n_iter2 inner iterations in one launch
 hipError_t launch_u_phase_gram(const ProblemView& p, const IterateView& it, int n_iter2, hipStream_t st);
@@ -247,7 +253,7 @@ hipError_t launch_u_phase_big(const ProblemView& p, const IterateView& it, int n
 // any-shape Gram accumulation on the matrix cores (dmf_kernels_gram_mfma.hip): jobs [0, n_dense) have l < K,
 // the rest are the "v" column; the slab ([ny][count][S]) is then summed by launch_gram_reduce
 hipError_t launch_gram_mfma(const ProblemView& p, const double* u, int n_u, GramJobTable jobs, int n_dense, double* slab,
-                            int64_t slab_doubles, const int* done_flag, int* ny_out, hipStream_t st);
+                            int64_t slab_doubles, const int* done_flag, int* ny_out, hipStream_t st, GramRan* ran = nullptr);
 int64_t gram_mfma_slab_doubles(int64_t N, int S, int n_jobs);
 
 // ---- second-generation row pass (dmf_kernels_rowpass2.hip) + integer-matrix-core Gram (dmf_kernels_gram_i8.hip)
@@ -296,6 +302,22 @@ hipError_t launch_rowpass_v2(const ProblemView& p, const IterateView& it, int n_
 // the X16 row pass can run two blocks per phase B at this shape: 2..4 waves, and the grid's workgroups per CU fit the LDS
 bool rowpass_v2_pair_fits(int S, int n_u, int n_iter2);
 bool gram_i8_supported(int n_c, int n_u, int ND, int64_t N, int SD);
+// What launch_gram_i8 launches for a shape -- the one geometry result that the launcher dispatches on and that
+// describe_gram_i8_plan prints (dmf_gram_i8_describe), so that the text cannot say anything else than what runs.
+// n_u = 0: the known block (features = pairs of R_trunc columns).
+struct GramI8Plan {
+    bool supported = false;
+    int xl = 1, nd = 1, ring = 8;  // template arguments of k_gram_i8_w8: DMA pieces of a block's row image, count digits, ring slots
+    int nf = 0, launches = 0;      // features, launches of 64 features each
+    int nsh = 0, ny = 0;           // workgroups per row range (128 samples each), row ranges: the grid is nsh * ny
+    int64_t rows_per_wg = 0;       // rows of a range (a multiple of 32)
+    int blocks = 0, last = 0;      // 32-row blocks of a full range, of the last range
+    int tail = 0;                  // N % 32: rows of the ragged last block (0: none)
+    bool xcd = false;              // ny % 8 == 0: the kernel maps the workgroups of a range onto one XCD
+};
+GramI8Plan gram_i8_plan(int64_t N, int SD, int n_c, int n_u, int ND);
+// "k_gram_i8_w8<2,2,6> launches=3 nsh=16 ny=16 blocks=9 last=8 tail=27 xcd=1"
+void describe_gram_i8_plan(const GramI8Plan& g, char* buf, size_t cap);
 int64_t gram_i8_slab_words(int64_t N, int SD, int n_c, int n_u);  // i64 words of the slab
 int64_t gram_i8_acc_words(int S, int n_c, int n_u);               // i64 words of the reduction scratch (zero-initialised)
 // the known block of the packed Gram through the same kernels (features = pairs of R_trunc columns; n_u = 0)
@@ -306,7 +328,8 @@ int64_t gram_i8_acc_words_nf(int S, int nf, int n_bu);
 // Rtp = the padded R_trunc copy (rows of 4 ceil(n_c / 4) doubles); Rtp, u, Dt8 16-byte aligned, u allocated to a
 // multiple of 16 bytes
 hipError_t launch_gram_i8(const ProblemView& p, const double* u, int n_u, const short* feat_a, const short* feat_b, int NF,
-                          long long* slab, int64_t slab_words, const int* done_flag, int* ny_out, hipStream_t st);
+                          long long* slab, int64_t slab_words, const int* done_flag, int* ny_out, hipStream_t st,
+                          GramRan* ran = nullptr);
 // b_u alone (for u phases that are kernels of their own): slab [n_slabs][n_u][S] doubles, n_u <= 20
 int bu_cols_grid(int64_t N);
 hipError_t launch_bu_cols(const ProblemView& p, const double* u, int n_u, double* slab, const int* done_flag,

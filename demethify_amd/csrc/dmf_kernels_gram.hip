@@ -8,6 +8,8 @@
 //     uu[j<=l]    += d * u_ij * u_il         (NU (NU+1) / 2)
 //     bu[j]       += d * v * u_ij            (NU)
 // Job order of the slab = the solver's job table (dmf_api_solver.hip: l = n_c..K, k <= l).
+#include <cstdio>
+
 #include "dmf_device.h"
 #include "dmf_dispatch.h"
 #include "dmf_internal.h"
@@ -148,7 +150,7 @@ int64_t gram_u_slab_doubles(int64_t N, int S, int n_c, int n_u) {
 }
 
 hipError_t launch_gram_u(const ProblemView& p, const double* u, int n_u, double* slab, const int* done_flag, int* ny_out,
-                         hipStream_t st) {
+                         hipStream_t st, GramRan* ran) {
     return dispatch_int<0, 4>((p.n_c + 3) / 4, [&](auto nkc) {
         return dispatch_int<1, 13>(n_u, [&](auto nu) {
             constexpr int NCT = 4 * decltype(nkc)::value, NU = decltype(nu)::value;
@@ -159,6 +161,7 @@ hipError_t launch_gram_u(const ProblemView& p, const double* u, int n_u, double*
                 *ny_out = ny;
                 hipLaunchKernelGGL((k_gram_u<NCT, NU>), dim3(nsx, ny), dim3(256), 0, st, p.V, p.D, p.Rtp, u, p.N, p.S, p.n_c, rpc,
                                    slab, done_flag);
+                if (ran != nullptr) snprintf(ran->text, sizeof(ran->text), "k_gram_u<%d,%d> launches=1 ny=%d", NCT, NU, ny);
                 return hipGetLastError();
             } else {
                 return hipErrorInvalidValue;

@@ -22,6 +22,7 @@
 // dtype-independent 32x32 map.  A workgroup = 8 waves = 4 sample blocks (128 samples) x 2 feature halves x one row
 // range, accumulators in registers over the whole range (7 or 8 tiles of 16 VGPRs per wave, two waves per SIMD).
 #include <cstdint>
+#include <cstdio>
 #include <cstdlib>
 
 #include "dmf_device.h"
@@ -876,27 +877,42 @@ void gram_i8_geometry(int64_t N, int SD, int* nsh, int* ny, int64_t* rows_per_wg
     *ny = (int)((N + rpw - 1) / rpw);
 }
 
+// The one geometry result of a shape: launch_gram_i8 dispatches on it and describe_gram_i8_plan prints it.
+GramI8Plan gram_i8_plan(int64_t N, int SD, int n_c, int n_u, int ND) {
+    GramI8Plan g;
+    if (N < 1 || SD < 64 || SD % 64 != 0 || n_c < 0 || n_u < 0) return g;
+    const int nct = (n_c + 3) / 4 * 4;
+    g.nf = n_u > 0 ? n_c * n_u + n_u * (n_u + 1) / 2 : n_c * (n_c + 1) / 2;
+    g.nd = ND;
+    g.xl = nct + n_u > 16 ? 2 : 1;  // x image of a block beyond 4 KB: two DMA pieces per thread
+    // (wide with two digits: 16-KB block slots: a ring of six is what the LDS holds beside the three A tiles)
+    g.ring = g.xl == 2 && ND == 2 ? 6 : kRing;
+    g.launches = (g.nf + 63) / 64;  // 64 features per launch (lane = feature slot of a 64-lane wave; two feature halves of 32)
+    gram_i8_geometry(N, SD, &g.nsh, &g.ny, &g.rows_per_wg);
+    g.blocks = (int)(g.rows_per_wg / 32);
+    g.last = (int)((N - (int64_t)(g.ny - 1) * g.rows_per_wg + 31) / 32);
+    g.tail = (int)(N & 31);
+    g.xcd = g.ny % 8 == 0;
+    // (a block's x image -- 32 rows of the padded R_trunc copy and of u -- is fetched as at most two 4-KB pieces;
+    // i32 accumulators cannot overflow within a row range)
+    g.supported = nct + n_u <= 32 && g.nf >= 1 && g.nf <= kMaxFeat && ND >= 1 && ND <= 2 &&
+                  g.rows_per_wg * 128 * 128 * ND < (int64_t)1 << 31;
+    return g;
+}
+
+void describe_gram_i8_plan(const GramI8Plan& g, char* buf, size_t cap) {
+    snprintf(buf, cap, "k_gram_i8_w8<%d,%d,%d> launches=%d nsh=%d ny=%d blocks=%d last=%d tail=%d xcd=%d", g.xl, g.nd, g.ring,
+             g.launches, g.nsh, g.ny, g.blocks, g.last, g.tail, g.xcd ? 1 : 0);
+}
+
 bool gram_i8_supported(int n_c, int n_u, int ND, int64_t N, int SD) {
-    const int nf = n_c * n_u + n_u * (n_u + 1) / 2;
-    // (a block's x image -- 32 rows of the padded R_trunc copy and of u -- is fetched as at most two 4-KB pieces)
-    if ((n_c + 3) / 4 * 4 + n_u > 32 || nf < 1 || nf > kMaxFeat || ND < 1 || ND > 2) return false;
-    int nsh, ny;
-    int64_t rpw;
-    gram_i8_geometry(N, SD, &nsh, &ny, &rpw);
-    return rpw * 128 * 128 * ND < (int64_t)1 << 31;  // i32 accumulators cannot overflow within a row range
+    return n_u >= 1 && gram_i8_plan(N, SD, n_c, n_u, ND).supported;
 }
 
 // The known block of a problem's packed Gram (dmf_api_problem.hip, problem_finalize) through the same kernels: its dense pairs
 // (R_trunc column k x column l) are features whose two factors both come from the R_trunc image (n_u = 0), its
 // right-hand sides sum_i Rt_ik d_is v_is are k_bu_cols with R_trunc in the place of u.
-bool gram_i8_known_supported(int n_c, int ND, int64_t N, int SD) {
-    const int nf = n_c * (n_c + 1) / 2;
-    if (n_c < 1 || (n_c + 3) / 4 * 4 > 32 || nf > kMaxFeat || ND < 1 || ND > 2) return false;
-    int nsh, ny;
-    int64_t rpw;
-    gram_i8_geometry(N, SD, &nsh, &ny, &rpw);
-    return rpw * 128 * 128 * ND < (int64_t)1 << 31;
-}
+bool gram_i8_known_supported(int n_c, int ND, int64_t N, int SD) { return gram_i8_plan(N, SD, n_c, 0, ND).supported; }
 int64_t gram_i8_slab_words_nf(int64_t N, int SD, int nf) {
     int nsh, ny;
     int64_t rpw;
@@ -921,31 +937,32 @@ int64_t gram_i8_acc_words(int S, int n_c, int n_u) {
 size_t gram_i8_w8_lds_bytes(int xl, int nd, int ring) { return (size_t)ring * (4096 * nd + xl * 4096) + (size_t)3 * 2 * (kNSL * 64) * 16; }
 
 hipError_t launch_gram_i8(const ProblemView& p, const double* u, int n_u, const short* fa, const short* fb, int NF,
-                          long long* slab, int64_t slab_words, const int* done_flag, int* ny_out, hipStream_t st) {
+                          long long* slab, int64_t slab_words, const int* done_flag, int* ny_out, hipStream_t st, GramRan* ran) {
     const int SD = p.SD, n_c = p.n_c;
-    int nsh, ny;
-    int64_t rpw;
-    gram_i8_geometry(p.N, SD, &nsh, &ny, &rpw);
+    const GramI8Plan g = gram_i8_plan(p.N, SD, n_c, n_u, p.ND);
+    if (!g.supported || g.nf != NF) return hipErrorInvalidValue;
+    const int ny = g.ny;
     *ny_out = ny;
     const int MFtot = (NF + 31) / 32 * 32;
     // every workgroup (row range) writes its own [2][MFtot][SD] slab: the buffer must hold all of them
-    if ((int64_t)ny * 2 * MFtot * SD > slab_words || rpw * 128 * 128 * p.ND >= (int64_t)1 << 31) return hipErrorInvalidValue;
+    if ((int64_t)ny * 2 * MFtot * SD > slab_words) return hipErrorInvalidValue;
     // more than 64 features = more launches over the (small) 8-bit planes
-    const int chunk = 64;  // features per launch (lane = feature slot of a 64-lane wave; two feature halves of 32)
-    const bool wide = (n_c + 3) / 4 * 4 + n_u > 16;  // x image of a block beyond 4 KB: two DMA pieces per thread
+    const int chunk = 64;
+    int launches = 0;
     for (int p0 = 0; p0 < NF; p0 += chunk) {
         const int nf = NF - p0 < chunk ? NF - p0 : chunk;
         // one count digit, or two (some count above 127: what sequencing data looks like)
-        const hipError_t e = dispatch_bool(p.ND == 1, [&](auto one_digit) {
-            return dispatch_bool(wide, [&](auto wide_t) {
+        const hipError_t e = dispatch_bool(g.nd == 1, [&](auto one_digit) {
+            return dispatch_bool(g.xl == 2, [&](auto wide_t) {
                 constexpr int XL = decltype(wide_t)::value ? 2 : 1, ND = decltype(one_digit)::value ? 1 : 2;
-                // (wide with two digits: 16-KB block slots: a ring of six is what the LDS holds beside the three A tiles)
                 constexpr int RING = XL == 2 && ND == 2 ? 6 : kRing;
+                if (RING != g.ring) return hipErrorInvalidValue;  // (the plan names the instance)
                 const size_t lds = gram_i8_w8_lds_bytes(XL, ND, RING);
                 const hipError_t e_lds = raise_dynamic_lds<k_gram_i8_w8<XL, ND, RING>>(lds);
                 if (e_lds != hipSuccess) return e_lds;
-                hipLaunchKernelGGL((k_gram_i8_w8<XL, ND, RING>), dim3(nsh * ny), dim3(512), lds, st, p.Dt8, p.plane_stride, SD / 32,
-                                   p.Rtp, (n_c + 3) / 4 * 4, u, p.N, n_c, n_u, fa, fb, nf, p0, MFtot, rpw, slab, SD, done_flag
+                hipLaunchKernelGGL((k_gram_i8_w8<XL, ND, RING>), dim3(g.nsh * ny), dim3(512), lds, st, p.Dt8, p.plane_stride, SD / 32,
+                                   p.Rtp, (n_c + 3) / 4 * 4, u, p.N, n_c, n_u, fa, fb, nf, p0, MFtot, g.rows_per_wg, slab, SD,
+                                   done_flag
 #ifdef DMF_STAMPS
                                    , (unsigned long long*)nullptr
 #endif
@@ -954,7 +971,10 @@ hipError_t launch_gram_i8(const ProblemView& p, const double* u, int n_u, const 
             });
         });
         if (e != hipSuccess) return e;
+        ++launches;
     }
+    if (launches != g.launches) return hipErrorInvalidValue;
+    if (ran != nullptr) describe_gram_i8_plan(g, ran->text, sizeof(ran->text));
     return hipSuccess;
 }
 

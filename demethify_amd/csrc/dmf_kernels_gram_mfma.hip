@@ -16,6 +16,8 @@
 // Layouts (tools/mfma_probe.hip): A[i][k]: lane (i = l & 15, k = l >> 4); B[k][j]: lane (k = l >> 4, j = l & 15);
 // C register r of lane l = C[(l >> 4) + 4 r][l & 15].
 // Output: slab[y][job][s] per row chunk y, summed in fixed order by k_gram_reduce: deterministic.
+#include <cstdio>
+
 #include "dmf_dispatch.h"
 #include "dmf_internal.h"
 
@@ -243,7 +245,7 @@ int64_t gram_mfma_slab_doubles(int64_t N, int S, int n_jobs) {
 
 // jobs [0, n_dense) have B = D, jobs [n_dense, count) are the "v" column (B = D * V); ny_out = slab rows per job
 hipError_t launch_gram_mfma(const ProblemView& p, const double* u, int n_u, GramJobTable jobs, int n_dense, double* slab,
-                            int64_t slab_doubles, const int* done_flag, int* ny_out, hipStream_t st) {
+                            int64_t slab_doubles, const int* done_flag, int* ny_out, hipStream_t st, GramRan* ran) {
     const int S = p.S;
     if (jobs.count <= 0 || n_dense < 0 || n_dense > jobs.count || p.n_c + n_u > kMaxK) return hipErrorInvalidValue;
     int nsx, ny;
@@ -253,7 +255,7 @@ hipError_t launch_gram_mfma(const ProblemView& p, const double* u, int n_u, Gram
     *ny_out = ny;
     const dim3 grid(nsx, ny), block(kGramMfmaWaves * 64);
     const bool dma = (S & 1) == 0 && S >= 2 && ((uintptr_t)p.D & 15) == 0 && ((uintptr_t)p.V & 15) == 0;
-    int d_begin = 0, v_begin = n_dense;
+    int d_begin = 0, v_begin = n_dense, launches = 0, mtw_first = 0;
     while (d_begin < n_dense || v_begin < jobs.count) {
         const int tiles_d = (n_dense - d_begin + 15) / 16, tiles_v = (jobs.count - v_begin + 15) / 16;
         // smallest tiles-per-wave that fits both kinds on 8 waves; what does not fit waits for the next launch
@@ -277,9 +279,13 @@ hipError_t launch_gram_mfma(const ProblemView& p, const double* u, int n_u, Gram
             });
         });
         if (e != hipSuccess) return e;
+        if (launches++ == 0) mtw_first = mtw;
         d_begin = d_end;
         v_begin = v_end;
     }
+    // (the tiles per wave of the first launch: a later launch takes what was left over and may need fewer)
+    if (ran != nullptr)
+        snprintf(ran->text, sizeof(ran->text), "k_gram_mfma<%d,%s> launches=%d ny=%d", mtw_first, dma ? "dma" : "reg", launches, ny);
     return hipSuccess;
 }
 

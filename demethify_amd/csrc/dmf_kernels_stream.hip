@@ -698,7 +698,7 @@ hipError_t launch_gram_reduce(const double* slab, int ny, int n_jobs, int S, con
 }
 
 hipError_t launch_gram(const ProblemView& p, const double* u, int n_u, GramJobTable jobs, double* slab, int64_t slab_doubles,
-                       double* gb, const int* done_flag, hipStream_t st) {
+                       double* gb, const int* done_flag, hipStream_t st, GramRan* ran) {
     if (jobs.count <= 0) return hipSuccess;
     const int S = p.S;
     int nsx, nz, ny;
@@ -709,6 +709,7 @@ hipError_t launch_gram(const ProblemView& p, const double* u, int n_u, GramJobTa
                        jobs.k_idx, jobs.l_idx, jobs.count, rpc, slab, done_flag);
     hipLaunchKernelGGL(k_gram_reduce, dim3((S + 31) / 32, jobs.count), dim3(256), 0, st, slab, ny,
                        jobs.count, S, jobs.dst_row, gb, done_flag);
+    if (ran != nullptr) snprintf(ran->text, sizeof(ran->text), "k_gram launches=1 ny=%d nz=%d", ny, nz);
     return hipGetLastError();
 }
 

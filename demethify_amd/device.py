@@ -69,6 +69,7 @@ class Context:
                 "dmf_context_create")
         self._h = h
         self.device = int(device)
+        self.generic_level = 0  # what set_generic last set: tests that change it put it back
 
     def close(self):
         if getattr(self, "_h", None):
@@ -97,6 +98,7 @@ class Context:
         then 3), 1 any-shape Gram-form kernels, 2 schedule-faithful one-launch-per-inner-step kernels, 3 the unfused
         MFMA row pass + one-pass Gram pair, 4 the first-generation fused FP64 row pass.  Set before creating Problems."""
         L.check(self._lib.dmf_context_set_generic(self._h, int(level)), "dmf_context_set_generic")
+        self.generic_level = int(level)
 
     def set_x16(self, enabled: bool):
         """Whether Problems created from now on carry X16, the methylated read counts x = rint(v d) as u16, when every
@@ -323,6 +325,15 @@ class Problem:
         L.check(self._lib.dmf_problem_cost_describe(self.ctx._h, self._h, int(n_u), buf, len(buf)),
                 "dmf_problem_cost_describe")
         return buf.value.decode()
+
+    def gram_known(self):
+        """(gb_known, text): the known block of the packed Gram as problem creation left it -- ((n_c + 1)(n_c + 2) / 2, S),
+        row l (l + 1) / 2 + k for k <= l over (R_trunc columns, v) -- and the route that computed it, "int_known ..." or
+        "fp64 ..." (dmf_problem_gram_known).  For tests."""
+        out = np.empty(((self.n_c + 1) * (self.n_c + 2) // 2, self.S), dtype=np.float64)
+        buf = C.create_string_buffer(256)
+        L.check(self._lib.dmf_problem_gram_known(self._h, _ptr(out), buf, len(buf)), "dmf_problem_gram_known")
+        return out, buf.value.decode()
 
     def wls_intercept(self, u=None, target="v", host_arrays=None, f64_arrays=False):
         """``wls_intercept`` (init_func.py:8-14) of every sample at once on the device (dmf_wls_intercept), with
@@ -616,6 +627,20 @@ class Solver:
         buf = C.create_string_buffer(512)
         L.check(self._lib.dmf_solver_describe(self._h, int(n_iter2), buf, len(buf)), "dmf_solver_describe")
         return buf.value.decode()
+
+    def gram(self, kind="integer"):
+        """(gb, text): the packed Gram ((K + 1)(K + 2) / 2, S) for the solver's CURRENT u, computed now by the kernels a step
+        calls, and what ran (dmf_solver_gram).  ``kind``: "integer" (k_bu_cols + k_gram_i8_w8 + reduce + finish; u must lie
+        in [0, 1]; DMF_ERR_UNSUPPORTED where the integer Gram does not take the problem) or "fp64" (k_gram_u / k_gram_mfma /
+        k_gram, as the solver's selection names).  For tests: the iterate and a later step() are unaffected."""
+        try:
+            k = {"integer": L.DMF_GRAM_INTEGER, "fp64": L.DMF_GRAM_FP64}[kind]
+        except KeyError:
+            raise ValueError(f'kind must be "integer" or "fp64", got {kind!r}') from None
+        out = np.empty(((self.K + 1) * (self.K + 2) // 2, self.problem.S), dtype=np.float64)
+        buf = C.create_string_buffer(256)
+        L.check(self._lib.dmf_solver_gram(self._h, k, _ptr(out), buf, len(buf)), "dmf_solver_gram")
+        return out, buf.value.decode()
 
     def stop_info(self):
         """How the stop tests of this solver's step() calls were decided (dmf_solver_stop_info): a dict with

@@ -141,6 +141,14 @@ int dmf_problem_gather_device(dmf_context* ctx, const dmf_problem* src, const in
 int dmf_problem_mask(dmf_context* ctx, const dmf_problem* src, const uint8_t* train_bits, int flags, dmf_problem** out);
 int dmf_problem_destroy(dmf_problem* p);
 int dmf_problem_shape(const dmf_problem* p, int64_t* N, int64_t* S, int64_t* n_c);
+/* The known block of the problem's packed Gram as dmf_problem_create left it, for tests: out ((n_c + 1)(n_c + 2) / 2 x S host
+ * doubles) <- row tri(k, l) = l (l + 1) / 2 + k, k <= l <= n_c, over the extended indices (R_trunc columns, then v): the dense
+ * pairs sum_i Rt_ik Rt_il d_is, the right-hand sides sum_i Rt_ik d_is v_is (l = n_c) and v^T D v (k = l = n_c).  out_text (may
+ * be NULL) names the route and every launcher that wrote rows, in launch order: "int_known k_gram_i8_w8<...> ... + k_bu_cols2
+ * with vDv" (the integer matrix cores, the text of dmf_gram_i8_describe with n_u = 0, then the stream kernel of the right-hand
+ * sides; "+ k_bu_cols + k_vdv_cols" or "+ k_bu_cols + k_gram launches=1 .." where v^T D v takes a kernel of its own), "fp64 k_gram_mfma<...> launches=.. ny=.. +
+ * k_vdv_cols", "fp64 k_gram launches=1 ..." (levels 1 and 2), "fp64 k_vdv_cols" (n_c = 0). */
+int dmf_problem_gram_known(const dmf_problem* p, double* out, char* out_text, int64_t cap);
 
 /* ---- single-function entry points (KAT parity of SURVEY.md section 8a rows 1-4) --------- */
 /* cost_f_w(y, R, alpha, d_x), deconvolution.py:15-17, with R = [Rt | u]. */
@@ -159,6 +167,15 @@ int dmf_cost(dmf_context* ctx, const dmf_problem* p, const double* u, int64_t n_
 int dmf_cost_describe(int64_t S, int64_t n_c, int64_t n_u, int has_u16, int64_t SD, int v_align, int rtp_present, int level,
                       char* buf, int64_t cap);
 int dmf_problem_cost_describe(dmf_context* ctx, const dmf_problem* p, int64_t n_u, char* buf, int64_t cap);
+/* What the integer Gram (k_gram_i8_w8, csrc/dmf_kernels_gram_i8.hip) launches for a shape with nd = 1 | 2 count digit planes,
+ * a pure function like dmf_cost_describe: "k_gram_i8_w8<2,2,6> launches=3 nsh=16 ny=16 blocks=9 last=8 tail=27 xcd=1" --
+ * the template arguments <XL, ND, RING> (DMA pieces of a block's row image: 2 when padded n_c + n_u > 16; count digits; block
+ * slots of the LDS ring), launches of 64 features each, nsh workgroups of 128 samples per row range, ny row ranges, 32-row
+ * blocks of a full range and of the last one, tail = N % 32, xcd = 1 when ny % 8 == 0 (the kernel then keeps a range's
+ * workgroups on one XCD).  n_u = 0 describes the known block (features = pairs of R_trunc columns).  The launcher dispatches on
+ * the same plan.  DMF_ERR_UNSUPPORTED where the kernel does not take the shape (padded n_c + n_u > 32, more than 576
+ * features, a row range whose i32 sums could overflow). */
+int dmf_gram_i8_describe(int64_t N, int64_t S, int64_t n_c, int64_t n_u, int nd, char* buf, int64_t cap);
 /* projection_simplex_sort_2d(v, z), deconvolution.py:21-37; X and out are K x S. */
 int dmf_project_simplex(dmf_context* ctx, const double* X, int64_t K, int64_t S, double z,
                         int flags, double* out);
@@ -276,6 +293,19 @@ int dmf_solver_cost_end(dmf_solver* s, double* out_cost);
  * weights, run by the cost kernels where the iterate lives.  `full`: the problem the mask was applied to (same N, S, n_c:
  * DMF_ERR_BAD_SHAPE otherwise).  DMF_ERR_BAD_ARG when the solver's problem is not a masked one.  Nothing held out: 0, 0. */
 int dmf_solver_holdout_error(dmf_solver* s, const dmf_problem* full, double* sum_sq, int64_t* n_test);
+/* The solver's packed Gram for its CURRENT u, computed now, for tests: out_gb ((K + 1)(K + 2) / 2 x S host doubles, row
+ * tri(k, l) as above over (R_trunc columns, u columns, v)) <- the known block as it stands plus the u-dependent entries
+ * (cross, uu) and b_u, by the functions a step itself calls.  kind = DMF_GRAM_INTEGER: k_bu_cols / k_bu_cols2, k_gram_i8_w8,
+ * k_gram_v2_reduce, k_gram_v2_finish, whatever path the solver itself runs, in temporaries of its own; u MUST lie in [0, 1]
+ * (the fixed-point features: true of every iterate behind a u phase, the caller's business for a u0); DMF_ERR_UNSUPPORTED
+ * without integer count copies or where dmf_gram_i8_describe says so.  kind = DMF_GRAM_FP64: k_gram_u, k_gram_mfma or k_gram,
+ * as the solver's selection names at the level it was created at.  A converged solver computes too (no done flag is passed);
+ * u_norm2 / l_h and the iterate are left alone, and the solver's own Gram buffer is rewritten by the next step before it
+ * is read, so stepping on gives the same bits as without this call.  out_text (may be NULL): what ran, the text of
+ * dmf_gram_i8_describe, or "k_gram_u<NCT,NU> launches=1 ny=..", "k_gram_mfma<MTW,dma|reg> launches=.. ny=..",
+ * "k_gram launches=1 ny=.. nz=..". */
+enum { DMF_GRAM_INTEGER = 0, DMF_GRAM_FP64 = 1 };
+int dmf_solver_gram(dmf_solver* s, int kind, double* out_gb, char* out_text, int64_t cap);
 int dmf_solver_destroy(dmf_solver* s);
 /* Which kernels a step with n_iter2 inner iterations would launch for this solver, as text, e.g.
  * "rowpass=k_rowpass_fused<3,4> nw=4 grid=256 tail=5 gram=fused alpha=k_alpha_phase_row16".  For tests (every
