@@ -20,7 +20,8 @@ DMF_WLS_TARGET_V, DMF_WLS_TARGET_DV = 0, 1
 DMF_WLS_F64_ARRAYS = 8
 DMF_ERR_BAD_ARG, DMF_ERR_NONFINITE, DMF_ERR_UNSUPPORTED = 1, 4, 5
 DMF_ERR_BAD_SHAPE = 2
-DMF_GRAM_INTEGER, DMF_GRAM_FP64 = 0, 1
+DMF_GRAM_INTEGER, DMF_GRAM_FP64, DMF_GRAM_LAST = 0, 1, 2
+DMF_ROUTE_SOLVER, DMF_ROUTE_UPDATE_U = 0, 1
 DMF_MODE_PARTIAL = 0
 DMF_MODE_UNSUPERVISED = 1
 MAX_K = 64  # dmf::kMaxK: largest n_c + n_u the kernels are built for (DMF_ERR_UNSUPPORTED beyond)
@@ -87,6 +88,8 @@ SIGNATURES = {
     "dmf_solver_destroy": (C.c_int, [_p]),
     "dmf_solver_describe": (C.c_int, [_p, _i64, C.c_char_p, _i64]),
     "dmf_select_describe": (C.c_int, [_i64, _i64, _i64, _i64, C.c_int, C.c_int, _i64, C.c_int, C.c_char_p, _i64]),
+    "dmf_u_phase_describe": (C.c_int, [_i64, _i64, _i64, _i64, C.c_int, C.c_int, _i64, C.c_int, C.c_int, C.c_char_p, _i64]),
+    "dmf_solver_u_phase_describe": (C.c_int, [_p, _i64, C.c_int, C.c_char_p, _i64]),
     "dmf_solver_stop_info": (C.c_int, [_p, C.POINTER(C.c_int), C.POINTER(_i64), C.POINTER(_i64), _dbl_p]),
     "dmf_solver_rowpass_launches": (C.c_int, [_p, C.POINTER(_i64), C.POINTER(_i64)]),
     "dmf_table_scan": (C.c_int, [C.c_char_p, C.c_char, C.POINTER(_i64), C.POINTER(C.c_int), C.POINTER(C.c_int),

@@ -234,6 +234,8 @@ struct dmf_solver {
     dmf_api::DevBuf<double> u, u_prev, u_next;
     dmf_api::DevBuf<double> alpha, alpha_prev;
     dmf_api::DevBuf<double> gb;
+    dmf::GramRan last_gram;  // what wrote the u-dependent rows of gb in the last outer iteration, as text (DMF_GRAM_LAST)
+    int last_gram_source = -1;
     dmf_api::DevBuf<double> slab;
     int64_t slab_doubles = 0;
     dmf_api::DevBuf<double> partials;

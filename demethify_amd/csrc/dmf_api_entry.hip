@@ -45,12 +45,12 @@ static int deliver_result(dmf_context* ctx, const double* dev, size_t count, int
 
 extern "C" {
 
-int dmf_select_describe(int64_t N, int64_t S, int64_t n_c, int64_t n_u, int nd, int level, int64_t n_iter2, int flags,
-                        char* buf, int64_t cap) {
+// the key of dmf_select_describe / dmf_u_phase_describe: what dmf_solver_create makes of such a problem
+static int select_key(int64_t N, int64_t S, int64_t n_c, int64_t n_u, int nd, int level, int64_t n_iter2, int flags,
+                      const char* buf, int64_t cap, dmf::ShapeKey& key) {
     if (buf == nullptr || cap < 1 || N < 1 || S < 1 || n_c < 0 || n_u < 1 || nd < 0 || nd > 2 || n_iter2 < 0 ||
         n_c + n_u > dmf::kMaxK)
         return DMF_ERR_BAD_ARG;
-    dmf::ShapeKey key;
     key.N = N;
     key.S = (int)S;
     key.n_c = (int)n_c;
@@ -65,6 +65,24 @@ int dmf_select_describe(int64_t N, int64_t S, int64_t n_c, int64_t n_u, int nd, 
     key.x16 = key.nd > 0 && (flags & DMF_SELECT_X16) != 0;
     key.rtp_align = 0;
     key.alpha_unit = !(flags & DMF_SELECT_ALPHA_OUTSIDE_UNIT);
+    return DMF_OK;
+}
+
+int dmf_u_phase_describe(int64_t N, int64_t S, int64_t n_c, int64_t n_u, int nd, int level, int64_t n_iter2, int flags, int route,
+                         char* buf, int64_t cap) {
+    dmf::ShapeKey key;
+    if (n_iter2 > (1 << 20) || S > (1 << 24) || (route != DMF_ROUTE_SOLVER && route != DMF_ROUTE_UPDATE_U)) return DMF_ERR_BAD_ARG;
+    DMF_TRY(select_key(N, S, n_c, n_u, nd, level, n_iter2, flags, buf, cap, key));
+    const dmf::PathSpec spec = dmf::select_path(key);
+    if (!spec.supported) return DMF_ERR_UNSUPPORTED;
+    dmf::describe_u_phase(key, spec, (int)n_iter2, (flags & DMF_SELECT_PURITY) != 0, route == DMF_ROUTE_UPDATE_U, buf, (size_t)cap);
+    return DMF_OK;
+}
+
+int dmf_select_describe(int64_t N, int64_t S, int64_t n_c, int64_t n_u, int nd, int level, int64_t n_iter2, int flags,
+                        char* buf, int64_t cap) {
+    dmf::ShapeKey key;
+    DMF_TRY(select_key(N, S, n_c, n_u, nd, level, n_iter2, flags, buf, cap, key));
     const dmf::PathSpec spec = dmf::select_path(key);
     if (!spec.supported) return DMF_ERR_UNSUPPORTED;
     const dmf::IterationPlan plan = dmf::plan_iteration(key, spec, (int)n_iter2, (flags & DMF_SELECT_PURITY) != 0);

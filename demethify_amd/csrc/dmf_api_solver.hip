@@ -54,11 +54,7 @@ int enqueue_u_phase(dmf_solver* s, int n_iter2, dmf::RowKind row) {
 
 // the row kind of a u phase that runs as a kernel of its own (the single-function entry points: dmf_update_u)
 dmf::RowKind standalone_row_kind(const dmf_solver* s, int n_iter2) {
-    dmf::PathSpec spec = s->spec;
-    spec.use_v2 = false;  // (plan_iteration then describes the split / fall-back u phase of this solver)
-    spec.use_fused = false;
-    spec.use_gram_i8 = false;
-    return dmf::plan_iteration(s->key, spec, n_iter2, false).row;
+    return dmf::plan_iteration(s->key, dmf::standalone_spec(s->spec), n_iter2, false).row;
 }
 
 // What the integer Gram route of a solver writes and works in: the solver's own buffers in the loop, temporaries of the
@@ -141,11 +137,20 @@ int enqueue_alpha_phase(dmf_solver* s, dmf::AlphaKind kind, int n_iter2) {
     return DMF_OK;
 }
 
+// Where the loop records what wrote its Gram (dmf_solver::last_gram, for DMF_GRAM_LAST) -- or null while the source is
+// the one already recorded: on one solver the text of a source does not change, and the loop formats nothing per iteration.
+constexpr int kLastGramI8Tail = 100, kLastGramFused = 101;  // (other sources: the GramKind of enqueue_gram)
+static dmf::GramRan* last_gram_slot(dmf_solver* s, int source) {
+    if (s->last_gram_source == source) return nullptr;
+    s->last_gram_source = source;
+    return &s->last_gram;
+}
+
 // what follows a row kernel that left `grid` b_u slabs and ||u||^2 shares: the integer Gram, its reduce, the alpha phase
 static int enqueue_gram_i8_tail(dmf_solver* s, dmf::AlphaKind alpha, int n_iter2, int grid) {
     {
         FamilyScope scope(s->ctx, DMF_KERNEL_GRAM);
-        DMF_TRY(gram_i8_and_reduce(s, solver_i8_buffers(s), grid, s->u2_partials, grid));
+        DMF_TRY(gram_i8_and_reduce(s, solver_i8_buffers(s), grid, s->u2_partials, grid, last_gram_slot(s, kLastGramI8Tail)));
     }
     return enqueue_alpha_phase(s, alpha, n_iter2);
 }
@@ -204,6 +209,9 @@ static int enqueue_outer_iteration(dmf_solver* s, int n_iter2) {
             HIP_TRY(dmf::launch_gram_u(tail, it_tail.u, it_tail.n_u, s->slab + (int64_t)2 * grid * s->jobs.n * S,
                                        &s->state->done, &ny_tail, ctx->stream));
         }
+        if (dmf::GramRan* ran = last_gram_slot(s, kLastGramFused))
+            snprintf(ran->text, sizeof(ran->text), "k_rowpass_fused<%d,%d> phase C slabs=%d%s", (int)(p->n_c + 3) / 4, (int)s->n_u,
+                     2 * grid, n_tail > 0 ? " + k_gram_u tail" : "");
         HIP_TRY(dmf::launch_finish_u_norm(s->u2_partials, grid + (n_tail > 0 ? 1 : 0), s->state, ctx->stream));
         {
             FamilyScope scope(ctx, DMF_KERNEL_GRAM);
@@ -216,7 +224,7 @@ static int enqueue_outer_iteration(dmf_solver* s, int n_iter2) {
     HIP_TRY(dmf::launch_sumsq_f64(s->u, p->N * s->n_u, ctx->scratch, &s->state->u_norm2, &s->state->done,
                                   ctx->stream));
     HIP_TRY(dmf::launch_set_lh(s->state, ctx->stream));
-    DMF_TRY(enqueue_gram(s, plan.gram));
+    DMF_TRY(enqueue_gram(s, plan.gram, true, last_gram_slot(s, (int)plan.gram)));
     return enqueue_alpha_phase(s, plan.alpha, n_iter2);
 }
 
@@ -628,7 +636,9 @@ static int solver_gram_enqueue(dmf_solver* s, int kind, double* out_gb, dmf::Gra
     const size_t gbn = (size_t)(K + 1) * (K + 2) / 2 * S;
     DevBuf<double> slab_bu;  // (the temporaries of the integer kind live until the wait at the bottom)
     DevBuf<long long> slab_i8, acc;
-    if (kind == DMF_GRAM_FP64) {
+    if (kind == DMF_GRAM_LAST) {
+        *ran = s->last_gram;  // nothing is computed: gb as the last outer iteration left it
+    } else if (kind == DMF_GRAM_FP64) {
         DMF_TRY(enqueue_gram(s, fp64_gram_kind(s), false, ran));
     } else {
         // whatever select_path chose for the solver: temporaries of the sizes problem_finalize / solver_setup allocate
@@ -649,7 +659,8 @@ static int solver_gram_enqueue(dmf_solver* s, int kind, double* out_gb, dmf::Gra
 }
 
 int dmf_solver_gram(dmf_solver* s, int kind, double* out_gb, char* out_text, int64_t cap) {
-    if (s == nullptr || out_gb == nullptr || (kind != DMF_GRAM_INTEGER && kind != DMF_GRAM_FP64)) return DMF_ERR_BAD_ARG;
+    if (s == nullptr || out_gb == nullptr || (kind != DMF_GRAM_INTEGER && kind != DMF_GRAM_FP64 && kind != DMF_GRAM_LAST))
+        return DMF_ERR_BAD_ARG;
     if (out_text != nullptr && cap < 1) return DMF_ERR_BAD_ARG;
     dmf_context* ctx = s->ctx;
     DMF_TRY(check_ctx(ctx));
@@ -689,6 +700,14 @@ int dmf_solver_describe(const dmf_solver* s, int64_t n_iter2, char* buf, int64_t
     if (s == nullptr || buf == nullptr || cap < 1 || n_iter2 < 0) return DMF_ERR_BAD_ARG;
     const dmf::IterationPlan plan = dmf::plan_iteration(s->key, s->spec, (int)n_iter2, s->purity != nullptr);
     dmf::describe_plan(s->key, plan, buf, (size_t)cap);
+    return DMF_OK;
+}
+
+int dmf_solver_u_phase_describe(const dmf_solver* s, int64_t n_iter2, int route, char* buf, int64_t cap) {
+    if (s == nullptr || buf == nullptr || cap < 1 || n_iter2 < 0 || n_iter2 > (1 << 20) ||
+        (route != DMF_ROUTE_SOLVER && route != DMF_ROUTE_UPDATE_U))
+        return DMF_ERR_BAD_ARG;
+    dmf::describe_u_phase(s->key, s->spec, (int)n_iter2, s->purity != nullptr, route == DMF_ROUTE_UPDATE_U, buf, (size_t)cap);
     return DMF_OK;
 }
 

@@ -193,6 +193,48 @@ int64_t gram_u_slab_doubles(int64_t N, int S, int n_c, int n_u);
 hipError_t launch_gram_u(const ProblemView& p, const double* u, int n_u, double* slab, const int* done_flag, int* ny_out,
                          hipStream_t st, GramRan* ran = nullptr);
 
+// ---- what the first-generation FP64 row kernels launch for a shape.  Each launcher below computes ONE such plan and
+// launches from it; describe_u_phase (dmf_select.h: dmf_u_phase_describe) prints the same plan, so the text cannot say
+// anything else than what runs.  Pure host functions of the shape -- no pointers, no context.
+struct RowLaunch {
+    bool supported = false;     // false: the launcher answers hipErrorInvalidValue
+    int nw = 0;                 // waves per workgroup (k_rowpass_fused: column groups; 3 nw waves run)
+    int grid = 0;               // workgroups
+    size_t lds = 0;             // dynamic LDS bytes
+    bool raise = false;         // the launcher raises the kernel's dynamic-LDS limit first (more than 48 KB)
+    int64_t blocks_per_wg = 0;  // the largest number of row blocks any workgroup takes (workgroup 0's)
+};
+struct UPhaseMfmaPlan : RowLaunch {  // k_u_phase_mfma<NKC,NU,VEC,D16T>; row block = 16 rows
+    int nkc = 0, nu = 0;
+    bool vec = false, d16 = false;
+    bool split = false;  // cm_out given: c_i / M_i per row go out, k_u_inner_rows runs the inner steps
+};
+// has_d16 / SD: the problem carries the u16 copy of its counts, and its padded row length
+UPhaseMfmaPlan u_phase_mfma_plan(int64_t N, int S, int n_c, int n_u, int n_iter2, bool has_d16, int SD, bool split);
+struct RowpassFusedPlan : RowLaunch {  // k_rowpass_fused<NKC,NU>; N = the whole 16-row blocks (the caller runs the tail)
+    int nkc = 0, nu = 0;
+};
+RowpassFusedPlan rowpass_fused_plan(int64_t N, int S, int n_c, int n_u, int n_iter2);
+struct UPhaseBigPlan : RowLaunch {  // k_u_phase_big<NKC,GS>; row block = 16 rows
+    int nkc = 0, gs = 16, n_u = 0;
+};
+UPhaseBigPlan u_phase_big_plan(int64_t N, int S, int n_c, int n_u, int n_iter2);
+struct UPhaseGramPlan : RowLaunch {  // k_u_phase_gram<NU>; row block = kRowsPerBlockU rows, one per workgroup
+    int nu = 0;
+    bool alpha_in_lds = false;
+};
+UPhaseGramPlan u_phase_gram_plan(int64_t N, int S, int n_c, int n_u);
+struct UStepDirectPlan : RowLaunch {  // k_u_step_direct, one launch per inner step; row block = 4 rows (one per wave)
+    int n_u = 0;
+};
+UStepDirectPlan u_step_direct_plan(int64_t N, int S, int n_c, int n_u);
+// "k_u_phase_mfma<2,3,vec,d16> split nw=2 grid=512 lds=6912 raise=0 blocks/wg=3"
+int describe_row_launch(const UPhaseMfmaPlan& g, char* buf, size_t cap);
+int describe_row_launch(const RowpassFusedPlan& g, char* buf, size_t cap);
+int describe_row_launch(const UPhaseBigPlan& g, char* buf, size_t cap);
+int describe_row_launch(const UPhaseGramPlan& g, char* buf, size_t cap);
+int describe_row_launch(const UStepDirectPlan& g, char* buf, size_t cap);
+
 // u phase, Gram form (n_u <= 8): all n_iter2 inner iterations in one launch
 hipError_t launch_u_phase_gram(const ProblemView& p, const IterateView& it, int n_iter2, hipStream_t st);
 bool u_phase_gram_supported(int S, int n_c, int n_u);

@@ -564,26 +564,37 @@ int64_t rowpass_fused_slab_doubles(int64_t N, int S, int n_c, int n_u) {
     return (int64_t)2 * rowpass_fused_grid(N, S) * (n_c * n_u + n_u * (n_u + 1) / 2 + n_u) * S;
 }
 
+RowpassFusedPlan rowpass_fused_plan(int64_t N, int S, int n_c, int n_u, int n_iter2) {
+    RowpassFusedPlan g;
+    if (n_iter2 < 0 || (N & 15) != 0 || N < 16 || !rowpass_fused_supported(S, n_c, n_u)) return g;
+    g.nkc = (n_c + 3) / 4, g.nu = n_u;
+    g.nw = (S + 63) / 64;
+    g.lds = fused_lds_bytes(S, 4 * g.nkc, n_u, n_iter2);
+    g.raise = g.lds > 48 * 1024;
+    g.grid = rowpass_fused_grid(N, S);
+    g.blocks_per_wg = (N / 16 + g.grid - 1) / g.grid;
+    g.supported = g.lds <= 160 * 1024;
+    return g;
+}
+
 hipError_t launch_rowpass_fused(const ProblemView& p, const IterateView& it, int n_iter2, const UScratch& scratch,
                                 int* grid_out, hipStream_t st) {
-    return dispatch_int<0, 4>((p.n_c + 3) / 4, [&](auto nkc) {
-        return dispatch_int<1, 4>(it.n_u, [&](auto nu) {
+    const RowpassFusedPlan g = rowpass_fused_plan(p.N, p.S, p.n_c, it.n_u, n_iter2);
+    if (!g.supported) return hipErrorInvalidValue;
+    return dispatch_int<0, 4>(g.nkc, [&](auto nkc) {
+        return dispatch_int<1, 4>(g.nu, [&](auto nu) {
             constexpr int NKC = decltype(nkc)::value, NU = decltype(nu)::value;
             if constexpr (4 * NKC * NU + NU * (NU + 1) / 2 + NU > 80) {
                 return hipErrorInvalidValue;
             } else {
-                const int S = p.S, NW = (S + 63) / 64;
-                const size_t lds = fused_lds_bytes(S, 4 * NKC, NU, n_iter2);
-                if (lds > 160 * 1024 || (p.N & 15) != 0 || p.N < 16) return hipErrorInvalidValue;
-                if (lds > 48 * 1024) {
+                if (g.raise) {
                     const hipError_t e = raise_dynamic_lds<k_rowpass_fused<NKC, NU>>(160 * 1024);
                     if (e != hipSuccess) return e;
                 }
-                const int grid = rowpass_fused_grid(p.N, S);
-                *grid_out = grid;
-                hipLaunchKernelGGL((k_rowpass_fused<NKC, NU>), dim3(grid), dim3(DMF_WAVES_PER_WG(NW) * 64), lds, st, p.V, p.D,
-                                   p.Rtp, it.alpha, it.u, it.u_prev, it.state, p.N, S, p.n_c, n_iter2, it.mode, scratch.slab,
-                                   scratch.u2_partials
+                *grid_out = g.grid;
+                hipLaunchKernelGGL((k_rowpass_fused<NKC, NU>), dim3(g.grid), dim3(DMF_WAVES_PER_WG(g.nw) * 64), g.lds, st, p.V,
+                                   p.D, p.Rtp, it.alpha, it.u, it.u_prev, it.state, p.N, p.S, p.n_c, n_iter2, it.mode,
+                                   scratch.slab, scratch.u2_partials
 #ifdef DMF_STAMPS
                                    , (unsigned long long*)nullptr
 #endif

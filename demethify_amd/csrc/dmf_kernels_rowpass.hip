@@ -128,14 +128,27 @@ bool u_phase_gram_supported(int S, int n_c, int n_u) {
     return n_u >= 1 && n_u <= 16;  // 9..16: c and M (up to 152 doubles) still fit the register file
 }
 
+UPhaseGramPlan u_phase_gram_plan(int64_t N, int S, int n_c, int n_u) {
+    UPhaseGramPlan g;
+    if (N < 1 || S < 1 || n_c < 0 || !u_phase_gram_supported(S, n_c, n_u)) return g;
+    g.nu = n_u;
+    g.nw = 4;
+    const size_t alpha_bytes = (size_t)(n_c + n_u) * S * sizeof(double);
+    g.alpha_in_lds = alpha_bytes <= 36 * 1024;
+    g.lds = g.alpha_in_lds ? alpha_bytes : 0;
+    g.grid = (int)((N + kRowsPerBlockU - 1) / kRowsPerBlockU);
+    g.blocks_per_wg = 1;
+    g.supported = true;
+    return g;
+}
+
 hipError_t launch_u_phase_gram(const ProblemView& p, const IterateView& it, int n_iter2, hipStream_t st) {
-    return dispatch_int<1, 16>(it.n_u, [&](auto nu) {
+    const UPhaseGramPlan g = u_phase_gram_plan(p.N, p.S, p.n_c, it.n_u);
+    if (!g.supported) return hipErrorInvalidValue;
+    return dispatch_int<1, 16>(g.nu, [&](auto nu) {
         constexpr int NU = decltype(nu)::value;
-        const size_t lds = (size_t)(p.n_c + NU) * p.S * sizeof(double);
-        const int in_lds = lds <= 36 * 1024;
-        const int64_t nb = (p.N + kRowsPerBlockU - 1) / kRowsPerBlockU;
-        hipLaunchKernelGGL(k_u_phase_gram<NU>, dim3((unsigned)nb), dim3(256), in_lds ? lds : 0, st, p.V, p.D, p.Rt, it.alpha,
-                           it.u, it.u_prev, it.state, p.N, p.S, p.n_c, n_iter2, it.mode, in_lds);
+        hipLaunchKernelGGL(k_u_phase_gram<NU>, dim3((unsigned)g.grid), dim3(g.nw * 64), g.lds, st, p.V, p.D, p.Rt, it.alpha,
+                           it.u, it.u_prev, it.state, p.N, p.S, p.n_c, n_iter2, it.mode, (int)g.alpha_in_lds);
         return hipGetLastError();
     });
 }
@@ -192,11 +205,23 @@ bool u_step_direct_supported(int S, int n_c, int n_u) {
     return n_u >= 1 && n_u <= 64 && (size_t)4 * (S + 128) * sizeof(double) <= 60 * 1024;
 }
 
+UStepDirectPlan u_step_direct_plan(int64_t N, int S, int n_c, int n_u) {
+    UStepDirectPlan g;
+    if (N < 1 || S < 1 || n_c < 0 || !u_step_direct_supported(S, n_c, n_u)) return g;
+    g.n_u = n_u;
+    g.nw = 4;
+    g.lds = (size_t)4 * (S + 128) * sizeof(double);  // (at most 60 KB; launched without raising the limit)
+    const int64_t nb = (N + 3) / 4;
+    g.grid = (int)(nb > 4096 ? 4096 : nb);
+    g.blocks_per_wg = (nb + g.grid - 1) / g.grid;
+    g.supported = true;
+    return g;
+}
+
 hipError_t launch_u_step_direct(const ProblemView& p, const IterateView& it, double* u_next, int t, hipStream_t st) {
-    const size_t lds = (size_t)4 * (p.S + 128) * sizeof(double);
-    int64_t nb = (p.N + 3) / 4;
-    if (nb > 4096) nb = 4096;
-    hipLaunchKernelGGL(k_u_step_direct, dim3((unsigned)nb), dim3(256), lds, st, p.V, p.D, p.Rt, it.alpha, it.u,
+    const UStepDirectPlan g = u_step_direct_plan(p.N, p.S, p.n_c, it.n_u);
+    if (!g.supported) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_u_step_direct, dim3((unsigned)g.grid), dim3(g.nw * 64), g.lds, st, p.V, p.D, p.Rt, it.alpha, it.u,
                        it.u_prev, u_next, it.state, p.N, p.S, p.n_c, it.n_u, t, it.mode);
     return hipGetLastError();
 }

@@ -265,21 +265,33 @@ bool u_phase_big_supported(int S, int n_c, int n_u, int n_iter2) {
     return (size_t)big_layout(S, n_c, n_u, n_iter2, GS).total * sizeof(double) <= 160 * 1024;
 }
 
+UPhaseBigPlan u_phase_big_plan(int64_t N, int S, int n_c, int n_u, int n_iter2) {
+    UPhaseBigPlan g;
+    if (N < 1 || n_c < 0 || n_iter2 < 0 || !u_phase_big_supported(S, n_c, n_u, n_iter2)) return g;
+    g.nkc = (n_c + 3) / 4, g.n_u = n_u;
+    g.gs = big_group_size(n_u);
+    g.nw = g.gs == 16 ? 4 : 8;
+    g.lds = (size_t)big_layout(S, n_c, n_u, n_iter2, g.gs).total * sizeof(double);
+    g.raise = g.lds > 48 * 1024;
+    const int64_t nblk = (N + 15) / 16;
+    const int64_t want = 256 * per_cu_knob("DMF_UBIG_PER_CU", g.lds <= 78 * 1024 ? 2 : 1);
+    g.grid = (int)(nblk < want ? nblk : want);
+    g.blocks_per_wg = (nblk + g.grid - 1) / g.grid;
+    g.supported = true;  // (u_phase_big_supported holds the layout to 160 KB)
+    return g;
+}
+
 hipError_t launch_u_phase_big(const ProblemView& p, const IterateView& it, int n_iter2, hipStream_t st) {
-    const int gs = big_group_size(it.n_u);
-    return dispatch_int<0, 4>((p.n_c + 3) / 4, [&](auto nkc) {
-        return dispatch_bool(gs == 16, [&](auto gs16) {
+    const UPhaseBigPlan g = u_phase_big_plan(p.N, p.S, p.n_c, it.n_u, n_iter2);
+    if (!g.supported) return hipErrorInvalidValue;
+    return dispatch_int<0, 4>(g.nkc, [&](auto nkc) {
+        return dispatch_bool(g.gs == 16, [&](auto gs16) {
             constexpr int NKC = decltype(nkc)::value, GS = decltype(gs16)::value ? 16 : 32;
-            const size_t lds = (size_t)big_layout(p.S, p.n_c, it.n_u, n_iter2, GS).total * sizeof(double);
-            if (lds > 160 * 1024) return hipErrorInvalidValue;
-            if (lds > 48 * 1024) {
+            if (g.raise) {
                 const hipError_t e = raise_dynamic_lds<k_u_phase_big<NKC, GS>>(160 * 1024);
                 if (e != hipSuccess) return e;
             }
-            const int64_t nblk = (p.N + 15) / 16;
-            const int64_t want = 256 * per_cu_knob("DMF_UBIG_PER_CU", lds <= 78 * 1024 ? 2 : 1);
-            const int64_t grid = nblk < want ? nblk : want;
-            hipLaunchKernelGGL((k_u_phase_big<NKC, GS>), dim3((unsigned)grid), dim3(GS == 16 ? 256 : 512), lds, st, p.V, p.D, p.Rtp,
+            hipLaunchKernelGGL((k_u_phase_big<NKC, GS>), dim3((unsigned)g.grid), dim3(g.nw * 64), g.lds, st, p.V, p.D, p.Rtp,
                                it.alpha, it.u, it.u_prev, it.state, p.N, p.S, p.n_c, it.n_u, n_iter2, it.mode);
             return hipGetLastError();
         });

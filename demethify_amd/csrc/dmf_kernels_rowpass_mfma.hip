@@ -284,36 +284,48 @@ bool u_phase_mfma_supported(int S, int n_c, int n_u) {
     return n_u >= 1 && n_u <= 8 && n_c <= 16 && S <= 16 * kStripsPerWave * kMfmaMaxWaves;
 }
 
-// cm_out: null, or where the split mode leaves the per-row c_i / M_i (see the kernel)
-hipError_t launch_u_phase_mfma_impl(const ProblemView& p, const IterateView& it, int n_iter2, double* cm_out, hipStream_t st) {
-    const int S = p.S;
+UPhaseMfmaPlan u_phase_mfma_plan(int64_t N, int S, int n_c, int n_u, int n_iter2, bool has_d16, int SD, bool split) {
+    UPhaseMfmaPlan g;
+    if (N < 1 || S < 1 || n_c < 0 || n_c > 16 || n_u < 1 || n_u > 8 || n_iter2 < 0) return g;
     const int nstrips = (S + 15) / 16;
-    const int NW = (nstrips + kStripsPerWave - 1) / kStripsPerWave;
-    const bool vec = (S & 3) == 0;
-    const bool d16 = vec && p.D16 != nullptr && (p.SD & 3) == 0;
+    g.nw = (nstrips + kStripsPerWave - 1) / kStripsPerWave;
+    g.nkc = (n_c + 3) / 4, g.nu = n_u;
+    g.vec = (S & 3) == 0;
+    g.d16 = g.vec && has_d16 && (SD & 3) == 0;
+    g.split = split;
     // persistent workgroups: as many as fit two waves per SIMD (the kernel needs ~250 registers) -- 3 per CU at
     // NW = 2 left a quarter of the wave slots empty
-    const int per_cu = per_cu_knob("DMF_UMFMA_PER_CU", NW >= 8 ? 1 : 8 / NW);
-    const int64_t nblk = (p.N + 15) / 16, cap = (int64_t)256 * per_cu;
-    const int64_t grid = nblk < cap ? nblk : cap;
-    return dispatch_int<0, 4>((p.n_c + 3) / 4, [&](auto nkc) {
-        return dispatch_int<1, 8>(it.n_u, [&](auto nu) {
-            constexpr int NKC = decltype(nkc)::value, NU = decltype(nu)::value, NV = NU + NU * (NU + 1) / 2;
-            // (split mode keeps no momentum table in LDS)
-            const size_t lds = ((size_t)(cm_out ? 0 : ((n_iter2 + 1) & ~1)) + (size_t)2 * NW * NV * 16) * sizeof(double);
-            if (lds > 150 * 1024) return hipErrorInvalidValue;
+    const int per_cu = per_cu_knob("DMF_UMFMA_PER_CU", g.nw >= 8 ? 1 : 8 / g.nw);
+    const int64_t nblk = (N + 15) / 16, cap = (int64_t)256 * per_cu;
+    g.grid = (int)(nblk < cap ? nblk : cap);
+    g.blocks_per_wg = (nblk + g.grid - 1) / g.grid;
+    const int nv = n_u + n_u * (n_u + 1) / 2;
+    // (split mode keeps no momentum table in LDS)
+    g.lds = ((size_t)(split ? 0 : ((n_iter2 + 1) & ~1)) + (size_t)2 * g.nw * nv * 16) * sizeof(double);
+    g.raise = g.lds > 48 * 1024;
+    g.supported = g.nw <= kMfmaMaxWaves && g.lds <= 150 * 1024;
+    return g;
+}
+
+// cm_out: null, or where the split mode leaves the per-row c_i / M_i (see the kernel)
+hipError_t launch_u_phase_mfma_impl(const ProblemView& p, const IterateView& it, int n_iter2, double* cm_out, hipStream_t st) {
+    const UPhaseMfmaPlan g = u_phase_mfma_plan(p.N, p.S, p.n_c, it.n_u, n_iter2, p.D16 != nullptr, p.SD, cm_out != nullptr);
+    if (!g.supported) return hipErrorInvalidValue;
+    return dispatch_int<0, 4>(g.nkc, [&](auto nkc) {
+        return dispatch_int<1, 8>(g.nu, [&](auto nu) {
+            constexpr int NKC = decltype(nkc)::value, NU = decltype(nu)::value;
             const auto launch = [&](auto vec_t, auto d16_t) {
                 constexpr auto kernel = k_u_phase_mfma<NKC, NU, decltype(vec_t)::value, decltype(d16_t)::value>;
-                if (lds > 48 * 1024) {
-                    const hipError_t e = raise_dynamic_lds<kernel>(lds);
+                if (g.raise) {
+                    const hipError_t e = raise_dynamic_lds<kernel>(g.lds);
                     if (e != hipSuccess) return e;
                 }
-                hipLaunchKernelGGL(kernel, dim3((unsigned)grid), dim3(NW * 64), lds, st, p.V, p.D, p.D16, p.SD, p.Rtp, it.alpha,
-                                   it.u, it.u_prev, it.state, p.N, S, p.n_c, n_iter2, it.mode, cm_out);
+                hipLaunchKernelGGL(kernel, dim3((unsigned)g.grid), dim3(g.nw * 64), g.lds, st, p.V, p.D, p.D16, p.SD, p.Rtp,
+                                   it.alpha, it.u, it.u_prev, it.state, p.N, p.S, p.n_c, n_iter2, it.mode, cm_out);
                 return hipGetLastError();
             };
-            if (d16) return launch(std::true_type{}, std::true_type{});
-            if (vec) return launch(std::true_type{}, std::false_type{});
+            if (g.d16) return launch(std::true_type{}, std::true_type{});
+            if (g.vec) return launch(std::true_type{}, std::false_type{});
             return launch(std::false_type{}, std::false_type{});
         });
     });

@@ -66,6 +66,13 @@ PathSpec select_path(const ShapeKey& k);
 IterationPlan plan_iteration(const ShapeKey& k, const PathSpec& s, int n_iter2, bool purity);
 // "rowpass=... gram=... alpha=..." (what dmf_solver_describe reports and the parity tests assert)
 int describe_plan(const ShapeKey& k, const IterationPlan& plan, char* buf, size_t cap);
+// the PathSpec behind a u phase that runs as a kernel of its own (dmf_update_u): no one-launch row pass, no integer Gram
+PathSpec standalone_spec(PathSpec s);
+// The u phase alone, with what its launcher launches (dmf_u_phase_describe).  standalone: the u phase of dmf_update_u
+// instead of the solver's loop.  For the first-generation FP64 row kernels the text is the launcher's own plan
+// (dmf_internal.h: "k_u_phase_mfma<2,3,vec,d16> split nw=2 grid=512 lds=6912 raise=0 blocks/wg=3"); for the others it is
+// the rowpass= part of describe_plan.
+int describe_u_phase(const ShapeKey& k, const PathSpec& s, int n_iter2, bool purity, bool standalone, char* buf, size_t cap);
 
 // ---- the streaming cost (cost_f_w, deconvolution.py:15-17; the kernels and the plan: dmf_kernels_stream.hip).  Like the
 // table above a pure function of a key, read by the launch (launch_cost_plan), by what the hold-out error asks about it

@@ -101,26 +101,31 @@ IterationPlan plan_iteration(const ShapeKey& k, const PathSpec& s, int n_iter2, 
     return plan;
 }
 
-int describe_plan(const ShapeKey& k, const IterationPlan& plan, char* buf, size_t cap) {
-    char row[160], gram[64];
+// the rowpass= part of describe_plan
+static void describe_row(const ShapeKey& k, RowKind kind, char* row, size_t cap) {
     const int S = k.S, n_c = k.n_c, n_u = k.n_u;
-    switch (plan.row) {
+    switch (kind) {
         case RowKind::RowpassV2:
-            snprintf(row, sizeof(row), "k_rowpass_v2<%d,%d> nw=%d grid=%d tail=%d%s", (n_c + 3) / 4, n_u, (S + 63) / 64,
+            snprintf(row, cap, "k_rowpass_v2<%d,%d> nw=%d grid=%d tail=%d%s", (n_c + 3) / 4, n_u, (S + 63) / 64,
                      rowpass_v2_grid(k.N, S), (int)(k.N & 15), k.x16 ? " x16" : "");
             break;
         case RowKind::RowpassFused:
-            snprintf(row, sizeof(row), "k_rowpass_fused<%d,%d> nw=%d grid=%d tail=%d", (n_c + 3) / 4, n_u, (S + 63) / 64,
+            snprintf(row, cap, "k_rowpass_fused<%d,%d> nw=%d grid=%d tail=%d", (n_c + 3) / 4, n_u, (S + 63) / 64,
                      rowpass_fused_grid(k.N - (k.N & 15), S), (int)(k.N & 15));
             break;
-        case RowKind::CmI8InnerBu: snprintf(row, sizeof(row), "k_cm_i8<nd=%d>+k_inner_bu", k.nd); break;
-        case RowKind::CmI8InnerRows: snprintf(row, sizeof(row), "k_cm_i8<nd=%d>+k_u_inner_rows", k.nd); break;
-        case RowKind::UPhaseBig: snprintf(row, sizeof(row), "k_u_phase_big"); break;
-        case RowKind::UPhaseMfmaSplit: snprintf(row, sizeof(row), "k_u_phase_mfma(split)+k_u_inner_rows"); break;
-        case RowKind::UPhaseMfma: snprintf(row, sizeof(row), "k_u_phase_mfma"); break;
-        case RowKind::UPhaseGram: snprintf(row, sizeof(row), "k_u_phase_gram"); break;
-        case RowKind::UStepDirect: snprintf(row, sizeof(row), "k_u_step_direct"); break;
+        case RowKind::CmI8InnerBu: snprintf(row, cap, "k_cm_i8<nd=%d>+k_inner_bu", k.nd); break;
+        case RowKind::CmI8InnerRows: snprintf(row, cap, "k_cm_i8<nd=%d>+k_u_inner_rows", k.nd); break;
+        case RowKind::UPhaseBig: snprintf(row, cap, "k_u_phase_big"); break;
+        case RowKind::UPhaseMfmaSplit: snprintf(row, cap, "k_u_phase_mfma(split)+k_u_inner_rows"); break;
+        case RowKind::UPhaseMfma: snprintf(row, cap, "k_u_phase_mfma"); break;
+        case RowKind::UPhaseGram: snprintf(row, cap, "k_u_phase_gram"); break;
+        case RowKind::UStepDirect: snprintf(row, cap, "k_u_step_direct"); break;
     }
+}
+
+int describe_plan(const ShapeKey& k, const IterationPlan& plan, char* buf, size_t cap) {
+    char row[160], gram[64];
+    describe_row(k, plan.row, row, sizeof(row));
     switch (plan.gram) {
         case GramKind::InRowPass: snprintf(gram, sizeof(gram), "fused"); break;
         case GramKind::I8: snprintf(gram, sizeof(gram), "k_gram_i8<nd=%d>/w8", k.nd); break;
@@ -139,6 +144,79 @@ int describe_plan(const ShapeKey& k, const IterationPlan& plan, char* buf, size_
         case AlphaKind::PhaseDyn: alpha = "k_alpha_phase_dyn"; break;
     }
     return snprintf(buf, cap, "rowpass=%s gram=%s alpha=%s", row, gram, alpha);
+}
+
+// ---- the launch plans of the first-generation FP64 row kernels as text (dmf_internal.h)
+static int describe_launch_tail(const RowLaunch& g, char* buf, size_t cap) {
+    return snprintf(buf, cap, "nw=%d grid=%d lds=%zu raise=%d blocks/wg=%lld", g.nw, g.grid, g.lds, g.raise ? 1 : 0,
+                    (long long)g.blocks_per_wg);
+}
+
+int describe_row_launch(const UPhaseMfmaPlan& g, char* buf, size_t cap) {
+    char tail[96];
+    describe_launch_tail(g, tail, sizeof(tail));
+    return snprintf(buf, cap, "k_u_phase_mfma<%d,%d,%s> %s %s", g.nkc, g.nu, g.d16 ? "vec,d16" : g.vec ? "vec" : "scalar",
+                    g.split ? "split" : "one-launch", tail);
+}
+
+int describe_row_launch(const RowpassFusedPlan& g, char* buf, size_t cap) {
+    char tail[96];
+    describe_launch_tail(g, tail, sizeof(tail));
+    return snprintf(buf, cap, "k_rowpass_fused<%d,%d> %s", g.nkc, g.nu, tail);
+}
+
+int describe_row_launch(const UPhaseBigPlan& g, char* buf, size_t cap) {
+    char tail[96];
+    describe_launch_tail(g, tail, sizeof(tail));
+    return snprintf(buf, cap, "k_u_phase_big<%d,%d> n_u=%d %s", g.nkc, g.gs, g.n_u, tail);
+}
+
+int describe_row_launch(const UPhaseGramPlan& g, char* buf, size_t cap) {
+    char tail[96];
+    describe_launch_tail(g, tail, sizeof(tail));
+    return snprintf(buf, cap, "k_u_phase_gram<%d> alpha=%s %s", g.nu, g.alpha_in_lds ? "lds" : "global", tail);
+}
+
+int describe_row_launch(const UStepDirectPlan& g, char* buf, size_t cap) {
+    char tail[96];
+    describe_launch_tail(g, tail, sizeof(tail));
+    return snprintf(buf, cap, "k_u_step_direct n_u=%d %s", g.n_u, tail);
+}
+
+PathSpec standalone_spec(PathSpec s) {
+    s.use_v2 = false;  // (plan_iteration then names the split / fall-back u phase of this shape)
+    s.use_fused = false;
+    s.use_gram_i8 = false;
+    return s;
+}
+
+int describe_u_phase(const ShapeKey& k, const PathSpec& s, int n_iter2, bool purity, bool standalone, char* buf, size_t cap) {
+    const RowKind row = plan_iteration(k, standalone ? standalone_spec(s) : s, n_iter2, standalone ? false : purity).row;
+    const bool has_d16 = k.nd > 0;
+    switch (row) {
+        case RowKind::UPhaseMfma:
+        case RowKind::UPhaseMfmaSplit:
+            return describe_row_launch(u_phase_mfma_plan(k.N, k.S, k.n_c, k.n_u, n_iter2, has_d16, k.SD, row == RowKind::UPhaseMfmaSplit),
+                                       buf, cap);
+        case RowKind::RowpassFused: {
+            // (the solver runs the ragged tail, N % 16 rows, through k_u_phase_mfma and k_gram_u on the rows' f64 arrays)
+            char head[160];
+            describe_row_launch(rowpass_fused_plan(k.N - (k.N & 15), k.S, k.n_c, k.n_u, n_iter2), head, sizeof(head));
+            return snprintf(buf, cap, "%s tail=%d", head, (int)(k.N & 15));
+        }
+        case RowKind::UPhaseBig: return describe_row_launch(u_phase_big_plan(k.N, k.S, k.n_c, k.n_u, n_iter2), buf, cap);
+        case RowKind::UPhaseGram: return describe_row_launch(u_phase_gram_plan(k.N, k.S, k.n_c, k.n_u), buf, cap);
+        case RowKind::UStepDirect: {
+            char head[160];
+            describe_row_launch(u_step_direct_plan(k.N, k.S, k.n_c, k.n_u), head, sizeof(head));
+            return snprintf(buf, cap, "%s launches=%d", head, n_iter2);
+        }
+        default: {
+            char rowtext[160];
+            describe_row(k, row, rowtext, sizeof(rowtext));
+            return snprintf(buf, cap, "%s", rowtext);
+        }
+    }
 }
 
 }  // namespace dmf

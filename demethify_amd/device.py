@@ -174,6 +174,25 @@ def get_context(device: int | None = None) -> Context:
     return ctx
 
 
+def _route(route) -> int:
+    try:
+        return {"solver": L.DMF_ROUTE_SOLVER, "update_u": L.DMF_ROUTE_UPDATE_U}[route]
+    except KeyError:
+        raise ValueError(f'route must be "solver" or "update_u", got {route!r}') from None
+
+
+def u_phase_describe(N, S, n_c, n_u, nd=0, level=0, n_iter2=20, flags=0, route="solver"):
+    """dmf_u_phase_describe: the u phase of a shape with its launch plan -- a pure function of the key, no GPU is touched.
+    None where no kernel takes the shape (DMF_ERR_UNSUPPORTED)."""
+    buf = C.create_string_buffer(512)
+    st = L.load().dmf_u_phase_describe(int(N), int(S), int(n_c), int(n_u), int(nd), int(level), int(n_iter2), int(flags),
+                                       _route(route), buf, len(buf))
+    if st == L.DMF_ERR_UNSUPPORTED:
+        return None
+    L.check(st, "dmf_u_phase_describe")
+    return buf.value.decode()
+
+
 class Problem:
     """dmf_problem: meth_frequency (N x S), counts (N x S), R_trunc (N x n_c or None)."""
 
@@ -628,15 +647,25 @@ class Solver:
         L.check(self._lib.dmf_solver_describe(self._h, int(n_iter2), buf, len(buf)), "dmf_solver_describe")
         return buf.value.decode()
 
+    def u_phase_describe(self, n_iter2: int = 20, route="solver") -> str:
+        """What the u phase of this solver launches, with its launch plan (dmf_solver_u_phase_describe).  ``route``:
+        "solver" (an outer iteration of step()) or "update_u" (the stand-alone u phase of Problem.update_u)."""
+        buf = C.create_string_buffer(512)
+        L.check(self._lib.dmf_solver_u_phase_describe(self._h, int(n_iter2), _route(route), buf, len(buf)),
+                "dmf_solver_u_phase_describe")
+        return buf.value.decode()
+
     def gram(self, kind="integer"):
         """(gb, text): the packed Gram ((K + 1)(K + 2) / 2, S) for the solver's CURRENT u, computed now by the kernels a step
         calls, and what ran (dmf_solver_gram).  ``kind``: "integer" (k_bu_cols + k_gram_i8_w8 + reduce + finish; u must lie
         in [0, 1]; DMF_ERR_UNSUPPORTED where the integer Gram does not take the problem) or "fp64" (k_gram_u / k_gram_mfma /
-        k_gram, as the solver's selection names).  For tests: the iterate and a later step() are unaffected."""
+        k_gram, as the solver's selection names) -- or "last": nothing is computed, the solver's own packed Gram as the last
+        outer iteration of step() left it, with the text of what wrote it.  For tests: the iterate and a later step() are
+        unaffected."""
         try:
-            k = {"integer": L.DMF_GRAM_INTEGER, "fp64": L.DMF_GRAM_FP64}[kind]
+            k = {"integer": L.DMF_GRAM_INTEGER, "fp64": L.DMF_GRAM_FP64, "last": L.DMF_GRAM_LAST}[kind]
         except KeyError:
-            raise ValueError(f'kind must be "integer" or "fp64", got {kind!r}') from None
+            raise ValueError(f'kind must be "integer", "fp64" or "last", got {kind!r}') from None
         out = np.empty(((self.K + 1) * (self.K + 2) // 2, self.problem.S), dtype=np.float64)
         buf = C.create_string_buffer(256)
         L.check(self._lib.dmf_solver_gram(self._h, k, _ptr(out), buf, len(buf)), "dmf_solver_gram")

@@ -303,8 +303,12 @@ int dmf_solver_holdout_error(dmf_solver* s, const dmf_problem* full, double* sum
  * u_norm2 / l_h and the iterate are left alone, and the solver's own Gram buffer is rewritten by the next step before it
  * is read, so stepping on gives the same bits as without this call.  out_text (may be NULL): what ran, the text of
  * dmf_gram_i8_describe, or "k_gram_u<NCT,NU> launches=1 ny=..", "k_gram_mfma<MTW,dma|reg> launches=.. ny=..",
- * "k_gram launches=1 ny=.. nz=..". */
-enum { DMF_GRAM_INTEGER = 0, DMF_GRAM_FP64 = 1 };
+ * "k_gram launches=1 ny=.. nz=..".  kind = DMF_GRAM_LAST computes nothing: out_gb <- the solver's own packed Gram exactly as
+ * the last outer iteration of dmf_solver_step left it -- the Gram of the current u, since the alpha phase behind it does not
+ * change u -- and out_text <- what wrote its u-dependent rows there ("k_rowpass_fused<3,4> phase C slabs=512 + k_gram_u
+ * tail", or the text of the loop's Gram launcher); before any iteration the u-dependent rows are zero and the text empty.
+ * (A call with one of the other two kinds rewrites that buffer: ask for DMF_GRAM_LAST first.) */
+enum { DMF_GRAM_INTEGER = 0, DMF_GRAM_FP64 = 1, DMF_GRAM_LAST = 2 };
 int dmf_solver_gram(dmf_solver* s, int kind, double* out_gb, char* out_text, int64_t cap);
 int dmf_solver_destroy(dmf_solver* s);
 /* Which kernels a step with n_iter2 inner iterations would launch for this solver, as text, e.g.
@@ -318,6 +322,22 @@ int dmf_solver_describe(const dmf_solver* s, int64_t n_iter2, char* buf, int64_t
  * DMF_ERR_UNSUPPORTED where no kernel takes the shape. */
 int dmf_select_describe(int64_t N, int64_t S, int64_t n_c, int64_t n_u, int nd, int level, int64_t n_iter2, int flags,
                         char* buf, int64_t cap);
+/* The u phase alone, with what its launcher launches, for the same key (dmf_u_phase_describe: pure, no GPU is touched) or
+ * for a live solver.  route = DMF_ROUTE_SOLVER: the u phase of an outer iteration of dmf_solver_step; DMF_ROUTE_UPDATE_U:
+ * the stand-alone u phase of dmf_update_u (no one-launch row pass, no fused kernel).  For the first-generation FP64 row
+ * kernels the text is the plan the launcher itself launches from -- template arguments, mode, waves per workgroup, grid,
+ * dynamic LDS bytes, whether the LDS limit is raised first, and the largest number of row blocks a workgroup takes:
+ *   "k_u_phase_mfma<2,3,vec,d16> split nw=2 grid=512 lds=6912 raise=0 blocks/wg=3"   (scalar | vec | vec,d16; one-launch | split)
+ *   "k_rowpass_fused<3,4> nw=4 grid=256 lds=.. raise=1 blocks/wg=3 tail=5"           (nw column groups; 3 nw waves run)
+ *   "k_u_phase_big<0,16> n_u=12 nw=4 grid=512 lds=.. raise=0 blocks/wg=2"
+ *   "k_u_phase_gram<3> alpha=lds nw=4 grid=.. lds=.. raise=0 blocks/wg=1"            (alpha=lds | global)
+ *   "k_u_step_direct n_u=5 nw=4 grid=.. lds=.. raise=0 blocks/wg=2 launches=20"
+ * (row blocks of 16 rows; k_u_phase_gram 64, k_u_step_direct 4).  For every other u phase it is the rowpass= part of
+ * dmf_select_describe.  DMF_ERR_UNSUPPORTED where no kernel takes the shape. */
+enum { DMF_ROUTE_SOLVER = 0, DMF_ROUTE_UPDATE_U = 1 };
+int dmf_u_phase_describe(int64_t N, int64_t S, int64_t n_c, int64_t n_u, int nd, int level, int64_t n_iter2, int flags, int route,
+                         char* buf, int64_t cap);
+int dmf_solver_u_phase_describe(const dmf_solver* s, int64_t n_iter2, int route, char* buf, int64_t cap);
 /* How the stop test |cf - cf_0| < tol (deconvolution.py:218-220) of this solver's dmf_solver_step calls was decided.
  * The loop's cost is the Gram form v^T D v - 2 a.b + a^T G a; where its error bound (it grows with N S max(counts)) is
  * not far below tol, an iteration whose Gram-form difference falls below 10 tol is decided on the STREAMING cost of

@@ -23,7 +23,9 @@ FUSED_CASES = [
     (2048, 192, 16, 3, 4, "NKC = 4 (n_c 13..16), NU = 3, nw = 3"),
     (3000, 128, 0, 4, 4, "unsupervised gradient point, no known types, nw = 2 (two workgroups per CU)"),
     (2048, 256, 5, 1, 4, "NU = 1, n_c not a multiple of 4 (padded R_trunc copy)"),
-    (8192 + 9, 64, 6, 2, 4, "config 2's instantiation <2,2> nw=1, several blocks per workgroup"),
+    # (512 full blocks on a grid of 512 at nw <= 2: ONE block per workgroup on the first-generation kernel; its launches
+    # with several blocks per workgroup at every nw are test_gpu_fp64_rowpass.py's)
+    (8192 + 9, 64, 6, 2, 4, "config 2's instantiation <2,2> nw=1, 512 full blocks and a ragged 9-row tail"),
 ]
 
 
