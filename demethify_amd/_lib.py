@@ -65,6 +65,7 @@ SIGNATURES = {
     "dmf_problem_gram_known": (C.c_int, [_p, _p, C.c_char_p, _i64]),
     "dmf_gram_i8_describe": (C.c_int, [_i64, _i64, _i64, _i64, C.c_int, C.c_char_p, _i64]),
     "dmf_solver_gram": (C.c_int, [_p, C.c_int, _p, C.c_char_p, _i64]),
+    "dmf_solver_row_moments": (C.c_int, [_p, _p, C.c_char_p, _i64]),
     "dmf_cost": (C.c_int, [_p, _p, _p, _i64, _p, C.c_int, _dbl_p]),
     "dmf_cost_describe": (C.c_int, [_i64, _i64, _i64, C.c_int, _i64, C.c_int, C.c_int, C.c_int, C.c_char_p, _i64]),
     "dmf_problem_cost_describe": (C.c_int, [_p, _p, _i64, C.c_char_p, _i64]),

@@ -680,6 +680,51 @@ int dmf_solver_gram(dmf_solver* s, int kind, double* out_gb, char* out_text, int
     return status;
 }
 
+// The row kind whose producer dmf_solver_row_moments runs: the stand-alone u phase of this solver in its split form -- what
+// it takes beyond kSplitInnerSteps inner steps (wide row groups take it at every count).
+static dmf::RowKind row_moments_kind(const dmf_solver* s) { return standalone_row_kind(s, kSplitInnerSteps + 1); }
+
+// dmf_solver_row_moments once its arguments are checked: the producer and the copy on the stream, and the wait for both
+static int solver_row_moments_enqueue(dmf_solver* s, dmf::RowKind row, double* out_cm, dmf::CmRan* ran) {
+    dmf_context* ctx = s->ctx;
+    const dmf::ProblemView pv = s->p->view();
+    const int n_iter2 = kSplitInnerSteps + 1;
+    DMF_TRY(ensure_split_scratch(s, 1));
+    {
+        FamilyScope scope(ctx, DMF_KERNEL_ROWPASS);
+        if (row == dmf::RowKind::UPhaseMfmaSplit) {
+            HIP_TRY(dmf::launch_u_phase_mfma_impl(pv, s->iterate(), n_iter2, s->cm, ctx->stream));
+            dmf::describe_row_launch(dmf::u_phase_mfma_plan(pv.N, pv.S, pv.n_c, (int)s->n_u, n_iter2, pv.D16 != nullptr, pv.SD, true),
+                                     ran->text, sizeof(ran->text));
+        } else {
+            HIP_TRY(dmf::launch_cm_i8(pv, s->iterate(), s->cm, ctx->stream, ran));
+        }
+    }
+    const size_t n = (size_t)dmf::u_phase_split_cm_doubles(pv.N, (int)s->n_u);
+    HIP_TRY(hipMemcpyAsync(out_cm, s->cm, n * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    return DMF_OK;
+}
+
+int dmf_solver_row_moments(dmf_solver* s, double* out_cm, char* out_text, int64_t cap) {
+    if (s == nullptr || out_cm == nullptr || (out_text != nullptr && cap < 1)) return DMF_ERR_BAD_ARG;
+    dmf_context* ctx = s->ctx;
+    DMF_TRY(check_ctx(ctx));
+    const dmf::RowKind row = row_moments_kind(s);
+    if (row != dmf::RowKind::CmI8InnerRows && row != dmf::RowKind::CmI8InnerBu && row != dmf::RowKind::UPhaseMfmaSplit)
+        return DMF_ERR_UNSUPPORTED;  // (a u phase that keeps c_i / M_i in its registers or never forms them)
+    // the producers return at once when the stop test has fired: what is in the scratch then is an earlier iteration's
+    DMF_TRY(fetch_state(s));
+    if (s->h_state->done != 0) return DMF_ERR_BAD_ARG;
+    dmf::CmRan ran;
+    s->in_flight = true;
+    const int status = solver_row_moments_enqueue(s, row, out_cm, &ran);
+    if (status != DMF_OK) (void)hipStreamSynchronize(ctx->stream);
+    s->in_flight = false;
+    if (status == DMF_OK && out_text != nullptr) snprintf(out_text, (size_t)cap, "%s", ran.text);
+    return status;
+}
+
 int dmf_solver_destroy(dmf_solver* s) {
     if (s == nullptr) return DMF_OK;
     dmf_context* ctx = s->ctx;

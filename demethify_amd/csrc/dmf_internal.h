@@ -277,7 +277,42 @@ hipError_t launch_u_phase_split(const ProblemView& p, const IterateView& it, int
 // split u phase whose producer runs M_i on the integer matrix cores (dmf_kernels_cm_i8.hip): n_u <= 16, 2 <= S <= 2048
 // (panels of 256 samples), u16 counts with ND digit planes, alpha in [0, 1]; v_align = ProblemView::v_align()
 bool cm_i8_supported(unsigned v_align, int S, int n_c, int n_u, int ND, int SD);
-hipError_t launch_cm_i8(const ProblemView& p, const IterateView& it, double* cm, hipStream_t st);
+// What launch_cm_i8 launches for a shape: panels of up to 256 samples, per panel one or more launches that each hold
+// `tpl` 16-pair tiles of M_i in the LDS (the last one what is left) and one 16-unknown tile of c.  The launcher dispatches
+// on it and describe_cm_i8_plan prints it (dmf_u_phase_describe, dmf_solver_row_moments).  Pure host code.
+struct CmI8Launch {  // launch li of a panel
+    int mt0 = 0, mt1 = 0;         // pair tiles [mt0, mt1)
+    int c_tile = 0, c_store = 0;  // the c tile it computes, and whether it stores it
+    size_t lds = 0;               // dynamic LDS bytes
+    int grid = 0;                 // workgroups of 8 waves, a wave per 32-row block at a time
+    int64_t blocks_per_wave = 0;  // the largest number of 32-row blocks any wave takes
+};
+struct CmI8Panel {
+    int col0 = 0, Sp = 0;  // samples col0 .. col0 + Sp - 1
+    bool s4 = false;       // template argument S4: the plain 16-byte strip loads
+    int ncgx = 2;          // template argument NCGX: 2 column groups of 64 samples, 4 beyond 128 samples
+    int tpl = 0;           // pair tiles per launch
+    int n_launch = 0;
+    CmI8Launch first, last;  // the first and the last launch (the ones between equal the first but for their tiles)
+};
+constexpr int kCmMaxPanels = 8;  // 2048 samples
+struct CmI8Plan {
+    bool supported = false;
+    int64_t N = 0;
+    int S = 0, n_c = 0, n_u = 0;
+    int nkc = 0, nd = 1;    // template arguments NKC (12 = kCmNkcWide: more than 16 known types) and ND
+    int nmt = 0, n_ct = 0;  // 16-pair tiles of M_i, 16-unknown tiles of c
+    int n_panels = 0;
+    CmI8Panel panel[kCmMaxPanels];
+};
+CmI8Plan cm_i8_plan(int64_t N, int S, int n_c, int n_u, int ND);
+CmI8Launch cm_i8_launch_of(const CmI8Plan& g, int panel, int li);
+// "panels=2 tiles=10 | col0=0 sp=256 k_cm_i8<1,2,4,s4> tpl=5 launches=2 ctiles=2 lds=.. grid=.. blocks/wave=.. | col0=256 .."
+int describe_cm_i8_plan(const CmI8Plan& g, char* buf, size_t cap);
+struct CmRan {  // what a producer of the split u phase ran, as text (dmf_solver_row_moments)
+    char text[2048] = "";
+};
+hipError_t launch_cm_i8(const ProblemView& p, const IterateView& it, double* cm, hipStream_t st, CmRan* ran = nullptr);
 hipError_t launch_u_phase_split_i8(const ProblemView& p, const IterateView& it, int n_iter2, const UScratch& scratch,
                                    hipStream_t st);
 

@@ -22,6 +22,7 @@
 // Layout facts used (tools/mfma_probe.hip): FP64 A[i][k]: lane (i = l & 15, k = l >> 4); B[k][j]: lane (k = l >> 4,
 // j = l & 15); C register r of lane l = C[(l >> 4) + 4 r][l & 15].  i8 16x16x64: A lane (row l & 15), B lane (column
 // l & 15), byte b of register g of lane-group l >> 4 is the same k on both sides; C register r = row 4 (l >> 4) + r.
+#include <cstdio>
 #include <cstdlib>
 
 #include "dmf_device.h"
@@ -389,52 +390,123 @@ bool cm_i8_supported(unsigned v_align, int S, int n_c, int n_u, int ND, int SD) 
 
 // cm: N x (n_u + n_u (n_u + 1) / 2) doubles.  Preconditions (cm_i8_supported + the caller): counts integral in
 // [0, 127] (ND = 1) or [0, 32639] (ND = 2) in D16 (row stride SD, zero padded to a multiple of 64 samples, rows to a
-// multiple of 16), alpha in [0, 1], Rtp = padded R_trunc (row stride 4 ceil(n_c / 4)).
-hipError_t launch_cm_i8(const ProblemView& p, const IterateView& it, double* cm, hipStream_t st) {
+// multiple of 16), alpha in [0, 1], Rtp = padded R_trunc (row stride 4 ceil(n_c / 4)).  The geometry is cm_i8_plan's.
+// launch li of panel `panel`: its pair tiles, its c tile, the LDS they need and the grid that follows from it
+CmI8Launch cm_i8_launch_of(const CmI8Plan& g, int panel, int li) {
+    const CmI8Panel& pn = g.panel[panel];
+    CmI8Launch l;
+    l.mt0 = li * pn.tpl < g.nmt ? li * pn.tpl : g.nmt;
+    l.mt1 = l.mt0 + pn.tpl < g.nmt ? l.mt0 + pn.tpl : g.nmt;
+    l.c_tile = li < g.n_ct ? li : g.n_ct - 1;
+    l.c_store = li < g.n_ct ? 1 : 0;
+    // (a launch without tiles must never be sized: cm_layout reads zero tiles as "all of them")
+    l.lds = l.mt1 > l.mt0 ? cm_layout(pn.Sp, g.n_c, g.n_u, l.mt1 - l.mt0).bytes : 0;
+    const int64_t nblk = (g.N + 31) / 32;
+    const int64_t want = (nblk + kCmWaves - 1) / kCmWaves;
+    // one workgroup (two waves per SIMD at ~200 registers) per CU, two where the tables leave room
+    const int64_t cap = (int64_t)256 * per_cu_knob("DMF_CM_PER_CU", l.lds <= 76 * 1024 ? 2 : 1);
+    l.grid = (int)(want < cap ? want : cap);
+    l.blocks_per_wave = (nblk + (int64_t)l.grid * kCmWaves - 1) / ((int64_t)l.grid * kCmWaves);
+    return l;
+}
+
+// The one geometry result of a shape: launch_cm_i8 dispatches on it, describe_cm_i8_plan prints it.
+CmI8Plan cm_i8_plan(int64_t N, int S, int n_c, int n_u, int ND) {
+    CmI8Plan g;
+    if (N < 1 || n_u < 1 || n_u > 32 || n_c < 0 || n_c > 4 * kCmNkcWide || n_c + n_u > 64 || S < 2 || S > kCmMaxPanels * kCmPanel ||
+        (ND != 1 && ND != 2))
+        return g;
+    g.N = N, g.S = S, g.n_c = n_c, g.n_u = n_u;
+    // template parameters: known-type chunks (beyond four: kCmNkcWide), digit planes, column groups (four on panels of
+    // more than 128 samples, else two), whole float4 columns
+    g.nkc = (n_c + 3) / 4 <= 4 ? (n_c + 3) / 4 : kCmNkcWide;
+    g.nd = ND;
+    g.nmt = (n_u * (n_u + 1) / 2 + 15) / 16, g.n_ct = (n_u + 15) / 16;
+    g.supported = true;
+    for (int col0 = 0; col0 < S; col0 += kCmPanel) {  // panels of 256 samples; the second and later ones add to cm
+        CmI8Panel& pn = g.panel[g.n_panels];
+        pn.col0 = col0;
+        pn.Sp = S - col0 < kCmPanel ? S - col0 : kCmPanel;
+        if (cm_layout(pn.Sp, n_c, n_u, 1).bytes > (size_t)160 * 1024) g.supported = false;  // (at least one pair tile per launch)
+        // pair tiles per launch: what the LDS holds beside the alpha copy; at least one launch per c tile
+        int tpl = g.nmt;
+        while (tpl > 1 && cm_layout(pn.Sp, n_c, n_u, tpl).bytes > (size_t)160 * 1024) --tpl;
+        int n_launch = (g.nmt + tpl - 1) / tpl;
+        if (n_launch < g.n_ct) n_launch = g.n_ct;
+        pn.tpl = (g.nmt + n_launch - 1) / n_launch;
+        pn.n_launch = n_launch;
+        pn.s4 = (pn.Sp & 3) == 0 && (S & 1) == 0;  // (odd S: rows of V are 8-byte aligned only)
+        pn.ncgx = pn.Sp > 128 ? 4 : 2;
+        ++g.n_panels;
+        pn.first = cm_i8_launch_of(g, g.n_panels - 1, 0);
+        pn.last = cm_i8_launch_of(g, g.n_panels - 1, n_launch - 1);
+        // every launch holds at least one tile: (n_launch - 1) tpl < nmt.  True of every shape the rule above admits
+        // (tests/test_cm_exact_host.py enumerates them); a plan that broke it is refused, not launched
+        if (pn.last.mt1 <= pn.last.mt0) g.supported = false;
+    }
+    return g;
+}
+
+static int describe_cm_i8_launch(const CmI8Launch& l, char* buf, size_t cap) {
+    return snprintf(buf, cap, "lds=%zu grid=%d blocks/wave=%lld", l.lds, l.grid, (long long)l.blocks_per_wave);
+}
+
+int describe_cm_i8_plan(const CmI8Plan& g, char* buf, size_t cap) {
+    if (cap < 1) return 0;
+    size_t n = 0;
+    const auto add = [&](const char* piece) {
+        const int w = snprintf(buf + n, cap - n, "%s", piece);
+        if (w > 0) n = n + (size_t)w < cap ? n + (size_t)w : cap - 1;
+    };
+    char piece[256], l0[96], l1[96];
+    snprintf(piece, sizeof(piece), "panels=%d tiles=%d", g.n_panels, g.nmt);
+    add(piece);
+    for (int i = 0; i < g.n_panels; ++i) {
+        const CmI8Panel& pn = g.panel[i];
+        describe_cm_i8_launch(pn.first, l0, sizeof(l0));
+        snprintf(piece, sizeof(piece), " | col0=%d sp=%d k_cm_i8<%d,%d,%d,%s> tpl=%d launches=%d ctiles=%d %s", pn.col0, pn.Sp,
+                 g.nkc, g.nd, pn.ncgx, pn.s4 ? "s4" : "pairs", pn.tpl, pn.n_launch, g.n_ct, l0);
+        add(piece);
+        if (pn.last.mt1 - pn.last.mt0 != pn.first.mt1 - pn.first.mt0) {  // a shorter last launch: its own LDS and grid
+            describe_cm_i8_launch(pn.last, l1, sizeof(l1));
+            snprintf(piece, sizeof(piece), " last: tiles=%d %s", pn.last.mt1 - pn.last.mt0, l1);
+            add(piece);
+        }
+    }
+    return (int)n;
+}
+
+hipError_t launch_cm_i8(const ProblemView& p, const IterateView& it, double* cm, hipStream_t st, CmRan* ran) {
     const int S = p.S, n_c = p.n_c, n_u = it.n_u;
     if (!cm_i8_supported(p.v_align(), S, n_c, n_u, p.ND, p.SD) || cm == nullptr || p.D16 == nullptr) return hipErrorInvalidValue;
-    const int nmt = (n_u * (n_u + 1) / 2 + 15) / 16, n_ct = (n_u + 15) / 16;
-    for (int col0 = 0; col0 < S; col0 += kCmPanel) {  // panels of 256 samples; the second and later ones add to cm
-        const int Sp = S - col0 < kCmPanel ? S - col0 : kCmPanel;
-        // pair tiles per launch: what the LDS holds beside the alpha copy; at least one launch per c tile
-        int tpl = nmt;
-        while (tpl > 1 && cm_layout(Sp, n_c, n_u, tpl).bytes > (size_t)160 * 1024) --tpl;
-        int n_launch = (nmt + tpl - 1) / tpl;
-        if (n_launch < n_ct) n_launch = n_ct;
-        tpl = (nmt + n_launch - 1) / n_launch;
-        const bool s4 = (Sp & 3) == 0 && (S & 1) == 0;  // (odd S: rows of V are 8-byte aligned only)
-        for (int li = 0; li < n_launch; ++li) {
-            const int mt0 = li * tpl < nmt ? li * tpl : nmt, mt1 = mt0 + tpl < nmt ? mt0 + tpl : nmt;
-            const int c_tile = li < n_ct ? li : n_ct - 1, c_store = li < n_ct ? 1 : 0;
-            const size_t lds = cm_layout(Sp, n_c, n_u, mt1 - mt0).bytes;
-            const int64_t nblk = (p.N + 31) / 32;
-            const int64_t want = (nblk + kCmWaves - 1) / kCmWaves;
-            // one workgroup (two waves per SIMD at ~200 registers) per CU, two where the tables leave room
-            const int64_t cap = (int64_t)256 * per_cu_knob("DMF_CM_PER_CU", lds <= 76 * 1024 ? 2 : 1);
-            const int64_t grid = want < cap ? want : cap;
-            // template parameters: known-type chunks (beyond four: kCmNkcWide), digit planes, column groups (four on panels
-            // of more than 128 samples, else two), whole float4 columns
+    const CmI8Plan g = cm_i8_plan(p.N, S, n_c, n_u, p.ND);
+    if (!g.supported) return hipErrorInvalidValue;
+    for (int ip = 0; ip < g.n_panels; ++ip) {
+        const CmI8Panel& pn = g.panel[ip];
+        for (int li = 0; li < pn.n_launch; ++li) {
+            const CmI8Launch l = cm_i8_launch_of(g, ip, li);
+            if (l.mt1 <= l.mt0) return hipErrorInvalidValue;  // (cm_i8_plan has refused such a plan)
             const auto launch = [&](auto nkc) {
-                return dispatch_int<1, 2>(p.ND, [&](auto nd) {
-                    return dispatch_bool(Sp > 128, [&](auto wide) {
-                        return dispatch_bool(s4, [&](auto s4_t) {
+                return dispatch_int<1, 2>(g.nd, [&](auto nd) {
+                    return dispatch_bool(pn.ncgx == 4, [&](auto wide) {
+                        return dispatch_bool(pn.s4, [&](auto s4_t) {
                             constexpr auto kernel = k_cm_i8<decltype(nkc)::value, decltype(nd)::value,
                                                             decltype(wide)::value ? 4 : 2, decltype(s4_t)::value>;
                             const hipError_t e = raise_dynamic_lds<kernel>(160 * 1024);
                             if (e != hipSuccess) return e;
-                            hipLaunchKernelGGL(kernel, dim3((unsigned)grid), dim3(kCmWaves * 64), lds, st, p.V, p.D16, p.SD, p.Rtp,
-                                               it.alpha, it.state, p.N, S, n_c, n_u, cm, col0, Sp, col0 > 0 ? 1 : 0, c_tile,
-                                               c_store, mt0, mt1);
+                            hipLaunchKernelGGL(kernel, dim3((unsigned)l.grid), dim3(kCmWaves * 64), l.lds, st, p.V, p.D16, p.SD,
+                                               p.Rtp, it.alpha, it.state, p.N, S, n_c, n_u, cm, pn.col0, pn.Sp, pn.col0 > 0 ? 1 : 0,
+                                               l.c_tile, l.c_store, l.mt0, l.mt1);
                             return hipGetLastError();
                         });
                     });
                 });
             };
-            const int nkc = (n_c + 3) / 4;
-            const hipError_t e = nkc <= 4 ? dispatch_int<0, 4>(nkc, launch) : launch(std::integral_constant<int, kCmNkcWide>{});
+            const hipError_t e = g.nkc <= 4 ? dispatch_int<0, 4>(g.nkc, launch) : launch(std::integral_constant<int, kCmNkcWide>{});
             if (e != hipSuccess) return e;
         }
     }
+    if (ran != nullptr) describe_cm_i8_plan(g, ran->text, sizeof(ran->text));
     return hipSuccess;
 }
 

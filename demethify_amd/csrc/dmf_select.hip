@@ -211,6 +211,14 @@ int describe_u_phase(const ShapeKey& k, const PathSpec& s, int n_iter2, bool pur
             describe_row_launch(u_step_direct_plan(k.N, k.S, k.n_c, k.n_u), head, sizeof(head));
             return snprintf(buf, cap, "%s launches=%d", head, n_iter2);
         }
+        case RowKind::CmI8InnerRows:
+        case RowKind::CmI8InnerBu: {
+            // the rowpass= text, then the producer's launch plan (the one launch_cm_i8 dispatches on)
+            char rowtext[160], plan[2048];
+            describe_row(k, row, rowtext, sizeof(rowtext));
+            describe_cm_i8_plan(cm_i8_plan(k.N, k.S, k.n_c, k.n_u, k.nd), plan, sizeof(plan));
+            return snprintf(buf, cap, "%s %s", rowtext, plan);
+        }
         default: {
             char rowtext[160];
             describe_row(k, row, rowtext, sizeof(rowtext));

@@ -183,8 +183,9 @@ def _route(route) -> int:
 
 def u_phase_describe(N, S, n_c, n_u, nd=0, level=0, n_iter2=20, flags=0, route="solver"):
     """dmf_u_phase_describe: the u phase of a shape with its launch plan -- a pure function of the key, no GPU is touched.
-    None where no kernel takes the shape (DMF_ERR_UNSUPPORTED)."""
-    buf = C.create_string_buffer(512)
+    None where no kernel takes the shape (DMF_ERR_UNSUPPORTED).  (2 KB: the producer k_cm_i8 prints one entry per panel of
+    256 samples.)"""
+    buf = C.create_string_buffer(2048)
     st = L.load().dmf_u_phase_describe(int(N), int(S), int(n_c), int(n_u), int(nd), int(level), int(n_iter2), int(flags),
                                        _route(route), buf, len(buf))
     if st == L.DMF_ERR_UNSUPPORTED:
@@ -650,7 +651,7 @@ class Solver:
     def u_phase_describe(self, n_iter2: int = 20, route="solver") -> str:
         """What the u phase of this solver launches, with its launch plan (dmf_solver_u_phase_describe).  ``route``:
         "solver" (an outer iteration of step()) or "update_u" (the stand-alone u phase of Problem.update_u)."""
-        buf = C.create_string_buffer(512)
+        buf = C.create_string_buffer(2048)
         L.check(self._lib.dmf_solver_u_phase_describe(self._h, int(n_iter2), _route(route), buf, len(buf)),
                 "dmf_solver_u_phase_describe")
         return buf.value.decode()
@@ -669,6 +670,18 @@ class Solver:
         out = np.empty(((self.K + 1) * (self.K + 2) // 2, self.problem.S), dtype=np.float64)
         buf = C.create_string_buffer(256)
         L.check(self._lib.dmf_solver_gram(self._h, k, _ptr(out), buf, len(buf)), "dmf_solver_gram")
+        return out, buf.value.decode()
+
+    def row_moments(self):
+        """(cm, text): the per-row moments of the split u phase, (N, n_u + n_u (n_u + 1) / 2) doubles -- c_i, then M_i in
+        packed pair order p = l (l + 1) / 2 + j, j <= l -- for the solver's CURRENT alpha, computed now by the producer that
+        the split form of its stand-alone u phase launches (k_cm_i8, or k_u_phase_mfma in split mode), and that producer's
+        launch plan (dmf_solver_row_moments).  DMF_ERR_UNSUPPORTED where that u phase has no split form; DMF_ERR_BAD_ARG on
+        a solver that has stopped (its producers do nothing).  For tests: the iterate and a later step() are unaffected."""
+        n_u = self.n_u
+        out = np.empty((self.problem.N, n_u + n_u * (n_u + 1) // 2), dtype=np.float64)
+        buf = C.create_string_buffer(2048)
+        L.check(self._lib.dmf_solver_row_moments(self._h, _ptr(out), buf, len(buf)), "dmf_solver_row_moments")
         return out, buf.value.decode()
 
     def stop_info(self):

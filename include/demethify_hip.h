@@ -310,6 +310,18 @@ int dmf_solver_holdout_error(dmf_solver* s, const dmf_problem* full, double* sum
  * (A call with one of the other two kinds rewrites that buffer: ask for DMF_GRAM_LAST first.) */
 enum { DMF_GRAM_INTEGER = 0, DMF_GRAM_FP64 = 1, DMF_GRAM_LAST = 2 };
 int dmf_solver_gram(dmf_solver* s, int kind, double* out_gb, char* out_text, int64_t cap);
+/* The per-row moments of the split u phase for the solver's CURRENT alpha, computed now, for tests: out_cm (N x NV host
+ * doubles, NV = n_u + n_u (n_u + 1) / 2) <- row i: c_i = alpha_unk (d_i * (v_i - Rt_i alpha_known))^T (n_u values), then
+ * M_i[p] = sum_s alpha_js alpha_ls d_is in packed pair order p = l (l + 1) / 2 + j, j <= l.  It runs the PRODUCER that the
+ * split form of this solver's stand-alone u phase launches (what dmf_update_u takes beyond 50 inner steps, and at every count
+ * for wide row groups) -- k_cm_i8, or k_u_phase_mfma in split mode -- into the solver's own scratch and copies that out; no
+ * inner iteration runs, the iterate is left alone, and every u phase rewrites the scratch before it reads it, so stepping on
+ * gives the same bits as without this call.  out_text (may be NULL; 2 KB hold every plan): the producer's launch plan --
+ * the part of dmf_solver_u_phase_describe(.., DMF_ROUTE_UPDATE_U, ..) behind "k_cm_i8<nd=..>+k_u_inner_rows ", or the whole
+ * "k_u_phase_mfma<..> split .." text.  DMF_ERR_UNSUPPORTED where that u phase has no split form (k_u_phase_big,
+ * k_u_phase_gram, k_u_step_direct).  The producers do nothing once the stop test has fired, so a solver that has stopped is
+ * refused with DMF_ERR_BAD_ARG instead of handing out an earlier iteration's scratch. */
+int dmf_solver_row_moments(dmf_solver* s, double* out_cm, char* out_text, int64_t cap);
 int dmf_solver_destroy(dmf_solver* s);
 /* Which kernels a step with n_iter2 inner iterations would launch for this solver, as text, e.g.
  * "rowpass=k_rowpass_fused<3,4> nw=4 grid=256 tail=5 gram=fused alpha=k_alpha_phase_row16".  For tests (every
@@ -332,8 +344,14 @@ int dmf_select_describe(int64_t N, int64_t S, int64_t n_c, int64_t n_u, int nd, 
  *   "k_u_phase_big<0,16> n_u=12 nw=4 grid=512 lds=.. raise=0 blocks/wg=2"
  *   "k_u_phase_gram<3> alpha=lds nw=4 grid=.. lds=.. raise=0 blocks/wg=1"            (alpha=lds | global)
  *   "k_u_step_direct n_u=5 nw=4 grid=.. lds=.. raise=0 blocks/wg=2 launches=20"
- * (row blocks of 16 rows; k_u_phase_gram 64, k_u_step_direct 4).  For every other u phase it is the rowpass= part of
- * dmf_select_describe.  DMF_ERR_UNSUPPORTED where no kernel takes the shape. */
+ * (row blocks of 16 rows; k_u_phase_gram 64, k_u_step_direct 4).  For the split u phase on the integer producer it is the
+ * rowpass= part of dmf_select_describe, then the plan launch_cm_i8 dispatches on, one entry per panel of 256 samples:
+ *   "k_cm_i8<nd=1>+k_u_inner_rows panels=2 tiles=10 | col0=0 sp=256 k_cm_i8<1,1,4,s4> tpl=5 launches=2 ctiles=2 lds=..
+ *    grid=.. blocks/wave=1 | col0=256 sp=44 k_cm_i8<1,1,2,s4> tpl=5 .."
+ * k_cm_i8<NKC,ND,NCGX,s4|pairs>; tiles: 16-pair tiles of M_i, tpl of them per launch; ctiles: 16-unknown tiles of c; lds, grid
+ * and blocks/wave (32-row blocks of the busiest wave) are the first launch's -- where the last launch holds fewer tiles,
+ * " last: tiles=.. lds=.. grid=.. blocks/wave=.." follows.  (2 KB hold every such text.)  For every other u phase it is the
+ * rowpass= part of dmf_select_describe.  DMF_ERR_UNSUPPORTED where no kernel takes the shape. */
 enum { DMF_ROUTE_SOLVER = 0, DMF_ROUTE_UPDATE_U = 1 };
 int dmf_u_phase_describe(int64_t N, int64_t S, int64_t n_c, int64_t n_u, int nd, int level, int64_t n_iter2, int flags, int route,
                          char* buf, int64_t cap);

@@ -191,12 +191,18 @@ def test_supported_boundaries():
 
 
 def test_second_generation_kernels_keep_their_row_text():
-    """For a u phase that is not one of the five kernels the accessor answers the rowpass= part of dmf_select_describe."""
+    """For a u phase that is not one of the five kernels the accessor answers the rowpass= part of dmf_select_describe --
+    followed, for the integer producer k_cm_i8, by that producer's launch plan (tests/cm_exact.py writes it down)."""
+    import cm_exact as cm
+
     flags = F32 | L.DMF_SELECT_X16
-    for key in ((1000, 64, 6, 2, 1, 0, 20), (1000, 640, 6, 2, 1, 0, 20), (1000, 64, 0, 12, 1, 0, 20)):
+    for key, producer in (((1000, 64, 6, 2, 1, 0, 20), False), ((1000, 640, 6, 2, 1, 0, 20), True), ((1000, 64, 0, 12, 1, 0, 20), True)):
         st, sel = _select(*key, flags)
         assert st == L.DMF_OK
-        assert "rowpass=" + u_phase_describe(*key, flags) == sel.split(" gram=")[0]
+        N, S, n_c, n_u, nd = key[:5]
+        plan = " " + cm.plan_text(N, S, n_c, n_u, nd) if producer else ""
+        assert ("k_cm_i8<" in sel) == producer
+        assert "rowpass=" + u_phase_describe(*key, flags) == sel.split(" gram=")[0] + plan
 
 
 def test_describe_argument_checks():
