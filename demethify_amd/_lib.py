@@ -22,6 +22,9 @@ DMF_ERR_BAD_ARG, DMF_ERR_NONFINITE, DMF_ERR_UNSUPPORTED = 1, 4, 5
 DMF_ERR_BAD_SHAPE = 2
 DMF_GRAM_INTEGER, DMF_GRAM_FP64, DMF_GRAM_LAST = 0, 1, 2
 DMF_ROUTE_SOLVER, DMF_ROUTE_UPDATE_U = 0, 1
+# dmf_solver_momentum_state's scalars, in order (DMF_MOMENTUM_SCALARS of them; the last five are integers)
+MOMENTUM_SCALARS = ("a1", "a2", "l_w", "l_w_prev", "l_h", "l_h_prev", "dsq", "rt_norm2", "u_norm2", "cf", "cf_prev",
+                    "iters", "done", "arrive", "mom_n", "mom_i")
 DMF_MODE_PARTIAL = 0
 DMF_MODE_UNSUPERVISED = 1
 MAX_K = 64  # dmf::kMaxK: largest n_c + n_u the kernels are built for (DMF_ERR_UNSUPPORTED beyond)
@@ -66,6 +69,7 @@ SIGNATURES = {
     "dmf_gram_i8_describe": (C.c_int, [_i64, _i64, _i64, _i64, C.c_int, C.c_char_p, _i64]),
     "dmf_solver_gram": (C.c_int, [_p, C.c_int, _p, C.c_char_p, _i64]),
     "dmf_solver_row_moments": (C.c_int, [_p, _p, C.c_char_p, _i64]),
+    "dmf_solver_momentum_state": (C.c_int, [_p, _dbl_p, _p, _p]),
     "dmf_cost": (C.c_int, [_p, _p, _p, _i64, _p, C.c_int, _dbl_p]),
     "dmf_cost_describe": (C.c_int, [_i64, _i64, _i64, C.c_int, _i64, C.c_int, C.c_int, C.c_int, C.c_char_p, _i64]),
     "dmf_problem_cost_describe": (C.c_int, [_p, _p, _i64, C.c_char_p, _i64]),

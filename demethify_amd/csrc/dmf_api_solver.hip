@@ -725,6 +725,26 @@ int dmf_solver_row_moments(dmf_solver* s, double* out_cm, char* out_text, int64_
     return status;
 }
 
+int dmf_solver_momentum_state(const dmf_solver* s, double* scalars, double* alpha_prev, double* u_prev) {
+    if (s == nullptr || scalars == nullptr) return DMF_ERR_BAD_ARG;
+    dmf_context* ctx = s->ctx;
+    DMF_TRY(check_ctx(ctx));
+    const dmf_problem* p = s->p;
+    SolverState st;  // (a copy of its own: the solver's page-locked mirror is the stepping loop's)
+    HIP_TRY(hipMemcpyAsync(&st, s->state.get(), sizeof(SolverState), hipMemcpyDeviceToHost, ctx->stream));
+    if (alpha_prev != nullptr)
+        HIP_TRY(hipMemcpyAsync(alpha_prev, s->alpha_prev.get(), (size_t)(p->n_c + s->n_u) * p->S * sizeof(double), hipMemcpyDeviceToHost,
+                               ctx->stream));
+    if (u_prev != nullptr)
+        HIP_TRY(hipMemcpyAsync(u_prev, s->u_prev.get(), (size_t)p->N * s->n_u * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    const double out[DMF_MOMENTUM_SCALARS] = {st.a1, st.a2, st.l_w, st.l_w_prev, st.l_h, st.l_h_prev, st.dsq, st.rt_norm2,
+                                              st.u_norm2, st.cf, st.cf_prev, (double)st.iters, (double)st.done,
+                                              (double)st.arrive, (double)st.mom_n, (double)st.mom_i};
+    for (int i = 0; i < DMF_MOMENTUM_SCALARS; ++i) scalars[i] = out[i];
+    return DMF_OK;
+}
+
 int dmf_solver_destroy(dmf_solver* s) {
     if (s == nullptr) return DMF_OK;
     dmf_context* ctx = s->ctx;

@@ -684,6 +684,21 @@ class Solver:
         L.check(self._lib.dmf_solver_row_moments(self._h, _ptr(out), buf, len(buf)), "dmf_solver_row_moments")
         return out, buf.value.decode()
 
+    def momentum_state(self, arrays=True):
+        """The momentum state of the outer loop as it stands on the device (dmf_solver_momentum_state): a dict of the
+        scalars ``_lib.MOMENTUM_SCALARS`` -- a1, a2, l_w, l_w_prev, l_h, l_h_prev, dsq, rt_norm2, u_norm2, cf, cf_prev as
+        floats, iters, done, arrive, mom_n, mom_i as ints -- and, with ``arrays``, "alpha_prev" (K x S) and "u_prev"
+        (N x n_u) as fresh host arrays.  For tests: read-only, the iterate and a later step() are unaffected."""
+        sc = (C.c_double * len(L.MOMENTUM_SCALARS))()
+        alpha_prev = np.empty((self.K, self.problem.S), dtype=np.float64) if arrays else None
+        u_prev = np.empty((self.problem.N, self.n_u), dtype=np.float64) if arrays else None
+        L.check(self._lib.dmf_solver_momentum_state(self._h, sc, _ptr(alpha_prev), _ptr(u_prev)),
+                "dmf_solver_momentum_state")
+        out = {name: (int(v) if i >= 11 else float(v)) for i, (name, v) in enumerate(zip(L.MOMENTUM_SCALARS, sc))}
+        if arrays:
+            out["alpha_prev"], out["u_prev"] = alpha_prev, u_prev
+        return out
+
     def stop_info(self):
         """How the stop tests of this solver's step() calls were decided (dmf_solver_stop_info): a dict with
         confirm_stops (streaming-cost confirmation active for the last step() call), n_confirmed, n_unconfirmed and

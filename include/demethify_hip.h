@@ -322,6 +322,14 @@ int dmf_solver_gram(dmf_solver* s, int kind, double* out_gb, char* out_text, int
  * k_u_phase_gram, k_u_step_direct).  The producers do nothing once the stop test has fired, so a solver that has stopped is
  * refused with DMF_ERR_BAD_ARG instead of handing out an earlier iteration's scratch. */
 int dmf_solver_row_moments(dmf_solver* s, double* out_cm, char* out_text, int64_t cap);
+/* The momentum state of the outer loop as it stands on the device, for tests: waits for the context's stream, then
+ * scalars (DMF_MOMENTUM_SCALARS host doubles) <- a1, a2, l_w, l_w_prev, l_h, l_h_prev, dsq, rt_norm2, u_norm2, cf, cf_prev,
+ * then iters, done, arrive, mom_n, mom_i as doubles (mom_n = -1 / 0: no momentum rows in use); alpha_prev (K x S host
+ * doubles, may be NULL) <- the previous alpha of the alpha phase; u_prev (N x n_u host doubles, may be NULL) <- the previous u
+ * of the u phase.  Read-only: nothing is launched and nothing on the device or in the solver changes, so stepping on gives
+ * the same bits as without this call.  (cf is the loop's cost only once an iteration has run.) */
+enum { DMF_MOMENTUM_SCALARS = 16 };
+int dmf_solver_momentum_state(const dmf_solver* s, double* scalars, double* alpha_prev, double* u_prev);
 int dmf_solver_destroy(dmf_solver* s);
 /* Which kernels a step with n_iter2 inner iterations would launch for this solver, as text, e.g.
  * "rowpass=k_rowpass_fused<3,4> nw=4 grid=256 tail=5 gram=fused alpha=k_alpha_phase_row16".  For tests (every

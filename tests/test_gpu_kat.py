@@ -72,17 +72,28 @@ def test_projection_matches_oracle(ctx, K, S):
     assert np.abs(got2 - osol.simplex_project_columns(X, z=2.5)).max() <= 1e-14 * max(1.0, np.abs(X).max())
 
 
-@pytest.mark.parametrize("generic", [0, 1, 2, 3])
-@pytest.mark.parametrize("N,S,n_c,n_u", SHAPES)
-def test_update_u_matches_oracle(ctx, N, S, n_c, n_u, generic):
-    """update_u with a NON-initial momentum state (a1 > 1, l_w_ != l_w, u_ != u)."""
+# (a1, l_w_prev / l_w) of test_update_u_matches_oracle.  QUIET leaves (a1 - 1) / a_next below the cap 0.9999 sqrt(l_w_prev / l_w)
+# throughout; under SQRT the cap decides the first inner step, under FLAT every one (tests/momentum_ref.py)
+U_STATES = {"QUIET": (2.7, 0.8), "SQRT": (40.0, 0.5), "FLAT": (3e4, 1.0)}
+
+
+def _update_u_cases():
+    """(N, S, n_c, n_u, generic, state); the QUIET cases keep the ids they had before the other states came."""
+    return [pytest.param(N, S, n_c, n_u, generic, state,
+                         id=f"{N}-{S}-{n_c}-{n_u}-{generic}" + ("" if state == "QUIET" else "-" + state))
+            for state in U_STATES for N, S, n_c, n_u in SHAPES for generic in (0, 1, 2, 3)]
+
+
+@pytest.mark.parametrize("N,S,n_c,n_u,generic,state", _update_u_cases())
+def test_update_u_matches_oracle(ctx, N, S, n_c, n_u, generic, state):
+    """update_u with a NON-initial momentum state (a1 > 1, l_w_ != l_w or the cap at 0.9999, u_ != u)."""
     from demethify_amd.device import Problem
 
     V, D, Rt, u, alpha, rs = _problem(N, S, n_c, n_u, 3)
     u_prev = np.clip(u + 0.05 * rs.randn(N, n_u), 0, 1)
     d = float(D.max()) ** 2
     l_w = np.linalg.norm(alpha[-n_u:]) ** 2 * d
-    a1, l_w_prev = 2.7, 0.8 * l_w
+    a1, l_w_prev = U_STATES[state][0], U_STATES[state][1] * l_w
     want = osol.u_phase(u, alpha, 5, a1, l_w_prev, l_w, u_prev, V, Rt, n_u, D)
     ctx.set_generic(generic)
     try:
