@@ -25,6 +25,12 @@ DMF_ROUTE_SOLVER, DMF_ROUTE_UPDATE_U = 0, 1
 # dmf_solver_momentum_state's scalars, in order (DMF_MOMENTUM_SCALARS of them; the last five are integers)
 MOMENTUM_SCALARS = ("a1", "a2", "l_w", "l_w_prev", "l_h", "l_h_prev", "dsq", "rt_norm2", "u_norm2", "cf", "cf_prev",
                     "iters", "done", "arrive", "mom_n", "mom_i")
+# dmf_problem_report's integers and doubles, in order (DMF_REPORT_INTS / DMF_REPORT_DBLS of them)
+REPORT_INTS = ("N", "S", "n_c", "ND", "SD", "N16", "plane_stride", "has_D16", "has_X16", "has_W16", "has_Dt8", "has_mask_bits",
+               "rtp_width", "rtp_borrows_rt", "n_test", "d_f32_exact")
+REPORT_DBLS = ("kDsq", "kRtSumsq", "kDmax", "kF32ResidualMax", "kIntCountMax", "kRtOutsideUnit", "x16_dev", "x16_sum")
+# dmf_problem_copy_out's arrays: name -> DMF_ARRAY_* (V, D, Rt, Rtp, consts hold doubles, D16 / X16 / W16 u16, Dt8 i8, mask_bits u8)
+PROBLEM_ARRAYS = {"V": 0, "D": 1, "Rt": 2, "Rtp": 3, "D16": 4, "X16": 5, "W16": 6, "Dt8": 7, "mask_bits": 8, "consts": 9}
 DMF_MODE_PARTIAL = 0
 DMF_MODE_UNSUPERVISED = 1
 MAX_K = 64  # dmf::kMaxK: largest n_c + n_u the kernels are built for (DMF_ERR_UNSUPPORTED beyond)
@@ -66,6 +72,8 @@ SIGNATURES = {
     "dmf_problem_destroy": (C.c_int, [_p]),
     "dmf_problem_shape": (C.c_int, [_p, C.POINTER(_i64), C.POINTER(_i64), C.POINTER(_i64)]),
     "dmf_problem_gram_known": (C.c_int, [_p, _p, C.c_char_p, _i64]),
+    "dmf_problem_report": (C.c_int, [_p, C.POINTER(_i64), _dbl_p]),
+    "dmf_problem_copy_out": (C.c_int, [_p, C.c_int, _p, _i64]),
     "dmf_gram_i8_describe": (C.c_int, [_i64, _i64, _i64, _i64, C.c_int, C.c_char_p, _i64]),
     "dmf_solver_gram": (C.c_int, [_p, C.c_int, _p, C.c_char_p, _i64]),
     "dmf_solver_row_moments": (C.c_int, [_p, _p, C.c_char_p, _i64]),

@@ -395,6 +395,45 @@ int dmf_problem_gram_known(const dmf_problem* p, double* out, char* out_text, in
     return DMF_OK;
 }
 
+int dmf_problem_report(const dmf_problem* p, int64_t* out_ints, double* out_dbls) {
+    if (p == nullptr || out_ints == nullptr || out_dbls == nullptr) return DMF_ERR_BAD_ARG;
+    const int64_t rtp_width = p->Rtp != nullptr ? (p->n_c + 3) / 4 * 4 : 0;
+    const int64_t ints[DMF_REPORT_INTS] = {p->N, p->S, p->n_c, p->ND, p->SD, p->N16, p->plane_stride,
+                                           p->D16 != nullptr, p->X16 != nullptr, p->W16 != nullptr, p->Dt8 != nullptr,
+                                           p->mask_bits != nullptr, rtp_width,
+                                           p->Rtp != nullptr && p->Rtp.get() == p->Rt.get(), p->n_test, p->d_f32_exact};
+    std::memcpy(out_ints, ints, sizeof(ints));
+    for (int i = 0; i < kProblemConsts; ++i) out_dbls[i] = p->h_consts[i];
+    out_dbls[kProblemConsts] = p->x16_dev;
+    out_dbls[kProblemConsts + 1] = p->x16_sum;
+    return DMF_OK;
+}
+
+int dmf_problem_copy_out(const dmf_problem* p, int which, void* out, int64_t bytes) {
+    if (p == nullptr || out == nullptr) return DMF_ERR_BAD_ARG;
+    dmf_context* ctx = p->ctx;
+    DMF_TRY(check_ctx(ctx));
+    const size_t elems = (size_t)p->N * p->S, u16_bytes = (size_t)p->N16 * p->SD * sizeof(unsigned short);
+    const void* src = nullptr;
+    size_t size = 0;
+    switch (which) {
+        case DMF_ARRAY_V: src = p->V, size = elems * sizeof(double); break;
+        case DMF_ARRAY_D: src = p->D, size = elems * sizeof(double); break;
+        case DMF_ARRAY_RT: src = p->Rt, size = (size_t)p->N * p->n_c * sizeof(double); break;
+        case DMF_ARRAY_RTP: src = p->Rtp, size = (size_t)p->N * ((p->n_c + 3) / 4 * 4) * sizeof(double); break;
+        case DMF_ARRAY_D16: src = p->D16, size = u16_bytes; break;
+        case DMF_ARRAY_X16: src = p->X16, size = u16_bytes; break;
+        case DMF_ARRAY_W16: src = p->W16, size = u16_bytes; break;
+        case DMF_ARRAY_DT8: src = p->Dt8, size = (size_t)p->plane_stride * p->ND; break;
+        case DMF_ARRAY_MASK_BITS: src = p->mask_bits, size = (size_t)p->N * (size_t)((p->S + 7) / 8); break;
+        case DMF_ARRAY_CONSTS: src = p->consts, size = kProblemConsts * sizeof(double); break;
+        default: return DMF_ERR_BAD_ARG;
+    }
+    if (src == nullptr || size == 0) return DMF_ERR_BAD_ARG;
+    if (bytes < 0 || (size_t)bytes != size) return DMF_ERR_BAD_SHAPE;
+    return export_array(ctx, src, size, 0, out);
+}
+
 int dmf_problem_shape(const dmf_problem* p, int64_t* N, int64_t* S, int64_t* n_c) {
     if (p == nullptr) return DMF_ERR_BAD_ARG;
     if (N) *N = p->N;

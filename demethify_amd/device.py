@@ -307,7 +307,10 @@ class Problem:
 
     def close(self):
         if getattr(self, "_h", None):
-            self._lib.dmf_problem_destroy(self._h)
+            # (a context that is already closed took its pool, and with it this problem's buffers: the garbage collector may
+            # finalise a Context before the Problems of a reference cycle that holds both)
+            if getattr(self.ctx, "_h", None):
+                self._lib.dmf_problem_destroy(self._h)
             self._h = None
             self._keep = ()
 
@@ -354,6 +357,38 @@ class Problem:
         buf = C.create_string_buffer(256)
         L.check(self._lib.dmf_problem_gram_known(self._h, _ptr(out), buf, len(buf)), "dmf_problem_gram_known")
         return out, buf.value.decode()
+
+    def report(self) -> dict:
+        """What the builder of this problem (create, gather, mask) left behind, as a dict: the integers ``_lib.REPORT_INTS``
+        -- shapes, digit count, which integer copies and mask bits exist, the padded R_trunc copy's row width and whether
+        it is R_trunc itself, n_test, d_f32_exact -- and the doubles ``_lib.REPORT_DBLS`` -- the host copy of the six
+        constants, x16_dev, x16_sum (dmf_problem_report).  For tests."""
+        ints = (C.c_int64 * len(L.REPORT_INTS))()
+        dbls = (C.c_double * len(L.REPORT_DBLS))()
+        L.check(self._lib.dmf_problem_report(self._h, ints, dbls), "dmf_problem_report")
+        out = {k: int(v) for k, v in zip(L.REPORT_INTS, ints)}
+        out.update({k: float(v) for k, v in zip(L.REPORT_DBLS, dbls)})
+        return out
+
+    def copy_out(self, name: str, report: dict | None = None) -> np.ndarray:
+        """One device array of this problem, by its name in ``_lib.PROBLEM_ARRAYS``, in its own shape: V, D (N, S), Rt
+        (N, n_c), Rtp (N, rtp_width), D16 / X16 / W16 (N16, SD) uint16, Dt8 (ND, ceil(N / 32), SD / 32, 32, 32) int8 indexed
+        [plane, row block, sample block, n, k], mask_bits (N, ceil(S / 8)) uint8, consts (6,) (dmf_problem_copy_out;
+        DMF_ERR_BAD_ARG for an array the problem does not have).  ``report``: this problem's ``report()``, if the caller has
+        it already.  For tests."""
+        r = self.report() if report is None else report
+        shape, dtype = {
+            "V": ((r["N"], r["S"]), np.float64), "D": ((r["N"], r["S"]), np.float64),
+            "Rt": ((r["N"], r["n_c"]), np.float64), "Rtp": ((r["N"], r["rtp_width"]), np.float64),
+            "D16": ((r["N16"], r["SD"]), np.uint16), "X16": ((r["N16"], r["SD"]), np.uint16),
+            "W16": ((r["N16"], r["SD"]), np.uint16),
+            "Dt8": ((r["ND"], (r["N"] + 31) // 32, r["SD"] // 32, 32, 32), np.int8),
+            "mask_bits": ((r["N"], (r["S"] + 7) // 8), np.uint8), "consts": ((6,), np.float64),
+        }[name]
+        out = np.empty(shape, dtype=dtype)
+        L.check(self._lib.dmf_problem_copy_out(self._h, L.PROBLEM_ARRAYS[name], _ptr(out), out.nbytes),
+                "dmf_problem_copy_out")
+        return out
 
     def wls_intercept(self, u=None, target="v", host_arrays=None, f64_arrays=False):
         """``wls_intercept`` (init_func.py:8-14) of every sample at once on the device (dmf_wls_intercept), with

@@ -149,6 +149,26 @@ int dmf_problem_shape(const dmf_problem* p, int64_t* N, int64_t* S, int64_t* n_c
  * sides; "+ k_bu_cols + k_vdv_cols" or "+ k_bu_cols + k_gram launches=1 .." where v^T D v takes a kernel of its own), "fp64 k_gram_mfma<...> launches=.. ny=.. +
  * k_vdv_cols", "fp64 k_gram launches=1 ..." (levels 1 and 2), "fp64 k_vdv_cols" (n_c = 0). */
 int dmf_problem_gram_known(const dmf_problem* p, double* out, char* out_text, int64_t cap);
+/* What a problem builder (create, gather, mask) left behind, for tests: the scalars here, the arrays through
+ * dmf_problem_copy_out.  out_ints (DMF_REPORT_INTS host int64) <- N, S, n_c, ND (count digits; 0 = no integer copies), SD, N16,
+ * plane_stride, then five 0 / 1 flags -- D16, X16, W16, Dt8 and the mask bits exist --, the row width of the padded R_trunc
+ * copy in doubles (0: there is none), whether that copy is R_trunc itself (n_c % 4 == 0), n_test (held-out elements of a
+ * masked problem) and d_f32_exact.  out_dbls (DMF_REPORT_DBLS host doubles) <- the six constants of the host copy in the
+ * order of DMF_ARRAY_CONSTS, then x16_dev and x16_sum.  No address leaves the library.  DMF_ERR_BAD_ARG on a null pointer. */
+enum { DMF_REPORT_INTS = 16, DMF_REPORT_DBLS = 8 };
+int dmf_problem_report(const dmf_problem* p, int64_t* out_ints, double* out_dbls);
+/* One array of a problem as it stands on the device, for tests: waits for the context's stream and copies `bytes` bytes to the
+ * host buffer `out`.  `bytes` must be the array's size (DMF_ERR_BAD_SHAPE otherwise): V, D N x S doubles; RT N x n_c; RTP
+ * N x 4 ceil(n_c / 4) doubles (R_trunc itself where the report says so); D16, X16, W16 N16 x SD u16; DT8 ND planes of
+ * plane_stride bytes, [plane][row block of 32][sample block of 32][n][k]; MASK_BITS N x ceil(S / 8) bytes; CONSTS the
+ * device copy of the constants, six doubles: max(D)^2, ||Rt||_F^2, max(D), max |D - f32(D)|, max(D) if every count is a
+ * non-negative integer else inf, 1 if R_trunc leaves [0, 1] else 0.  DMF_ERR_BAD_ARG for an array the problem does not have,
+ * an unknown name or a null pointer. */
+enum {
+    DMF_ARRAY_V = 0, DMF_ARRAY_D = 1, DMF_ARRAY_RT = 2, DMF_ARRAY_RTP = 3, DMF_ARRAY_D16 = 4, DMF_ARRAY_X16 = 5,
+    DMF_ARRAY_W16 = 6, DMF_ARRAY_DT8 = 7, DMF_ARRAY_MASK_BITS = 8, DMF_ARRAY_CONSTS = 9
+};
+int dmf_problem_copy_out(const dmf_problem* p, int which, void* out, int64_t bytes);
 
 /* ---- single-function entry points (KAT parity of SURVEY.md section 8a rows 1-4) --------- */
 /* cost_f_w(y, R, alpha, d_x), deconvolution.py:15-17, with R = [Rt | u]. */
