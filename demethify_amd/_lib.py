@@ -89,12 +89,14 @@ SIGNATURES = {
     "dmf_svd_factor": (C.c_int, [_p, _p, _p, _p, _i64, C.c_int, _p, C.POINTER(_p)]),
     "dmf_svd_finish": (C.c_int, [_p, _p, _i64, _i64, _p, _p, C.c_int, _p]),
     "dmf_percentile_axis0": (C.c_int, [_p, _p, _i64, _i64, _p, _i64, C.c_int, _p]),
+    "dmf_nanpercentile_axis0": (C.c_int, [_p, _p, _i64, _i64, _p, _i64, C.c_int, _p]),
     "dmf_solver_create": (C.c_int, [_p, _p, _p, _p, _i64, C.c_int, C.c_int, C.POINTER(_p)]),
     "dmf_solver_set_purity": (C.c_int, [_p, _p, C.c_int]),
     "dmf_solver_step": (C.c_int, [_p, _i64, _i64, C.c_double, C.POINTER(_i64), C.POINTER(C.c_int)]),
     "dmf_solver_get": (C.c_int, [_p, C.c_int, _p, _p, _dbl_p, C.POINTER(_i64)]),
     "dmf_solver_match_components": (C.c_int, [_p, _p, _i64, _p, _p]),
     "dmf_solver_get_u_permuted": (C.c_int, [_p, C.POINTER(C.c_int32), _p]),
+    "dmf_solver_get_u_by_row": (C.c_int, [_p, _p, _i64, C.POINTER(C.c_int32), _p]),
     "dmf_solver_cost": (C.c_int, [_p, _dbl_p]),
     "dmf_solver_cost_begin": (C.c_int, [_p]),
     "dmf_solver_cost_end": (C.c_int, [_p, _dbl_p]),

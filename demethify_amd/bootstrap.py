@@ -71,7 +71,8 @@ def _device_stack(n_local, width):
 
 
 def bt_ci(confidence_level, n_bootstrap, n_u, meth_f, counts, ref, init_option, n_iter1, n_iter2, tol, header,
-          outdir, samples, purity, seed, materialize=True, _observe=None, anchor=None, align_unknown=None):
+          outdir, samples, purity, seed, materialize=True, _observe=None, anchor=None, align_unknown=None,
+          profile_rows="position"):
     """bootstrap.py:10-93 -> [proportions CI DataFrame, (profile CI DataFrame)]; writes the two CSVs.
     materialize=False (the CLI, which ignores the return value) skips building the N-row DataFrame of tuples for the
     profile intervals: the CSV is written by the library and the second result is the (lower, upper) array pair.
@@ -87,7 +88,16 @@ def bt_ci(confidence_level, n_bootstrap, n_u, meth_f, counts, ref, init_option, 
     the replicate's profile columns / proportion rows are stored in the anchor's order.  None = True without a reference
     and False with one (upstream's unaligned percentiles, every existing call as before); skipped for n_u == 1.
     ``anchor`` = (u, alpha) of the solve the components are named after (the CLI passes its point estimate); absent, it is
-    solved here on every rank from the unresampled data, ``seed`` and the same initialiser."""
+    solved here on every rank from the unresampled data, ``seed`` and the same initialiser.
+
+    ``profile_rows``: what row j of the profile intervals speaks about.  "position" (the default, upstream's): the j-th
+    resampled row of every replicate, B different CpGs.  "cpg": CpG j's own estimates -- replicate i contributes
+    ``u_i[first_i[j]]``, the row of the lowest position that drew CpG j, and nothing where it did not draw it (NaN in the
+    stack); the bounds are ``np.nanpercentile`` over the replicates, (nan, nan) for a CpG no replicate drew (DESIGN.md
+    section 6.1).  Composes with ``align_unknown``; ignored for n_u == 0; the proportions table is the same either way."""
+    if profile_rows not in ("position", "cpg"):
+        raise ValueError(f'profile_rows must be "position" or "cpg", got {profile_rows!r}')
+    by_cpg = profile_rows == "cpg"
     if ref is None:
         if n_u < 1:
             raise ValueError("a bootstrap without a reference needs at least one unknown cell type")
@@ -243,12 +253,17 @@ def bt_ci(confidence_level, n_bootstrap, n_u, meth_f, counts, ref, init_option, 
                         if _observe is not None:
                             _observe(i, seeds[i], idx, s)
                         if u_stack is not None:
-                            s.copy_u_to(u_stack[j], columns=order)
+                            if by_cpg:
+                                s.copy_u_by_cpg(u_stack[j], idx_dev, n_rows, columns=order)
+                            else:
+                                s.copy_u_to(u_stack[j], columns=order)
                             u, alpha = None, s.get_alpha()
                         else:
                             u, alpha, _, _ = s.get()
                             if align:
                                 u = np.ascontiguousarray(u[:, order])
+                            if by_cpg:
+                                u = _rows_by_cpg(u, idx, n_rows)
                         if align:
                             alpha[n_ct:] = alpha[n_ct:][order]
                         local.append((i, (u, alpha)))
@@ -285,9 +300,11 @@ def bt_ci(confidence_level, n_bootstrap, n_u, meth_f, counts, ref, init_option, 
             local_u = u_stack
         else:
             local_u = (np.stack([pu.reshape(-1) for _, (pu, _) in local]) if local else np.empty((0, n_rows * n_u)))
-        bounds = shard.percentile_over_replicates(local_u, n_bootstrap, q, get_context().percentile_axis0)
+        percentile_fn = get_context().nanpercentile_axis0 if by_cpg else get_context().percentile_axis0
+        bounds = shard.percentile_over_replicates(local_u, n_bootstrap, q, percentile_fn)
         if bounds is not None:
-            lower_u, upper_u = (b.reshape(n_rows, n_u) for b in bounds)  # by resampled position, as upstream
+            # by resampled position, as upstream, or by CpG (profile_rows)
+            lower_u, upper_u = (b.reshape(n_rows, n_u) for b in bounds)
             path = outdir + "/confidence_interval_methylation_estimate.csv"
             if not _write_interval_csv(path, unknown_header, lower_u, upper_u) or materialize:
                 # upstream's way (bootstrap.py:85-91): N Python tuples per column through DataFrame.to_csv, ~20 s at 1e6 rows
@@ -301,9 +318,19 @@ def bt_ci(confidence_level, n_bootstrap, n_u, meth_f, counts, ref, init_option, 
     return results
 
 
+def _rows_by_cpg(u, idx, n_rows):
+    """``u`` (one row per resampled position, position j being CpG ``idx[j]``) as one row per CpG: the row of the lowest
+    position that drew it, NaN where none did -- the host twin of Solver.copy_u_by_cpg."""
+    out = np.full((n_rows, u.shape[1]), np.nan)
+    cpgs, first = np.unique(idx, return_index=True)
+    out[cpgs] = u[first]
+    return out
+
+
 def _write_interval_csv(path, columns, lower, upper) -> bool:
     """The (lower, upper) table as DataFrame.to_csv writes a DataFrame of tuples, by the library's writer
-    (dmf_write_interval_csv: byte-identical, tests/test_host.py).  False if a column name would need CSV quoting."""
+    (dmf_write_interval_csv: byte-identical, tests/test_host.py; a NaN bound is written ``nan``, as repr writes it).
+    False if a column name would need CSV quoting."""
     import ctypes as C
 
     if any(ch in name for name in columns for ch in ',"\r\n'):

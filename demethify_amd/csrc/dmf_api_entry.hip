@@ -151,8 +151,9 @@ int dmf_project_simplex(dmf_context* ctx, const double* X, int64_t K, int64_t S,
     return deliver_result(ctx, dout, count, flags, out);
 }
 
-int dmf_percentile_axis0(dmf_context* ctx, const double* x, int64_t n, int64_t m, const double* q, int64_t n_q,
-                         int flags, double* out) {
+// np.percentile (skip_nan false) or np.nanpercentile over axis 0, two percentiles per launch
+static int percentile_axis0(dmf_context* ctx, const double* x, int64_t n, int64_t m, const double* q, int64_t n_q, int flags,
+                            double* out, bool skip_nan) {
     DMF_TRY(check_ctx(ctx));
     if (x == nullptr || q == nullptr || out == nullptr || n < 1 || m < 1 || n_q < 1) return DMF_ERR_BAD_ARG;
     for (int64_t i = 0; i < n_q; ++i)
@@ -165,9 +166,25 @@ int dmf_percentile_axis0(dmf_context* ctx, const double* x, int64_t n, int64_t m
         const dmf::PercentilePlan p0 = percentile_plan(n, q[i]);
         const bool two = i + 1 < n_q;
         const dmf::PercentilePlan p1 = two ? percentile_plan(n, q[i + 1]) : p0;
-        HIP_TRY(dmf::launch_percentile_pair(dx, n, m, p0, p1, dout + i * m, two ? dout + (i + 1) * m : nullptr, ctx->stream));
+        double* out0 = dout + i * m;
+        double* out1 = two ? dout + (i + 1) * m : nullptr;
+        // (the kernels plan each column from the quantile, q / 100 as percentile_plan divides it, and its own count)
+        if (skip_nan)
+            HIP_TRY(dmf::launch_nanpercentile_pair(dx, n, m, p0, p1, q[i] / 100.0, q[two ? i + 1 : i] / 100.0, out0, out1,
+                                                   ctx->stream));
+        else HIP_TRY(dmf::launch_percentile_pair(dx, n, m, p0, p1, out0, out1, ctx->stream));
     }
     return deliver_result(ctx, dout, (size_t)n_q * m, flags, out);
+}
+
+int dmf_percentile_axis0(dmf_context* ctx, const double* x, int64_t n, int64_t m, const double* q, int64_t n_q,
+                         int flags, double* out) {
+    return percentile_axis0(ctx, x, n, m, q, n_q, flags, out, false);
+}
+
+int dmf_nanpercentile_axis0(dmf_context* ctx, const double* x, int64_t n, int64_t m, const double* q, int64_t n_q,
+                            int flags, double* out) {
+    return percentile_axis0(ctx, x, n, m, q, n_q, flags, out, true);
 }
 
 int dmf_update_u(dmf_context* ctx, const dmf_problem* p, const double* u, const double* u_prev,

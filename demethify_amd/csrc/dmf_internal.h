@@ -421,6 +421,10 @@ hipError_t launch_gram_v2_reduce(const long long* slab_i8, int ny, int NF, int S
 // two percentiles over axis 0 of x[n][m] -> out0[m], out1[m] (out1 may be null); dmf_kernels_percentile.hip
 hipError_t launch_percentile_pair(const double* x, int64_t n, int64_t m, PercentilePlan p0, PercentilePlan p1,
                                   double* out0, double* out1, hipStream_t st);
+// the same with the NaNs of a column left out (np.nanpercentile): p0 / p1 are the plans for the full n, q0 / q1 the
+// quantiles (percentile / 100) from which the kernels plan each column for its own count of numbers
+hipError_t launch_nanpercentile_pair(const double* x, int64_t n, int64_t m, PercentilePlan p0, PercentilePlan p1, double q0,
+                                     double q1, double* out0, double* out1, hipStream_t st);
 int64_t percentile_max_replicates();
 
 // wls_intercept for every sample at once (dmf_kernels_wls.hip).  launch_wls_moments: one pass over the rows for the first
@@ -470,5 +474,13 @@ hipError_t launch_match_gram(const double* u, const double* anchor, const long l
                              int n_u, double* slab, int* flags, double* P, hipStream_t st);
 hipError_t launch_copy_cols_permuted(const double* u, double* dst, int64_t N, int n_u, const MatchColumns& cols,
                                      hipStream_t st);
+// Profiles by CpG.  launch_first_occurrence: first[c] (n_dst_rows int64, device) = the lowest j < M with idx[j] == c, or
+// kNotDrawn; *n_bad (device) = how many idx[j] lie outside [0, n_dst_rows) -- those are not dereferenced.  The table depends
+// on idx alone.  launch_copy_rows_first: dst[c][b] = u[first[c]][cols.src[b]], or the quiet NaN where c was not drawn.
+constexpr long long kNotDrawn = 0x7fffffffffffffffLL;
+hipError_t launch_first_occurrence(const long long* idx, int64_t M, int64_t n_dst_rows, long long* first,
+                                   unsigned long long* n_bad, hipStream_t st);
+hipError_t launch_copy_rows_first(const double* u, const long long* first, double* dst, int64_t n_dst_rows, int n_u,
+                                  const MatchColumns& cols, hipStream_t st);
 
 }  // namespace dmf

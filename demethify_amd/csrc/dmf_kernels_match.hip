@@ -5,6 +5,7 @@
 // (N x n_u, in HBM), anchor n_anchor_rows x n_u, idx the replicate's int64 row draw (null: the identity).  One pass over u
 // and the gathered anchor rows: N (16 n_u + 8) bytes and N n_u^2 FMAs, plain vector FP64.
 // k_copy_cols_permuted: dst[i][b] = u[i][src_col[b]], the device-to-device copy of the profiles with the columns renamed.
+// k_first_fill / k_first_occurrence / k_copy_rows_first: the same copy with the rows put back by CpG (end of this file).
 //
 // Budget.  k_match_gram, 256 threads, at most one workgroup per CU (kMatchMaxGrid).  LDS, static: a tile of R = 2048 / n_u
 // rows of u (a contiguous chunk of at most 2048 doubles), the same rows of the anchor (gathered, n_u contiguous doubles
@@ -163,6 +164,64 @@ hipError_t launch_copy_cols_permuted(const double* u, double* dst, int64_t N, in
     int64_t blocks = (n + 255) / 256;
     if (blocks > 4096) blocks = 4096;
     hipLaunchKernelGGL(k_copy_cols_permuted, dim3((int)blocks), dim3(256), 0, st, u, dst, n, n_u, cols);
+    return hipGetLastError();
+}
+
+// --------------------------------------------------------------------------- dst[c] = u[first position that drew CpG c]
+// A replicate's rows by CpG: row j of u belongs to CpG idx[j]; CpG c takes the row of its lowest position, a pure gather.
+// k_first_fill marks every CpG "not drawn" and clears the counter; k_first_occurrence lowers first[idx[j]] to j with an
+// integer atomic minimum, whose result does not depend on the order the positions arrive in; k_copy_rows_first moves the
+// rows, one thread per destination element (coalesced stores, n_u contiguous doubles per gathered row), NaN where the CpG
+// was not drawn.  No floating-point arithmetic: a copied value keeps its bits.
+__global__ __launch_bounds__(256) void k_first_fill(long long* __restrict__ first, int64_t n, unsigned long long* n_bad) {
+    const int64_t stride = (int64_t)gridDim.x * 256;
+    for (int64_t c = (int64_t)blockIdx.x * 256 + threadIdx.x; c < n; c += stride) first[c] = kNotDrawn;
+    if (blockIdx.x == 0 && threadIdx.x == 0) *n_bad = 0;
+}
+
+__global__ __launch_bounds__(256) void k_first_occurrence(const long long* __restrict__ idx, int64_t M, int64_t n_dst_rows,
+                                                          long long* first, unsigned long long* n_bad) {
+    const int64_t stride = (int64_t)gridDim.x * 256;
+    unsigned long long bad = 0;
+    for (int64_t j = (int64_t)blockIdx.x * 256 + threadIdx.x; j < M; j += stride) {
+        const long long c = idx[j];
+        if (c < 0 || c >= n_dst_rows) ++bad;
+        else atomicMin(&first[c], (long long)j);
+    }
+    if (bad) atomicAdd(n_bad, bad);
+}
+
+__global__ __launch_bounds__(256) void k_copy_rows_first(const double* __restrict__ u, const long long* __restrict__ first,
+                                                         double* __restrict__ dst, int64_t n, int n_u, MatchColumns cols) {
+    const int64_t stride = (int64_t)gridDim.x * 256;
+    for (int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x; e < n; e += stride) {
+        const int64_t c = e / n_u;
+        const int b = (int)(e - c * n_u);
+        const long long j = first[c];
+        dst[e] = j == kNotDrawn ? __longlong_as_double(0x7ff8000000000000LL) : u[j * n_u + cols.src[b]];
+    }
+}
+
+static int copy_blocks(int64_t n) {
+    const int64_t blocks = (n + 255) / 256;
+    return (int)(blocks > 4096 ? 4096 : blocks);
+}
+
+hipError_t launch_first_occurrence(const long long* idx, int64_t M, int64_t n_dst_rows, long long* first,
+                                   unsigned long long* n_bad, hipStream_t st) {
+    if (M < 1 || n_dst_rows < 1) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_first_fill, dim3(copy_blocks(n_dst_rows)), dim3(256), 0, st, first, n_dst_rows, n_bad);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(k_first_occurrence, dim3(copy_blocks(M)), dim3(256), 0, st, idx, M, n_dst_rows, first, n_bad);
+    return hipGetLastError();
+}
+
+hipError_t launch_copy_rows_first(const double* u, const long long* first, double* dst, int64_t n_dst_rows, int n_u,
+                                  const MatchColumns& cols, hipStream_t st) {
+    if (n_u < 1 || n_u > kMaxK || n_dst_rows < 1) return hipErrorInvalidValue;
+    const int64_t n = n_dst_rows * n_u;
+    hipLaunchKernelGGL(k_copy_rows_first, dim3(copy_blocks(n)), dim3(256), 0, st, u, first, dst, n, n_u, cols);
     return hipGetLastError();
 }
 

@@ -13,6 +13,9 @@ Deliberate differences from upstream, all flagged at run time:
   * ``--confidence`` without ``--ref`` (upstream's bootstrap fails at ``ref.shape``): needs ``--nbunknown >= 1``; the point
     estimate runs first and every replicate's unknown types are matched to its profiles before the percentiles are taken
     (DESIGN.md section 6).  With ``--ref`` the intervals are upstream's, unaligned.
+  * ``DEMETHIFY_CI_ROWS=cpg`` (environment; default ``position``, upstream's): row j of
+    confidence_interval_methylation_estimate.csv is the interval of CpG j's own estimates over the replicates that drew it,
+    (nan, nan) where none did, instead of the percentiles by resampled position.
   * ``--ic NAME [n [lo hi]]``: upstream sweeps the hard-coded range 1..25 (ic.py:171); two more values after the
     restart count restrict the sweep to lo..hi unknown types (``--ic BIC 5 2 12``).  Without them: 1..25, as upstream.
 """
@@ -141,6 +144,11 @@ def main(argv=None):
         sys.stderr.write(f"Error: --init {args.init} (one-shot LAPACK initialiser, demethify/init_func.py) is not part "
                          "of this build; use uniform_, uniform or beta.\n")
         sys.exit(1)
+    # DEMETHIFY_CI_ROWS: what a row of confidence_interval_methylation_estimate.csv speaks about (bt_ci's profile_rows)
+    ci_rows = os.environ.get("DEMETHIFY_CI_ROWS", "position")
+    if ci_rows not in ("position", "cpg"):
+        sys.stderr.write(f'Error: DEMETHIFY_CI_ROWS must be "position" or "cpg", got "{ci_rows}".\n')
+        sys.exit(1)
     if args.plot:
         sys.stderr.write("Note: --plot is ignored, plotting (seaborn/colorcet) is outside this build's scope.\n")
 
@@ -178,7 +186,7 @@ def main(argv=None):
     def bootstrap(anchor=None):
         bt_ci(args.confidence[0], args.confidence[1], n_u, meth_f, counts, ref, args.init, args.iterations[0],
               args.iterations[1], args.termination, header if args.ref else [], outdir, args.methfreq, args.purity,
-              args.seed, materialize=False, anchor=anchor)
+              args.seed, materialize=False, anchor=anchor, profile_rows=ci_rows)
 
     if args.confidence and args.ref:
         bootstrap()

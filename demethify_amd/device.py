@@ -138,19 +138,28 @@ class Context:
         """``np.percentile(x, q, axis=0)`` (numpy's default "linear" method, bootstrap.py:51-54 / :75-78) on
         the device.  ``x``: (n replicates, ...) float64, a host array or a CUDA torch tensor; ``q``: a sequence
         of percentiles.  Returns an array / tensor of shape (len(q),) + x.shape[1:] of the same kind as ``x``."""
+        return self._percentile_axis0(x, q, "dmf_percentile_axis0")
+
+    def nanpercentile_axis0(self, x, q):
+        """``np.nanpercentile(x, q, axis=0)`` on the device, the twin of ``percentile_axis0``: a column's NaNs are left
+        out and its own count of numbers plans its percentiles; a column without a number gives NaN
+        (dmf_nanpercentile_axis0).  Without NaNs the same bits as ``percentile_axis0``."""
+        return self._percentile_axis0(x, q, "dmf_nanpercentile_axis0")
+
+    def _percentile_axis0(self, x, q, entry):
+        fn = getattr(self._lib, entry)
         qs = np.ascontiguousarray(np.atleast_1d(q), dtype=np.float64)
         if _is_torch(x) and x.is_cuda:
             import torch
 
             if x.dtype != torch.float64:
-                raise TypeError("percentile_axis0 takes float64 data")
+                raise TypeError(f"{entry[4:]} takes float64 data")
             x = x.contiguous()
             n, tail = x.shape[0], tuple(x.shape[1:])
             m = int(np.prod(tail, dtype=np.int64))
             out = torch.empty((len(qs),) + tail, dtype=torch.float64, device=x.device)
             torch.cuda.current_stream(x.device).synchronize()  # x was produced on torch's stream, not ours
-            L.check(self._lib.dmf_percentile_axis0(self._h, _ptr(x), n, m, _ptr(qs), len(qs), L.DMF_PTR_DEVICE,
-                                                   _ptr(out)), "dmf_percentile_axis0")
+            L.check(fn(self._h, _ptr(x), n, m, _ptr(qs), len(qs), L.DMF_PTR_DEVICE, _ptr(out)), entry)
             return out
         if _is_torch(x):
             x = x.numpy()
@@ -158,8 +167,7 @@ class Context:
         n, tail = x.shape[0], tuple(x.shape[1:])
         m = int(np.prod(tail, dtype=np.int64))
         out = np.empty((len(qs),) + tail, dtype=np.float64)
-        L.check(self._lib.dmf_percentile_axis0(self._h, _ptr(x), n, m, _ptr(qs), len(qs), 0, _ptr(out)),
-                "dmf_percentile_axis0")
+        L.check(fn(self._h, _ptr(x), n, m, _ptr(qs), len(qs), 0, _ptr(out)), entry)
         return out
 
 
@@ -757,6 +765,24 @@ class Solver:
         L.check(self._lib.dmf_solver_get(self._h, 0, None, _ptr(alpha), None, None), "dmf_solver_get")
         return alpha
 
+    def _on_device(self, t, floating):
+        """Is ``t`` a staging.DeviceArray of this context, or a contiguous float64 (``floating``) / int64 CUDA tensor on its
+        GPU?  (A tensor was produced on torch's stream and is read on ours: that stream is waited for.)"""
+        from .staging import DeviceArray
+
+        ctx = self.problem.ctx
+        if isinstance(t, DeviceArray):
+            return t.ctx is ctx
+        ok = (_is_torch(t) and t.is_cuda and t.is_contiguous() and t.element_size() == 8
+              and t.is_floating_point() == floating and t.device.index == ctx.device)
+        if ok:
+            import torch
+
+            ok = floating or t.dtype == torch.int64
+        if ok:
+            torch.cuda.current_stream(t.device).synchronize()
+        return ok
+
     def match_components(self, anchor, idx=None):
         """P (n_u x n_u host array), P[a, b] = sum_j u[j, a] * anchor[idx[j], b]: the inner products of this solver's profile
         columns with the anchor's, computed where both live (dmf_solver_match_components).  ``anchor``: the n_rows x n_u
@@ -764,25 +790,7 @@ class Solver:
         GPU; ``idx``: the int64 row indices this solver's problem was gathered with, as staging.indices_to_device returns
         them (or an int64 CUDA tensor); None = the identity (the anchor then has this problem's N rows).  An index outside
         the anchor's rows raises (DMF_ERR_BAD_ARG).  ``bootstrap.match_components(P)`` turns P into the assignment."""
-        from .staging import DeviceArray
-
-        ctx = self.problem.ctx
-
-        def on_device(t, floating):
-            if isinstance(t, DeviceArray):
-                return t.ctx is ctx
-            ok = (_is_torch(t) and t.is_cuda and t.is_contiguous() and t.element_size() == 8
-                  and t.is_floating_point() == floating and t.device.index == ctx.device)
-            if ok and not floating:
-                import torch
-
-                ok = t.dtype == torch.int64
-            if ok:
-                import torch
-
-                torch.cuda.current_stream(t.device).synchronize()  # (produced on torch's stream, read on ours)
-            return ok
-
+        on_device = self._on_device
         if not on_device(anchor, True):
             raise ValueError("anchor must be a float64 staging.DeviceArray / contiguous CUDA tensor on the context's GPU")
         n_el = int(np.prod(tuple(anchor.shape)))
@@ -814,6 +822,30 @@ class Solver:
                     "dmf_solver_get_u_permuted")
             return
         L.check(self._lib.dmf_solver_get(self._h, L.DMF_PTR_DEVICE, _ptr(tensor), None, None, None), "dmf_solver_get")
+
+    def copy_u_by_cpg(self, tensor, idx, n_rows, columns=None):
+        """The current profile estimate with its rows put back by CpG (dmf_solver_get_u_by_row): ``idx`` holds the int64 row
+        indices this solver's problem was gathered with (staging.indices_to_device, or an int64 CUDA tensor), so row j of u
+        is CpG ``idx[j]`` of ``n_rows``; ``tensor``, a contiguous float64 CUDA tensor of n_rows * n_u elements on the
+        context's GPU, receives in row c the row of u at the lowest position that drew CpG c -- ``u[np.unique(idx,
+        return_index=True)[1]]`` -- and NaN where c was not drawn.  ``columns`` as in ``copy_u_to``.  A pure gather: the
+        copied values keep their bits.  An index outside 0 .. n_rows - 1 raises (DMF_ERR_BAD_ARG), the tensor untouched."""
+        n_rows = int(n_rows)
+        if not (_is_torch(tensor) and tensor.is_cuda and tensor.is_contiguous() and tensor.numel() == n_rows * self.n_u
+                and n_rows >= 1 and tensor.element_size() == 8 and tensor.is_floating_point()
+                and tensor.device.index == self.problem.ctx.device):
+            raise ValueError("copy_u_by_cpg needs a contiguous float64 CUDA tensor of n_rows * n_u elements on the context's GPU")
+        if not self._on_device(idx, False):
+            raise ValueError("idx must be the int64 row indices in HBM (staging.indices_to_device) on the context's GPU")
+        if int(np.prod(tuple(idx.shape))) != self.problem.N:
+            raise ValueError(f"idx holds {int(np.prod(tuple(idx.shape)))} indices, the problem has {self.problem.N} rows")
+        cols = None
+        if columns is not None:
+            cols = np.ascontiguousarray(columns, dtype=np.int32).ravel()
+            if cols.size != self.n_u or not np.array_equal(np.sort(cols), np.arange(self.n_u)):
+                raise ValueError(f"columns must be a permutation of 0..{self.n_u - 1}, got {list(np.ravel(columns))}")
+            cols = cols.ctypes.data_as(C.POINTER(C.c_int32))
+        L.check(self._lib.dmf_solver_get_u_by_row(self._h, _ptr(idx), n_rows, cols, _ptr(tensor)), "dmf_solver_get_u_by_row")
 
     def get_cost(self):
         """(cost, iterations) of the current iterate without copying u / alpha back."""

@@ -265,6 +265,13 @@ int dmf_svd_finish(dmf_context* ctx, void* T, int64_t N, int64_t rank, const dou
  * (NaNs are not ordered: inputs are proportions / methylation levels, never NaN).  n <= 19456. */
 int dmf_percentile_axis0(dmf_context* ctx, const double* x, int64_t n, int64_t m, const double* q,
                          int64_t n_q, int flags, double* out);
+/* np.nanpercentile(x, q, axis=0), same method, arguments and flags: the NaNs of a column are left out and the column's own
+ * count n_c of numbers takes n's place in numpy's plan (virtual index (n_c - 1) q / 100, floor, gamma, clip to [0, n_c - 1]),
+ * computed per column on the device.  A column without a number gives NaN, one number gives that number for every q.
+ * Bit-identical to numpy; on input without NaNs the same bits as dmf_percentile_axis0.  n <= 19456.  For the profile
+ * intervals by CpG (dmf_solver_get_u_by_row): a CpG is absent from the replicates that did not draw it. */
+int dmf_nanpercentile_axis0(dmf_context* ctx, const double* x, int64_t n, int64_t m, const double* q,
+                            int64_t n_q, int flags, double* out);
 
 /* ---- solver: the outer loop, resident on the device --------------------------------------
  * mdwbssmf_deconv (deconvolution.py:190-223) / unsupervised_deconv's loop (:139-184).
@@ -293,10 +300,19 @@ int dmf_solver_get(dmf_solver* s, int flags, double* out_u, double* out_alpha,
  * dmf_solver_get_u_permuted: dst_dev (N x n_u device doubles, not the solver's own u) <- u[:, src_col], i.e.
  * dst[i][b] = u[i][src_col[b]]; src_col: n_u host ints, a permutation of 0 .. n_u - 1 (DMF_ERR_BAD_ARG otherwise).  Complete
  * when the call returns, like dmf_solver_get with DMF_PTR_DEVICE.
- * With profiling on, the launches of both are clocked under DMF_KERNEL_GRAM. */
+ * dmf_solver_get_u_by_row: the same copy with the rows put back by CpG.  idx_dev: the N int64 indices in HBM the solver's
+ * problem was gathered with, so row j of u is CpG idx[j]; dst_dev (n_dst_rows x n_u device doubles, not the solver's own u)
+ * <- dst[c][b] = u[first[c]][src_col[b]] with first[c] = min { j : idx[j] == c }, i.e. u[np.unique(idx,
+ * return_index=True)[1]] scattered to its CpGs, and the quiet NaN 0x7ff8000000000000 in the rows of the CpGs that were not
+ * drawn.  src_col as above, or NULL for the identity.  A pure gather: every copied value keeps its bits and two calls give
+ * the same bits.  An index outside [0, n_dst_rows) is never dereferenced: the call returns DMF_ERR_BAD_ARG and leaves dst_dev
+ * untouched.  Complete when the call returns.
+ * With profiling on, the launches of all three are clocked under DMF_KERNEL_GRAM. */
 int dmf_solver_match_components(dmf_solver* s, const void* anchor_dev, int64_t n_anchor_rows, const int64_t* idx_dev,
                                 double* out_P);
 int dmf_solver_get_u_permuted(dmf_solver* s, const int32_t* src_col, void* dst_dev);
+int dmf_solver_get_u_by_row(dmf_solver* s, const int64_t* idx_dev, int64_t n_dst_rows, const int32_t* src_col /* NULL = identity */,
+                            void* dst_dev);
 /* cost_f_w(meth_f, [Rt | u], alpha, counts) of the solver's CURRENT iterate by the streaming formula
  * (deconvolution.py:15-17), without moving u / alpha to the host: what the restart and model-selection loops
  * recompute after every solve (demethify.py:169,199; ic.py:206).  out_cost: host double. */
