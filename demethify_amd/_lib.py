@@ -85,6 +85,8 @@ SIGNATURES = {
     "dmf_update_u": (C.c_int, [_p, _p, _p, _p, _p, _i64, _i64, C.c_int, C.c_int, _dbl_p, _p, _p]),
     "dmf_update_alpha": (C.c_int, [_p, _p, _p, _i64, _p, _p, _i64, C.c_int, _dbl_p, _p, _p]),
     "dmf_wls_intercept": (C.c_int, [_p, _p, _p, _i64, C.c_int, C.c_int, _p, C.POINTER(C.c_int)]),
+    "dmf_wls_moments": (C.c_int, [_p, _p, _p, _i64, C.c_int, C.c_int, _p]),
+    "dmf_nnls_normal": (C.c_int, [_p, _p, _p, _i64, _i64, _p, C.POINTER(C.c_int)]),
     "dmf_svd_gram": (C.c_int, [_p, _p, _p, C.c_int, _p, C.POINTER(_i64)]),
     "dmf_svd_factor": (C.c_int, [_p, _p, _p, _p, _i64, C.c_int, _p, C.POINTER(_p)]),
     "dmf_svd_finish": (C.c_int, [_p, _p, _i64, _i64, _p, _p, C.c_int, _p]),

@@ -134,6 +134,32 @@ class Context:
                 "dmf_project_simplex")
         return out
 
+    def nnls_normal(self, G, mom):
+        """k_nnls_intercept on the caller's normal equations (dmf_nnls_normal) -> (proportions, status).  ``G``: (S, K, K)
+        symmetric, or the packed (K (K + 1) / 2, S) form the kernel reads (row j (j + 1) / 2 + i for i <= j); ``mom``: the
+        (2 K + 2, S) table of ``Problem.wls_moments``.  ``proportions`` (K x S) holds NaN in the columns whose status is not
+        0: the library leaves them untouched.  For tests."""
+        mom = np.ascontiguousarray(mom, dtype=np.float64)
+        if mom.ndim != 2 or mom.shape[0] < 4 or mom.shape[0] % 2:
+            raise ValueError(f"mom is (2 K + 2) x S, got shape {mom.shape}")
+        K, S = mom.shape[0] // 2 - 1, mom.shape[1]
+        G = np.asarray(G, dtype=np.float64)
+        if G.shape == (S, K, K):
+            if not np.array_equal(G, G.transpose(0, 2, 1)):
+                raise ValueError("G must be symmetric")
+            i, j = np.triu_indices(K)
+            gb = np.empty((K * (K + 1) // 2, S), dtype=np.float64)
+            gb[j * (j + 1) // 2 + i] = G[:, i, j].T
+        elif G.shape == (K * (K + 1) // 2, S):
+            gb = np.ascontiguousarray(G)
+        else:
+            raise ValueError(f"G shape {G.shape} is neither {(S, K, K)} nor {(K * (K + 1) // 2, S)}")
+        out = np.full((K, S), np.nan, dtype=np.float64)
+        status = np.full(S, -1, dtype=np.intc)
+        L.check(self._lib.dmf_nnls_normal(self._h, _ptr(gb), _ptr(mom), K, S, _ptr(out),
+                                          status.ctypes.data_as(C.POINTER(C.c_int))), "dmf_nnls_normal")
+        return out, status
+
     def percentile_axis0(self, x, q):
         """``np.percentile(x, q, axis=0)`` (numpy's default "linear" method, bootstrap.py:51-54 / :75-78) on
         the device.  ``x``: (n replicates, ...) float64, a host array or a CUDA torch tensor; ``q``: a sequence
@@ -410,6 +436,40 @@ class Problem:
         ZeroDivisionError, as the reference does.  ``self.wls_status`` keeps the per-sample status of the last call.
         ``f64_arrays``: take weights and target from the f64 arrays even where the problem carries X16 (DMF_WLS_F64_ARRAYS):
         the same result bit for bit with X16 on and off."""
+        tg, u, n_u, flags = self._wls_args(u, target, f64_arrays)
+        K = self.n_c + n_u
+        out = np.zeros((K, self.S), dtype=np.float64)
+        status = np.full(self.S, -1, dtype=np.intc)
+        L.check(self._lib.dmf_wls_intercept(self.ctx._h, self._h, _ptr(u) if n_u else None, n_u, tg, flags, _ptr(out),
+                                            status.ctypes.data_as(C.POINTER(C.c_int))), "dmf_wls_intercept")
+        self.wls_status = status
+        if (status == 2).any():
+            raise ZeroDivisionError("Weights sum to zero, can't be normalized")
+        redo = np.flatnonzero(status != 0)
+        if redo.size:
+            if host_arrays is None:
+                raise RuntimeError(f"wls_intercept: the device did not solve samples {redo.tolist()} (rank-deficient "
+                                   "profiles or iteration cap) and no host_arrays were given to solve them on the host")
+            from .init_func import wls_intercept as host_wls
+
+            meth_f, counts, R_full = host_arrays() if callable(host_arrays) else host_arrays
+            for k in redo:
+                x = counts[:, k:k + 1] * meth_f[:, k:k + 1] if target == "dv" else meth_f[:, k:k + 1]
+                out[:, k:k + 1] = host_wls(x, counts[:, k:k + 1], R_full)
+        return out
+
+    def wls_moments(self, u=None, target="v", f64_arrays=False):
+        """The first moments ``wls_intercept`` takes for the same arguments, read back (dmf_wls_moments): a (2 K + 2) x S
+        array, rows 0 .. K - 1 m_k = sum_i d R_k, rows K .. 2 K - 1 r_k = sum_i d t R_k, then sw = sum_i d and st = sum_i d t,
+        per sample, with t = meth_frequency (``"v"``) or counts * meth_frequency (``"dv"``).  For tests."""
+        tg, u, n_u, flags = self._wls_args(u, target, f64_arrays)
+        out = np.empty((2 * (self.n_c + n_u) + 2, self.S), dtype=np.float64)
+        L.check(self._lib.dmf_wls_moments(self.ctx._h, self._h, _ptr(u) if n_u else None, n_u, tg, flags, _ptr(out)),
+                "dmf_wls_moments")
+        return out
+
+    def _wls_args(self, u, target, f64_arrays):
+        """(target code, u as the library takes it, n_u, flags) of wls_intercept / wls_moments."""
         try:
             tg = {"v": L.DMF_WLS_TARGET_V, "dv": L.DMF_WLS_TARGET_DV}[target]
         except KeyError:
@@ -438,26 +498,7 @@ class Problem:
             n_u = int(u.shape[1])
         if f64_arrays:
             flags |= L.DMF_WLS_F64_ARRAYS
-        K = self.n_c + n_u
-        out = np.zeros((K, self.S), dtype=np.float64)
-        status = np.full(self.S, -1, dtype=np.intc)
-        L.check(self._lib.dmf_wls_intercept(self.ctx._h, self._h, _ptr(u) if n_u else None, n_u, tg, flags, _ptr(out),
-                                            status.ctypes.data_as(C.POINTER(C.c_int))), "dmf_wls_intercept")
-        self.wls_status = status
-        if (status == 2).any():
-            raise ZeroDivisionError("Weights sum to zero, can't be normalized")
-        redo = np.flatnonzero(status != 0)
-        if redo.size:
-            if host_arrays is None:
-                raise RuntimeError(f"wls_intercept: the device did not solve samples {redo.tolist()} (rank-deficient "
-                                   "profiles or iteration cap) and no host_arrays were given to solve them on the host")
-            from .init_func import wls_intercept as host_wls
-
-            meth_f, counts, R_full = host_arrays() if callable(host_arrays) else host_arrays
-            for k in redo:
-                x = counts[:, k:k + 1] * meth_f[:, k:k + 1] if target == "dv" else meth_f[:, k:k + 1]
-                out[:, k:k + 1] = host_wls(x, counts[:, k:k + 1], R_full)
-        return out
+        return tg, u, n_u, flags
 
     def svd_gram(self, H1=None):
         """``Yres.T @ Yres`` (S x S) of Yres = max(meth_frequency - R_trunc @ H1, 1e-8) -- meth_frequency itself without

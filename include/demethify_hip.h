@@ -227,6 +227,21 @@ enum { DMF_WLS_TARGET_V = 0, DMF_WLS_TARGET_DV = 1 };
 enum { DMF_WLS_F64_ARRAYS = 8 };
 int dmf_wls_intercept(dmf_context* ctx, const dmf_problem* p, const double* u, int64_t n_u, int target,
                       int flags, double* out_alpha, int* out_status);
+/* The two halves of dmf_wls_intercept on their own, for tests; host pointers (u as dmf_wls_intercept takes it).
+ * dmf_wls_moments: out_mom ((2 K + 2) x S host doubles) <- the first moments exactly as dmf_wls_intercept computes them for
+ * the same arguments -- the same set-up, the same k_wls_moments / k_wls_reduce launches, DMF_WLS_F64_ARRAYS honoured alike:
+ * rows 0 .. K - 1 m_k = sum_i d_is R_ik, rows K .. 2 K - 1 r_k = sum_i d_is t_is R_ik, row 2 K sw = sum_i d_is, row 2 K + 1
+ * st = sum_i d_is t_is, with t = v (DMF_WLS_TARGET_V) or d v (DMF_WLS_TARGET_DV) and R = [Rt | u].
+ * dmf_nnls_normal: k_nnls_intercept on a caller's system.  gb (K (K + 1) / 2 x S host doubles): the dense part of a packed
+ * Gram, sample s of G_ij (i <= j) at gb[(j (j + 1) / 2 + i) S + s]; mom: a table laid out as above.  Each sample solves the
+ * non-negative least squares problem with normal matrix G - m m^T / sw and right-hand side r - m st / sw.  out_status and
+ * out_alpha as dmf_wls_intercept leaves them: the proportions coef / max(sum coef, 1e-10) in the columns with status 0, every
+ * other column of out_alpha untouched.  K < 1 or S < 1: DMF_ERR_BAD_ARG; K > 64: DMF_ERR_UNSUPPORTED (both before the
+ * context is looked at). */
+int dmf_wls_moments(dmf_context* ctx, const dmf_problem* p, const double* u, int64_t n_u, int target, int flags,
+                    double* out_mom);
+int dmf_nnls_normal(dmf_context* ctx, const double* gb, const double* mom, int64_t K, int64_t S, double* out_alpha,
+                    int* out_status);
 
 /* The SVD initialiser -- constrained_nndsvd, init_func.py:17-37, and nndsvd_initialize, :40-82, reached from
  * deconvolution.py:68-71, :134-137 and :260-263 -- without an SVD of the N x S matrix.  With Yres = max(V - Rt H1, 1e-8)
