@@ -34,6 +34,8 @@ PROBLEM_ARRAYS = {"V": 0, "D": 1, "Rt": 2, "Rtp": 3, "D16": 4, "X16": 5, "W16": 
 DMF_MODE_PARTIAL = 0
 DMF_MODE_UNSUPERVISED = 1
 MAX_K = 64  # dmf::kMaxK: largest n_c + n_u the kernels are built for (DMF_ERR_UNSUPPORTED beyond)
+# dmf::kSmallMax*: the envelope of dmf_solve_small (S, n_c + n_u, n_u, N * S)
+SMALL_MAX_S, SMALL_MAX_K, SMALL_MAX_NU, SMALL_MAX_ELEMENTS = 64, 16, 4, 1 << 20
 SVD_MAX_S, SVD_MAX_NC, SVD_MAX_RANK, SVD_MAX_LDS = 512, 64, 64, 160 * 1024  # dmf::kSvdMax*: what the SVD initialiser's kernels take
 
 
@@ -122,6 +124,8 @@ SIGNATURES = {
                                 C.POINTER(_i64)]),
     "dmf_solve": (C.c_int, [_p, _p, _p, _p, _i64, C.c_int, _i64, _i64, C.c_double, C.c_int, _p, _p,
                             _dbl_p, C.POINTER(_i64)]),
+    "dmf_solve_small_supported": (C.c_int, [_i64, _i64, _i64, _i64, C.c_int]),
+    "dmf_solve_small": (C.c_int, [_p, _p, _i64, _p, _p, _p, _i64, C.c_int, _i64, _i64, C.c_double, _i64, C.c_int, _p, _p, _p, _p]),
 }
 
 _lib = None

@@ -70,9 +70,52 @@ def _device_stack(n_local, width):
     return torch.empty((n_local, width), dtype=torch.float64, device=torch.device("cuda", get_context().device))
 
 
+# The number of elements N x S up to which the command line (DEMETHIFY_BATCH=1) sends bootstrap replicates and restarts
+# through Problem.solve_many: the largest measured size at which the batched leg wins there and at every smaller measured
+# size.  Measured (tools/small_batch_bench.py, profiles/small_batch_bench.txt; medians of five, per-solve against batched):
+# 350 x 10 with 2 500 replicates 7.57 s against 0.27 s and with 64 restarts 153 ms against 15 ms, 1 000 x 16 with 64 restarts
+# 183 ms against 40 ms -- and 10 000 x 64 with 64 restarts 0.61 s against 4.05 s: there one workgroup per solve loses, so the
+# gate sits at 1 000 x 16.
+SMALL_BATCH_MAX_ELEMENTS = 16000
+
+
+def batched_ineligible(n_u, n_rows, n_samples, n_ct, init_option, purity, mode, observe=None, align=False,
+                       profile_rows="position"):
+    """Why a loop of solves cannot go through ``Problem.solve_many`` (one launch for many solves), as a sentence, or None
+    when it can: at least one unknown type, no purity constraint, nobody watching single replicates, no component
+    alignment, profile rows by position, an initialiser that does not read the data (``uniform_``, ``beta``, or the silent
+    replacement by ``uniform_`` when there are more unknown types than samples) and a shape the kernel takes.  Touches
+    no device."""
+    from .device import small_solve_supported
+
+    if n_u < 1:
+        return "there is no unknown cell type to solve for"
+    if purity is not None and np.size(purity) > 0:
+        return "the purity-constrained alpha phase is not part of the batched kernel"
+    if observe is not None:
+        return "_observe looks at one replicate's solver, which a batched solve does not have"
+    if align:
+        return "aligning the unknown components needs every replicate's solver"
+    if profile_rows != "position":
+        return 'profile_rows="cpg" needs every replicate\'s solver'
+    option = "uniform_" if (init_option != "uniform_" and n_u > n_samples) else init_option
+    if option not in ("uniform_", "beta"):
+        return f"the initialiser {init_option!r} reads the resampled data"
+    if not small_solve_supported(n_rows, n_samples, n_ct, n_u, mode):
+        return (f"the shape {n_rows} x {n_samples} with {n_ct} + {n_u} cell types is outside the batched kernel's envelope "
+                f"(n_u <= {L.SMALL_MAX_NU}, K <= {L.SMALL_MAX_K}, S <= {L.SMALL_MAX_S}, N S <= {L.SMALL_MAX_ELEMENTS})")
+    return None
+
+
+def batch_chunk(n_rows, n_u):
+    """How many solves one ``solve_many`` call of the drivers takes: enough to fill the GPU several times over, and at most
+    256 MB for the stack of profiles."""
+    return int(max(1, min(1024, (1 << 25) // max(1, n_rows * n_u))))
+
+
 def bt_ci(confidence_level, n_bootstrap, n_u, meth_f, counts, ref, init_option, n_iter1, n_iter2, tol, header,
           outdir, samples, purity, seed, materialize=True, _observe=None, anchor=None, align_unknown=None,
-          profile_rows="position"):
+          profile_rows="position", batched=False):
     """bootstrap.py:10-93 -> [proportions CI DataFrame, (profile CI DataFrame)]; writes the two CSVs.
     materialize=False (the CLI, which ignores the return value) skips building the N-row DataFrame of tuples for the
     profile intervals: the CSV is written by the library and the second result is the (lower, upper) array pair.
@@ -94,9 +137,21 @@ def bt_ci(confidence_level, n_bootstrap, n_u, meth_f, counts, ref, init_option, 
     resampled row of every replicate, B different CpGs.  "cpg": CpG j's own estimates -- replicate i contributes
     ``u_i[first_i[j]]``, the row of the lowest position that drew CpG j, and nothing where it did not draw it (NaN in the
     stack); the bounds are ``np.nanpercentile`` over the replicates, (nan, nan) for a CpG no replicate drew (DESIGN.md
-    section 6.1).  Composes with ``align_unknown``; ignored for n_u == 0; the proportions table is the same either way."""
+    section 6.1).  Composes with ``align_unknown``; ignored for n_u == 0; the proportions table is the same either way.
+
+    ``batched``: this rank's replicates go through ``Problem.solve_many`` in chunks, one workgroup per replicate, rows
+    read through the replicate's index list.  Row indices and initialisers are drawn per replicate
+    from seed_i in the reference's order, exactly as without it.  Only for the cases ``batched_ineligible`` accepts; any
+    other raises ValueError naming the reason before any device work."""
     if profile_rows not in ("position", "cpg"):
         raise ValueError(f'profile_rows must be "position" or "cpg", got {profile_rows!r}')
+    if batched:
+        will_align = bool(ref is None if align_unknown is None else align_unknown) and n_u >= 2
+        reason = batched_ineligible(n_u, meth_f.shape[0], meth_f.shape[1], 0 if ref is None else ref.shape[1], init_option,
+                                    purity, L.DMF_MODE_UNSUPERVISED if ref is None else L.DMF_MODE_PARTIAL, _observe,
+                                    will_align, profile_rows)
+        if reason is not None:
+            raise ValueError(f"bt_ci(batched=True): {reason}")
     by_cpg = profile_rows == "cpg"
     if ref is None:
         if n_u < 1:
@@ -147,6 +202,29 @@ def bt_ci(confidence_level, n_bootstrap, n_u, meth_f, counts, ref, init_option, 
             props = np.concatenate([wls_intercept(ct[:, k:k + 1] * mf[:, k:k + 1], ct[:, k:k + 1], rf)
                                     for k in range(n_samples)], axis=1)
             local.append((i, (None, props)))
+    elif batched:
+        # one resident problem, one solve_many call per chunk of this rank's replicates: replicate i reads its rows through
+        # idx_i and starts from the initialiser of seed_i (data-free: only the shapes of the arrays it is given matter)
+        u_stack = None
+        mine = shard.my_items(n_bootstrap, rank, world)
+        shape_f = np.broadcast_to(meth_f[:1], meth_f.shape)
+        chunk = batch_chunk(n_rows, n_u)
+        with Problem(get_context(), meth_f, counts, ref) as full:
+            for c0 in range(0, len(mine), chunk):
+                part = mine[c0:c0 + chunk]
+                idx = np.stack([bootstrap_row_indices(seeds[i], n_rows) for i in part])
+                inits = []
+                for i in part:
+                    if ref is None:
+                        inits.append(_init_unsupervised(init_option, shape_f, n_u, seeds[i]))
+                    else:
+                        u0, _, a0 = init_BSSMF_md(init_option, shape_f, np.broadcast_to(counts[:1], counts.shape),
+                                                  np.broadcast_to(ref[:1], ref.shape), n_u, rb_alg=wls_intercept, seed=seeds[i],
+                                                  _stack=False)
+                        inits.append((u0, a0))
+                us, alphas, _, _ = full.solve_many(np.stack([u0 for u0, _ in inits]), np.stack([a0 for _, a0 in inits]),
+                                                   mode, n_iter1, n_iter2, tol, idx=idx)
+                local.extend((i, (us[j], alphas[j])) for j, i in enumerate(part))
     else:
         # The host work of the replicates ahead (MT19937 index draw of N rows; uniform N x n_u + Dirichlet init: ~10 + ~13 ms
         # at 1e6 rows) runs on worker threads while the GPU gathers and solves replicate i.  The row draw has its own

@@ -1,0 +1,96 @@
+// C-ABI of libdemethify_hip.so, part 7: many independent small solves of one resident problem per launch
+// (dmf_solve_small; the kernel is dmf_kernels_small.hip).
+#include <algorithm>
+
+#include "dmf_api.h"
+#include "dmf_small.h"
+
+using namespace dmf_api;
+
+extern "C" {
+
+int dmf_solve_small_supported(int64_t N, int64_t S, int64_t n_c, int64_t n_u, int mode) {
+    return dmf::small_supported(N, S, n_c, n_u, mode) ? 1 : 0;
+}
+
+int dmf_solve_small(dmf_context* ctx, const dmf_problem* p, int64_t B, const int64_t* idx, const double* u0, const double* alpha0,
+                    int64_t n_u, int mode, int64_t n_iter1, int64_t n_iter2, double tol, int64_t iters_per_launch, int flags,
+                    double* out_u, double* out_alpha, double* out_cost, int64_t* out_iters) {
+    if (ctx == nullptr || p == nullptr || B < 1 || B > 0x7fffffff || u0 == nullptr || alpha0 == nullptr || out_u == nullptr ||
+        out_alpha == nullptr || out_cost == nullptr || out_iters == nullptr || n_iter1 < 0 || n_iter2 < 0 || iters_per_launch < 0)
+        return DMF_ERR_BAD_ARG;
+    if (p->ctx != ctx || p->mask_bits != nullptr) return DMF_ERR_BAD_ARG;  // (a masked problem's held-out zeros are not data)
+    if (!dmf::small_supported(p->N, p->S, p->n_c, n_u, mode)) return DMF_ERR_UNSUPPORTED;
+    DMF_TRY(check_ctx(ctx));
+    const int64_t N = p->N, S = p->S, K = p->n_c + n_u;
+    const size_t un = (size_t)B * N * n_u, an = (size_t)B * K * S;
+
+    DevBuf<long long> d_idx;
+    DevBuf<double> d_u0, d_a0;
+    if (idx != nullptr) {
+        DMF_TRY(import_array(ctx, idx, (size_t)B * N, flags, d_idx));
+        // every index is checked on the device before the first launch: no solve has started when one is refused
+        DevBuf<unsigned int> d_bad;
+        unsigned int h_bad = 1;
+        HIP_TRY(d_bad.alloc(ctx, 1));
+        HIP_TRY(dmf::launch_index_range_check(d_idx, B * N, N, d_bad, ctx->stream));
+        HIP_TRY(hipMemcpyAsync(&h_bad, d_bad, sizeof(h_bad), hipMemcpyDeviceToHost, ctx->stream));
+        HIP_TRY(hipStreamSynchronize(ctx->stream));
+        if (h_bad != 0) return DMF_ERR_BAD_ARG;
+    }
+    DMF_TRY(import_array(ctx, u0, un, flags, d_u0));
+    DMF_TRY(import_array(ctx, alpha0, an, flags, d_a0));
+
+    // the workspace: all per-solve state, so that the next launch continues where this one stopped
+    DevBuf<double> w_u, w_up, w_a, w_ap, w_gk, w_ratio, w_scal;
+    DevBuf<long long> w_iters;
+    DevBuf<int> w_done;
+    if (flags & DMF_PTR_DEVICE) w_u.borrow(out_u);  // (the iterate lives in the caller's result array)
+    else HIP_TRY(w_u.alloc(ctx, un));
+    HIP_TRY(w_up.alloc(ctx, un));
+    HIP_TRY(w_a.alloc(ctx, an));
+    HIP_TRY(w_ap.alloc(ctx, an));
+    HIP_TRY(w_gk.alloc(ctx, (size_t)B * (size_t)std::max<int64_t>(dmf::small_known_jobs((int)p->n_c) * S, 1)));
+    HIP_TRY(w_ratio.alloc(ctx, (size_t)B * 2 * (size_t)std::max<int64_t>(n_iter2, 1)));
+    HIP_TRY(w_scal.alloc(ctx, (size_t)B * dmf::kSmallScalars));
+    HIP_TRY(w_iters.alloc(ctx, (size_t)B));
+    HIP_TRY(w_done.alloc(ctx, (size_t)B));
+
+    dmf::SmallArgs a;
+    a.V = p->V, a.D = p->D, a.Rt = p->Rt;
+    a.idx = d_idx, a.u0 = d_u0, a.alpha0 = d_a0;
+    a.N = N, a.S = (int)S, a.n_c = (int)p->n_c, a.n_u = (int)n_u, a.mode = mode;
+    a.n_iter2 = n_iter2, a.tol = tol;
+    a.u = w_u, a.u_prev = w_up, a.alpha = w_a, a.alpha_prev = w_ap, a.gk = w_gk, a.ratio = w_ratio, a.scal = w_scal;
+    a.iters = w_iters, a.done = w_done;
+
+    const int64_t per_launch = iters_per_launch > 0 ? std::min<int64_t>(iters_per_launch, 1 << 20)
+                                                      : dmf::small_default_iters_per_launch(N, S);
+    std::vector<int> h_done((size_t)B);
+    int64_t ran = 0;  // outer iterations every unfinished solve has run
+    for (bool first = true;; first = false) {
+        a.first = first ? 1 : 0;
+        a.n_run = (int)std::min<int64_t>(per_launch, n_iter1 - ran);
+        HIP_TRY(dmf::launch_solve_small(a, B, ctx->stream));
+        ran += a.n_run;
+        if (ran >= n_iter1) break;
+        HIP_TRY(hipMemcpyAsync(h_done.data(), w_done, (size_t)B * sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+        HIP_TRY(hipStreamSynchronize(ctx->stream));
+        bool all = true;
+        for (int64_t b = 0; b < B && all; ++b) all = h_done[(size_t)b] != 0;
+        if (all) break;
+    }
+
+    // out_cost[b] = cost_f_w of the final iterate (the loop's own streaming cost), out_iters[b] = its outer iterations
+    std::vector<double> h_scal((size_t)B * dmf::kSmallScalars);
+    static_assert(sizeof(long long) == sizeof(int64_t), "out_iters is copied as long long");
+    HIP_TRY(hipMemcpyAsync(h_scal.data(), w_scal, h_scal.size() * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipMemcpyAsync(out_iters, w_iters, (size_t)B * sizeof(long long), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipMemcpyAsync(out_alpha, w_a, an * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    if (!(flags & DMF_PTR_DEVICE)) HIP_TRY(hipMemcpyAsync(out_u, w_u, un * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    for (int64_t b = 0; b < B; ++b) out_cost[b] = h_scal[(size_t)b * dmf::kSmallScalars + dmf::kSmCf];
+    return DMF_OK;
+}
+
+}  // extern "C"

@@ -1,0 +1,507 @@
+// k_solve_small: one workgroup is one solve.  The whole outer loop of mdwbssmf_deconv (demethify/deconvolution.py:190-223)
+// or unsupervised_deconv (:107-184) runs inside the kernel for problems small enough that a launch per phase is nothing
+// but launch latency: 1 <= n_u <= 4, K = n_c + n_u <= 16, S <= 64, N S <= 2^20.  The grid is B solves of one resident
+// problem; solve b has its own (u0, alpha0) and optionally its own row list idx[b][0..N): row i of the solve is row
+// idx[b][i] of the problem, read through the index (a bootstrap replicate, bootstrap.py:28, without a gathered copy).
+//
+// Plan of one outer iteration (DESIGN.md sections 3 and 6.2), 256 threads:
+//   u phase     a thread per row: c_i = sum_s d (v - Rt_i A_known) A_unk and M_i = sum_s d A_unk A_unk^T in registers, then
+//               the n_iter2 inner steps on those n_u + n_u (n_u + 1) / 2 numbers (:81-90; the gradient at u_temp in
+//               partial mode, at the previous iterate in unsupervised mode, :163)
+//   l_h         (||R_trunc||^2 + ||u||^2) d (:212)
+//   Gram        threads as (row slice r, sample s): the entries of G_s = R^T diag(d_s) R and b_s = R^T diag(d_s) v_s that
+//               involve u, kSmallChunk accumulators per pass over the rows, the slices added in rising order; the
+//               known x known block is formed once per solve and kept in the workspace
+//   alpha phase a thread per sample on its K x K Gram in LDS: n_iter2 steps with the sort-based projection (:93-102, :21-37)
+//   l_w         ||alpha[-n_u:]||^2 d (:216)
+//   cf          sum d (v - R alpha)^2 over the rows, streaming (:15-17), and the stop test |cf - cf_0| < tol on it (:220)
+//
+// Determinism: a thread adds its rows in rising order, thread partials are added by one fixed tree, slices in rising
+// order -- every order depends on (N, S, n_c, n_u) alone.  No atomics; a workgroup reads nothing another one writes, so
+// a solve's result does not depend on B, on its slot or on what else is resident.  All state a later launch needs goes to
+// the workspace (dmf_small.h) before the kernel returns, so a solve continues bit for bit however the iterations are cut
+// into launches.
+//
+// LDS: G and b (K (K + 1) / 2 + K rows of SP doubles, SP = S rounded up to a power of two), alpha, alpha_, the
+// extrapolated point and the sort scratch (4 K SP), 32 KB of reduction scratch, the job tables: 141 KB at S = 64, K = 16,
+// 40 KB for the 350 x 10 example with 5 + 1 types.
+#include "dmf_small.h"
+
+#include "../../include/demethify_hip.h"
+
+namespace dmf {
+
+namespace {
+
+constexpr int kMaxJobs = kSmallMaxK * (kSmallMaxK + 1) / 2 + kSmallMaxK;  // 152
+constexpr int kJobShorts = 3 * kMaxJobs + 8;                               // jk, jl, jd (padded to 8 bytes)
+constexpr int kRowsInFlight = 4;  // rows a thread of the (slice, sample) passes loads before it uses any
+
+__host__ __device__ inline int pow2_at_least(int s) {
+    int p = 1;
+    while (p < s) p <<= 1;
+    return p;
+}
+
+struct Lds {
+    double* gb;     // [K (K + 1) / 2 + K][SP]: packed G (row l (l + 1) / 2 + k, k <= l), then b
+    double* a;      // [K][SP] alpha
+    double* ap;     // [K][SP] alpha_
+    double* tmp;    // [K][SP] alpha_temp
+    double* srt;    // [K][SP] sort scratch
+    double* red;    // [kSmallChunk * 256] reduction scratch
+    double* sh;     // [8] broadcast slots
+    short* jk;      // job tables: x_k, x_l over (R_trunc columns, u columns, v) and the row of gb
+    short* jl;
+    short* jd;
+};
+
+__device__ __forceinline__ double block_sum(double x, double* red) {
+    const int t = threadIdx.x;
+    red[t] = x;
+    __syncthreads();
+#pragma unroll
+    for (int off = kSmallThreads / 2; off > 0; off >>= 1) {
+        if (t < off) red[t] += red[t + off];
+        __syncthreads();
+    }
+    const double r = red[0];
+    __syncthreads();
+    return r;
+}
+
+__device__ __forceinline__ double block_max(double x, double* red) {
+    const int t = threadIdx.x;
+    red[t] = x;
+    __syncthreads();
+#pragma unroll
+    for (int off = kSmallThreads / 2; off > 0; off >>= 1) {
+        if (t < off) red[t] = fmax(red[t], red[t + off]);
+        __syncthreads();
+    }
+    const double r = red[0];
+    __syncthreads();
+    return r;
+}
+
+// What a solve reads of the problem and of itself.
+struct Rows {
+    const double* V;
+    const double* D;
+    const double* Rt;
+    const long long* idx;  // null: the identity
+    const double* u;       // this solve's current u
+    int64_t N;
+    int S, n_c, n_u, K, SP, R;
+    __device__ __forceinline__ int64_t row(int64_t i) const { return idx != nullptr ? (int64_t)idx[i] : i; }
+};
+
+// Jobs [j0, j1) of the job tables: gb[jd][s] = sum_i d_is x_k x_l over the solve's rows.  Threads as (slice r, sample s);
+// slice r adds rows r, r + R, ... in rising order, the slices are added in rising order.
+__device__ void gram_jobs(const Rows& p, const Lds& m, int j0, int j1) {
+    const int t = threadIdx.x;
+    const int s = t & (p.SP - 1), r = t / p.SP;
+    const bool active = s < p.S;
+    for (int base = j0; base < j1; base += kSmallChunk) {
+        const int nj = min(kSmallChunk, j1 - base);
+        double acc[kSmallChunk];
+#pragma unroll
+        for (int j = 0; j < kSmallChunk; ++j) acc[j] = 0.0;
+        if (active) {
+            // kRowsInFlight rows per trip, so that their loads are in flight together (one wave per SIMD hides no latency);
+            // a row past the end reads row i again with weight 0: acc + 0, the sums and their order are the same
+            for (int64_t i = r; i < p.N; i += (int64_t)kRowsInFlight * p.R) {
+                double d[kRowsInFlight], v[kRowsInFlight];
+                const double* rt[kRowsInFlight];
+                const double* ui[kRowsInFlight];
+#pragma unroll
+                for (int q = 0; q < kRowsInFlight; ++q) {
+                    const int64_t iq = i + (int64_t)q * p.R;
+                    const bool in = iq < p.N;
+                    const int64_t ic = in ? iq : i, g = p.row(ic);
+                    d[q] = in ? p.D[g * p.S + s] : 0.0;
+                    v[q] = p.V[g * p.S + s];
+                    rt[q] = p.Rt + g * p.n_c;
+                    ui[q] = p.u + ic * p.n_u;
+                }
+#pragma unroll
+                for (int j = 0; j < kSmallChunk; ++j) {
+                    if (j < nj) {
+                        const int k = m.jk[base + j], l = m.jl[base + j];
+#pragma unroll
+                        for (int q = 0; q < kRowsInFlight; ++q) {
+                            const double xk = k < p.n_c ? rt[q][k] : ui[q][k - p.n_c];
+                            const double xl = l < p.n_c ? rt[q][l] : (l < p.K ? ui[q][l - p.n_c] : v[q]);
+                            acc[j] = fma(d[q] * xk, xl, acc[j]);
+                        }
+                    }
+                }
+            }
+        }
+#pragma unroll
+        for (int j = 0; j < kSmallChunk; ++j) m.red[(j * p.R + r) * p.SP + s] = acc[j];
+        __syncthreads();
+        for (int o = t; o < nj * p.SP; o += kSmallThreads) {
+            const int j = o / p.SP, so = o & (p.SP - 1);
+            double sum = 0.0;
+            for (int rr = 0; rr < p.R; ++rr) sum += m.red[(j * p.R + rr) * p.SP + so];
+            m.gb[(int)m.jd[base + j] * p.SP + so] = sum;
+        }
+        __syncthreads();
+    }
+}
+
+// sum_i sum_s d (v - [Rt | u] alpha)^2 over the solve's rows with alpha from LDS (deconvolution.py:15-17)
+__device__ double stream_cost(const Rows& p, const Lds& m) {
+    const int t = threadIdx.x;
+    const int s = t & (p.SP - 1), r = t / p.SP;
+    double acc = 0.0;
+    if (s < p.S) {
+        for (int64_t i = r; i < p.N; i += (int64_t)kRowsInFlight * p.R) {  // (rows in flight as in gram_jobs)
+            double d[kRowsInFlight], resid[kRowsInFlight];
+            const double* rt[kRowsInFlight];
+            const double* ui[kRowsInFlight];
+#pragma unroll
+            for (int q = 0; q < kRowsInFlight; ++q) {
+                const int64_t iq = i + (int64_t)q * p.R;
+                const bool in = iq < p.N;
+                const int64_t ic = in ? iq : i, g = p.row(ic);
+                d[q] = in ? p.D[g * p.S + s] : 0.0;
+                resid[q] = p.V[g * p.S + s];
+                rt[q] = p.Rt + g * p.n_c;
+                ui[q] = p.u + ic * p.n_u;
+            }
+            for (int k = 0; k < p.n_c; ++k) {
+                const double ak = m.a[k * p.SP + s];
+#pragma unroll
+                for (int q = 0; q < kRowsInFlight; ++q) resid[q] = fma(-rt[q][k], ak, resid[q]);
+            }
+            for (int j = 0; j < p.n_u; ++j) {
+                const double aj = m.a[(p.n_c + j) * p.SP + s];
+#pragma unroll
+                for (int q = 0; q < kRowsInFlight; ++q) resid[q] = fma(-ui[q][j], aj, resid[q]);
+            }
+#pragma unroll
+            for (int q = 0; q < kRowsInFlight; ++q) acc = fma(d[q] * resid[q], resid[q], acc);
+        }
+    }
+    return block_sum(acc, m.red);
+}
+
+// deconvolution.py:21-37 on column s of x (K values, stride SP), srt: the column's sort scratch
+__device__ void project_column_lds(double* x, double* srt, int K, int SP) {
+    for (int k = 0; k < K; ++k) {  // insertion sort, descending
+        const double v = x[k * SP];
+        int j = k;
+        while (j > 0 && srt[(j - 1) * SP] < v) {
+            srt[j * SP] = srt[(j - 1) * SP];
+            --j;
+        }
+        srt[j * SP] = v;
+    }
+    double run = 0.0, theta = 0.0, last_shift = 0.0;
+    bool any = false;
+    for (int j = 0; j < K; ++j) {
+        run += srt[j * SP];
+        const double shifted = run - 1.0;
+        if (srt[j * SP] - shifted / (double)(j + 1) > 0.0) {
+            theta = shifted / (double)(j + 1);
+            any = true;
+        }
+        last_shift = shifted;
+    }
+    if (!any) theta = last_shift / 0.0;  // upstream: rho = -1 -> pi[-1] / 0 (non-finite input only)
+    for (int k = 0; k < K; ++k) x[k * SP] = fmax(x[k * SP] - theta, 0.0);
+}
+
+}  // namespace
+
+template <int NU>
+__global__ __launch_bounds__(kSmallThreads) void k_solve_small(SmallArgs a) {
+    constexpr int NP = NU * (NU + 1) / 2;
+    const int64_t b = blockIdx.x;
+    if (!a.first && a.done[b]) return;  // a finished solve's workgroup returns at once
+    extern __shared__ double small_lds[];
+    const int t = threadIdx.x;
+    const int S = a.S, n_c = a.n_c, K = n_c + NU, SP = pow2_at_least(S);
+    const int n_pairs = K * (K + 1) / 2;
+    Lds m;
+    m.gb = small_lds;
+    m.a = m.gb + (n_pairs + K) * SP;
+    m.ap = m.a + K * SP;
+    m.tmp = m.ap + K * SP;
+    m.srt = m.tmp + K * SP;
+    m.red = m.srt + K * SP;
+    m.sh = m.red + kSmallChunk * kSmallThreads;
+    m.jk = reinterpret_cast<short*>(m.sh + 8);
+    m.jl = m.jk + kMaxJobs;
+    m.jd = m.jl + kMaxJobs;
+
+    const int64_t N = a.N;
+    double* u = a.u + b * N * NU;
+    double* u_prev = a.u_prev + b * N * NU;
+    double* ws_alpha = a.alpha + b * K * S;
+    double* ws_alpha_prev = a.alpha_prev + b * K * S;
+    const int n_known = (int)small_known_jobs(n_c);
+    double* gk = a.gk + b * (int64_t)n_known * S;
+    double* ratio_u = a.ratio + b * 2 * a.n_iter2;
+    double* ratio_h = ratio_u + a.n_iter2;
+    double* scal = a.scal + b * kSmallScalars;
+
+    Rows p;
+    p.V = a.V, p.D = a.D, p.Rt = a.Rt;
+    p.idx = a.idx != nullptr ? a.idx + b * N : nullptr;
+    p.u = u;
+    p.N = N, p.S = S, p.n_c = n_c, p.n_u = NU, p.K = K, p.SP = SP, p.R = kSmallThreads / SP;
+
+    // job tables: the known block (pairs of R_trunc columns in packed order, then their products with v), then what
+    // involves u (the packed rows l >= n_c, then b_u)
+    if (t == 0) {
+        int j = 0;
+        for (int l = 0; l < n_c; ++l)
+            for (int k = 0; k <= l; ++k) m.jk[j] = (short)k, m.jl[j] = (short)l, m.jd[j] = (short)(l * (l + 1) / 2 + k), ++j;
+        for (int k = 0; k < n_c; ++k) m.jk[j] = (short)k, m.jl[j] = (short)K, m.jd[j] = (short)(n_pairs + k), ++j;
+        for (int l = n_c; l < K; ++l)
+            for (int k = 0; k <= l; ++k) m.jk[j] = (short)k, m.jl[j] = (short)l, m.jd[j] = (short)(l * (l + 1) / 2 + k), ++j;
+        for (int k = n_c; k < K; ++k) m.jk[j] = (short)k, m.jl[j] = (short)K, m.jd[j] = (short)(n_pairs + k), ++j;
+    }
+    const int n_jobs = n_pairs + K;
+
+    double a1, a2, l_w, l_w_prev, l_h, l_h_prev, dsq, rt_norm2, cf;
+    long long iters;
+    if (a.first) {
+        // deconvolution.py:192-204: a1 = a2 = 1, u_ = u, alpha_ = alpha, d = max(D)^2 over the solve's rows, l_w, l_h, cf
+        const double* u0 = a.u0 + b * N * NU;
+        const double* alpha0 = a.alpha0 + b * K * S;
+        for (int e = t; e < K * S; e += kSmallThreads) {
+            const int k = e / S, s = e - k * S;
+            m.a[k * SP + s] = m.ap[k * SP + s] = alpha0[e];
+        }
+        double u2 = 0.0, rt2 = 0.0, dmax = -INFINITY;
+        for (int64_t i = t; i < N; i += kSmallThreads) {
+#pragma unroll
+            for (int j = 0; j < NU; ++j) {
+                const double x = u0[i * NU + j];
+                u[i * NU + j] = u_prev[i * NU + j] = x;
+                u2 = fma(x, x, u2);
+            }
+            const int64_t g = p.row(i);
+            for (int k = 0; k < n_c; ++k) rt2 = fma(p.Rt[g * n_c + k], p.Rt[g * n_c + k], rt2);
+        }
+        {
+            const int s = t & (SP - 1), r = t / SP;
+            if (s < S)
+                for (int64_t i = r; i < N; i += p.R) dmax = fmax(dmax, p.D[p.row(i) * S + s]);
+        }
+        dmax = block_max(dmax, m.red);
+        dsq = dmax * dmax;
+        rt_norm2 = block_sum(rt2, m.red);
+        u2 = block_sum(u2, m.red);  // (its barriers also publish u and the job tables)
+        double w2 = 0.0;
+        for (int e = t; e < NU * S; e += kSmallThreads) {
+            const int j = e / S, s = e - j * S;
+            w2 = fma(m.a[(n_c + j) * SP + s], m.a[(n_c + j) * SP + s], w2);
+        }
+        l_w = l_w_prev = block_sum(w2, m.red) * dsq;
+        l_h = l_h_prev = (rt_norm2 + u2) * dsq;
+        a1 = a2 = 1.0;
+        iters = 0;
+        gram_jobs(p, m, 0, n_known);
+        for (int e = t; e < n_known * S; e += kSmallThreads) {
+            const int j = e / S, s = e - j * S;
+            gk[e] = m.gb[(int)m.jd[j] * SP + s];
+        }
+        cf = stream_cost(p, m);
+    } else {
+        for (int e = t; e < K * S; e += kSmallThreads) {
+            const int k = e / S, s = e - k * S;
+            m.a[k * SP + s] = ws_alpha[e];
+            m.ap[k * SP + s] = ws_alpha_prev[e];
+        }
+        __syncthreads();  // (the job tables)
+        for (int e = t; e < n_known * S; e += kSmallThreads) {
+            const int j = e / S, s = e - j * S;
+            m.gb[(int)m.jd[j] * SP + s] = gk[e];
+        }
+        a1 = scal[kSmA1], a2 = scal[kSmA2], l_w = scal[kSmLw], l_w_prev = scal[kSmLwPrev], l_h = scal[kSmLh];
+        l_h_prev = scal[kSmLhPrev], dsq = scal[kSmDsq], rt_norm2 = scal[kSmRtNorm2], cf = scal[kSmCf];
+        iters = a.iters[b];
+        __syncthreads();
+    }
+
+    const int64_t T2 = a.n_iter2;
+    int done = 0;
+    for (int it = 0; it < a.n_run; ++it) {
+        // the momentum ratios (a_{t-1} - 1) / a_t of both phases (:83-84, :95-96): they do not depend on the data
+        if (t == 0 || t == 64) {
+            double am = t == 0 ? a1 : a2;
+            double* ratio = t == 0 ? ratio_u : ratio_h;
+            for (int64_t q = 0; q < T2; ++q) {
+                const double an = (1.0 + sqrt(1.0 + 4.0 * am * am)) / 2.0;
+                ratio[q] = (am - 1.0) / an;
+                am = an;
+            }
+            m.sh[t == 0 ? 0 : 1] = am;
+        }
+        __syncthreads();
+        a1 = m.sh[0], a2 = m.sh[1];
+
+        // ---- u phase (:81-90)
+        const double cap_w = 0.9999 * sqrt(l_w_prev / l_w);
+        double u2 = 0.0;
+        for (int64_t i = t; i < N; i += kSmallThreads) {
+            const int64_t g = p.row(i);
+            double rt[kSmallMaxK - 1];
+#pragma unroll
+            for (int k = 0; k < kSmallMaxK - 1; ++k) rt[k] = k < n_c ? p.Rt[g * n_c + k] : 0.0;
+            double c[NU], M[NP];
+#pragma unroll
+            for (int j = 0; j < NU; ++j) c[j] = 0.0;
+#pragma unroll
+            for (int q = 0; q < NP; ++q) M[q] = 0.0;
+            const double* Vr = p.V + g * S;
+            const double* Dr = p.D + g * S;
+#pragma unroll 4
+            for (int s = 0; s < S; ++s) {
+                const double d = Dr[s];
+                double x = Vr[s];
+#pragma unroll
+                for (int k = 0; k < kSmallMaxK - 1; ++k)
+                    if (k < n_c) x = fma(-rt[k], m.a[k * SP + s], x);
+                x *= d;
+                double au[NU];
+#pragma unroll
+                for (int j = 0; j < NU; ++j) au[j] = m.a[(n_c + j) * SP + s];
+#pragma unroll
+                for (int l = 0; l < NU; ++l) {
+                    c[l] = fma(x, au[l], c[l]);
+                    const double dl = d * au[l];
+#pragma unroll
+                    for (int j = 0; j <= l; ++j) M[l * (l + 1) / 2 + j] = fma(dl, au[j], M[l * (l + 1) / 2 + j]);
+                }
+            }
+            double uc[NU], up[NU];
+#pragma unroll
+            for (int j = 0; j < NU; ++j) uc[j] = u[i * NU + j], up[j] = u_prev[i * NU + j];
+            for (int64_t q = 0; q < T2; ++q) {
+                const double beta = fmin(ratio_u[q], q == 0 ? cap_w : 0.9999);
+                double ut[NU], at[NU];
+#pragma unroll
+                for (int j = 0; j < NU; ++j) {
+                    ut[j] = fma(beta, uc[j] - up[j], uc[j]);
+                    at[j] = a.mode == DMF_MODE_UNSUPERVISED ? uc[j] : ut[j];  // where the gradient is taken (:163)
+                }
+#pragma unroll
+                for (int j = 0; j < NU; ++j) {
+                    double gr = c[j];
+#pragma unroll
+                    for (int l = 0; l < NU; ++l) gr = fma(-M[j <= l ? l * (l + 1) / 2 + j : j * (j + 1) / 2 + l], at[l], gr);
+                    up[j] = uc[j];
+                    uc[j] = fmin(fmax(ut[j] + gr / l_w, 0.0), 1.0);
+                }
+            }
+#pragma unroll
+            for (int j = 0; j < NU; ++j) {
+                u[i * NU + j] = uc[j], u_prev[i * NU + j] = up[j];
+                u2 = fma(uc[j], uc[j], u2);
+            }
+        }
+        if (T2 > 0) l_w_prev = l_w;
+        u2 = block_sum(u2, m.red);  // (its barriers publish u to the workgroup)
+        l_h = (rt_norm2 + u2) * dsq;  // :212
+
+        // ---- the u-dependent entries of the per-sample Grams
+        gram_jobs(p, m, n_known, n_jobs);
+
+        // ---- alpha phase (:93-102): thread s owns column s
+        if (t < S) {
+            const int s = t;
+            const double cap_h = 0.9999 * sqrt(l_h_prev / l_h);
+            for (int64_t q = 0; q < T2; ++q) {
+                const double beta = fmin(ratio_h[q], q == 0 ? cap_h : 0.9999);
+                for (int k = 0; k < K; ++k) {
+                    const double ak = m.a[k * SP + s];
+                    m.tmp[k * SP + s] = fma(beta, ak - m.ap[k * SP + s], ak);
+                    m.ap[k * SP + s] = ak;
+                }
+                for (int k = 0; k < K; ++k) {
+                    double gr = m.gb[(n_pairs + k) * SP + s];
+                    for (int l = 0; l < K; ++l) {
+                        const int q2 = k <= l ? l * (l + 1) / 2 + k : k * (k + 1) / 2 + l;
+                        gr = fma(-m.gb[q2 * SP + s], m.tmp[l * SP + s], gr);
+                    }
+                    m.a[k * SP + s] = m.tmp[k * SP + s] + gr / l_h;
+                }
+                project_column_lds(m.a + s, m.srt + s, K, SP);
+            }
+        }
+        if (T2 > 0) l_h_prev = l_h;
+        __syncthreads();
+        double w2 = 0.0;
+        for (int e = t; e < NU * S; e += kSmallThreads) {
+            const int j = e / S, s = e - j * S;
+            w2 = fma(m.a[(n_c + j) * SP + s], m.a[(n_c + j) * SP + s], w2);
+        }
+        l_w = block_sum(w2, m.red) * dsq;  // :216
+
+        // ---- cost and stop test (:218-220)
+        const double cf_0 = cf;
+        cf = stream_cost(p, m);
+        ++iters;
+        if (fabs(cf - cf_0) < a.tol) {
+            done = 1;
+            break;
+        }
+    }
+
+    // everything the next launch (or the host) reads
+    for (int e = t; e < K * S; e += kSmallThreads) {
+        const int k = e / S, s = e - k * S;
+        ws_alpha[e] = m.a[k * SP + s];
+        ws_alpha_prev[e] = m.ap[k * SP + s];
+    }
+    if (t == 0) {
+        scal[kSmA1] = a1, scal[kSmA2] = a2, scal[kSmLw] = l_w, scal[kSmLwPrev] = l_w_prev, scal[kSmLh] = l_h;
+        scal[kSmLhPrev] = l_h_prev, scal[kSmDsq] = dsq, scal[kSmRtNorm2] = rt_norm2, scal[kSmCf] = cf;
+        a.iters[b] = iters;
+        a.done[b] = done;
+    }
+}
+
+bool small_supported(int64_t N, int64_t S, int64_t n_c, int64_t n_u, int mode) {
+    if (mode != DMF_MODE_PARTIAL && mode != DMF_MODE_UNSUPERVISED) return false;
+    if (N < 1 || S < 1 || S > kSmallMaxS || n_c < 0 || n_u < 1 || n_u > kSmallMaxNu || n_c + n_u > kSmallMaxK) return false;
+    return N <= kSmallMaxElements / S;
+}
+
+size_t small_lds_bytes(int S, int K) {
+    const int SP = pow2_at_least(S);
+    const size_t doubles = (size_t)(K * (K + 1) / 2 + K) * SP + 4 * (size_t)K * SP + kSmallChunk * kSmallThreads + 8;
+    return doubles * sizeof(double) + (kJobShorts * sizeof(short) + 7) / 8 * 8;
+}
+
+template <int NU>
+static hipError_t launch_nu(const SmallArgs& a, int64_t B, size_t lds, hipStream_t st) {
+    static bool raised = false;  // more than 64 KB of dynamic LDS need the kernel's limit raised, once
+    if (lds > 64 * 1024 && !raised) {
+        const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_solve_small<NU>),
+                                                 hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+        if (e != hipSuccess) return e;
+        raised = true;
+    }
+    hipLaunchKernelGGL(k_solve_small<NU>, dim3((unsigned)B), dim3(kSmallThreads), lds, st, a);
+    return hipGetLastError();
+}
+
+hipError_t launch_solve_small(const SmallArgs& a, int64_t B, hipStream_t st) {
+    if (!small_supported(a.N, a.S, a.n_c, a.n_u, a.mode) || B < 1 || B > 0x7fffffff) return hipErrorInvalidValue;
+    const size_t lds = small_lds_bytes(a.S, a.n_c + a.n_u);
+    switch (a.n_u) {
+        case 1: return launch_nu<1>(a, B, lds, st);
+        case 2: return launch_nu<2>(a, B, lds, st);
+        case 3: return launch_nu<3>(a, B, lds, st);
+        default: return launch_nu<4>(a, B, lds, st);
+    }
+}
+
+}  // namespace dmf

@@ -16,6 +16,10 @@ Deliberate differences from upstream, all flagged at run time:
   * ``DEMETHIFY_CI_ROWS=cpg`` (environment; default ``position``, upstream's): row j of
     confidence_interval_methylation_estimate.csv is the interval of CpG j's own estimates over the replicates that drew it,
     (nan, nan) where none did, instead of the percentiles by resampled position.
+  * ``DEMETHIFY_BATCH=1`` (environment; default ``0``): ``--confidence`` replicates and ``--restart`` restarts of a small
+    problem are solved many per kernel launch, one workgroup each, when the case is eligible
+    (bootstrap.batched_ineligible) and N x S is at most bootstrap.SMALL_BATCH_MAX_ELEMENTS; otherwise a one-line note says
+    why not and the run takes the per-solve path.
   * ``--ic NAME [n [lo hi]]``: upstream sweeps the hard-coded range 1..25 (ic.py:171); two more values after the
     restart count restrict the sweep to lo..hi unknown types (``--ic BIC 5 2 12``).  Without them: 1..25, as upstream.
 """
@@ -149,6 +153,11 @@ def main(argv=None):
     if ci_rows not in ("position", "cpg"):
         sys.stderr.write(f'Error: DEMETHIFY_CI_ROWS must be "position" or "cpg", got "{ci_rows}".\n')
         sys.exit(1)
+    # DEMETHIFY_BATCH=1: bootstrap replicates and restarts of small problems through Problem.solve_many, where eligible
+    batch_env = os.environ.get("DEMETHIFY_BATCH", "0")
+    if batch_env not in ("0", "1"):
+        sys.stderr.write(f'Error: DEMETHIFY_BATCH must be "0" or "1", got "{batch_env}".\n')
+        sys.exit(1)
     if args.plot:
         sys.stderr.write("Note: --plot is ignored, plotting (seaborn/colorcet) is outside this build's scope.\n")
 
@@ -172,6 +181,7 @@ def main(argv=None):
     # imported late so that ``--help`` and argument errors work on a box without the GPU library
     from . import _lib as L
     from . import shard, staging
+    from . import bootstrap as bootstrap_mod
     from .bootstrap import bt_ci
     from . import init_func
     from .deconvolution import _init_guard, _init_unsupervised, init_BSSMF_md, init_BSSMF_md_p, rd, set_seed
@@ -183,10 +193,26 @@ def main(argv=None):
     n_u = args.nbunknown[0]
     ic_n_u = None
 
+    def batch_route(what, align=False, profile_rows="position"):
+        """DEMETHIFY_BATCH=1: does `what` go through Problem.solve_many?  A one-line note says why not."""
+        if batch_env != "1":
+            return False
+        n_rows, n_samples = meth_f.shape
+        reason = bootstrap_mod.batched_ineligible(
+            n_u, n_rows, n_samples, ref.shape[1] if args.ref else 0, args.init, args.purity,
+            L.DMF_MODE_PARTIAL if args.ref else L.DMF_MODE_UNSUPERVISED, None, align, profile_rows)
+        if reason is None and n_rows * n_samples > bootstrap_mod.SMALL_BATCH_MAX_ELEMENTS:
+            reason = (f"{n_rows} x {n_samples} elements are more than SMALL_BATCH_MAX_ELEMENTS = "
+                      f"{bootstrap_mod.SMALL_BATCH_MAX_ELEMENTS}")
+        if reason is not None and rank == 0:
+            print(f"Note: DEMETHIFY_BATCH=1 is not used for {what}: {reason}; taking the per-solve path.")
+        return reason is None
+
     def bootstrap(anchor=None):
+        batched = batch_route("--confidence", align=not args.ref and n_u >= 2, profile_rows=ci_rows)
         bt_ci(args.confidence[0], args.confidence[1], n_u, meth_f, counts, ref, args.init, args.iterations[0],
               args.iterations[1], args.termination, header if args.ref else [], outdir, args.methfreq, args.purity,
-              args.seed, materialize=False, anchor=anchor, profile_rows=ci_rows)
+              args.seed, materialize=False, anchor=anchor, profile_rows=ci_rows, batched=batched)
 
     if args.confidence and args.ref:
         bootstrap()
@@ -206,8 +232,9 @@ def main(argv=None):
         K = (0 if unsupervised else ref.shape[1]) + n_u
         if args.restart > 1 and rank == 0:
             print(f"restart k > 0 uses seed + k (upstream repeats the same seed); {args.restart} restarts")
+        batch_restarts = args.restart > 1 and batch_route("--restart")
         with Problem(get_context(), meth_f, counts, None if unsupervised else ref) as problem:
-            if args.restart > 1:
+            if args.restart > 1 and not batch_restarts:
                 staging.reserve(((meth_f.shape[0], n_u), (K, meth_f.shape[1])), count=2)
 
             # --init uniform on a large problem: u0 is drawn on the host as init_BSSMF_md / init_BSSMF_md_p draw it (set_seed,
@@ -263,8 +290,31 @@ def main(argv=None):
                     u, alpha, _, _ = s.get()
                 return u, alpha, cost
 
-            ref_estimate, proportions, _best, _costs = shard.sharded_restarts(
-                args.restart, solve_one, ((meth_f.shape[0], n_u), (K, meth_f.shape[1])), prepare=prepare, solve_end=solve_end)
+            def solve_batch(ks):
+                # this rank's restarts, one workgroup each: the initialisers are drawn one after the other, as prepare draws them
+                mode = L.DMF_MODE_UNSUPERVISED if unsupervised else L.DMF_MODE_PARTIAL
+                chunk = bootstrap_mod.batch_chunk(meth_f.shape[0], n_u)
+                parts = []
+                for c0 in range(0, len(ks), chunk):
+                    inits = []
+                    for k in ks[c0:c0 + chunk]:
+                        seed_k = shard.restart_seed(args.seed, k)
+                        if unsupervised:
+                            inits.append(_init_unsupervised(args.init, meth_f, n_u, seed_k))
+                        else:
+                            u0, _, a0 = init_BSSMF_md(args.init, meth_f, counts, ref, n_u, rb_alg=wls_intercept, seed=seed_k,
+                                                      _stack=False)
+                            inits.append((u0, a0))
+                    parts.append(problem.solve_many(np.stack([u0 for u0, _ in inits]), np.stack([a0 for _, a0 in inits]), mode,
+                                                    args.iterations[0], args.iterations[1], args.termination)[:3])
+                return tuple(np.concatenate([part[j] for part in parts]) for j in range(3))
+
+            shapes = ((meth_f.shape[0], n_u), (K, meth_f.shape[1]))
+            if batch_restarts:
+                ref_estimate, proportions, _best, _costs = shard.sharded_restarts_batched(args.restart, solve_batch, shapes)
+            else:
+                ref_estimate, proportions, _best, _costs = shard.sharded_restarts(
+                    args.restart, solve_one, shapes, prepare=prepare, solve_end=solve_end)
         unknown_header = ["unknown_cell_" + str(i + 1) for i in range(n_u)]
         header = unknown_header if unsupervised else header + unknown_header
     elif n_u == 0 and meth_f.shape[1] >= 1:

@@ -228,6 +228,12 @@ def u_phase_describe(N, S, n_c, n_u, nd=0, level=0, n_iter2=20, flags=0, route="
     return buf.value.decode()
 
 
+def small_solve_supported(N, S, n_c, n_u, mode=L.DMF_MODE_PARTIAL) -> bool:
+    """dmf_solve_small_supported: does ``Problem.solve_many`` take the shape?  Modes partial and unsupervised,
+    1 <= n_u <= 4, n_c + n_u <= 16, S <= 64, N * S <= 2**20.  A pure function of its arguments: no GPU is touched."""
+    return bool(L.load().dmf_solve_small_supported(int(N), int(S), int(n_c), int(n_u), int(mode)))
+
+
 class Problem:
     """dmf_problem: meth_frequency (N x S), counts (N x S), R_trunc (N x n_c or None)."""
 
@@ -611,6 +617,35 @@ class Problem:
         finally:
             t_dev.close()
         return u0
+
+    def solve_many(self, u0s, alpha0s, mode, n_iter1, n_iter2, tol, idx=None, iters_per_launch=0):
+        """B independent solves of this problem in one call, one workgroup per solve (dmf_solve_small) ->
+        (u[B, N, n_u], alpha[B, K, S], cost[B], iters[B]).  ``u0s`` (B, N, n_u) and ``alpha0s`` (B, K, S): the starting
+        points; ``idx`` (B, N) integers or None: row i of solve b is row ``idx[b, i]`` of the problem (a bootstrap
+        replicate), None = the problem's own rows.  ``cost[b]`` is cost_f_w of solve b's final iterate, ``iters[b]`` its
+        outer iterations.  ``iters_per_launch``: outer iterations per kernel launch, 0 = the library's default; the results
+        do not depend on it.  Host arrays in, fresh host arrays out; nothing is mutated.  Shapes outside
+        ``small_solve_supported`` raise (DMF_ERR_UNSUPPORTED): there is no fall-back to the per-solve path here."""
+        u0s = np.ascontiguousarray(u0s, dtype=np.float64)
+        alpha0s = np.ascontiguousarray(alpha0s, dtype=np.float64)
+        if u0s.ndim != 3 or u0s.shape[1] != self.N:
+            raise ValueError(f"u0s is B x {self.N} x n_u, got shape {u0s.shape}")
+        B, _, n_u = u0s.shape
+        K = self.n_c + n_u
+        if alpha0s.shape != (B, K, self.S):
+            raise ValueError(f"alpha0s shape {alpha0s.shape} != {(B, K, self.S)}")
+        if idx is not None:
+            idx = np.ascontiguousarray(idx, dtype=np.int64)
+            if idx.shape != (B, self.N):
+                raise ValueError(f"idx shape {idx.shape} != {(B, self.N)}")
+        u = np.empty((B, self.N, n_u), dtype=np.float64)
+        alpha = np.empty((B, K, self.S), dtype=np.float64)
+        cost = np.empty(B, dtype=np.float64)
+        iters = np.empty(B, dtype=np.int64)
+        L.check(self._lib.dmf_solve_small(self.ctx._h, self._h, B, _ptr(idx), _ptr(u0s), _ptr(alpha0s), n_u, int(mode),
+                                          int(n_iter1), int(n_iter2), float(tol), int(iters_per_launch), 0, _ptr(u),
+                                          _ptr(alpha), _ptr(cost), _ptr(iters)), "dmf_solve_small")
+        return u, alpha, cost, iters
 
     def update_u(self, u, u_prev, alpha, n_iter2, a1, l_w_prev, l_w, mode=L.DMF_MODE_PARTIAL):
         u = np.ascontiguousarray(u, dtype=np.float64).reshape(self.N, -1)

@@ -252,6 +252,29 @@ def sharded_restarts(n_restarts, solve_one, shapes, prepare=None, solve_end=None
     finally:
         if feed is not None:
             feed.close()
+    return _pick_winner(n_restarts, local_costs, keep, shapes, rank, world)
+
+
+def sharded_restarts_batched(n_restarts, solve_many, shapes):
+    """``sharded_restarts`` with this rank's restarts solved in ONE call: solve_many(ks) -> (u[B], alpha[B], cost[B]) for
+    the restarts ``ks`` this rank owns (Problem.solve_many behind it: one workgroup per restart).  The pick is the same:
+    strict '<' keeps the first minimum locally, one all-reduce(min) over the cost vector, the winner's iterate to every
+    rank.  Returns (u, alpha, best_k, cost_vector)."""
+    rank, world, _ = dist_state()
+    local_costs, keep = {}, {}
+    mine = list(my_items(n_restarts, rank, world))
+    if mine:
+        us, alphas, costs = solve_many(mine)
+        for j, k in enumerate(mine):
+            cost = float(costs[j])
+            local_costs[k] = cost
+            if not keep or cost < keep["cost"]:
+                keep = {"k": k, "u": us[j], "alpha": alphas[j], "cost": cost}
+    return _pick_winner(n_restarts, local_costs, keep, shapes, rank, world)
+
+
+def _pick_winner(n_restarts, local_costs, keep, shapes, rank, world):
+    """The restarts' costs of every rank -> the first minimum and its iterate everywhere."""
     costs = allreduce_min_vector(local_costs, n_restarts)
     best_k = argmin_first(costs)
     owner = best_k % world

@@ -431,6 +431,34 @@ int dmf_solve(dmf_context* ctx, const dmf_problem* p, const double* u0, const do
               int64_t n_u, int mode, int64_t n_iter1, int64_t n_iter2, double tol, int flags,
               double* out_u, double* out_alpha, double* out_cost, int64_t* out_iters);
 
+/* ---- small problems: B independent solves of one resident problem per launch, one workgroup per solve.
+ * The whole outer loop of mdwbssmf_deconv (demethify/deconvolution.py:190-223, DMF_MODE_PARTIAL) or unsupervised_deconv
+ * (:107-184, DMF_MODE_UNSUPERVISED) runs inside one kernel: set-up as :192-204 (a1 = a2 = 1, u_ = u0, alpha_ = alpha0,
+ * d = max(counts)^2, l_w, l_h, the cost), then per outer iteration the u phase (:81-90; the gradient at u_temp in partial
+ * mode, at the previous iterate in unsupervised mode, :163), l_h (:212), the alpha phase with the sort-based simplex
+ * projection (:93-102, :21-37), l_w (:216), the streaming cost sum d (v - R alpha)^2 (:15-17) and the stop test
+ * fabs(cf - cf_0) < tol on that cost (:218-220).  No Gram-form cost and no confirmation of stops take part.
+ * dmf_solve_small_supported: 1 where the kernel takes the shape, else 0 -- modes DMF_MODE_PARTIAL and DMF_MODE_UNSUPERVISED,
+ * 1 <= n_u <= 4, n_c + n_u <= 16, S <= 64, N S <= 2^20 (that bounds how long one launch can run; it is not a measured
+ * cross-over).  Pure: no context, no GPU.
+ * dmf_solve_small: solve b of B starts from u0[b] (N x n_u) and alpha0[b] (K x S).  idx NULL: every solve runs on the problem's
+ * own N rows.  idx given (B x N int64): row i of solve b is row idx[b][i] of the problem, read through the index without a
+ * gathered copy -- a bootstrap replicate (demethify/bootstrap.py:28) -- and d is the maximum over the drawn rows.  With
+ * DMF_PTR_DEVICE in flags idx, u0, alpha0 and out_u are device arrays; out_alpha (B x K x S), out_cost (B) and out_iters (B)
+ * are host arrays.  out_cost[b] is cost_f_w of the final iterate, what the restart pick compares (demethify/demethify.py:199);
+ * out_iters[b] the outer iterations solve b ran (at most n_iter1).  A launch runs at most iters_per_launch outer iterations
+ * per solve (0: the library's default); between launches the host reads the B stop flags and ends when every solve has
+ * stopped or n_iter1 is reached.  All per-solve state is kept in HBM between launches, so the results are the same bit for
+ * bit for every iters_per_launch; they do not depend on B, on a solve's slot or on the other solves either.
+ * DMF_ERR_UNSUPPORTED outside the envelope, before the context is touched.  DMF_ERR_BAD_ARG: B < 1, a null array, a negative
+ * iteration count, a masked problem (as dmf_svd_gram), an index outside [0, N) -- every index is checked on the device
+ * before the first launch, as dmf_problem_gather_device checks its own, so no solve has started.  Inputs are never written. */
+int dmf_solve_small_supported(int64_t N, int64_t S, int64_t n_c, int64_t n_u, int mode);
+int dmf_solve_small(dmf_context* ctx, const dmf_problem* p, int64_t B, const int64_t* idx, const double* u0,
+                    const double* alpha0, int64_t n_u, int mode, int64_t n_iter1, int64_t n_iter2, double tol,
+                    int64_t iters_per_launch, int flags, double* out_u, double* out_alpha, double* out_cost,
+                    int64_t* out_iters);
+
 /* ---- input tables (host side) ---------------------------------------------------------------
  * demethify/demethify.py:103-143 reads each sample file with pandas.read_csv and stacks its `percent_modified` and
  * `valid_coverage` columns.  dmf_table_scan finds the two columns by header name and counts the data rows;
