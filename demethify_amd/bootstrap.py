@@ -77,21 +77,32 @@ def _device_stack(n_local, width):
 # 183 ms against 40 ms -- and 10 000 x 64 with 64 restarts 0.61 s against 4.05 s: there one workgroup per solve loses, so the
 # gate sits at 1 000 x 16.
 SMALL_BATCH_MAX_ELEMENTS = 16000
+# The same gate for purity-constrained runs (--purity; dmf_solve_small_purity), set from the --purity legs of the same tool
+# (profiles/small_batch_purity_bench.txt; 100 x 500 iterations, medians of five, per-solve against batched): 350 x 10 with
+# 2 500 replicates 21.37 s against 0.28 s and with 64 restarts 226 ms against 5.5 ms, 1 000 x 16 with 64 restarts 1.63 s
+# against 67 ms.  The batched leg wins at every measured size, so the gate is the largest of them; nothing larger has been
+# measured under purity (without it the batched leg loses at 10 000 x 64, above).
+SMALL_BATCH_PURITY_MAX_ELEMENTS = 16000
 
 
 def batched_ineligible(n_u, n_rows, n_samples, n_ct, init_option, purity, mode, observe=None, align=False,
-                       profile_rows="position"):
+                       profile_rows="position", purity_batched=False):
     """Why a loop of solves cannot go through ``Problem.solve_many`` (one launch for many solves), as a sentence, or None
     when it can: at least one unknown type, no purity constraint, nobody watching single replicates, no component
     alignment, profile rows by position, an initialiser that does not read the data (``uniform_``, ``beta``, or the silent
-    replacement by ``uniform_`` when there are more unknown types than samples) and a shape the kernel takes.  Touches
-    no device."""
+    replacement by ``uniform_`` when there are more unknown types than samples) and a shape the kernel takes.
+    ``purity_batched``: the caller has asked for the purity variant of the kernel (``solve_many(purity=...)``), so a purity
+    vector passes where there is a reference to hold at that mass.  Touches no device."""
     from .device import small_solve_supported
 
     if n_u < 1:
         return "there is no unknown cell type to solve for"
     if purity is not None and np.size(purity) > 0:
-        return "the purity-constrained alpha phase is not part of the batched kernel"
+        if not purity_batched:
+            return ("the purity-constrained alpha phase is not part of the batched kernel unless it is asked for "
+                    "(bt_ci(..., batched_purity=True), batched_ineligible(..., purity_batched=True))")
+        if mode != L.DMF_MODE_PARTIAL or n_ct < 1:
+            return "a purity constraint has no meaning without a reference: there is no known block to hold at that mass"
     if observe is not None:
         return "_observe looks at one replicate's solver, which a batched solve does not have"
     if align:
@@ -115,7 +126,7 @@ def batch_chunk(n_rows, n_u):
 
 def bt_ci(confidence_level, n_bootstrap, n_u, meth_f, counts, ref, init_option, n_iter1, n_iter2, tol, header,
           outdir, samples, purity, seed, materialize=True, _observe=None, anchor=None, align_unknown=None,
-          profile_rows="position", batched=False):
+          profile_rows="position", batched=False, batched_purity=False):
     """bootstrap.py:10-93 -> [proportions CI DataFrame, (profile CI DataFrame)]; writes the two CSVs.
     materialize=False (the CLI, which ignores the return value) skips building the N-row DataFrame of tuples for the
     profile intervals: the CSV is written by the library and the second result is the (lower, upper) array pair.
@@ -142,14 +153,16 @@ def bt_ci(confidence_level, n_bootstrap, n_u, meth_f, counts, ref, init_option, 
     ``batched``: this rank's replicates go through ``Problem.solve_many`` in chunks, one workgroup per replicate, rows
     read through the replicate's index list.  Row indices and initialisers are drawn per replicate
     from seed_i in the reference's order, exactly as without it.  Only for the cases ``batched_ineligible`` accepts; any
-    other raises ValueError naming the reason before any device work."""
+    other raises ValueError naming the reason before any device work.  A purity vector is among those reasons unless
+    ``batched_purity`` is set as well: the replicates then run the purity variant of the kernel (``solve_many(purity=p / 100)``)
+    from ``init_BSSMF_md_p``'s starting points.  (Two switches because ``batched=True`` alone is pinned to refuse purity.)"""
     if profile_rows not in ("position", "cpg"):
         raise ValueError(f'profile_rows must be "position" or "cpg", got {profile_rows!r}')
     if batched:
         will_align = bool(ref is None if align_unknown is None else align_unknown) and n_u >= 2
         reason = batched_ineligible(n_u, meth_f.shape[0], meth_f.shape[1], 0 if ref is None else ref.shape[1], init_option,
                                     purity, L.DMF_MODE_UNSUPERVISED if ref is None else L.DMF_MODE_PARTIAL, _observe,
-                                    will_align, profile_rows)
+                                    will_align, profile_rows, purity_batched=bool(batched_purity))
         if reason is not None:
             raise ValueError(f"bt_ci(batched=True): {reason}")
     by_cpg = profile_rows == "cpg"
@@ -217,13 +230,18 @@ def bt_ci(confidence_level, n_bootstrap, n_u, meth_f, counts, ref, init_option, 
                 for i in part:
                     if ref is None:
                         inits.append(_init_unsupervised(init_option, shape_f, n_u, seeds[i]))
+                    elif purity_frac is not None:
+                        u0, _, a0 = init_BSSMF_md_p(init_option, shape_f, np.broadcast_to(counts[:1], counts.shape),
+                                                    np.broadcast_to(ref[:1], ref.shape), n_u, purity_frac, seed=seeds[i],
+                                                    rb_alg=wls_intercept, _stack=False)
+                        inits.append((u0, a0))
                     else:
                         u0, _, a0 = init_BSSMF_md(init_option, shape_f, np.broadcast_to(counts[:1], counts.shape),
                                                   np.broadcast_to(ref[:1], ref.shape), n_u, rb_alg=wls_intercept, seed=seeds[i],
                                                   _stack=False)
                         inits.append((u0, a0))
                 us, alphas, _, _ = full.solve_many(np.stack([u0 for u0, _ in inits]), np.stack([a0 for _, a0 in inits]),
-                                                   mode, n_iter1, n_iter2, tol, idx=idx)
+                                                   mode, n_iter1, n_iter2, tol, idx=idx, purity=purity_frac)
                 local.extend((i, (us[j], alphas[j])) for j, i in enumerate(part))
     else:
         # The host work of the replicates ahead (MT19937 index draw of N rows; uniform N x n_u + Dirichlet init: ~10 + ~13 ms

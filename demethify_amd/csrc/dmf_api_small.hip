@@ -1,5 +1,5 @@
 // C-ABI of libdemethify_hip.so, part 7: many independent small solves of one resident problem per launch
-// (dmf_solve_small; the kernel is dmf_kernels_small.hip).
+// (dmf_solve_small, dmf_solve_small_purity; the kernel is dmf_kernels_small.hip).
 #include <algorithm>
 
 #include "dmf_api.h"
@@ -7,19 +7,17 @@
 
 using namespace dmf_api;
 
-extern "C" {
-
-int dmf_solve_small_supported(int64_t N, int64_t S, int64_t n_c, int64_t n_u, int mode) {
-    return dmf::small_supported(N, S, n_c, n_u, mode) ? 1 : 0;
-}
-
-int dmf_solve_small(dmf_context* ctx, const dmf_problem* p, int64_t B, const int64_t* idx, const double* u0, const double* alpha0,
-                    int64_t n_u, int mode, int64_t n_iter1, int64_t n_iter2, double tol, int64_t iters_per_launch, int flags,
-                    double* out_u, double* out_alpha, double* out_cost, int64_t* out_iters) {
+// The body of both entries.  with_purity: `purity` (S doubles) selects the purity variant of the kernel.
+static int solve_small(dmf_context* ctx, const dmf_problem* p, int64_t B, const int64_t* idx, const double* u0, const double* alpha0,
+                       int64_t n_u, int mode, int64_t n_iter1, int64_t n_iter2, double tol, int64_t iters_per_launch, int flags,
+                       bool with_purity, const double* purity, double* out_u, double* out_alpha, double* out_cost,
+                       int64_t* out_iters) {
     if (ctx == nullptr || p == nullptr || B < 1 || B > 0x7fffffff || u0 == nullptr || alpha0 == nullptr || out_u == nullptr ||
         out_alpha == nullptr || out_cost == nullptr || out_iters == nullptr || n_iter1 < 0 || n_iter2 < 0 || iters_per_launch < 0)
         return DMF_ERR_BAD_ARG;
     if (p->ctx != ctx || p->mask_bits != nullptr) return DMF_ERR_BAD_ARG;  // (a masked problem's held-out zeros are not data)
+    if (with_purity && (purity == nullptr || p->n_c < 1)) return DMF_ERR_BAD_ARG;  // (no known block to hold at that mass)
+    if (with_purity && mode != DMF_MODE_PARTIAL) return DMF_ERR_UNSUPPORTED;
     if (!dmf::small_supported(p->N, p->S, p->n_c, n_u, mode)) return DMF_ERR_UNSUPPORTED;
     DMF_TRY(check_ctx(ctx));
     const int64_t N = p->N, S = p->S, K = p->n_c + n_u;
@@ -40,6 +38,8 @@ int dmf_solve_small(dmf_context* ctx, const dmf_problem* p, int64_t B, const int
     }
     DMF_TRY(import_array(ctx, u0, un, flags, d_u0));
     DMF_TRY(import_array(ctx, alpha0, an, flags, d_a0));
+    DevBuf<double> d_purity;
+    if (with_purity) DMF_TRY(import_array(ctx, purity, (size_t)S, flags, d_purity));
 
     // the workspace: all per-solve state, so that the next launch continues where this one stopped
     DevBuf<double> w_u, w_up, w_a, w_ap, w_gk, w_ratio, w_scal;
@@ -63,9 +63,10 @@ int dmf_solve_small(dmf_context* ctx, const dmf_problem* p, int64_t B, const int
     a.n_iter2 = n_iter2, a.tol = tol;
     a.u = w_u, a.u_prev = w_up, a.alpha = w_a, a.alpha_prev = w_ap, a.gk = w_gk, a.ratio = w_ratio, a.scal = w_scal;
     a.iters = w_iters, a.done = w_done;
+    if (with_purity) a.purity = d_purity;
 
     const int64_t per_launch = iters_per_launch > 0 ? std::min<int64_t>(iters_per_launch, 1 << 20)
-                                                      : dmf::small_default_iters_per_launch(N, S);
+                                                      : dmf::small_default_iters_per_launch(N, S, with_purity);
     std::vector<int> h_done((size_t)B);
     int64_t ran = 0;  // outer iterations every unfinished solve has run
     for (bool first = true;; first = false) {
@@ -91,6 +92,27 @@ int dmf_solve_small(dmf_context* ctx, const dmf_problem* p, int64_t B, const int
     HIP_TRY(hipStreamSynchronize(ctx->stream));
     for (int64_t b = 0; b < B; ++b) out_cost[b] = h_scal[(size_t)b * dmf::kSmallScalars + dmf::kSmCf];
     return DMF_OK;
+}
+
+extern "C" {
+
+int dmf_solve_small_supported(int64_t N, int64_t S, int64_t n_c, int64_t n_u, int mode) {
+    return dmf::small_supported(N, S, n_c, n_u, mode) ? 1 : 0;
+}
+
+int dmf_solve_small(dmf_context* ctx, const dmf_problem* p, int64_t B, const int64_t* idx, const double* u0, const double* alpha0,
+                    int64_t n_u, int mode, int64_t n_iter1, int64_t n_iter2, double tol, int64_t iters_per_launch, int flags,
+                    double* out_u, double* out_alpha, double* out_cost, int64_t* out_iters) {
+    return solve_small(ctx, p, B, idx, u0, alpha0, n_u, mode, n_iter1, n_iter2, tol, iters_per_launch, flags, false, nullptr, out_u,
+                       out_alpha, out_cost, out_iters);
+}
+
+int dmf_solve_small_purity(dmf_context* ctx, const dmf_problem* p, int64_t B, const int64_t* idx, const double* u0,
+                           const double* alpha0, const double* purity, int64_t n_u, int mode, int64_t n_iter1, int64_t n_iter2,
+                           double tol, int64_t iters_per_launch, int flags, double* out_u, double* out_alpha, double* out_cost,
+                           int64_t* out_iters) {
+    return solve_small(ctx, p, B, idx, u0, alpha0, n_u, mode, n_iter1, n_iter2, tol, iters_per_launch, flags, true, purity, out_u,
+                       out_alpha, out_cost, out_iters);
 }
 
 }  // extern "C"

@@ -8,6 +8,7 @@
 #include "dmf_device.h"
 #include "dmf_dispatch.h"
 #include "dmf_internal.h"
+#include "dmf_rowlanes.h"
 
 namespace dmf {
 
@@ -448,34 +449,13 @@ __global__ __launch_bounds__(64) void k_alpha_phase_lanes(const double* __restri
 // The inner iteration of this kernel is one long dependent chain run by 64 waves at the headline size, i.e.
 // pure latency: a ds_bpermute round trip per shuffle (16 for the product, 10 sort stages, 4 scan steps) is what
 // the older kernel spends most of its 2.2 us per inner iteration on.
-template <int CTRL>
-__device__ __forceinline__ int row_mov(int x) {  // permutations, or values masked afterwards: no destination to initialise
-    return __builtin_amdgcn_mov_dpp(x, CTRL, 0xF, 0xF, false);
-}
-template <int CTRL>
-__device__ __forceinline__ double row_mov(double x) {
-    const int lo = row_mov<CTRL>(__double2loint(x)), hi = row_mov<CTRL>(__double2hiint(x));
-    return __hiloint2double(hi, lo);
-}
-
+// (row_mov, row_xor and argmin_step: dmf_rowlanes.h)
 // row_shr and the like: lanes without a source must read 0, which needs the "old" operand
 template <int CTRL>
 __device__ __forceinline__ double row_mov_or_zero(double x) {
     const int lo = __builtin_amdgcn_update_dpp(0, __double2loint(x), CTRL, 0xF, 0xF, true);
     const int hi = __builtin_amdgcn_update_dpp(0, __double2hiint(x), CTRL, 0xF, 0xF, true);
     return __hiloint2double(hi, lo);
-}
-
-// value of lane (k ^ J) of the 16-lane row, for a double or an int
-template <int J, class T>
-__device__ __forceinline__ T row_xor(T x, int k) {
-    if constexpr (J == 1) return row_mov<0xB1>(x);       // quad_perm [1, 0, 3, 2]
-    else if constexpr (J == 2) return row_mov<0x4E>(x);  // quad_perm [2, 3, 0, 1]
-    else if constexpr (J == 8) return row_mov<0x128>(x); // row_ror:8
-    else {                                               // J == 4: row_shl:4 for the lower half of an octet
-        const T from_above = row_mov<0x104>(x), from_below = row_mov<0x114>(x);
-        return (k & 4) ? from_below : from_above;
-    }
 }
 
 // acc += x[lane L of the row] * m   (the s_nop covers the VALU-write -> DPP-read hazard inside the asm: FIRST = the first
@@ -685,15 +665,6 @@ __global__ __launch_bounds__(64) void k_alpha_frank_wolfe(const double* __restri
 // moves, lowest index first among equal minima (np.argmin).  The row load and the cost epilogue are written out here:
 // through load_gram_row / lane_cost the kernel took 60 instead of 62 VGPRs and another instruction stream, with no gain in
 // time (profiles/r12_alpha_refactor.txt, section 6); as written it compiles to the stream it had before.
-template <int J>
-__device__ __forceinline__ void argmin_step(double& v, int& idx, int k) {
-    const double ov = row_xor<J>(v, k);
-    const int oi = row_xor<J>(idx, k);
-    const bool take = ov < v || (ov == v && oi < idx);
-    v = take ? ov : v;
-    idx = take ? oi : idx;
-}
-
 __global__ __launch_bounds__(64) void k_alpha_frank_wolfe_row16(const double* __restrict__ gb,
                                                                 double* __restrict__ alpha,
                                                                 const double* __restrict__ purity,

@@ -25,7 +25,13 @@
 // LDS: G and b (K (K + 1) / 2 + K rows of SP doubles, SP = S rounded up to a power of two), alpha, alpha_, the
 // extrapolated point and the sort scratch (4 K SP), 32 KB of reduction scratch, the job tables: 141 KB at S = 64, K = 16,
 // 40 KB for the 350 x 10 example with 5 + 1 types.
+//
+// The purity variant (PURITY; mdwbssmf_deconv_p, :306-337) keeps the u phase, the Gram, l_w, the cost and the stop test and
+// replaces the alpha phase by n_iter2 Frank-Wolfe steps per sample (frank_wolfe_nmf, :280-302) on the same G_s, b_s: one
+// sample per 16-lane row, lane k owning row k of G_s in registers, the 16 rows of the workgroup taking samples r, r + 16, ...
+// There is no a2, no l_h and no alpha_; the purity vector is an input, not state.
 #include "dmf_small.h"
+#include "dmf_rowlanes.h"
 
 #include "../../include/demethify_hip.h"
 
@@ -214,9 +220,68 @@ __device__ void project_column_lds(double* x, double* srt, int K, int SP) {
     for (int k = 0; k < K; ++k) x[k * SP] = fmax(x[k * SP] - theta, 0.0);
 }
 
+// g4[l % 4] += G[l] a[lane l of the row] for l = L .. 15, in this order (row_newbcast:l; four chains as in
+// k_alpha_frank_wolfe_row16)
+template <int L = 0>
+__device__ __forceinline__ void gram_row_times_a(double (&g4)[4], double a, const double (&G)[16]) {
+    if constexpr (L < 16) {
+        g4[L & 3] = fma(G[L], row_mov<0x150 + L>(a), g4[L & 3]);
+        gram_row_times_a<L + 1>(g4, a, G);
+    }
+}
+
+// a = (1 - gamma) a + gamma vertex as numpy evaluates it: two products and a sum, each rounded (:299-300)
+__device__ __forceinline__ double frank_wolfe_update(double a, double gamma, double vertex) {
+#pragma clang fp contract(off)
+    const double keep = (1.0 - gamma) * a, move = gamma * vertex;
+    return keep + move;
+}
+
+// The purity-constrained alpha phase (deconvolution.py:280-302) on the G_s, b_s of m.gb, alpha in m.a: per sample the known
+// block keeps mass purity[s] and the unknown block mass 1 - purity[s]; step k moves by 2 / (k + 2) towards the vertex with
+// the smallest gradient entry of each block, lowest index first among equal minima (np.argmin).  grad = G a - b.  Row r
+// of the workgroup's 16 sixteen-lane rows runs the whole chain of samples r, r + 16, ...; every loop bound is uniform over
+// the workgroup, so the DPP moves always find their row complete.
+__device__ void frank_wolfe_rows(const Lds& m, const double* __restrict__ purity, int S, int n_c, int K, int SP, int n_pairs,
+                                 int64_t n_steps) {
+    const int t = threadIdx.x, k = t & 15, row = t >> 4;
+    const bool row_ok = k < K, known = k < n_c, unknown = row_ok && !known;
+    const int kc = row_ok ? k : K - 1;
+    for (int s0 = 0; s0 < S; s0 += kSmallThreads / 16) {
+        const int s = s0 + row;
+        const bool col_ok = s < S;
+        const int sc = col_ok ? s : S - 1;
+        double Grow[16];
+#pragma unroll
+        for (int l = 0; l < 16; ++l) {
+            const int lc = l < K ? l : K - 1;
+            const int lo = kc < lc ? kc : lc, hi = kc < lc ? lc : kc;
+            const double v = m.gb[(hi * (hi + 1) / 2 + lo) * SP + sc];
+            Grow[l] = (row_ok && l < K) ? v : 0.0;
+        }
+        const double bk = row_ok ? m.gb[(n_pairs + kc) * SP + sc] : 0.0;
+        const double pur = purity[sc];
+        const double mass = known ? pur : 1.0 - pur;  // what this lane's vertex would put on row k
+        double a = row_ok ? m.a[kc * SP + sc] : 0.0;
+        for (int64_t it = 0; it < n_steps; ++it) {
+            double g4[4] = {-bk, 0.0, 0.0, 0.0};
+            gram_row_times_a(g4, a, Grow);
+            const double grad = (g4[0] + g4[1]) + (g4[2] + g4[3]);
+            double v1 = known ? grad : INFINITY, v2 = unknown ? grad : INFINITY;
+            int i1 = k, i2 = k;
+            argmin_step<1>(v1, i1, k); argmin_step<2>(v1, i1, k); argmin_step<4>(v1, i1, k); argmin_step<8>(v1, i1, k);
+            argmin_step<1>(v2, i2, k); argmin_step<2>(v2, i2, k); argmin_step<4>(v2, i2, k); argmin_step<8>(v2, i2, k);
+            const double gamma = 2.0 / (double)(it + 2);
+            const bool at_vertex = (known && k == i1) || (unknown && k == i2);
+            a = frank_wolfe_update(a, gamma, at_vertex ? mass : 0.0);
+        }
+        if (col_ok && row_ok) m.a[k * SP + s] = a;
+    }
+}
+
 }  // namespace
 
-template <int NU>
+template <int NU, bool PURITY>
 __global__ __launch_bounds__(kSmallThreads) void k_solve_small(SmallArgs a) {
     constexpr int NP = NU * (NU + 1) / 2;
     const int64_t b = blockIdx.x;
@@ -275,7 +340,8 @@ __global__ __launch_bounds__(kSmallThreads) void k_solve_small(SmallArgs a) {
         const double* alpha0 = a.alpha0 + b * K * S;
         for (int e = t; e < K * S; e += kSmallThreads) {
             const int k = e / S, s = e - k * S;
-            m.a[k * SP + s] = m.ap[k * SP + s] = alpha0[e];
+            if constexpr (PURITY) m.a[k * SP + s] = alpha0[e];
+            else m.a[k * SP + s] = m.ap[k * SP + s] = alpha0[e];
         }
         double u2 = 0.0, rt2 = 0.0, dmax = -INFINITY;
         for (int64_t i = t; i < N; i += kSmallThreads) {
@@ -316,7 +382,7 @@ __global__ __launch_bounds__(kSmallThreads) void k_solve_small(SmallArgs a) {
         for (int e = t; e < K * S; e += kSmallThreads) {
             const int k = e / S, s = e - k * S;
             m.a[k * SP + s] = ws_alpha[e];
-            m.ap[k * SP + s] = ws_alpha_prev[e];
+            if constexpr (!PURITY) m.ap[k * SP + s] = ws_alpha_prev[e];
         }
         __syncthreads();  // (the job tables)
         for (int e = t; e < n_known * S; e += kSmallThreads) {
@@ -333,7 +399,7 @@ __global__ __launch_bounds__(kSmallThreads) void k_solve_small(SmallArgs a) {
     int done = 0;
     for (int it = 0; it < a.n_run; ++it) {
         // the momentum ratios (a_{t-1} - 1) / a_t of both phases (:83-84, :95-96): they do not depend on the data
-        if (t == 0 || t == 64) {
+        if (t == 0 || (!PURITY && t == 64)) {
             double am = t == 0 ? a1 : a2;
             double* ratio = t == 0 ? ratio_u : ratio_h;
             for (int64_t q = 0; q < T2; ++q) {
@@ -344,7 +410,8 @@ __global__ __launch_bounds__(kSmallThreads) void k_solve_small(SmallArgs a) {
             m.sh[t == 0 ? 0 : 1] = am;
         }
         __syncthreads();
-        a1 = m.sh[0], a2 = m.sh[1];
+        a1 = m.sh[0];
+        if constexpr (!PURITY) a2 = m.sh[1];
 
         // ---- u phase (:81-90)
         const double cap_w = 0.9999 * sqrt(l_w_prev / l_w);
@@ -408,13 +475,15 @@ __global__ __launch_bounds__(kSmallThreads) void k_solve_small(SmallArgs a) {
         }
         if (T2 > 0) l_w_prev = l_w;
         u2 = block_sum(u2, m.red);  // (its barriers publish u to the workgroup)
-        l_h = (rt_norm2 + u2) * dsq;  // :212
+        if constexpr (!PURITY) l_h = (rt_norm2 + u2) * dsq;  // :212
 
         // ---- the u-dependent entries of the per-sample Grams
         gram_jobs(p, m, n_known, n_jobs);
 
-        // ---- alpha phase (:93-102): thread s owns column s
-        if (t < S) {
+        // ---- alpha phase: Frank-Wolfe under the purity constraint (:280-302), else (:93-102) thread s owns column s
+        if constexpr (PURITY) {
+            frank_wolfe_rows(m, a.purity, S, n_c, K, SP, n_pairs, T2);
+        } else if (t < S) {
             const int s = t;
             const double cap_h = 0.9999 * sqrt(l_h_prev / l_h);
             for (int64_t q = 0; q < T2; ++q) {
@@ -458,7 +527,7 @@ __global__ __launch_bounds__(kSmallThreads) void k_solve_small(SmallArgs a) {
     for (int e = t; e < K * S; e += kSmallThreads) {
         const int k = e / S, s = e - k * S;
         ws_alpha[e] = m.a[k * SP + s];
-        ws_alpha_prev[e] = m.ap[k * SP + s];
+        if constexpr (!PURITY) ws_alpha_prev[e] = m.ap[k * SP + s];
     }
     if (t == 0) {
         scal[kSmA1] = a1, scal[kSmA2] = a2, scal[kSmLw] = l_w, scal[kSmLwPrev] = l_w_prev, scal[kSmLh] = l_h;
@@ -480,27 +549,36 @@ size_t small_lds_bytes(int S, int K) {
     return doubles * sizeof(double) + (kJobShorts * sizeof(short) + 7) / 8 * 8;
 }
 
-template <int NU>
+template <int NU, bool PURITY>
 static hipError_t launch_nu(const SmallArgs& a, int64_t B, size_t lds, hipStream_t st) {
     static bool raised = false;  // more than 64 KB of dynamic LDS need the kernel's limit raised, once
     if (lds > 64 * 1024 && !raised) {
-        const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_solve_small<NU>),
+        const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_solve_small<NU, PURITY>),
                                                  hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
         if (e != hipSuccess) return e;
         raised = true;
     }
-    hipLaunchKernelGGL(k_solve_small<NU>, dim3((unsigned)B), dim3(kSmallThreads), lds, st, a);
+    hipLaunchKernelGGL((k_solve_small<NU, PURITY>), dim3((unsigned)B), dim3(kSmallThreads), lds, st, a);
     return hipGetLastError();
 }
 
 hipError_t launch_solve_small(const SmallArgs& a, int64_t B, hipStream_t st) {
     if (!small_supported(a.N, a.S, a.n_c, a.n_u, a.mode) || B < 1 || B > 0x7fffffff) return hipErrorInvalidValue;
     const size_t lds = small_lds_bytes(a.S, a.n_c + a.n_u);
+    if (a.purity != nullptr) {  // the purity variant: partial mode with a known block to hold at that mass
+        if (a.mode != DMF_MODE_PARTIAL || a.n_c < 1) return hipErrorInvalidValue;
+        switch (a.n_u) {
+            case 1: return launch_nu<1, true>(a, B, lds, st);
+            case 2: return launch_nu<2, true>(a, B, lds, st);
+            case 3: return launch_nu<3, true>(a, B, lds, st);
+            default: return launch_nu<4, true>(a, B, lds, st);
+        }
+    }
     switch (a.n_u) {
-        case 1: return launch_nu<1>(a, B, lds, st);
-        case 2: return launch_nu<2>(a, B, lds, st);
-        case 3: return launch_nu<3>(a, B, lds, st);
-        default: return launch_nu<4>(a, B, lds, st);
+        case 1: return launch_nu<1, false>(a, B, lds, st);
+        case 2: return launch_nu<2, false>(a, B, lds, st);
+        case 3: return launch_nu<3, false>(a, B, lds, st);
+        default: return launch_nu<4, false>(a, B, lds, st);
     }
 }
 

@@ -17,9 +17,18 @@ constexpr int64_t kSmallMaxElements = (int64_t)1 << 20;  // N S: bounds how long
 // default launch of 2 stays below 0.17 s there; the 350 x 10 example gets 64 iterations per launch.
 constexpr int64_t kSmallLaunchElements = (int64_t)1 << 21;
 constexpr int kSmallMinItersPerLaunch = 2, kSmallMaxItersPerLaunch = 64;
-inline int small_default_iters_per_launch(int64_t N, int64_t S) {
-    const int64_t q = kSmallLaunchElements / (N * S);
-    return (int)(q < kSmallMinItersPerLaunch ? kSmallMinItersPerLaunch : (q > kSmallMaxItersPerLaunch ? kSmallMaxItersPerLaunch : q));
+// The purity variant (dmf_solve_small_purity) is run with the command line's 500 inner steps, and there the row-local u phase
+// is what a launch spends its time on: measured at the same shapes with 500 inner steps (same tool,
+// profiles/small_batch_purity_bench.txt), one outer iteration takes 40 ms at 16384 x 64 (49 ms with 256 solves resident) and
+// 533 ms at 2^20 x 1 (551 ms with 16) -- about 0.5 us per row, whatever S.  Its default is therefore counted in rows:
+// kSmallPurityLaunchRows / N, at least 1: 2 iterations (0.10 s) at 16384 x 64, 64 for the 350 x 10 example, within 0.17 s per
+// launch up to about 3e5 rows.  Beyond that ONE outer iteration is longer than 0.17 s (0.55 s at 2^20 x 1) and a launch is
+// that one iteration: an outer iteration is not cut.
+constexpr int64_t kSmallPurityLaunchRows = (int64_t)1 << 15;
+inline int small_default_iters_per_launch(int64_t N, int64_t S, bool purity = false) {
+    const int64_t q = purity ? kSmallPurityLaunchRows / N : kSmallLaunchElements / (N * S);
+    const int64_t lo = purity ? 1 : kSmallMinItersPerLaunch;
+    return (int)(q < lo ? lo : (q > kSmallMaxItersPerLaunch ? kSmallMaxItersPerLaunch : q));
 }
 constexpr int kSmallThreads = 256;
 constexpr int kSmallChunk = 16;  // Gram accumulators per pass over the rows
@@ -54,6 +63,9 @@ struct SmallArgs {
     double* scal = nullptr;        // B x kSmallScalars
     long long* iters = nullptr;    // B
     int* done = nullptr;           // B
+    // S doubles or null.  Not null: the purity variant (mdwbssmf_deconv_p, deconvolution.py:306-337), whose alpha phase is
+    // Frank-Wolfe with mass purity[s] on the known block of sample s; alpha_prev and the second half of ratio are unused.
+    const double* purity = nullptr;
 };
 hipError_t launch_solve_small(const SmallArgs& a, int64_t B, hipStream_t st);
 

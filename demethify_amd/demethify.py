@@ -18,7 +18,8 @@ Deliberate differences from upstream, all flagged at run time:
     (nan, nan) where none did, instead of the percentiles by resampled position.
   * ``DEMETHIFY_BATCH=1`` (environment; default ``0``): ``--confidence`` replicates and ``--restart`` restarts of a small
     problem are solved many per kernel launch, one workgroup each, when the case is eligible
-    (bootstrap.batched_ineligible) and N x S is at most bootstrap.SMALL_BATCH_MAX_ELEMENTS; otherwise a one-line note says
+    (bootstrap.batched_ineligible) and N x S is at most bootstrap.SMALL_BATCH_MAX_ELEMENTS (with ``--purity``:
+    bootstrap.SMALL_BATCH_PURITY_MAX_ELEMENTS, the purity variant of the kernel); otherwise a one-line note says
     why not and the run takes the per-solve path.
   * ``--ic NAME [n [lo hi]]``: upstream sweeps the hard-coded range 1..25 (ic.py:171); two more values after the
     restart count restrict the sweep to lo..hi unknown types (``--ic BIC 5 2 12``).  Without them: 1..25, as upstream.
@@ -200,10 +201,12 @@ def main(argv=None):
         n_rows, n_samples = meth_f.shape
         reason = bootstrap_mod.batched_ineligible(
             n_u, n_rows, n_samples, ref.shape[1] if args.ref else 0, args.init, args.purity,
-            L.DMF_MODE_PARTIAL if args.ref else L.DMF_MODE_UNSUPERVISED, None, align, profile_rows)
-        if reason is None and n_rows * n_samples > bootstrap_mod.SMALL_BATCH_MAX_ELEMENTS:
-            reason = (f"{n_rows} x {n_samples} elements are more than SMALL_BATCH_MAX_ELEMENTS = "
-                      f"{bootstrap_mod.SMALL_BATCH_MAX_ELEMENTS}")
+            L.DMF_MODE_PARTIAL if args.ref else L.DMF_MODE_UNSUPERVISED, None, align, profile_rows, purity_batched=True)
+        # (--purity has a gate of its own: its batched kernel was measured on its own)
+        gate_name = "SMALL_BATCH_PURITY_MAX_ELEMENTS" if args.purity else "SMALL_BATCH_MAX_ELEMENTS"
+        gate = getattr(bootstrap_mod, gate_name)
+        if reason is None and n_rows * n_samples > gate:
+            reason = f"{n_rows} x {n_samples} elements are more than {gate_name} = {gate}"
         if reason is not None and rank == 0:
             print(f"Note: DEMETHIFY_BATCH=1 is not used for {what}: {reason}; taking the per-solve path.")
         return reason is None
@@ -212,7 +215,8 @@ def main(argv=None):
         batched = batch_route("--confidence", align=not args.ref and n_u >= 2, profile_rows=ci_rows)
         bt_ci(args.confidence[0], args.confidence[1], n_u, meth_f, counts, ref, args.init, args.iterations[0],
               args.iterations[1], args.termination, header if args.ref else [], outdir, args.methfreq, args.purity,
-              args.seed, materialize=False, anchor=anchor, profile_rows=ci_rows, batched=batched)
+              args.seed, materialize=False, anchor=anchor, profile_rows=ci_rows, batched=batched,
+              batched_purity=batched and bool(args.purity))
 
     if args.confidence and args.ref:
         bootstrap()
@@ -301,12 +305,17 @@ def main(argv=None):
                         seed_k = shard.restart_seed(args.seed, k)
                         if unsupervised:
                             inits.append(_init_unsupervised(args.init, meth_f, n_u, seed_k))
+                        elif purity is not None:
+                            u0, _, a0 = init_BSSMF_md_p(args.init, meth_f, counts, ref, n_u, purity, rb_alg=wls_intercept,
+                                                        seed=seed_k, _stack=False)
+                            inits.append((u0, a0))
                         else:
                             u0, _, a0 = init_BSSMF_md(args.init, meth_f, counts, ref, n_u, rb_alg=wls_intercept, seed=seed_k,
                                                       _stack=False)
                             inits.append((u0, a0))
                     parts.append(problem.solve_many(np.stack([u0 for u0, _ in inits]), np.stack([a0 for _, a0 in inits]), mode,
-                                                    args.iterations[0], args.iterations[1], args.termination)[:3])
+                                                    args.iterations[0], args.iterations[1], args.termination,
+                                                    purity=None if unsupervised else purity)[:3])
                 return tuple(np.concatenate([part[j] for part in parts]) for j in range(3))
 
             shapes = ((meth_f.shape[0], n_u), (K, meth_f.shape[1]))

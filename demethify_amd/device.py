@@ -618,14 +618,19 @@ class Problem:
             t_dev.close()
         return u0
 
-    def solve_many(self, u0s, alpha0s, mode, n_iter1, n_iter2, tol, idx=None, iters_per_launch=0):
+    def solve_many(self, u0s, alpha0s, mode, n_iter1, n_iter2, tol, idx=None, iters_per_launch=0, purity=None):
         """B independent solves of this problem in one call, one workgroup per solve (dmf_solve_small) ->
         (u[B, N, n_u], alpha[B, K, S], cost[B], iters[B]).  ``u0s`` (B, N, n_u) and ``alpha0s`` (B, K, S): the starting
         points; ``idx`` (B, N) integers or None: row i of solve b is row ``idx[b, i]`` of the problem (a bootstrap
         replicate), None = the problem's own rows.  ``cost[b]`` is cost_f_w of solve b's final iterate, ``iters[b]`` its
         outer iterations.  ``iters_per_launch``: outer iterations per kernel launch, 0 = the library's default; the results
         do not depend on it.  Host arrays in, fresh host arrays out; nothing is mutated.  Shapes outside
-        ``small_solve_supported`` raise (DMF_ERR_UNSUPPORTED): there is no fall-back to the per-solve path here."""
+        ``small_solve_supported`` raise (DMF_ERR_UNSUPPORTED): there is no fall-back to the per-solve path here.
+
+        ``purity`` (S fractions, shared by the B solves; None = no constraint): the purity-constrained solve
+        (dmf_solve_small_purity, ``mdwbssmf_deconv_p``) -- every sample's known block keeps mass ``purity[s]`` and its unknown
+        block ``1 - purity[s]``, the alpha phase is Frank-Wolfe.  Partial mode on a problem with a reference only, and a
+        vector of S values: anything else raises ValueError before any device call."""
         u0s = np.ascontiguousarray(u0s, dtype=np.float64)
         alpha0s = np.ascontiguousarray(alpha0s, dtype=np.float64)
         if u0s.ndim != 3 or u0s.shape[1] != self.N:
@@ -638,10 +643,24 @@ class Problem:
             idx = np.ascontiguousarray(idx, dtype=np.int64)
             if idx.shape != (B, self.N):
                 raise ValueError(f"idx shape {idx.shape} != {(B, self.N)}")
+        if purity is not None:
+            purity = np.ascontiguousarray(purity, dtype=np.float64)
+            if purity.shape != (self.S,):
+                raise ValueError(f"purity needs one value per sample ({self.S}), got shape {purity.shape}")
+            if int(mode) != L.DMF_MODE_PARTIAL:
+                raise ValueError("a purity constraint needs the partial-reference mode (DMF_MODE_PARTIAL)")
+            if self.n_c < 1:
+                raise ValueError("a purity constraint needs a reference: there is no known block to hold at that mass")
         u = np.empty((B, self.N, n_u), dtype=np.float64)
         alpha = np.empty((B, K, self.S), dtype=np.float64)
         cost = np.empty(B, dtype=np.float64)
         iters = np.empty(B, dtype=np.int64)
+        if purity is not None:
+            L.check(self._lib.dmf_solve_small_purity(self.ctx._h, self._h, B, _ptr(idx), _ptr(u0s), _ptr(alpha0s), _ptr(purity),
+                                                     n_u, int(mode), int(n_iter1), int(n_iter2), float(tol),
+                                                     int(iters_per_launch), 0, _ptr(u), _ptr(alpha), _ptr(cost), _ptr(iters)),
+                    "dmf_solve_small_purity")
+            return u, alpha, cost, iters
         L.check(self._lib.dmf_solve_small(self.ctx._h, self._h, B, _ptr(idx), _ptr(u0s), _ptr(alpha0s), n_u, int(mode),
                                           int(n_iter1), int(n_iter2), float(tol), int(iters_per_launch), 0, _ptr(u),
                                           _ptr(alpha), _ptr(cost), _ptr(iters)), "dmf_solve_small")

@@ -458,6 +458,21 @@ int dmf_solve_small(dmf_context* ctx, const dmf_problem* p, int64_t B, const int
                     const double* alpha0, int64_t n_u, int mode, int64_t n_iter1, int64_t n_iter2, double tol,
                     int64_t iters_per_launch, int flags, double* out_u, double* out_alpha, double* out_cost,
                     int64_t* out_iters);
+/* dmf_solve_small_purity: the same B solves under the purity constraint -- mdwbssmf_deconv_p
+ * (demethify/deconvolution.py:306-337) with the Frank-Wolfe alpha phase frank_wolfe_nmf (:280-302), i.e.
+ * deconvolution.py:280-302,306-337.  Set-up: a1 = 1, u_ = u0, d = max(counts)^2, l_w, the cost; there is no a2, no l_h and no
+ * alpha_.  Per outer iteration the u phase as above, then per sample n_iter2 Frank-Wolfe steps restarting at k = 0 from the
+ * current alpha: grad = G_s a - b_s, the first-index argmin over the known rows and over the unknown rows, mass purity[s] on
+ * the known vertex and 1 - purity[s] (taken in f64) on the unknown one, gamma = 2 / (k + 2),
+ * a = (1 - gamma) a + gamma vertex with every product and the sum rounded; then l_w, the streaming cost and the stop test.
+ * purity: S doubles shared by all B solves, a host array, or a device array with DMF_PTR_DEVICE in flags.  Everything else
+ * is dmf_solve_small's: arguments, envelope (dmf_solve_small_supported), workspace, idx, determinism.  DMF_MODE_PARTIAL only
+ * (another mode: DMF_ERR_UNSUPPORTED); a null purity or a problem without a reference (n_c < 1): DMF_ERR_BAD_ARG -- all
+ * before the context is touched.  A masked problem is refused as by dmf_solve_small. */
+int dmf_solve_small_purity(dmf_context* ctx, const dmf_problem* p, int64_t B, const int64_t* idx, const double* u0,
+                           const double* alpha0, const double* purity, int64_t n_u, int mode, int64_t n_iter1,
+                           int64_t n_iter2, double tol, int64_t iters_per_launch, int flags, double* out_u,
+                           double* out_alpha, double* out_cost, int64_t* out_iters);
 
 /* ---- input tables (host side) ---------------------------------------------------------------
  * demethify/demethify.py:103-143 reads each sample file with pandas.read_csv and stacks its `percent_modified` and
