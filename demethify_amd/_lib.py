@@ -65,6 +65,7 @@ SIGNATURES = {
     "dmf_context_set_generic": (C.c_int, [_p, C.c_int]),
     "dmf_context_set_x16": (C.c_int, [_p, C.c_int]),
     "dmf_context_set_rowpass_pair": (C.c_int, [_p, C.c_int]),
+    "dmf_context_set_rowpass_defer_c": (C.c_int, [_p, C.c_int]),
     "dmf_context_set_stop_confirmation": (C.c_int, [_p, C.c_int]),
     "dmf_problem_create": (C.c_int, [_p, _i64, _i64, _i64, _p, _p, _p, C.c_int, C.POINTER(_p)]),
     "dmf_problem_gather": (C.c_int, [_p, _p, _p, _i64, C.POINTER(_p)]),
@@ -111,6 +112,7 @@ SIGNATURES = {
     "dmf_solver_u_phase_describe": (C.c_int, [_p, _i64, C.c_int, C.c_char_p, _i64]),
     "dmf_solver_stop_info": (C.c_int, [_p, C.POINTER(C.c_int), C.POINTER(_i64), C.POINTER(_i64), _dbl_p]),
     "dmf_solver_rowpass_launches": (C.c_int, [_p, C.POINTER(_i64), C.POINTER(_i64)]),
+    "dmf_solver_rowpass_schedule_counts": (C.c_int, [_p, C.POINTER(_i64), C.POINTER(_i64), C.POINTER(_i64)]),
     "dmf_table_scan": (C.c_int, [C.c_char_p, C.c_char, C.POINTER(_i64), C.POINTER(C.c_int), C.POINTER(C.c_int),
                                  C.POINTER(C.c_int)]),
     "dmf_table_read": (C.c_int, [C.c_char_p, C.c_char, C.c_int, C.c_int, _i64, _p, _i64, C.c_double, _p, _i64, C.c_int]),

@@ -57,6 +57,7 @@ struct dmf_context {
                             // 3 separate MFMA row pass + one-pass Gram (the pieces the fused kernel is made of)
     bool x16 = true;        // dmf_context_set_x16: problems created from now on get the X16 copy when their data allow
     bool rowpass_pair = true;  // dmf_context_set_rowpass_pair: solvers created from now on run the row pass two blocks per phase B
+    bool rowpass_defer_c = true;  // dmf_context_set_rowpass_defer_c: ... with phase C deferred where that applies
     double* scratch = nullptr;  // 4096 doubles of reduction scratch
     hipMemPool_t pool = nullptr;  // the context's own stream-ordered pool (the device's default pool is not touched)
     std::unordered_map<void*, size_t> live;                // large blocks handed out by pool_alloc (size by address)
@@ -264,6 +265,7 @@ struct dmf_solver {
     double cf_stream = 0.0;
     long long cf_stream_iter = -1;
     long long n_rowpass = 0, n_rowpass_pair = 0;  // k_rowpass_v2 launches so far / of them on the pair schedule
+    long long n_rowpass_defer = 0;                // ... / of those with phase C deferred
     long long n_confirmed = 0, n_unconfirmed = 0;  // stop tests decided on streaming costs / on the Gram form inside the band
     // the iterate and the u phases' scratch as the launch wrappers take them (dmf_internal.h)
     dmf::IterateView iterate() const {

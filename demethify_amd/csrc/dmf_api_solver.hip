@@ -167,15 +167,16 @@ static int enqueue_outer_iteration(dmf_solver* s, int n_iter2) {
         // the u phase and b_u, then the exact
         // integer-matrix-core GEMM for the u-dependent Gram entries on the 8-bit count planes.
         int grid = 0;
-        bool paired = false;
+        bool paired = false, deferred = false;
         {
             FamilyScope scope(ctx, DMF_KERNEL_ROWPASS);
             dmf::ProblemView pv = p->view();
             if (!s->key.x16) pv.X16 = nullptr;
             HIP_TRY(dmf::launch_rowpass_v2(pv, s->iterate(), n_iter2, s->scratch(), &grid, s->key.rowpass_pair, &paired,
-                                           ctx->stream));
+                                           s->key.rowpass_defer_c && s->key.x_byte, &deferred, ctx->stream));
             ++s->n_rowpass;
             s->n_rowpass_pair += paired ? 1 : 0;
+            s->n_rowpass_defer += deferred ? 1 : 0;
         }
         return enqueue_gram_i8_tail(s, plan.alpha, n_iter2, grid);
     }
@@ -325,6 +326,8 @@ static int solver_setup(dmf_solver* s, const double* u0, const double* alpha0, i
     key.SD = p->SD;
     key.x16 = key.nd > 0 && p->X16 != nullptr;
     key.rowpass_pair = ctx->rowpass_pair;
+    key.rowpass_defer_c = ctx->rowpass_defer_c;
+    key.x_byte = key.x16 && p->h_consts[kIntCountMax] <= 255.0;  // (0 <= x <= d for every element of X16)
     key.level = ctx->generic_level;
     key.d_f32_exact = p->d_f32_exact;
     key.rtp_present = n_c == 0 || p->Rtp != nullptr;
@@ -790,6 +793,14 @@ int dmf_solver_rowpass_launches(const dmf_solver* s, int64_t* total, int64_t* pa
     if (s == nullptr) return DMF_ERR_BAD_ARG;
     if (total) *total = s->n_rowpass;
     if (paired) *paired = s->n_rowpass_pair;
+    return DMF_OK;
+}
+
+int dmf_solver_rowpass_schedule_counts(const dmf_solver* s, int64_t* total, int64_t* paired, int64_t* deferred) {
+    if (s == nullptr) return DMF_ERR_BAD_ARG;
+    if (total) *total = s->n_rowpass;
+    if (paired) *paired = s->n_rowpass_pair;
+    if (deferred) *deferred = s->n_rowpass_defer;
     return DMF_OK;
 }
 

@@ -375,7 +375,7 @@ int rowpass_v2_grid(int64_t N, int S);
 // D16 -- or, when p.X16 is not null, of X16 and D16 (V is not read).  pair: two blocks per phase B where the X16 form allows
 // it (rowpass_v2_pair_fits); the same results bit for bit.  *paired_out (may be null): whether the pair schedule was launched
 hipError_t launch_rowpass_v2(const ProblemView& p, const IterateView& it, int n_iter2, const UScratch& scratch, int* grid_out,
-                             bool pair, bool* paired_out, hipStream_t st);
+                             bool pair, bool* paired_out, bool defer_c, bool* deferred_out, hipStream_t st);
 // the X16 row pass can run two blocks per phase B at this shape: 2..4 waves, and the grid's workgroups per CU fit the LDS
 bool rowpass_v2_pair_fits(int S, int n_u, int n_iter2);
 bool gram_i8_supported(int n_c, int n_u, int ND, int64_t N, int SD);

@@ -46,12 +46,13 @@ typedef int v4i __attribute__((ext_vector_type(4)));
 // Diagnostic build only (tools/rowpass2_probe.hip defines DMF_STAMPS): per-wave cycle sums of the kernel's segments
 // go to a debug buffer of their own; the product build compiles none of it.
 #ifdef DMF_STAMPS
-#define DMF2_STAMP_DECL unsigned long long st_last = dmf2_stamp(), st_seg[16] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+#define DMF2_NSTAMP 20  // (16..19: the deferred-C schedule's segments of a wave's phase-C cycles)
+#define DMF2_STAMP_DECL unsigned long long st_last = dmf2_stamp(), st_seg[DMF2_NSTAMP] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
 #define DMF2_STAMP(i) { const unsigned long long st_now = dmf2_stamp(); st_seg[i] += st_now - st_last; st_last = st_now; }
 // (slot 15: the wave's HW_ID register -- SIMD in bits 5:4 -- so the probe can see where the waves sit)
 #define DMF2_STAMP_FLUSH                                                                                        \
     st_seg[15] = __builtin_amdgcn_s_getreg(4 | (31 << 11));                                                     \
-    if (lane == 0) for (int i_ = 0; i_ < 16; ++i_) stamps_out[((size_t)blockIdx.x * 4 + wave) * 16 + i_] = st_seg[i_];
+    if (lane == 0) for (int i_ = 0; i_ < DMF2_NSTAMP; ++i_) stamps_out[((size_t)blockIdx.x * 4 + wave) * DMF2_NSTAMP + i_] = st_seg[i_];
 __device__ __forceinline__ unsigned long long dmf2_stamp() {
     unsigned long long t;
     __builtin_amdgcn_sched_barrier(0);
@@ -74,6 +75,12 @@ __device__ __forceinline__ unsigned long long dmf2_stamp() {
 #ifndef DMF_V2_STAGGER
 #define DMF_V2_STAGGER 12  // x 64 cycles: how long the waves that do not run phase B hold back their prefetch
 #endif
+#ifndef DMF_V2_DEFER_PRIO
+#define DMF_V2_DEFER_PRIO 1  // s_setprio of the deferred phase C (phase B runs at 3, the tile stores at 1)
+#endif
+#ifndef DMF_V2_STAGGER_DEFER
+#define DMF_V2_STAGGER_DEFER 0  // the same on the deferred-C schedule, whose other waves are not idle
+#endif
 
 namespace {
 constexpr int kRowV = 66;  // V tile row: 64 samples + 16 B pad (f64)
@@ -82,6 +89,9 @@ constexpr int kTileVBytes2 = 16 * kRowV * 8;
 constexpr int kTileDBytes2 = 16 * kRowD * 2;
 constexpr int kTileBytes2 = kTileVBytes2 + kTileDBytes2;  // one column group: V (f64), counts (u16, as they arrive)
 constexpr int kTileBytesX = 2 * kTileDBytes2;               // X16 form: counts and methylated counts, both u16
+constexpr int kRingBlockBytes = 16 * 64;                    // deferred-C schedule: a block's x as bytes, 16 rows x 64 samples
+constexpr int kRingBytes = 6 * kRingBlockBytes;             // ... a wave's ring: three pairs of blocks
+constexpr int kDeferUbufSets = 6;                           // ... and the workgroup's u of three pairs
 }  // namespace
 
 template <int NU, bool AT_PREV>
@@ -125,7 +135,11 @@ __device__ __forceinline__ void inner_steps_unrolled(double& uu, double& up, dou
 // fma(d, -Rt a1, x), phase C multiplies u by x -- and reads 4 bytes per element instead of 10.  V is not read.
 // PAIR (XS, MAXW = 4, NW >= 2, launched where rowpass_v2_pair_fits): two blocks per barrier cycle, their phases B at the
 // same time on two waves -- see the block loop.  Each block of a pair has its own tile, slot and ubuf set.
-template <int NKC, int NU, int MAXW = 4, bool XS = false, bool PAIR = false>
+// DEFER_C (PAIR, four waves, every x <= 255, launched where rowpass_v2_defer_fits): a wave runs phase C only in the barrier
+// cycles in which it is not one of the two phase-B waves, for the two pairs then pending, between barriers X and Y; x
+// goes from the staging registers into a ring of three pairs per wave as BYTES and is kept nowhere else (phase A reads
+// it there too: no x tile), u waits in ubuf sets of three pairs -- see the block loop.
+template <int NKC, int NU, int MAXW = 4, bool XS = false, bool PAIR = false, bool DEFER_C = false>
 __global__ __launch_bounds__(64 * MAXW, MAXW == 4 ? 2 : 1) void k_rowpass_v2(
     const double* __restrict__ V, const unsigned short* __restrict__ D16, const unsigned short* __restrict__ X16, int SD,
     const double* __restrict__ Rtp,
@@ -138,7 +152,9 @@ __global__ __launch_bounds__(64 * MAXW, MAXW == 4 ? 2 : 1) void k_rowpass_v2(
     ) {
     static_assert(NU >= 1 && NU <= 4, "one phase-B pass per block, 4x4x4 MFMA for the c product");
     static_assert(!PAIR || (XS && MAXW == 4), "the pair schedule: X16 form, two workgroups per CU");
-    constexpr int NSET = PAIR ? 2 : 1;  // tile / slot / ubuf sets: blocks in flight per barrier cycle
+    static_assert(!DEFER_C || PAIR, "the deferred-C schedule is a pair schedule");
+    constexpr int NSET = PAIR ? 2 : 1;  // tile / slot sets: blocks in flight per barrier cycle
+    constexpr int NUB = DEFER_C ? kDeferUbufSets : NSET;  // ubuf sets (DEFER_C: pair p's blocks in sets 2 (p % 3), + 1)
     constexpr int NCT = 4 * NKC;
     constexpr int NP = NU * (NU + 1) / 2;
     // a (row, unknown j) slot of a wave's partial sums: { c_j, M_jj, M_j(j+1), .. (round the row) } pre-scaled by 1 / l_w (M negated),
@@ -153,13 +169,14 @@ __global__ __launch_bounds__(64 * MAXW, MAXW == 4 ? 2 : 1) void k_rowpass_v2(
     const int lane = threadIdx.x & 63;
     const int wcol0 = wave * 64;
 
-    // LDS carve-up (doubles unless noted): beta[n_iter2 (even)] | ubuf[NSET][16][NU] | red[NSET][MAXW][16][NU][SLOT] |
+    // LDS carve-up (doubles unless noted): beta[n_iter2 (even)] | ubuf[NUB][16][NU] | red[NSET][MAXW][16][NU][SLOT] |
     //   u2[MAXW] | tiles[NSET][NW]{ V f64 [16][66], counts u16 [16][72] }  (XS: { counts u16 [16][72], x u16 [16][72] })
+    //   (DEFER_C: tiles hold the counts only) | ring[NW][3 pairs][2 blocks]{ x u8 [16][64] }
     double* __restrict__ beta_tab = lds_dyn;
     double* __restrict__ ubuf = beta_tab + ((n_iter2 + 1) & ~1);
-    double* __restrict__ red = ubuf + NSET * 16 * NU;
+    double* __restrict__ red = ubuf + NUB * 16 * NU;
     double* __restrict__ u2red = red + NSET * MAXW * NV * 16;
-    constexpr int TB = XS ? kTileBytesX : kTileBytes2;
+    constexpr int TB = XS ? (DEFER_C ? kTileDBytes2 : kTileBytesX) : kTileBytes2;
     char* __restrict__ tile = reinterpret_cast<char*>(u2red + MAXW) + (size_t)wave * TB;  // (this wave's tile of set 0)
     // the counts stay u16 in the tile (LINEAR rows: no piece swap): phase A and phase C convert what they read, the integer
     // product builds its balanced byte digits from 32 bytes of a row -- converting at the tile store (f32 copy + two digit
@@ -173,6 +190,15 @@ __global__ __launch_bounds__(64 * MAXW, MAXW == 4 ? 2 : 1) void k_rowpass_v2(
         char* const t = tile + (size_t)set * NW * TB;
         unsigned short* const d = reinterpret_cast<unsigned short*>(t + (XS ? 0 : kTileVBytes2));
         return BlockTile{reinterpret_cast<double*>(t), d, d + 16 * kRowD};
+    };
+    // (DEFER_C) this wave's x ring behind the tiles: block b of pair p in slot 2 (p % 3) + b, from its tile store in cycle p to
+    // its last phase C in cycle p + 2 (the drain at the latest); pair p + 3 follows behind that in this wave's own program
+    // order.  A slot's 16 rows of 64 bytes stand in the order (row & 3, row >> 2), and row r's 16 dwords are rotated by
+    // 4 (r & 3): the four rows R, R + 4, R + 8, R + 12 that one phase-C read touches are then 64 consecutive dwords, and the
+    // 16 rows x 4 dwords of one phase-A read fall into 64 different banks -- no padding, no bank conflict on either.
+    unsigned int* const ring = reinterpret_cast<unsigned int*>(tile + (size_t)(NSET * NW - wave) * TB + (size_t)wave * kRingBytes);
+    auto ring_at = [&](int slot, int row, int dword) {
+        return ring + slot * (kRingBlockBytes / 4) + (4 * (row & 3) + (row >> 2)) * 16 + ((dword + 4 * (row & 3)) & 15);
     };
 
     // momentum coefficients of the inner steps (deconvolution.py:83-85): from the host's row of ratios when there is one
@@ -361,9 +387,16 @@ __global__ __launch_bounds__(64 * MAXW, MAXW == 4 ? 2 : 1) void k_rowpass_v2(
     double* __restrict__ const mine_m2 = red + (size_t)wave * NV * 16 + (4 * q * NU + pj) * SLOT + 1 + (pl - pj) % NU;
 
     // ---- tile store of staging set `set` into the wave's tile of that set (waits for the prefetched loads)
-    auto tile_store = [&](int set) {
+    auto tile_store = [&](int set, int rslot) {
         const BlockTile T = block_tile(set);
-        if constexpr (XS) {
+        if constexpr (DEFER_C) {
+            // x as bytes (the low byte of each u16: every x <= 255) into ring slot rslot: two dwords of row 8 i + d_row
+#pragma unroll
+            for (int i = 0; i < 2; ++i)
+                *reinterpret_cast<v2u*>(ring_at(rslot, 8 * i + d_row, 2 * (lane & 7))) =
+                    v2u{__builtin_amdgcn_perm(px[set][i].y, px[set][i].x, 0x06040200u),
+                        __builtin_amdgcn_perm(px[set][i].w, px[set][i].z, 0x06040200u)};
+        } else if constexpr (XS) {
 #pragma unroll
             for (int i = 0; i < 2; ++i) *reinterpret_cast<v4u*>(T.X + (8 * i + d_row) * kRowD + d_col) = px[set][i];
         } else {
@@ -378,7 +411,7 @@ __global__ __launch_bounds__(64 * MAXW, MAXW == 4 ? 2 : 1) void k_rowpass_v2(
     };
 
     // ---- phase A of the block in tile set `set` (R_trunc rows: staging set `set`) -> partial sums in slot set `set`
-    auto phase_a = [&](int set, int st_a, int st_p) {
+    auto phase_a = [&](int set, int rslot, int st_a, int st_p) {
         const BlockTile T = block_tile(set);
         const double* __restrict__ const tileV = T.V;
         unsigned short* __restrict__ const tileD = T.D;
@@ -395,7 +428,9 @@ __global__ __launch_bounds__(64 * MAXW, MAXW == 4 ? 2 : 1) void k_rowpass_v2(
         };
         using Strip = std::conditional_t<XS, StripX, StripV>;
         auto load_strip = [&](int t, Strip& R) {
-            if constexpr (XS) {
+            if constexpr (DEFER_C) {
+                R.xw.x = *ring_at(rslot, m16, 4 * t + q);  // the piece's four x as bytes
+            } else if constexpr (XS) {
                 R.xw = *reinterpret_cast<const v2u*>(tileX + m16 * kRowD + t * 16 + 4 * q);
             } else {
                 const double* __restrict__ tv = tileV + m16 * kRowV + t * 16 + 4 * qs;
@@ -415,7 +450,8 @@ __global__ __launch_bounds__(64 * MAXW, MAXW == 4 ? 2 : 1) void k_rowpass_v2(
             const v4d d = {(double)(R.dw.x & 0xFFFFu), (double)(R.dw.x >> 16), (double)(R.dw.y & 0xFFFFu), (double)(R.dw.y >> 16)};
             v4d w;
             if constexpr (XS) {  // w = d (v - Rt a1) = fma(d, -Rt a1, x)
-                const v4d x = {(double)(R.xw.x & 0xFFFFu), (double)(R.xw.x >> 16), (double)(R.xw.y & 0xFFFFu), (double)(R.xw.y >> 16)};
+                const v4d x = DEFER_C ? v4d{(double)(R.xw.x & 0xFFu), (double)((R.xw.x >> 8) & 0xFFu), (double)((R.xw.x >> 16) & 0xFFu), (double)(R.xw.x >> 24)}
+                                      : v4d{(double)(R.xw.x & 0xFFFFu), (double)(R.xw.x >> 16), (double)(R.xw.y & 0xFFFFu), (double)(R.xw.y >> 16)};
 #pragma unroll
                 for (int r = 0; r < 4; ++r) w[r] = fma(d[r], e[r], x[r]);
             } else {
@@ -513,9 +549,9 @@ __global__ __launch_bounds__(64 * MAXW, MAXW == 4 ? 2 : 1) void k_rowpass_v2(
         DMF2_STAMP(st_p)  // partials
     };
 
-    // ---- phase B of the block at row0 (its partial sums in slot set `set`, its u in ubuf set `set`): row-local inner
+    // ---- phase B of the block at row0 (its partial sums in slot set `set`, its u into ubuf set `uset`): row-local inner
     // iterations, lane = (row, unknown j); c and M pre-scaled by 1 / l_w
-    auto phase_b = [&](int set, int64_t row0, double uu0, double up0) {
+    auto phase_b = [&](int uset, int set, int64_t row0, double uu0, double up0) {
         __builtin_amdgcn_s_setprio(3);  // a dependent chain on the workgroup's critical path
         DMF2_SUB_BEGIN
         const bool ok = b_lane && row0 + rl < N;
@@ -575,7 +611,7 @@ __global__ __launch_bounds__(64 * MAXW, MAXW == 4 ? 2 : 1) void k_rowpass_v2(
             }
         }
         DMF2_SUB(9)
-        if (b_lane) ubuf[set * 16 * NU + rl * NU + jb] = ok ? uu : 0.0;  // rows beyond N: phase C multiplies them by zero counts
+        if (b_lane) ubuf[uset * 16 * NU + rl * NU + jb] = ok ? uu : 0.0;  // rows beyond N: phase C multiplies them by zero counts
         if (ok) {
             // (buffer stores, like the loads: scalar base of the block + this lane's constant offset)
             const __amdgpu_buffer_rsrc_t ru = __builtin_amdgcn_make_buffer_rsrc((void*)(u + row0 * NU), 0, span((N - row0) * NU * 8), 0x00020000);
@@ -626,18 +662,51 @@ __global__ __launch_bounds__(64 * MAXW, MAXW == 4 ? 2 : 1) void k_rowpass_v2(
 #endif
     };
 
-    // The block loop: NSET blocks per barrier cycle.  One block (NSET = 1): its phase B runs on wave s % NW while the
+    // ---- (DEFER_C) phase C of block `b01` of pair `pp`: x from the ring, u from the pair's ubuf sets.  The same products in
+    // the same order as phase_c on every sample; lane (q, m16) reads ONE dword per row -- samples 4 m16 .. 4 m16 + 3 -- so
+    // bu[t] is b_u[unknown q][sample 4 m16 + t] on this schedule (the slab write-out below knows), and a block takes four
+    // tile reads instead of sixteen.
+    auto phase_c_ring = [&](int pp, int b01) {
+        const int rslot = 2 * (pp % 3) + b01;
+        const double* __restrict__ const ub = ubuf + (2 * (pp % 3) + b01) * 16 * NU;
+        unsigned int xw[4];
+        double ua[4];
+#pragma unroll
+        for (int R = 0; R < 4; ++R) {
+            xw[R] = *ring_at(rslot, R + c_row, m16);
+            ua[R] = (m16 & 3) < NU ? ub[(R + c_row) * NU + (m16 & 3)] : 0.0;
+        }
+#pragma unroll
+        for (int R = 0; R < 4; ++R)
+#pragma unroll
+            for (int t = 0; t < 4; ++t)
+                bu[t] = __builtin_amdgcn_mfma_f64_4x4x4f64(ua[R], (double)((xw[R] >> (8 * t)) & 0xFFu), bu[t], 0, 0, 0);
+    };
+
+    // The block loop: NSET blocks per barrier cycle. One block (NSET = 1): its phase B runs on wave s % NW while the
     // other waves wait at barrier Y.  A pair (NSET = 2): blocks s and s + 1 run their phases A and C one after the other
     // on every wave, their phases B at the same time on waves s % NW and (s + 1) % NW (different waves for NW >= 2, so
     // different SIMDs).  Each block keeps its own tile, slot and ubuf set, the wave and the order of every sum stay those
     // of one block at a time (phase C adds block s before block s + 1), so the results are the same bit for bit.  A
     // workgroup with an odd number of blocks runs its last one alone.
+    // Deferred C (DEFER_C, four waves): the phase-B waves of cycle p = s / 2 are {0, 1} for even p and {2, 3} for odd p.  The
+    // OTHER two run, between barriers X and Y, phase C of the pairs p - 2 and p - 1 in block order -- both complete pairs,
+    // whose phases B ended before an earlier barrier Y -- and nothing follows barrier Y.  Every wave so runs phase C in every
+    // second cycle, for every pair once and in order, into the same accumulators: the same sums bit for bit.  Pair p's x
+    // stands in ring slots 2 (p % 3), + 1 from its tile store (the slots' former pair p - 3 was last read in cycle p - 1, by
+    // this wave itself); pair p's u stands in ubuf sets 2 (p % 3), + 1
+    // from its phase B until phase B of pair p + 3, two barriers behind its last reader in cycle p + 2.  What is pending after
+    // the last cycle -- its pair, and the one before on the waves that ran its phase B -- is drained behind the loop.
+    // (tests/rowpass_schedule_model.py walks this schedule for every block count.)
     for (int s = 0; s < nk; s += NSET) {
         const bool has2 = PAIR && s + 1 < nk;
         const int64_t blk = blockIdx.x + (int64_t)s * gridDim.x;
+        const int cyc = s >> 1;                                    // (DEFER_C)
+        const bool b_role = !DEFER_C || (wave >> 1) == (cyc & 1);  // (DEFER_C) may run a phase B in this cycle
         __builtin_amdgcn_s_setprio(1);
-        tile_store(0);
-        if (has2) tile_store(1);
+        const int rs0 = 2 * (cyc % 3);  // (DEFER_C) ring slots = ubuf sets of this cycle's blocks: rs0, rs0 + 1
+        tile_store(0, rs0);
+        if (has2) tile_store(1, rs0 + 1);
         const int bset = pair_set(s);
         const bool my_turn = bset == 1 || wave == s % NW;
         // the u / u_ of this wave's own block arrived with the tiles (the next prefetch reuses pu / pup before phase B runs)
@@ -646,8 +715,8 @@ __global__ __launch_bounds__(64 * MAXW, MAXW == 4 ? 2 : 1) void k_rowpass_v2(
         __builtin_amdgcn_wave_barrier();
         __builtin_amdgcn_s_setprio(0);
         DMF2_STAMP(0)  // tile stores (vmcnt wait for the prefetch)
-        phase_a(0, 1, 2);
-        if (has2) phase_a(1, 11, 12);
+        phase_a(0, rs0, 1, 2);
+        if (has2) phase_a(1, rs0 + 1, 11, 12);
         // (a bare barrier behind an LDS-only wait: __syncthreads() would also drain vmcnt)
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
         __builtin_amdgcn_s_barrier();  // ---- barrier X
@@ -658,7 +727,11 @@ __global__ __launch_bounds__(64 * MAXW, MAXW == 4 ? 2 : 1) void k_rowpass_v2(
         // two branches the register allocator gave them different destinations and put copies -- and the waits for the
         // data -- behind one of them.)
 #ifndef DMF_V2_NO_STAGGER
-        if (!my_turn) __builtin_amdgcn_s_sleep(DMF_V2_STAGGER);
+        if constexpr (!DEFER_C) {
+            if (!my_turn) __builtin_amdgcn_s_sleep(DMF_V2_STAGGER);
+        } else if (DMF_V2_STAGGER_DEFER > 0) {
+            if (!b_role) __builtin_amdgcn_s_sleep(DMF_V2_STAGGER_DEFER);
+        }
 #endif
         if (s + NSET < nk) {
             const int64_t nb = blk + NSET * (int64_t)gridDim.x;
@@ -666,19 +739,48 @@ __global__ __launch_bounds__(64 * MAXW, MAXW == 4 ? 2 : 1) void k_rowpass_v2(
             prefetch_tile(nb, 0);
             if (PAIR && s + 3 < nk) prefetch_tile(nb + gridDim.x, 1);
         }
-        DMF2_STAMP(7)  // prefetch issue
-        if (my_turn) phase_b(bset, (blk + (int64_t)bset * gridDim.x) * 16, uu0, up0);
+        if (b_role) { DMF2_STAMP(7) } else { DMF2_STAMP(16) }  // prefetch issue (16: in a cycle whose window this wave spends on phase C)
+        if (my_turn) phase_b((DEFER_C ? rs0 : 0) + bset, bset, (blk + (int64_t)bset * gridDim.x) * 16, uu0, up0);
         DMF2_STAMP(4)  // phase B (or nothing)
+        if constexpr (DEFER_C) {
+            if (!b_role) {  // (the window's critical chain: above the other workgroup's phase A, below phase B)
+                if (DMF_V2_DEFER_PRIO > 0) __builtin_amdgcn_s_setprio(DMF_V2_DEFER_PRIO);
+#pragma unroll 1
+                for (int pp = cyc < 2 ? 0 : cyc - 2; pp < cyc; ++pp) {
+                    phase_c_ring(pp, 0);
+                    phase_c_ring(pp, 1);
+                }
+                if (DMF_V2_DEFER_PRIO > 0) __builtin_amdgcn_s_setprio(0);
+            }
+            DMF2_STAMP(6)  // deferred phase C in the window
+        }
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
         __builtin_amdgcn_s_barrier();  // ---- barrier Y
-        DMF2_STAMP(5)  // wait Y
-        phase_c(0);
-        DMF2_STAMP(6)  // phase C, block s
-        if (has2) phase_c(1);
-        __builtin_amdgcn_s_setprio(0);
-        DMF2_STAMP(13)  // phase C, block s + 1
+        if (b_role) { DMF2_STAMP(5) } else { DMF2_STAMP(17) }  // wait Y (17: behind phase C)
+        if constexpr (!DEFER_C) {
+            phase_c(0);
+            DMF2_STAMP(6)  // phase C, block s
+            if (has2) phase_c(1);
+            __builtin_amdgcn_s_setprio(0);
+            DMF2_STAMP(13)  // phase C, block s + 1
+        }
         // (the next cycle's tile stores touch this wave's own tiles only; ubuf and red are rewritten behind the next
         // barrier X / by phase A after this wave's own phase C)
+    }
+    if constexpr (DEFER_C) {
+        if (nk > 0) {
+            // the drain: the last pair (a lone last block: its first half only) and, on the waves that ran the last
+            // cycle's phase B, the pair before; their u stands behind the last barrier Y
+            const int last = (nk - 1) >> 1;
+            const bool lone = (nk & 1) != 0;
+            const int first = ((wave >> 1) != (last & 1) || last == 0) ? last : last - 1;
+#pragma unroll 1
+            for (int pp = first; pp <= last; ++pp) {
+                phase_c_ring(pp, 0);
+                if (pp < last || !lone) phase_c_ring(pp, 1);
+            }
+        }
+        DMF2_STAMP(13)  // the drain
     }
 
     DMF2_STAMP_FLUSH
@@ -689,7 +791,7 @@ __global__ __launch_bounds__(64 * MAXW, MAXW == 4 ? 2 : 1) void k_rowpass_v2(
     if (q < NU) {
 #pragma unroll
         for (int t = 0; t < 4; ++t) {
-            const int sC = wcol0 + 16 * t + m16;
+            const int sC = wcol0 + (DEFER_C ? 4 * m16 + t : 16 * t + m16);  // (DEFER_C: phase_c_ring's sample order)
             if (sC < S) slab[((int64_t)blockIdx.x * NU + q) * S + sC] = bu[t];
         }
     }
@@ -700,13 +802,15 @@ __global__ __launch_bounds__(64 * MAXW, MAXW == 4 ? 2 : 1) void k_rowpass_v2(
     }
 }
 
-size_t rowpass_v2_lds_bytes(int S, int n_u, int n_iter2, bool x16, bool pair = false) {
+size_t rowpass_v2_lds_bytes(int S, int n_u, int n_iter2, bool x16, bool pair = false, bool defer_c = false) {
     const int NW = (S + 63) / 64;
     const int maxw = NW <= 4 ? 4 : 8;
     const int nset = pair ? 2 : 1;
+    const int nub = defer_c ? kDeferUbufSets : nset;
     const int nv = n_u * ((n_u + 2) & ~1);  // a row's partial-sum slots (k_rowpass_v2: NV)
-    const size_t doubles = (size_t)((n_iter2 + 1) & ~1) + (size_t)nset * (16 * n_u + maxw * nv * 16) + maxw;
-    return doubles * sizeof(double) + (size_t)nset * NW * (x16 ? kTileBytesX : kTileBytes2);
+    const size_t doubles = (size_t)((n_iter2 + 1) & ~1) + (size_t)nub * 16 * n_u + (size_t)nset * maxw * nv * 16 + maxw;
+    const int tile = defer_c ? kTileDBytes2 : (x16 ? kTileBytesX : kTileBytes2);  // (deferred C: x stands in the ring only)
+    return doubles * sizeof(double) + (size_t)nset * NW * tile + (defer_c ? (size_t)NW * kRingBytes : 0);
 }
 
 bool rowpass_v2_supported(int S, int n_c, int n_u, int n_iter2) {
@@ -731,6 +835,19 @@ bool rowpass_v2_pair_fits(int S, int n_u, int n_iter2) {
     return rowpass_v2_lds_bytes(S, n_u, n_iter2, true, true) * (size_t)rowpass_v2_per_cu(NW) <= (size_t)160 * 1024;
 }
 
+// The deferred-C schedule applies to the pair schedule at four waves when two workgroups, each with the x ring and six
+// ubuf sets, still fit the CU's 160 KB (a workgroup's share counted in whole 2 KB pieces, the coarsest the LDS is handed
+// out in): 70 848 B at n_u = 4 and 20 inner steps -- the ring of three pairs costs 24 KB, the x tiles it replaces 18 KB.
+// The instances <NKC = 4, NU = 3 or 4> (13..16 known types with three or four unknowns) would spill a register on this
+// schedule (tools/kernel_regs.sh --x16): they are not built and keep the pair schedule.
+constexpr bool rowpass_v2_defer_instance(int nkc, int nu) { return !(nkc == 4 && nu >= 3); }
+bool rowpass_v2_defer_fits(int S, int n_c, int n_u, int n_iter2) {
+    const int NW = (S + 63) / 64;
+    if (NW != 4 || !rowpass_v2_pair_fits(S, n_u, n_iter2) || !rowpass_v2_defer_instance((n_c + 3) / 4, n_u)) return false;
+    const size_t lds = (rowpass_v2_lds_bytes(S, n_u, n_iter2, true, true, true) + 2047) & ~(size_t)2047;
+    return lds * (size_t)rowpass_v2_per_cu(NW) <= (size_t)160 * 1024;
+}
+
 int rowpass_v2_grid(int64_t N, int S) {
     const int per_cu = rowpass_v2_per_cu((S + 63) / 64);
     const int64_t nblk = (N + 15) / 16;
@@ -739,21 +856,24 @@ int rowpass_v2_grid(int64_t N, int S) {
 }
 
 hipError_t launch_rowpass_v2(const ProblemView& p, const IterateView& it, int n_iter2, const UScratch& scratch, int* grid_out,
-                             bool pair, bool* paired_out, hipStream_t st) {
+                             bool pair, bool* paired_out, bool defer_c, bool* deferred_out, hipStream_t st) {
     const int S = p.S, NW = (S + 63) / 64;
     // the pair schedule where it applies (rowpass_v2_pair_fits), else one block per barrier cycle
     pair = pair && p.X16 != nullptr && rowpass_v2_pair_fits(S, it.n_u, n_iter2);
     if (paired_out != nullptr) *paired_out = pair;
+    // ... with phase C deferred where that applies (the caller vouches for x <= 255 with `defer_c`)
+    defer_c = defer_c && pair && rowpass_v2_defer_fits(S, p.n_c, it.n_u, n_iter2);
+    if (deferred_out != nullptr) *deferred_out = defer_c;
     return dispatch_int<0, 4>((p.n_c + 3) / 4, [&](auto nkc) {
         return dispatch_bool(p.X16 != nullptr, [&](auto xs) {
             return dispatch_int<1, 4>(it.n_u, [&](auto nu) {
-                const auto launch = [&](auto maxw, auto pair_t) {
+                const auto launch = [&](auto maxw, auto pair_t, auto defer_t) {
                     constexpr int NU = decltype(nu)::value, MAXW = decltype(maxw)::value;
-                    constexpr bool XS = decltype(xs)::value, PAIR = decltype(pair_t)::value;
-                    constexpr auto kernel = k_rowpass_v2<decltype(nkc)::value, NU, MAXW, XS, PAIR>;
-                    const size_t lds = rowpass_v2_lds_bytes(S, NU, n_iter2, XS, PAIR);
+                    constexpr bool XS = decltype(xs)::value, PAIR = decltype(pair_t)::value, DEFER_C = decltype(defer_t)::value;
+                    constexpr auto kernel = k_rowpass_v2<decltype(nkc)::value, NU, MAXW, XS, PAIR, DEFER_C>;
+                    const size_t lds = rowpass_v2_lds_bytes(S, NU, n_iter2, XS, PAIR, DEFER_C);
                     constexpr size_t kLdsCap = (size_t)(MAXW == 4 ? 80 : 160) * 1024;
-                    if (NW > MAXW || (MAXW == 8 && NW <= 4) || (PAIR && NW < 2) || lds > kLdsCap || p.N < 1 ||
+                    if (NW > MAXW || (MAXW == 8 && NW <= 4) || (PAIR && NW < 2) || (DEFER_C && NW != 4) || lds > kLdsCap || p.N < 1 ||
                         p.SD < NW * 64 || (p.SD & 7) != 0 || p.ND < 1 || p.ND > 2)
                         return hipErrorInvalidValue;
                     if (lds > 48 * 1024) {
@@ -772,11 +892,14 @@ hipError_t launch_rowpass_v2(const ProblemView& p, const IterateView& it, int n_
                     return hipGetLastError();
                 };
                 // more than 256 samples: one workgroup of up to eight waves; the pair leg only on X16
-                if (S > 256) return launch(std::integral_constant<int, 8>{}, std::false_type{});
+                if (S > 256) return launch(std::integral_constant<int, 8>{}, std::false_type{}, std::false_type{});
                 if constexpr (decltype(xs)::value) {
-                    if (pair) return launch(std::integral_constant<int, 4>{}, std::true_type{});
+                    if constexpr (rowpass_v2_defer_instance(decltype(nkc)::value, decltype(nu)::value)) {
+                        if (pair && defer_c) return launch(std::integral_constant<int, 4>{}, std::true_type{}, std::true_type{});
+                    }
+                    if (pair) return launch(std::integral_constant<int, 4>{}, std::true_type{}, std::false_type{});
                 }
-                return launch(std::integral_constant<int, 4>{}, std::false_type{});
+                return launch(std::integral_constant<int, 4>{}, std::false_type{}, std::false_type{});
             });
         });
     });

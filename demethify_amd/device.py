@@ -110,6 +110,11 @@ class Context:
         On by default; off for A/B runs and tests.  Both forms compute the same results bit for bit."""
         L.check(self._lib.dmf_context_set_rowpass_pair(self._h, int(bool(enabled))), "dmf_context_set_rowpass_pair")
 
+    def set_rowpass_defer_c(self, enabled: bool):
+        """Whether Solvers created from now on run the pair schedule with phase C deferred (193..256 samples, every count
+        at most 255).  On by default; off for A/B runs and tests.  Both forms compute the same results bit for bit."""
+        L.check(self._lib.dmf_context_set_rowpass_defer_c(self._h, int(bool(enabled))), "dmf_context_set_rowpass_defer_c")
+
     def set_stop_confirmation(self, mode: int):
         """How step() decides |cf - cf_0| < tol: 0 (default) Gram-form cost, confirmed on the streaming cost where the
         Gram form's error bound reaches tol / 20; 1 always on streaming costs near the threshold; 2 Gram form only."""
@@ -853,6 +858,14 @@ class Solver:
         L.check(self._lib.dmf_solver_rowpass_launches(self._h, C.byref(total), C.byref(paired)),
                 "dmf_solver_rowpass_launches")
         return total.value, paired.value
+
+    def rowpass_schedule_counts(self):
+        """(k_rowpass_v2 launches so far, of them on the pair schedule, of those with phase C deferred) --
+        dmf_solver_rowpass_schedule_counts."""
+        total, paired, deferred = C.c_int64(), C.c_int64(), C.c_int64()
+        L.check(self._lib.dmf_solver_rowpass_schedule_counts(self._h, C.byref(total), C.byref(paired), C.byref(deferred)),
+                "dmf_solver_rowpass_schedule_counts")
+        return total.value, paired.value, deferred.value
 
     def get_alpha(self):
         """The current proportions (K x S) as a fresh host array; u stays on the device."""

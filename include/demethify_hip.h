@@ -105,6 +105,11 @@ int dmf_context_set_x16(dmf_context* ctx, int enabled);
  * three unknowns, where the LDS of four workgroups per CU allows it) two 16-row blocks per barrier cycle, the two blocks' inner iterations at the same time on two waves; 0: one block at a time.  Both compute the
  * same results bit for bit.  Tests and A/B runs. */
 int dmf_context_set_rowpass_pair(dmf_context* ctx, int enabled);
+/* 1 (default): solvers created from now on run the pair schedule at 193..256 samples with phase C deferred -- a wave runs it
+ * only in the barrier cycles in which it runs no inner iterations, beside the two waves that do -- when every count of the
+ * problem is at most 255 and two workgroups with the schedule's x ring still fit a CU's LDS; 0: the pair schedule as it is.
+ * Both compute the same results bit for bit.  Tests and A/B runs. */
+int dmf_context_set_rowpass_defer_c(dmf_context* ctx, int enabled);
 /* How dmf_solver_step decides |cf - cf_0| < tol (deconvolution.py:218-220) for the solvers of this context:
  * 0 (default) = on the Gram-form cost of the loop, with the decisions near the threshold confirmed on the streaming
  * cost of deconvolution.py:15-17 where the Gram form's error bound (1e-15 N S max(counts)) reaches tol / 20;
@@ -426,6 +431,9 @@ int dmf_solver_stop_info(const dmf_solver* s, int* confirm_stops, int64_t* n_con
 /* How many k_rowpass_v2 launches this solver's steps have enqueued (total) and how many of them ran the pair schedule
  * (paired; see dmf_context_set_rowpass_pair).  Tests and A/B runs.  Either pointer may be NULL. */
 int dmf_solver_rowpass_launches(const dmf_solver* s, int64_t* total, int64_t* paired);
+/* The same, and how many of the paired launches ran the deferred-C schedule (deferred; see
+ * dmf_context_set_rowpass_defer_c).  Any pointer may be NULL. */
+int dmf_solver_rowpass_schedule_counts(const dmf_solver* s, int64_t* total, int64_t* paired, int64_t* deferred);
 /* One-shot convenience: create + step(n_iter1) + get + destroy. */
 int dmf_solve(dmf_context* ctx, const dmf_problem* p, const double* u0, const double* alpha0,
               int64_t n_u, int mode, int64_t n_iter1, int64_t n_iter2, double tol, int flags,

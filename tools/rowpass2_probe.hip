@@ -3,6 +3,9 @@
 //   -DPROBE_NO_STAMPS: the kernel as it ships (launch times only); -DPROBE_KERNEL_SRC="\"file\"": another version of the source
 //   -DPROBE_X16: the form on the methylated read counts (X16 + D16, V not read)
 //   -DPROBE_PAIR (with -DPROBE_X16): the pair schedule, two blocks per phase B; cycles then also per pair of blocks
+//   -DPROBE_DEFER_C (with -DPROBE_X16 -DPROBE_PAIR): phase C deferred into the other waves' phase-B window; the window is then
+//     reported per role and the drain as a segment of its own (the x ring is written by the tile store: no copy to time);
+//     -DDMF_V2_STAGGER_DEFER=n: its stagger, -DDMF_V2_DEFER_PRIO=n: the s_setprio of the deferred phase C
 //   -DDMF_CHAIN_NO_UNROLL: the inner steps as a loop at every step count (T2 = 20 otherwise runs them written out)
 //   -DDMF_CHAIN_NO_I32: the M combine with eight conversions per value instead of digit pairs joined in i32
 //   both together: the kernel before either, from this source
@@ -29,6 +32,16 @@ static_assert(kXS, "the pair schedule is an X16 form");
 #else
 constexpr bool kPair = false;
 #endif
+#ifdef PROBE_DEFER_C
+constexpr bool kDefer = true;
+static_assert(kPair, "the deferred-C schedule is a pair schedule");
+#else
+constexpr bool kDefer = false;
+#endif
+#ifndef DMF2_NSTAMP
+#define DMF2_NSTAMP 16
+#endif
+constexpr int kNS = DMF2_NSTAMP;
 int main(int argc, char** argv) {
     const int64_t N = 1000000; const int S = 256, n_c = 12, n_u = 4, K = 16;
     const int T2 = argc > 1 ? atoi(argv[1]) : 20;
@@ -43,22 +56,22 @@ int main(int argc, char** argv) {
     hipMalloc(&V, hV.size() * 8); hipMalloc(&D, hD.size() * 2); hipMalloc(&X, hX.size() * 2); hipMalloc(&R, hR.size() * 8); hipMalloc(&u, hu.size() * 8);
     hipMalloc(&up, hu.size() * 8); hipMalloc(&a, ha.size() * 8); hipMalloc(&u2, 8192 * 8); hipMalloc(&st, sizeof(SolverState));
     const int grid = 256 * per_cu;
-    hipMalloc(&slab, (size_t)grid * n_u * S * 8); hipMalloc(&stamps, (size_t)grid * 4 * 16 * 8);
+    hipMalloc(&slab, (size_t)grid * n_u * S * 8); hipMalloc(&stamps, (size_t)grid * 4 * kNS * 8);
     hipMemcpy(V, hV.data(), hV.size() * 8, hipMemcpyHostToDevice); hipMemcpy(D, hD.data(), hD.size() * 2, hipMemcpyHostToDevice);
     hipMemcpy(X, hX.data(), hX.size() * 2, hipMemcpyHostToDevice);
     hipMemcpy(R, hR.data(), hR.size() * 8, hipMemcpyHostToDevice); hipMemcpy(u, hu.data(), hu.size() * 8, hipMemcpyHostToDevice);
     hipMemcpy(up, hu.data(), hu.size() * 8, hipMemcpyHostToDevice); hipMemcpy(a, ha.data(), ha.size() * 8, hipMemcpyHostToDevice);
     SolverState h{}; h.a1 = 1; h.a2 = 1; h.l_w = 1e4; h.l_w_prev = 1e4; h.l_h = 1e6; h.l_h_prev = 1e6; h.dsq = 6400;
-    hipMemcpy(st, &h, sizeof(h), hipMemcpyHostToDevice); hipMemset(stamps, 0, (size_t)grid * 4 * 16 * 8);
-    const size_t lds = rowpass_v2_lds_bytes(S, n_u, T2, kXS, kPair);
-    hipFuncSetAttribute((const void*)k_rowpass_v2<3, 4, 4, kXS, kPair>, hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024);
+    hipMemcpy(st, &h, sizeof(h), hipMemcpyHostToDevice); hipMemset(stamps, 0, (size_t)grid * 4 * kNS * 8);
+    const size_t lds = rowpass_v2_lds_bytes(S, n_u, T2, kXS, kPair, kDefer);
+    hipFuncSetAttribute((const void*)k_rowpass_v2<3, 4, 4, kXS, kPair, kDefer>, hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024);
     hipEvent_t e0, e1; hipEventCreate(&e0); hipEventCreate(&e1);
     for (int rep = 0; rep < (argc > 3 ? atoi(argv[3]) : 3); ++rep) {
         hipEventRecord(e0);
 #ifdef PROBE_NO_STAMPS
-        hipLaunchKernelGGL((k_rowpass_v2<3, 4, 4, kXS, kPair>), dim3(grid), dim3(256), lds, 0, V, D, X, 256, R, a, u, up, st, N, S, n_c, T2, 0, 1, slab, u2);
+        hipLaunchKernelGGL((k_rowpass_v2<3, 4, 4, kXS, kPair, kDefer>), dim3(grid), dim3(256), lds, 0, V, D, X, 256, R, a, u, up, st, N, S, n_c, T2, 0, 1, slab, u2);
 #else
-        hipLaunchKernelGGL((k_rowpass_v2<3, 4, 4, kXS, kPair>), dim3(grid), dim3(256), lds, 0, V, D, X, 256, R, a, u, up, st, N, S, n_c, T2, 0, 1, slab, u2, stamps);
+        hipLaunchKernelGGL((k_rowpass_v2<3, 4, 4, kXS, kPair, kDefer>), dim3(grid), dim3(256), lds, 0, V, D, X, 256, R, a, u, up, st, N, S, n_c, T2, 0, 1, slab, u2, stamps);
 #endif
         hipEventRecord(e1); hipEventSynchronize(e1);
         float ms; hipEventElapsedTime(&ms, e0, e1); printf("launch %d: %.3f ms  (%s)\n", rep, ms, hipGetErrorString(hipGetLastError()));
@@ -66,23 +79,36 @@ int main(int argc, char** argv) {
 #ifdef PROBE_NO_STAMPS
     return 0;
 #endif
-    std::vector<unsigned long long> hs((size_t)grid * 4 * 16);
+    std::vector<unsigned long long> hs((size_t)grid * 4 * kNS);
     hipMemcpy(hs.data(), stamps, hs.size() * 8, hipMemcpyDeviceToHost);
     const char* an[16] = {"tile store (vmcnt wait)", "phase A (MFMA)", "partials", "wait X", "phase B / nothing", "wait Y", "phase C", "prefetch issue", "B: partial sums", "B: inner steps", "B: stores", "phase A, 2nd block", "partials, 2nd block", "phase C, 2nd block", "-", "-"};
-    double sum[16] = {0}; int cnt = 0;
-    for (int b = 0; b < grid; ++b) for (int w = 0; w < 4; ++w) { for (int i = 0; i < 15; ++i) sum[i] += (double)hs[((size_t)b * 4 + w) * 16 + i]; ++cnt; }
+    double sum[20] = {0}; int cnt = 0;
+    for (int b = 0; b < grid; ++b) for (int w = 0; w < 4; ++w) { for (int i = 0; i < kNS; ++i) if (i != 15) sum[i] += (double)hs[((size_t)b * 4 + w) * kNS + i]; ++cnt; }
     double tot = 0; for (int i = 0; i < 8; ++i) tot += sum[i];  // (8..10: sub-segments of phase B, already inside segment 4)
-    for (int i = 11; i < 14; ++i) tot += sum[i];
+    for (int i = 11; i < 15; ++i) tot += sum[i];
+    for (int i = 16; i < 20; ++i) tot += sum[i];
+    if (kDefer) {
+        // a wave runs phase B's role in every second cycle and phase C's in the others: its sums hold both, one after the other
+        an[4] = "window, B role: phase B"; an[7] = "window, B role: issue"; an[5] = "window, B role: wait Y";
+        an[6] = "window, C role: phase C x 4"; an[13] = "drain (whole kernel)";  // (x goes into the ring at the tile store: no copy to time)
+    }
     const double steps = (N / 16.0) / grid;
     printf("T2 = %d, %d workgroups per CU%s: mean cycles per wave %.0f over the kernel, %.0f per block, %.0f per pair of blocks\n", T2, per_cu,
            kPair ? ", pair schedule" : "", tot / cnt, tot / cnt / steps, 2 * tot / cnt / steps);
-    for (int i = 0; i < 14; ++i) if (an[i][0] != '-' && (kPair || i < 11)) printf("   %-28s %6.1f %%  (%.0f cycles per block, %.0f per pair)\n", an[i], 100 * sum[i] / tot, sum[i] / cnt / steps, 2 * sum[i] / cnt / steps);
+    for (int i = 0; i < 15; ++i) if (an[i][0] != '-' && (kPair || i < 11)) printf("   %-28s %6.1f %%  (%.0f cycles per block, %.0f per pair)\n", an[i], 100 * sum[i] / tot, sum[i] / cnt / steps, 2 * sum[i] / cnt / steps);
+    if (kDefer) {
+        // per cycle of that role (a wave has each role in half of its cycles: 4 x the per-block mean)
+        printf("   window, C role: issue %.0f, wait Y %.0f cycles per pair\n", 2 * sum[16] / cnt / steps, 2 * sum[17] / cnt / steps);
+        printf("   X -> Y window per cycle of the role: B role %.0f (issue %.0f + phase B %.0f + wait %.0f), C role %.0f (issue %.0f + phase C %.0f + wait %.0f)\n",
+               4 * (sum[7] + sum[4] + sum[5]) / cnt / steps, 4 * sum[7] / cnt / steps, 4 * sum[4] / cnt / steps, 4 * sum[5] / cnt / steps,
+               4 * (sum[16] + sum[6] + sum[17]) / cnt / steps, 4 * sum[16] / cnt / steps, 4 * sum[6] / cnt / steps, 4 * sum[17] / cnt / steps);
+    }
     // where the waves sit: HW_ID bits 5:4 = SIMD.  Phase B of block s runs on wave s % 4: the pair schedule wants waves
     // w and w + 1 (mod 4) on different SIMDs
     int distinct = 0, adjacent_apart = 0;
     for (int b = 0; b < grid; ++b) {
         int simd[4], mask = 0;
-        for (int w = 0; w < 4; ++w) { simd[w] = (int)((hs[((size_t)b * 4 + w) * 16 + 15] >> 4) & 3); mask |= 1 << simd[w]; }
+        for (int w = 0; w < 4; ++w) { simd[w] = (int)((hs[((size_t)b * 4 + w) * kNS + 15] >> 4) & 3); mask |= 1 << simd[w]; }
         distinct += mask == 15;
         bool ok = true;
         for (int w = 0; w < 4; ++w) ok = ok && simd[w] != simd[(w + 1) % 4];
