@@ -31,6 +31,8 @@ REPORT_INTS = ("N", "S", "n_c", "ND", "SD", "N16", "plane_stride", "has_D16", "h
 REPORT_DBLS = ("kDsq", "kRtSumsq", "kDmax", "kF32ResidualMax", "kIntCountMax", "kRtOutsideUnit", "x16_dev", "x16_sum")
 # dmf_problem_copy_out's arrays: name -> DMF_ARRAY_* (V, D, Rt, Rtp, consts hold doubles, D16 / X16 / W16 u16, Dt8 i8, mask_bits u8)
 PROBLEM_ARRAYS = {"V": 0, "D": 1, "Rt": 2, "Rtp": 3, "D16": 4, "X16": 5, "W16": 6, "Dt8": 7, "mask_bits": 8, "consts": 9}
+# ... and the byte images of X16 / D16 for the row pass (dmf_problem_has_byte_images; u8, [N16 / 16][SD / 64][1024]): ids of their own
+PROBLEM_BYTE_IMAGES = {"X8": 10, "D8": 11}
 DMF_MODE_PARTIAL = 0
 DMF_MODE_UNSUPERVISED = 1
 MAX_K = 64  # dmf::kMaxK: largest n_c + n_u the kernels are built for (DMF_ERR_UNSUPPORTED beyond)
@@ -66,6 +68,10 @@ SIGNATURES = {
     "dmf_context_set_x16": (C.c_int, [_p, C.c_int]),
     "dmf_context_set_rowpass_pair": (C.c_int, [_p, C.c_int]),
     "dmf_context_set_rowpass_defer_c": (C.c_int, [_p, C.c_int]),
+    "dmf_context_set_rowpass_bytes": (C.c_int, [_p, C.c_int]),
+    "dmf_problem_has_byte_images": (C.c_int, [_p, C.POINTER(C.c_int)]),
+    "dmf_rowpass_image_offset": (C.c_int, [C.c_int, C.c_int]),
+    "dmf_solver_rowpass_byte_launches": (C.c_int, [_p, C.POINTER(_i64)]),
     "dmf_context_set_stop_confirmation": (C.c_int, [_p, C.c_int]),
     "dmf_problem_create": (C.c_int, [_p, _i64, _i64, _i64, _p, _p, _p, C.c_int, C.POINTER(_p)]),
     "dmf_problem_gather": (C.c_int, [_p, _p, _p, _i64, C.POINTER(_p)]),

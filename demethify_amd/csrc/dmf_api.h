@@ -16,6 +16,7 @@
 
 #include "../../include/demethify_hip.h"
 #include "dmf_internal.h"
+#include "dmf_rowpass_image.h"
 #include "dmf_select.h"
 
 using dmf::SolverState;
@@ -58,6 +59,7 @@ struct dmf_context {
     bool x16 = true;        // dmf_context_set_x16: problems created from now on get the X16 copy when their data allow
     bool rowpass_pair = true;  // dmf_context_set_rowpass_pair: solvers created from now on run the row pass two blocks per phase B
     bool rowpass_defer_c = true;  // dmf_context_set_rowpass_defer_c: ... with phase C deferred where that applies
+    bool rowpass_bytes = true;    // dmf_context_set_rowpass_bytes: ... reading the problem's byte images where it has them
     double* scratch = nullptr;  // 4096 doubles of reduction scratch
     hipMemPool_t pool = nullptr;  // the context's own stream-ordered pool (the device's default pool is not touched)
     std::unordered_map<void*, size_t> live;                // large blocks handed out by pool_alloc (size by address)
@@ -194,6 +196,9 @@ struct dmf_problem {
     // seen, x16_sum: sum of x -- their product bounds what the substitution changes in the Gram-form cost.
     dmf_api::DevBuf<unsigned short> X16;
     double x16_dev = 0.0, x16_sum = 0.0;
+    // byte images of X16 / D16 ([N16 / 16][SD / 64][1024], dmf_rowpass_image.h) for the row pass's deferred-C schedule: built
+    // (build_rowpass_images) when the problem can run it at all -- X16, every count <= 255, 193..256 samples
+    dmf_api::DevBuf<unsigned char> X8, D8;
     bool d_f32_exact = false;    // every count survives a round trip through f32 (the fused tile stores D as f32)
     dmf_api::DevBuf<double> gb_known;  // [(n_c+1)(n_c+2)/2][S]
     dmf::GramRan known_ran;            // which route problem_finalize took for it, as text (dmf_problem_gram_known)
@@ -207,6 +212,7 @@ struct dmf_problem {
     dmf::ProblemView view() const {
         dmf::ProblemView v;
         v.V = V, v.D = D, v.D16 = D16, v.X16 = X16, v.Dt8 = Dt8;
+        v.X8 = X8, v.D8 = D8;
         v.plane_stride = plane_stride, v.SD = SD, v.ND = ND;
         v.Rt = Rt, v.Rtp = Rtp;
         v.N = N, v.S = (int)S, v.n_c = (int)n_c;
@@ -266,6 +272,7 @@ struct dmf_solver {
     long long cf_stream_iter = -1;
     long long n_rowpass = 0, n_rowpass_pair = 0;  // k_rowpass_v2 launches so far / of them on the pair schedule
     long long n_rowpass_defer = 0;                // ... / of those with phase C deferred
+    long long n_rowpass_bytes = 0;                // ... / of those from the problem's byte images
     long long n_confirmed = 0, n_unconfirmed = 0;  // stop tests decided on streaming costs / on the Gram form inside the band
     // the iterate and the u phases' scratch as the launch wrappers take them (dmf_internal.h)
     dmf::IterateView iterate() const {

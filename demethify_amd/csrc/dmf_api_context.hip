@@ -350,6 +350,12 @@ int dmf_context_set_rowpass_defer_c(dmf_context* ctx, int enabled) {
     return DMF_OK;
 }
 
+int dmf_context_set_rowpass_bytes(dmf_context* ctx, int enabled) {
+    if (ctx == nullptr || enabled < 0 || enabled > 1) return DMF_ERR_BAD_ARG;
+    ctx->rowpass_bytes = enabled != 0;
+    return DMF_OK;
+}
+
 int dmf_context_set_stop_confirmation(dmf_context* ctx, int mode) {
     if (ctx == nullptr || mode < 0 || mode > 2) return DMF_ERR_BAD_ARG;
     ctx->stop_confirmation = mode;

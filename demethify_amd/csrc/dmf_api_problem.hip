@@ -20,6 +20,20 @@ static int alloc_count_copies(dmf_problem* p, int ND, bool x16, bool w16) {
     return DMF_OK;
 }
 
+// The byte images X8 / D8 of the problem's X16 / D16, where the problem can run the row pass's deferred-C schedule at all: X16
+// present, every count (so every x) at most 255, four column groups of which the last is not empty.  Called by
+// problem_finalize once the integer copies and the largest count stand, so for every problem that is created, gathered or
+// masked -- a masked problem's X16 / D16 carry the masked counts, and so do its images.
+static int build_rowpass_images(dmf_problem* p) {
+    dmf_context* ctx = p->ctx;
+    if (p->X16 == nullptr || p->D16 == nullptr || !(p->h_consts[kIntCountMax] <= 255.0) || p->S < 193 || p->S > 256) return DMF_OK;
+    const size_t bytes = (size_t)p->N16 * p->SD;
+    HIP_TRY(p->X8.alloc(ctx, bytes));
+    HIP_TRY(p->D8.alloc(ctx, bytes));
+    HIP_TRY(dmf::launch_build_rowpass_images(p->X16, p->D16, p->N16, p->SD, p->X8, p->D8, ctx->stream));
+    return DMF_OK;
+}
+
 // one more piece of dmf_problem::known_ran, the text of dmf_problem_gram_known: "int_known" / "fp64" (without either: fp64),
 // then every launcher that contributed rows, in launch order, separated by blanks
 static void known_route(dmf_problem* p, const char* piece) {
@@ -87,6 +101,8 @@ static int problem_finalize(dmf_problem* p, bool counts_done = false) {
             }
         }
     }
+
+    DMF_TRY(build_rowpass_images(p));
 
     // padded copy of R_trunc for the shape-specialised kernels (aligned, branch-free row loads)
     if (n_c > 0 && n_c <= 48) {  // (<= 16: every shape-specialised kernel; beyond: the wide-row-group producer, the integer Gram)
@@ -427,11 +443,24 @@ int dmf_problem_copy_out(const dmf_problem* p, int which, void* out, int64_t byt
         case DMF_ARRAY_DT8: src = p->Dt8, size = (size_t)p->plane_stride * p->ND; break;
         case DMF_ARRAY_MASK_BITS: src = p->mask_bits, size = (size_t)p->N * (size_t)((p->S + 7) / 8); break;
         case DMF_ARRAY_CONSTS: src = p->consts, size = kProblemConsts * sizeof(double); break;
+        case DMF_ARRAY_X8: src = p->X8, size = (size_t)p->N16 * p->SD; break;
+        case DMF_ARRAY_D8: src = p->D8, size = (size_t)p->N16 * p->SD; break;
         default: return DMF_ERR_BAD_ARG;
     }
     if (src == nullptr || size == 0) return DMF_ERR_BAD_ARG;
     if (bytes < 0 || (size_t)bytes != size) return DMF_ERR_BAD_SHAPE;
     return export_array(ctx, src, size, 0, out);
+}
+
+int dmf_problem_has_byte_images(const dmf_problem* p, int* out) {
+    if (p == nullptr || out == nullptr) return DMF_ERR_BAD_ARG;
+    *out = p->X8 != nullptr && p->D8 != nullptr;
+    return DMF_OK;
+}
+
+int dmf_rowpass_image_offset(int row, int sample) {
+    if (row < 0 || row > 15 || sample < 0 || sample > 63) return -1;
+    return dmf::rowpass_image_byte(row, sample);
 }
 
 int dmf_problem_shape(const dmf_problem* p, int64_t* N, int64_t* S, int64_t* n_c) {

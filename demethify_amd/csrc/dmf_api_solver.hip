@@ -167,16 +167,18 @@ static int enqueue_outer_iteration(dmf_solver* s, int n_iter2) {
         // the u phase and b_u, then the exact
         // integer-matrix-core GEMM for the u-dependent Gram entries on the 8-bit count planes.
         int grid = 0;
-        bool paired = false, deferred = false;
+        bool paired = false, deferred = false, bytes = false;
         {
             FamilyScope scope(ctx, DMF_KERNEL_ROWPASS);
             dmf::ProblemView pv = p->view();
             if (!s->key.x16) pv.X16 = nullptr;
+            if (!s->key.rowpass_bytes) pv.X8 = nullptr, pv.D8 = nullptr;
             HIP_TRY(dmf::launch_rowpass_v2(pv, s->iterate(), n_iter2, s->scratch(), &grid, s->key.rowpass_pair, &paired,
-                                           s->key.rowpass_defer_c && s->key.x_byte, &deferred, ctx->stream));
+                                           s->key.rowpass_defer_c && s->key.x_byte, &deferred, &bytes, ctx->stream));
             ++s->n_rowpass;
             s->n_rowpass_pair += paired ? 1 : 0;
             s->n_rowpass_defer += deferred ? 1 : 0;
+            s->n_rowpass_bytes += bytes ? 1 : 0;
         }
         return enqueue_gram_i8_tail(s, plan.alpha, n_iter2, grid);
     }
@@ -327,6 +329,7 @@ static int solver_setup(dmf_solver* s, const double* u0, const double* alpha0, i
     key.x16 = key.nd > 0 && p->X16 != nullptr;
     key.rowpass_pair = ctx->rowpass_pair;
     key.rowpass_defer_c = ctx->rowpass_defer_c;
+    key.rowpass_bytes = ctx->rowpass_bytes;
     key.x_byte = key.x16 && p->h_consts[kIntCountMax] <= 255.0;  // (0 <= x <= d for every element of X16)
     key.level = ctx->generic_level;
     key.d_f32_exact = p->d_f32_exact;
@@ -801,6 +804,12 @@ int dmf_solver_rowpass_schedule_counts(const dmf_solver* s, int64_t* total, int6
     if (total) *total = s->n_rowpass;
     if (paired) *paired = s->n_rowpass_pair;
     if (deferred) *deferred = s->n_rowpass_defer;
+    return DMF_OK;
+}
+
+int dmf_solver_rowpass_byte_launches(const dmf_solver* s, int64_t* bytes) {
+    if (s == nullptr || bytes == nullptr) return DMF_ERR_BAD_ARG;
+    *bytes = s->n_rowpass_bytes;
     return DMF_OK;
 }
 

@@ -74,6 +74,8 @@ struct ProblemView {
     const double* D = nullptr;
     const unsigned short* D16 = nullptr;
     const unsigned short* X16 = nullptr;
+    const unsigned char* X8 = nullptr;  // byte images of X16 / D16 for the deferred-C row pass (dmf_rowpass_image.h); null: none
+    const unsigned char* D8 = nullptr;
     const signed char* Dt8 = nullptr;
     int64_t plane_stride = 0;
     int SD = 0, ND = 0;
@@ -373,9 +375,13 @@ bool rowpass_v2_supported(int S, int n_c, int n_u, int n_iter2);
 int rowpass_v2_grid(int64_t N, int S);
 // u phase + b_u slab (scratch.slab: [grid][n_u][S] doubles) + per-workgroup ||u||^2 shares in one read of V (f64) and
 // D16 -- or, when p.X16 is not null, of X16 and D16 (V is not read).  pair: two blocks per phase B where the X16 form allows
-// it (rowpass_v2_pair_fits); the same results bit for bit.  *paired_out (may be null): whether the pair schedule was launched
+// it (rowpass_v2_pair_fits); the same results bit for bit.  *paired_out (may be null): whether the pair schedule was launched;
+// defer_c / *deferred_out: the same for its deferred-C form; *bytes_out: whether that read the byte images p.X8 / p.D8
 hipError_t launch_rowpass_v2(const ProblemView& p, const IterateView& it, int n_iter2, const UScratch& scratch, int* grid_out,
-                             bool pair, bool* paired_out, bool defer_c, bool* deferred_out, hipStream_t st);
+                             bool pair, bool* paired_out, bool defer_c, bool* deferred_out, bool* bytes_out, hipStream_t st);
+// the byte images X8 / D8 ([N16 / 16][SD / 64][1024], dmf_rowpass_image.h) of X16 / D16 ([N16][SD], every element <= 255)
+hipError_t launch_build_rowpass_images(const unsigned short* X16, const unsigned short* D16, int64_t N16, int SD,
+                                       unsigned char* X8, unsigned char* D8, hipStream_t st);
 // the X16 row pass can run two blocks per phase B at this shape: 2..4 waves, and the grid's workgroups per CU fit the LDS
 bool rowpass_v2_pair_fits(int S, int n_u, int n_iter2);
 bool gram_i8_supported(int n_c, int n_u, int ND, int64_t N, int SD);

@@ -32,6 +32,7 @@
 #include "dmf_internal.h"
 #include "dmf_ustep.h"
 #include "dmf_fixedpoint.h"
+#include "dmf_rowpass_image.h"
 #include <cstdlib>
 #include <type_traits>
 
@@ -92,6 +93,7 @@ constexpr int kTileBytesX = 2 * kTileDBytes2;               // X16 form: counts 
 constexpr int kRingBlockBytes = 16 * 64;                    // deferred-C schedule: a block's x as bytes, 16 rows x 64 samples
 constexpr int kRingBytes = 6 * kRingBlockBytes;             // ... a wave's ring: three pairs of blocks
 constexpr int kDeferUbufSets = 6;                           // ... and the workgroup's u of three pairs
+constexpr int kTileDBytes8 = kRowpassImageBytes;            // byte form: a block's counts as bytes, the image of D8 (no padding)
 }  // namespace
 
 template <int NU, bool AT_PREV>
@@ -139,7 +141,11 @@ __device__ __forceinline__ void inner_steps_unrolled(double& uu, double& up, dou
 // cycles in which it is not one of the two phase-B waves, for the two pairs then pending, between barriers X and Y; x
 // goes from the staging registers into a ring of three pairs per wave as BYTES and is kept nowhere else (phase A reads
 // it there too: no x tile), u waits in ubuf sets of three pairs -- see the block loop.
-template <int NKC, int NU, int MAXW = 4, bool XS = false, bool PAIR = false, bool DEFER_C = false>
+// BYTES (DEFER_C, the problem carries the byte images X8 / D8 of dmf_rowpass_image.h): x and the counts arrive as the bytes
+// the ring and the count tile hold -- one 16-byte load and one 16-byte LDS write per lane, block and array, no permute;
+// phase A reads its four counts as one dword, the integer product its digits from bytes.  X16 / D16 are not read: the
+// images come in their parameters (D16 = D8, X16 = X8), so that the other instances' arguments stay what they were.
+template <int NKC, int NU, int MAXW = 4, bool XS = false, bool PAIR = false, bool DEFER_C = false, bool BYTES = false>
 __global__ __launch_bounds__(64 * MAXW, MAXW == 4 ? 2 : 1) void k_rowpass_v2(
     const double* __restrict__ V, const unsigned short* __restrict__ D16, const unsigned short* __restrict__ X16, int SD,
     const double* __restrict__ Rtp,
@@ -153,6 +159,7 @@ __global__ __launch_bounds__(64 * MAXW, MAXW == 4 ? 2 : 1) void k_rowpass_v2(
     static_assert(NU >= 1 && NU <= 4, "one phase-B pass per block, 4x4x4 MFMA for the c product");
     static_assert(!PAIR || (XS && MAXW == 4), "the pair schedule: X16 form, two workgroups per CU");
     static_assert(!DEFER_C || PAIR, "the deferred-C schedule is a pair schedule");
+    static_assert(!BYTES || DEFER_C, "the byte images are the deferred-C schedule's");
     constexpr int NSET = PAIR ? 2 : 1;  // tile / slot sets: blocks in flight per barrier cycle
     constexpr int NUB = DEFER_C ? kDeferUbufSets : NSET;  // ubuf sets (DEFER_C: pair p's blocks in sets 2 (p % 3), + 1)
     constexpr int NCT = 4 * NKC;
@@ -171,12 +178,12 @@ __global__ __launch_bounds__(64 * MAXW, MAXW == 4 ? 2 : 1) void k_rowpass_v2(
 
     // LDS carve-up (doubles unless noted): beta[n_iter2 (even)] | ubuf[NUB][16][NU] | red[NSET][MAXW][16][NU][SLOT] |
     //   u2[MAXW] | tiles[NSET][NW]{ V f64 [16][66], counts u16 [16][72] }  (XS: { counts u16 [16][72], x u16 [16][72] })
-    //   (DEFER_C: tiles hold the counts only) | ring[NW][3 pairs][2 blocks]{ x u8 [16][64] }
+    //   (DEFER_C: tiles hold the counts only; BYTES: as u8 [16][64] in the ring slot's order) | ring[NW][3 pairs][2 blocks]{ x u8 [16][64] }
     double* __restrict__ beta_tab = lds_dyn;
     double* __restrict__ ubuf = beta_tab + ((n_iter2 + 1) & ~1);
     double* __restrict__ red = ubuf + NUB * 16 * NU;
     double* __restrict__ u2red = red + NSET * MAXW * NV * 16;
-    constexpr int TB = XS ? (DEFER_C ? kTileDBytes2 : kTileBytesX) : kTileBytes2;
+    constexpr int TB = XS ? (BYTES ? kTileDBytes8 : DEFER_C ? kTileDBytes2 : kTileBytesX) : kTileBytes2;
     char* __restrict__ tile = reinterpret_cast<char*>(u2red + MAXW) + (size_t)wave * TB;  // (this wave's tile of set 0)
     // the counts stay u16 in the tile (LINEAR rows: no piece swap): phase A and phase C convert what they read, the integer
     // product builds its balanced byte digits from 32 bytes of a row -- converting at the tile store (f32 copy + two digit
@@ -200,6 +207,12 @@ __global__ __launch_bounds__(64 * MAXW, MAXW == 4 ? 2 : 1) void k_rowpass_v2(
     auto ring_at = [&](int slot, int row, int dword) {
         return ring + slot * (kRingBlockBytes / 4) + (4 * (row & 3) + (row >> 2)) * 16 + ((dword + 4 * (row & 3)) & 15);
     };
+    static_assert(rowpass_image_dword(7, 9) == (4 * 3 + 1) * 16 + ((9 + 12) & 15) && kRingBlockBytes == kRowpassImageBytes,
+                  "a ring slot is an image of dmf_rowpass_image.h");
+    // (BYTES) the count tile of set `set` holds the same image: the strip read of phase A is the ring's, and the 16 samples
+    // 16 q .. 16 q + 15 of row m16 that the integer product reads per lane are one 16-byte piece of it -- the 16 lanes that a
+    // ds_read_b128 serves together (see the tile swizzle below) touch 16 different pieces modulo 256 bytes
+    auto dtile8 = [&](int set) { return reinterpret_cast<unsigned int*>(tile + (size_t)set * NW * TB); };
 
     // momentum coefficients of the inner steps (deconvolution.py:83-85): from the host's row of ratios when there is one
     // (SolverState), else the recurrence itself by one thread -- n_iter2 square roots and divisions in a row, ~5 us
@@ -309,7 +322,7 @@ __global__ __launch_bounds__(64 * MAXW, MAXW == 4 ? 2 : 1) void k_rowpass_v2(
     // (tile swizzle at the stores: V rows 2 i, 2 i + 1 are swapped rows for i = 2..5)
     const int ld_col_sw = ((lane & 31) ^ 2) * 2;
     v2d pv[NSET][XS ? 1 : 8];  // (XS: V is not read)
-    v4u pd[NSET][2], px[NSET][XS ? 2 : 1];
+    v4u pd[NSET][BYTES ? 1 : 2], px[NSET][BYTES ? 1 : XS ? 2 : 1];  // (BYTES: a lane's 16 bytes of the block's image)
     double nrt[NSET][NKC > 0 ? NKC : 1];
     double pu, pup;  // u / u_ of lane (row, unknown) for the wave that runs the block's inner iterations
     constexpr int RPWB = 64 / NU;  // >= 16 rows per wave: one phase-B pass covers the block
@@ -321,7 +334,8 @@ __global__ __launch_bounds__(64 * MAXW, MAXW == 4 ? 2 : 1) void k_rowpass_v2(
     // and the row pass is bound by the SIMD's issue slots).  The descriptor's range check replaces the clamps of the
     // last, partial block: rows at or beyond N read as zero, and their counts are zero.
     const unsigned int v_off = (unsigned int)(ld_row * S + ld_gcol) * 8u;               // V: row ld_row of a row pair
-    const unsigned int d_off = (unsigned int)(d_row * SD + wcol0 + d_col) * 2u;         // counts: row d_row of eight
+    const unsigned int d_off = BYTES ? (unsigned int)(wave * kRowpassImageBytes + lane * 16)  // (BYTES) piece `lane` of the wave's image
+                                     : (unsigned int)(d_row * SD + wcol0 + d_col) * 2u;     // counts: row d_row of eight
     const unsigned int r_off = (unsigned int)(m16 * NCT + q) * 8u;                      // R_trunc (padded copy): row m16
     const unsigned int u_off = b_lane ? (unsigned int)lane * 8u : 0xFFFFFFF0u;          // u / u_: (row, unknown) = lane
     auto span = [](int64_t bytes) { return (unsigned int)(bytes < 0 ? 0 : (bytes > 0x7FFFFFFF ? 0x7FFFFFFF : bytes)); };
@@ -350,7 +364,15 @@ __global__ __launch_bounds__(64 * MAXW, MAXW == 4 ? 2 : 1) void k_rowpass_v2(
                 nrt[set][kc] = __hiloint2double((int)a.y, (int)a.x);
             }
         }
-        if constexpr (!XS) {
+        if constexpr (BYTES) {
+            // (both images are zero-padded to whole blocks and to SD: always in range; a block's SD / 64 images are consecutive)
+            const unsigned char* const X8 = reinterpret_cast<const unsigned char*>(X16);
+            const unsigned char* const D8 = reinterpret_cast<const unsigned char*>(D16);
+            const __amdgpu_buffer_rsrc_t rx = __builtin_amdgcn_make_buffer_rsrc((void*)(X8 + r0 * SD), 0, span((int64_t)16 * SD), 0x00020000);
+            const __amdgpu_buffer_rsrc_t rd = __builtin_amdgcn_make_buffer_rsrc((void*)(D8 + r0 * SD), 0, span((int64_t)16 * SD), 0x00020000);
+            px[set][0] = __builtin_amdgcn_raw_buffer_load_b128(rx, d_off, 0, 0);
+            pd[set][0] = __builtin_amdgcn_raw_buffer_load_b128(rd, d_off, 0, 0);
+        } else if constexpr (!XS) {
             const __amdgpu_buffer_rsrc_t rv = __builtin_amdgcn_make_buffer_rsrc((void*)(V + r0 * S), 0, span(left * S * 8), 0x00020000);
 #pragma unroll
             for (int i = 0; i < 8; ++i) {
@@ -363,7 +385,7 @@ __global__ __launch_bounds__(64 * MAXW, MAXW == 4 ? 2 : 1) void k_rowpass_v2(
             px[set][0] = __builtin_amdgcn_raw_buffer_load_b128(rx, d_off, 0, 0);
             px[set][1] = __builtin_amdgcn_raw_buffer_load_b128(rx, d_off, 8 * SD * 2, 0);
         }
-        {
+        if constexpr (!BYTES) {
             // (the count copy is zero-padded to whole blocks of 16 rows: always in range)
             const __amdgpu_buffer_rsrc_t rd = __builtin_amdgcn_make_buffer_rsrc((void*)(D16 + r0 * SD), 0, span((int64_t)16 * SD * 2), 0x00020000);
             pd[set][0] = __builtin_amdgcn_raw_buffer_load_b128(rd, d_off, 0, 0);
@@ -389,7 +411,13 @@ __global__ __launch_bounds__(64 * MAXW, MAXW == 4 ? 2 : 1) void k_rowpass_v2(
     // ---- tile store of staging set `set` into the wave's tile of that set (waits for the prefetched loads)
     auto tile_store = [&](int set, int rslot) {
         const BlockTile T = block_tile(set);
-        if constexpr (DEFER_C) {
+        if constexpr (BYTES) {
+            // the images as they arrived: piece `lane` of ring slot rslot and of the count tile
+            *reinterpret_cast<v4u*>(ring + rslot * (kRingBlockBytes / 4) + 4 * lane) = px[set][0];
+#ifndef DMF_ABLATE_DSTORE
+            *reinterpret_cast<v4u*>(dtile8(set) + 4 * lane) = pd[set][0];
+#endif
+        } else if constexpr (DEFER_C) {
             // x as bytes (the low byte of each u16: every x <= 255) into ring slot rslot: two dwords of row 8 i + d_row
 #pragma unroll
             for (int i = 0; i < 2; ++i)
@@ -405,8 +433,10 @@ __global__ __launch_bounds__(64 * MAXW, MAXW == 4 ? 2 : 1) void k_rowpass_v2(
                 *reinterpret_cast<v2d*>(T.V + (2 * i + ld_row) * kRowV + ((i >= 2 && i < 6) ? ld_col_sw : ld_col)) = pv[set][i];
         }
 #ifndef DMF_ABLATE_DSTORE
+        if constexpr (!BYTES) {
 #pragma unroll
-        for (int i = 0; i < 2; ++i) *reinterpret_cast<v4u*>(T.D + (8 * i + d_row) * kRowD + d_col) = pd[set][i];
+            for (int i = 0; i < 2; ++i) *reinterpret_cast<v4u*>(T.D + (8 * i + d_row) * kRowD + d_col) = pd[set][i];
+        }
 #endif
     };
 
@@ -437,7 +467,8 @@ __global__ __launch_bounds__(64 * MAXW, MAXW == 4 ? 2 : 1) void k_rowpass_v2(
                 R.v01 = *reinterpret_cast<const v2d*>(tv);
                 R.v23 = *reinterpret_cast<const v2d*>(tv + 2);
             }
-            R.dw = *reinterpret_cast<const v2u*>(tileD + m16 * kRowD + t * 16 + 4 * q);
+            if constexpr (BYTES) R.dw.x = dtile8(set)[rowpass_image_dword(m16, 4 * t + q)];  // the piece's four counts as bytes
+            else R.dw = *reinterpret_cast<const v2u*>(tileD + m16 * kRowD + t * 16 + 4 * q);
         };
         double csm0 = 0.0, csm1 = 0.0;  // c[unknown q][row m16], one double per lane
         // E = V - Rt a_known; XS: E = -Rt a_known, and V enters through x below
@@ -447,7 +478,8 @@ __global__ __launch_bounds__(64 * MAXW, MAXW == 4 ? 2 : 1) void k_rowpass_v2(
         };
         auto run_strip = [&](const Strip& R, v4d e, const Strip& Rn, const double (&a1n)[NKC > 0 ? NKC : 1],
                              const double (&a2)[4], bool has_next) {
-            const v4d d = {(double)(R.dw.x & 0xFFFFu), (double)(R.dw.x >> 16), (double)(R.dw.y & 0xFFFFu), (double)(R.dw.y >> 16)};
+            const v4d d = BYTES ? v4d{(double)(R.dw.x & 0xFFu), (double)((R.dw.x >> 8) & 0xFFu), (double)((R.dw.x >> 16) & 0xFFu), (double)(R.dw.x >> 24)}
+                                : v4d{(double)(R.dw.x & 0xFFFFu), (double)(R.dw.x >> 16), (double)(R.dw.y & 0xFFFFu), (double)(R.dw.y >> 16)};
             v4d w;
             if constexpr (XS) {  // w = d (v - Rt a1) = fma(d, -Rt a1, x)
                 const v4d x = DEFER_C ? v4d{(double)(R.xw.x & 0xFFu), (double)((R.xw.x >> 8) & 0xFFu), (double)((R.xw.x >> 16) & 0xFFu), (double)(R.xw.x >> 24)}
@@ -491,7 +523,20 @@ __global__ __launch_bounds__(64 * MAXW, MAXW == 4 ? 2 : 1) void k_rowpass_v2(
 #pragma unroll
         for (int w8 = 0; w8 < 8; ++w8) mw[w8] = v4i{0, 0, 0, 0};
 #ifndef DMF_ABLATE_M  // (diagnostic builds of tools/rowpass2_probe.hip leave pieces out to see what they cost)
-        {
+        if constexpr (BYTES) {
+            // A from bytes: d + 128 = b0 + 256 b1 with b0 = d ^ 0x80, so digit 0 = b0 - 128 is the byte d itself read as i8, and
+            // digit 1 = b1 is its top bit -- the same digits as below
+            const v4u wd = *reinterpret_cast<const v4u*>(dtile8(set) + rowpass_image_dword(m16, 4 * q));
+            const v4i c0 = {(int)wd.x, (int)wd.y, (int)wd.z, (int)wd.w};
+#pragma unroll
+            for (int t = 0; t < 7; ++t) mw[t] = __builtin_amdgcn_mfma_i32_16x16x64_i8(c0, pdg[t], mw[t], 0, 0, 0);
+            if (nd == 2) {
+                const v4i c1 = {(int)((wd.x >> 7) & 0x01010101u), (int)((wd.y >> 7) & 0x01010101u),
+                                (int)((wd.z >> 7) & 0x01010101u), (int)((wd.w >> 7) & 0x01010101u)};
+#pragma unroll
+                for (int t = 0; t < 7; ++t) mw[t + 1] = __builtin_amdgcn_mfma_i32_16x16x64_i8(c1, pdg[t], mw[t + 1], 0, 0, 0);
+            }
+        } else {
             // A: counts [row m16][samples 16 q .. 16 q + 15] as balanced digits: d + 128 = b0 + 256 b1, digit 0 = b0 - 128
             // (b0 ^ 0x80 as i8), digit 1 = b1
             const v4u wa = *reinterpret_cast<const v4u*>(tileD + m16 * kRowD + 16 * q);
@@ -802,14 +847,47 @@ __global__ __launch_bounds__(64 * MAXW, MAXW == 4 ? 2 : 1) void k_rowpass_v2(
     }
 }
 
-size_t rowpass_v2_lds_bytes(int S, int n_u, int n_iter2, bool x16, bool pair = false, bool defer_c = false) {
+// The byte images of a problem (dmf_rowpass_image.h), once per problem: a thread gathers one 16-byte piece of an image of X8
+// and of D8 -- 16 consecutive samples of one row, the low bytes of two 16-byte loads of X16 / D16 (every element <= 255).
+// pieces = N16 * SD / 16: piece (block, column group, l) is thread (block * SD / 64 + group) * 64 + l.
+__global__ __launch_bounds__(256) void k_build_rowpass_images(const unsigned short* __restrict__ X16, const unsigned short* __restrict__ D16,
+                                                              int SD, int64_t pieces, unsigned char* __restrict__ X8,
+                                                              unsigned char* __restrict__ D8) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= pieces) return;
+    const int l = (int)(i & 63), groups = SD >> 6;
+    const int64_t img = i >> 6, blk = img / groups;
+    const int g = (int)(img - blk * groups);
+    const int64_t src = (blk * 16 + rowpass_image_piece_row(l)) * SD + g * 64 + 16 * rowpass_image_piece_col(l);
+    auto pack = [&](const unsigned short* __restrict__ a) {
+        const v4u lo = *reinterpret_cast<const v4u*>(a + src), hi = *reinterpret_cast<const v4u*>(a + src + 8);
+        return v4u{__builtin_amdgcn_perm(lo.y, lo.x, 0x06040200u), __builtin_amdgcn_perm(lo.w, lo.z, 0x06040200u),
+                   __builtin_amdgcn_perm(hi.y, hi.x, 0x06040200u), __builtin_amdgcn_perm(hi.w, hi.z, 0x06040200u)};
+    };
+    *reinterpret_cast<v4u*>(X8 + i * 16) = pack(X16);
+    *reinterpret_cast<v4u*>(D8 + i * 16) = pack(D16);
+}
+
+hipError_t launch_build_rowpass_images(const unsigned short* X16, const unsigned short* D16, int64_t N16, int SD,
+                                       unsigned char* X8, unsigned char* D8, hipStream_t st) {
+    if (X16 == nullptr || D16 == nullptr || X8 == nullptr || D8 == nullptr || N16 < 16 || (N16 & 15) != 0 || SD < 64 || (SD & 63) != 0)
+        return hipErrorInvalidValue;
+    const int64_t pieces = N16 * SD / 16;
+    const int64_t grid = (pieces + 255) / 256;
+    if (grid > 0x7FFFFFFF) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_build_rowpass_images, dim3((unsigned)grid), dim3(256), 0, st, X16, D16, SD, pieces, X8, D8);
+    return hipGetLastError();
+}
+
+size_t rowpass_v2_lds_bytes(int S, int n_u, int n_iter2, bool x16, bool pair = false, bool defer_c = false, bool bytes = false) {
     const int NW = (S + 63) / 64;
     const int maxw = NW <= 4 ? 4 : 8;
     const int nset = pair ? 2 : 1;
     const int nub = defer_c ? kDeferUbufSets : nset;
     const int nv = n_u * ((n_u + 2) & ~1);  // a row's partial-sum slots (k_rowpass_v2: NV)
     const size_t doubles = (size_t)((n_iter2 + 1) & ~1) + (size_t)nub * 16 * n_u + (size_t)nset * maxw * nv * 16 + maxw;
-    const int tile = defer_c ? kTileDBytes2 : (x16 ? kTileBytesX : kTileBytes2);  // (deferred C: x stands in the ring only)
+    // (deferred C: x stands in the ring only; its byte form: the counts as the 1 KB image)
+    const int tile = bytes ? kTileDBytes8 : defer_c ? kTileDBytes2 : (x16 ? kTileBytesX : kTileBytes2);
     return doubles * sizeof(double) + (size_t)nset * NW * tile + (defer_c ? (size_t)NW * kRingBytes : 0);
 }
 
@@ -840,6 +918,8 @@ bool rowpass_v2_pair_fits(int S, int n_u, int n_iter2) {
 // out in): 70 848 B at n_u = 4 and 20 inner steps -- the ring of three pairs costs 24 KB, the x tiles it replaces 18 KB.
 // The instances <NKC = 4, NU = 3 or 4> (13..16 known types with three or four unknowns) would spill a register on this
 // schedule (tools/kernel_regs.sh --x16): they are not built and keep the pair schedule.
+// The byte form (BYTES) is the same schedule with 1 KB count tiles instead of 2.25 KB: 60 KB at the same shape, so it fits
+// wherever the u16 form does.
 constexpr bool rowpass_v2_defer_instance(int nkc, int nu) { return !(nkc == 4 && nu >= 3); }
 bool rowpass_v2_defer_fits(int S, int n_c, int n_u, int n_iter2) {
     const int NW = (S + 63) / 64;
@@ -856,7 +936,7 @@ int rowpass_v2_grid(int64_t N, int S) {
 }
 
 hipError_t launch_rowpass_v2(const ProblemView& p, const IterateView& it, int n_iter2, const UScratch& scratch, int* grid_out,
-                             bool pair, bool* paired_out, bool defer_c, bool* deferred_out, hipStream_t st) {
+                             bool pair, bool* paired_out, bool defer_c, bool* deferred_out, bool* bytes_out, hipStream_t st) {
     const int S = p.S, NW = (S + 63) / 64;
     // the pair schedule where it applies (rowpass_v2_pair_fits), else one block per barrier cycle
     pair = pair && p.X16 != nullptr && rowpass_v2_pair_fits(S, it.n_u, n_iter2);
@@ -864,14 +944,18 @@ hipError_t launch_rowpass_v2(const ProblemView& p, const IterateView& it, int n_
     // ... with phase C deferred where that applies (the caller vouches for x <= 255 with `defer_c`)
     defer_c = defer_c && pair && rowpass_v2_defer_fits(S, p.n_c, it.n_u, n_iter2);
     if (deferred_out != nullptr) *deferred_out = defer_c;
+    // ... from the byte images where the problem carries them (built only where every count is <= 255 at 193..256 samples)
+    const bool bytes = defer_c && p.X8 != nullptr && p.D8 != nullptr;
+    if (bytes_out != nullptr) *bytes_out = bytes;
     return dispatch_int<0, 4>((p.n_c + 3) / 4, [&](auto nkc) {
         return dispatch_bool(p.X16 != nullptr, [&](auto xs) {
             return dispatch_int<1, 4>(it.n_u, [&](auto nu) {
-                const auto launch = [&](auto maxw, auto pair_t, auto defer_t) {
+                const auto launch = [&](auto maxw, auto pair_t, auto defer_t, auto bytes_t) {
                     constexpr int NU = decltype(nu)::value, MAXW = decltype(maxw)::value;
                     constexpr bool XS = decltype(xs)::value, PAIR = decltype(pair_t)::value, DEFER_C = decltype(defer_t)::value;
-                    constexpr auto kernel = k_rowpass_v2<decltype(nkc)::value, NU, MAXW, XS, PAIR, DEFER_C>;
-                    const size_t lds = rowpass_v2_lds_bytes(S, NU, n_iter2, XS, PAIR, DEFER_C);
+                    constexpr bool BYTES = decltype(bytes_t)::value;
+                    constexpr auto kernel = k_rowpass_v2<decltype(nkc)::value, NU, MAXW, XS, PAIR, DEFER_C, BYTES>;
+                    const size_t lds = rowpass_v2_lds_bytes(S, NU, n_iter2, XS, PAIR, DEFER_C, BYTES);
                     constexpr size_t kLdsCap = (size_t)(MAXW == 4 ? 80 : 160) * 1024;
                     if (NW > MAXW || (MAXW == 8 && NW <= 4) || (PAIR && NW < 2) || (DEFER_C && NW != 4) || lds > kLdsCap || p.N < 1 ||
                         p.SD < NW * 64 || (p.SD & 7) != 0 || p.ND < 1 || p.ND > 2)
@@ -882,7 +966,8 @@ hipError_t launch_rowpass_v2(const ProblemView& p, const IterateView& it, int n_
                     }
                     const int grid = rowpass_v2_grid(p.N, S);
                     *grid_out = grid;
-                    hipLaunchKernelGGL(kernel, dim3(grid), dim3(NW * 64), lds, st, p.V, p.D16, p.X16, p.SD, p.Rtp, it.alpha,
+                    hipLaunchKernelGGL(kernel, dim3(grid), dim3(NW * 64), lds, st, p.V, BYTES ? reinterpret_cast<const unsigned short*>(p.D8) : p.D16,
+                                       BYTES ? reinterpret_cast<const unsigned short*>(p.X8) : p.X16, p.SD, p.Rtp, it.alpha,
                                        it.u, it.u_prev, it.state, p.N, S, p.n_c, n_iter2, it.mode, p.ND, scratch.slab,
                                        scratch.u2_partials
 #ifdef DMF_STAMPS
@@ -892,14 +977,15 @@ hipError_t launch_rowpass_v2(const ProblemView& p, const IterateView& it, int n_
                     return hipGetLastError();
                 };
                 // more than 256 samples: one workgroup of up to eight waves; the pair leg only on X16
-                if (S > 256) return launch(std::integral_constant<int, 8>{}, std::false_type{}, std::false_type{});
+                if (S > 256) return launch(std::integral_constant<int, 8>{}, std::false_type{}, std::false_type{}, std::false_type{});
                 if constexpr (decltype(xs)::value) {
                     if constexpr (rowpass_v2_defer_instance(decltype(nkc)::value, decltype(nu)::value)) {
-                        if (pair && defer_c) return launch(std::integral_constant<int, 4>{}, std::true_type{}, std::true_type{});
+                        if (pair && defer_c && bytes) return launch(std::integral_constant<int, 4>{}, std::true_type{}, std::true_type{}, std::true_type{});
+                        if (pair && defer_c) return launch(std::integral_constant<int, 4>{}, std::true_type{}, std::true_type{}, std::false_type{});
                     }
-                    if (pair) return launch(std::integral_constant<int, 4>{}, std::true_type{}, std::false_type{});
+                    if (pair) return launch(std::integral_constant<int, 4>{}, std::true_type{}, std::false_type{}, std::false_type{});
                 }
-                return launch(std::integral_constant<int, 4>{}, std::false_type{}, std::false_type{});
+                return launch(std::integral_constant<int, 4>{}, std::false_type{}, std::false_type{}, std::false_type{});
             });
         });
     });

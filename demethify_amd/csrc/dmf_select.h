@@ -26,6 +26,7 @@ struct ShapeKey {
     bool x16 = false;          // the problem carries X16 (the row pass reads x = d v as u16 instead of V)
     bool rowpass_pair = true;  // k_rowpass_v2 may run two blocks per phase B (X16 form; same kernel name, same results)
     bool rowpass_defer_c = true;  // ... and phase C deferred (four waves, x_byte; same results)
+    bool rowpass_bytes = true;    // ... from the problem's byte images where it has them (same results; not in the text)
     bool x_byte = false;       // every count of the problem, so every x, is at most 255
     int level = 0;             // kernel selection level (dmf_context_set_generic): 0 fastest .. 4
     bool d_f32_exact = false;  // every count survives a round trip through f32

@@ -115,6 +115,12 @@ class Context:
         at most 255).  On by default; off for A/B runs and tests.  Both forms compute the same results bit for bit."""
         L.check(self._lib.dmf_context_set_rowpass_defer_c(self._h, int(bool(enabled))), "dmf_context_set_rowpass_defer_c")
 
+    def set_rowpass_bytes(self, enabled: bool):
+        """Whether Solvers created from now on run the deferred-C schedule from the problem's byte images (one byte per
+        element of x and of the counts instead of two) where it has them.  On by default; off for A/B runs and tests.  Both
+        forms compute the same results bit for bit."""
+        L.check(self._lib.dmf_context_set_rowpass_bytes(self._h, int(bool(enabled))), "dmf_context_set_rowpass_bytes")
+
     def set_stop_confirmation(self, mode: int):
         """How step() decides |cf - cf_0| < tol: 0 (default) Gram-form cost, confirmed on the streaming cost where the
         Gram form's error bound reaches tol / 20; 1 always on streaming costs near the threshold; 2 Gram form only."""
@@ -432,6 +438,23 @@ class Problem:
         }[name]
         out = np.empty(shape, dtype=dtype)
         L.check(self._lib.dmf_problem_copy_out(self._h, L.PROBLEM_ARRAYS[name], _ptr(out), out.nbytes),
+                "dmf_problem_copy_out")
+        return out
+
+    def has_byte_images(self) -> bool:
+        """Whether this problem carries the byte images X8 / D8 of its X16 / D16 that the row pass's deferred-C schedule streams
+        (X16 present, every count <= 255, 193 <= S <= 256) -- dmf_problem_has_byte_images."""
+        out = C.c_int()
+        L.check(self._lib.dmf_problem_has_byte_images(self._h, C.byref(out)), "dmf_problem_has_byte_images")
+        return bool(out.value)
+
+    def copy_out_image(self, name: str, report: dict | None = None) -> np.ndarray:
+        """One byte image of this problem, "X8" or "D8" (``_lib.PROBLEM_BYTE_IMAGES``), as (N16 / 16, SD / 64, 1024) uint8
+        indexed [16-row block, 64-sample column group, dmf_rowpass_image_offset(row, sample)] (dmf_problem_copy_out;
+        DMF_ERR_BAD_ARG where the problem has none).  For tests."""
+        r = self.report() if report is None else report
+        out = np.empty((r["N16"] // 16, r["SD"] // 64, 1024), dtype=np.uint8)
+        L.check(self._lib.dmf_problem_copy_out(self._h, L.PROBLEM_BYTE_IMAGES[name], _ptr(out), out.nbytes),
                 "dmf_problem_copy_out")
         return out
 
@@ -858,6 +881,12 @@ class Solver:
         L.check(self._lib.dmf_solver_rowpass_launches(self._h, C.byref(total), C.byref(paired)),
                 "dmf_solver_rowpass_launches")
         return total.value, paired.value
+
+    def rowpass_byte_launches(self):
+        """How many of the deferred-C launches so far read the problem's byte images -- dmf_solver_rowpass_byte_launches."""
+        n = C.c_int64()
+        L.check(self._lib.dmf_solver_rowpass_byte_launches(self._h, C.byref(n)), "dmf_solver_rowpass_byte_launches")
+        return n.value
 
     def rowpass_schedule_counts(self):
         """(k_rowpass_v2 launches so far, of them on the pair schedule, of those with phase C deferred) --

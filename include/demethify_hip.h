@@ -110,6 +110,10 @@ int dmf_context_set_rowpass_pair(dmf_context* ctx, int enabled);
  * problem is at most 255 and two workgroups with the schedule's x ring still fit a CU's LDS; 0: the pair schedule as it is.
  * Both compute the same results bit for bit.  Tests and A/B runs. */
 int dmf_context_set_rowpass_defer_c(dmf_context* ctx, int enabled);
+/* 1 (default): solvers created from now on run the deferred-C schedule from the problem's byte images where it has them
+ * (dmf_problem_has_byte_images): x and the counts stream as one byte per element, in the order the kernel's LDS holds them,
+ * instead of two; 0: from X16 / D16.  Both compute the same results bit for bit.  Tests and A/B runs. */
+int dmf_context_set_rowpass_bytes(dmf_context* ctx, int enabled);
 /* How dmf_solver_step decides |cf - cf_0| < tol (deconvolution.py:218-220) for the solvers of this context:
  * 0 (default) = on the Gram-form cost of the loop, with the decisions near the threshold confirmed on the streaming
  * cost of deconvolution.py:15-17 where the Gram form's error bound (1e-15 N S max(counts)) reaches tol / 20;
@@ -162,16 +166,22 @@ int dmf_problem_gram_known(const dmf_problem* p, double* out, char* out_text, in
  * order of DMF_ARRAY_CONSTS, then x16_dev and x16_sum.  No address leaves the library.  DMF_ERR_BAD_ARG on a null pointer. */
 enum { DMF_REPORT_INTS = 16, DMF_REPORT_DBLS = 8 };
 int dmf_problem_report(const dmf_problem* p, int64_t* out_ints, double* out_dbls);
+/* *out <- 1 when the problem carries the byte images X8 / D8 of its X16 / D16 (built by create, gather and mask alike when the
+ * problem has X16, every count is at most 255 and 193 <= S <= 256: two more bytes per padded element), else 0. */
+int dmf_problem_has_byte_images(const dmf_problem* p, int* out);
+/* Where (row, sample) of a 16-row block and a 64-sample column group stands in its 1024-byte image; -1 outside 0..15 x 0..63.
+ * A pure function, no GPU is touched.  The images: X8, D8 [N16 / 16][SD / 64][1024] bytes, the low bytes of X16 / D16. */
+int dmf_rowpass_image_offset(int row, int sample);
 /* One array of a problem as it stands on the device, for tests: waits for the context's stream and copies `bytes` bytes to the
  * host buffer `out`.  `bytes` must be the array's size (DMF_ERR_BAD_SHAPE otherwise): V, D N x S doubles; RT N x n_c; RTP
  * N x 4 ceil(n_c / 4) doubles (R_trunc itself where the report says so); D16, X16, W16 N16 x SD u16; DT8 ND planes of
- * plane_stride bytes, [plane][row block of 32][sample block of 32][n][k]; MASK_BITS N x ceil(S / 8) bytes; CONSTS the
+ * plane_stride bytes, [plane][row block of 32][sample block of 32][n][k]; X8, D8 N16 x SD bytes (dmf_rowpass_image_offset); MASK_BITS N x ceil(S / 8) bytes; CONSTS the
  * device copy of the constants, six doubles: max(D)^2, ||Rt||_F^2, max(D), max |D - f32(D)|, max(D) if every count is a
  * non-negative integer else inf, 1 if R_trunc leaves [0, 1] else 0.  DMF_ERR_BAD_ARG for an array the problem does not have,
  * an unknown name or a null pointer. */
 enum {
     DMF_ARRAY_V = 0, DMF_ARRAY_D = 1, DMF_ARRAY_RT = 2, DMF_ARRAY_RTP = 3, DMF_ARRAY_D16 = 4, DMF_ARRAY_X16 = 5,
-    DMF_ARRAY_W16 = 6, DMF_ARRAY_DT8 = 7, DMF_ARRAY_MASK_BITS = 8, DMF_ARRAY_CONSTS = 9
+    DMF_ARRAY_W16 = 6, DMF_ARRAY_DT8 = 7, DMF_ARRAY_MASK_BITS = 8, DMF_ARRAY_CONSTS = 9, DMF_ARRAY_X8 = 10, DMF_ARRAY_D8 = 11
 };
 int dmf_problem_copy_out(const dmf_problem* p, int which, void* out, int64_t bytes);
 
@@ -434,6 +444,8 @@ int dmf_solver_rowpass_launches(const dmf_solver* s, int64_t* total, int64_t* pa
 /* The same, and how many of the paired launches ran the deferred-C schedule (deferred; see
  * dmf_context_set_rowpass_defer_c).  Any pointer may be NULL. */
 int dmf_solver_rowpass_schedule_counts(const dmf_solver* s, int64_t* total, int64_t* paired, int64_t* deferred);
+/* How many of the deferred launches read the problem's byte images (see dmf_context_set_rowpass_bytes). */
+int dmf_solver_rowpass_byte_launches(const dmf_solver* s, int64_t* bytes);
 /* One-shot convenience: create + step(n_iter1) + get + destroy. */
 int dmf_solve(dmf_context* ctx, const dmf_problem* p, const double* u0, const double* alpha0,
               int64_t n_u, int mode, int64_t n_iter1, int64_t n_iter2, double tol, int flags,

@@ -1,7 +1,7 @@
 #!/bin/bash
 # kernel_regs.sh <file.hip> [name filter] [extra hipcc flags...]: registers / spills / occupancy per kernel (compiler remarks, no GPU)
 # kernel_regs.sh --x16 [extra hipcc flags...]: every X16 instance of k_rowpass_v2 -- the 20 pair instances <NKC, NU, 4, true, true>
-#   (<.., true, true, true>: the 18 with phase C deferred) and the one-block ones <NKC, NU, 4 or 8, true, false>; each must show scratch 0, spill 0 / 0, at most 256 VGPRs and, at
+#   (<.., true, true, true, false>: the 18 with phase C deferred; <.., true, true, true, true>: their byte form) and the one-block ones <NKC, NU, 4 or 8, true, false>; each must show scratch 0, spill 0 / 0, at most 256 VGPRs and, at
 #   four waves, occupancy >= 2
 if [ "$1" = "--x16" ]; then
   shift

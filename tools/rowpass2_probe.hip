@@ -6,6 +6,9 @@
 //   -DPROBE_DEFER_C (with -DPROBE_X16 -DPROBE_PAIR): phase C deferred into the other waves' phase-B window; the window is then
 //     reported per role and the drain as a segment of its own (the x ring is written by the tile store: no copy to time);
 //     -DDMF_V2_STAGGER_DEFER=n: its stagger, -DDMF_V2_DEFER_PRIO=n: the s_setprio of the deferred phase C
+//   -DPROBE_BYTES (with -DPROBE_X16 -DPROBE_PAIR -DPROBE_DEFER_C): the byte form <.., BYTES> on the images X8 / D8 (built here by
+//     k_build_rowpass_images, which is timed too) beside the u16 deferred-C form of the same source: the launches alternate,
+//     and the stamps are reported for the u16 form first, then for the byte form
 //   -DDMF_CHAIN_NO_UNROLL: the inner steps as a loop at every step count (T2 = 20 otherwise runs them written out)
 //   -DDMF_CHAIN_NO_I32: the M combine with eight conversions per value instead of digit pairs joined in i32
 //   both together: the kernel before either, from this source
@@ -38,6 +41,12 @@ static_assert(kPair, "the deferred-C schedule is a pair schedule");
 #else
 constexpr bool kDefer = false;
 #endif
+#ifdef PROBE_BYTES
+constexpr bool kBytes = true;
+static_assert(kDefer, "the byte form is a deferred-C form");
+#else
+constexpr bool kBytes = false;
+#endif
 #ifndef DMF2_NSTAMP
 #define DMF2_NSTAMP 16
 #endif
@@ -66,6 +75,24 @@ int main(int argc, char** argv) {
     const size_t lds = rowpass_v2_lds_bytes(S, n_u, T2, kXS, kPair, kDefer);
     hipFuncSetAttribute((const void*)k_rowpass_v2<3, 4, 4, kXS, kPair, kDefer>, hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024);
     hipEvent_t e0, e1; hipEventCreate(&e0); hipEventCreate(&e1);
+    // (PROBE_BYTES) the images of X / D (N is a multiple of 16 and S of 64 here: the arrays are their own padded copies), and
+    // stamps of their own for the byte form
+    unsigned char *X8 = nullptr, *D8 = nullptr; unsigned long long* stamps8 = nullptr;
+    size_t lds8 = 0;
+    if constexpr (kBytes) {
+        static_assert(!kBytes || (N % 16 == 0 && S % 64 == 0), "X / D stand in for the padded copies");
+        hipMalloc(&X8, (size_t)N * S); hipMalloc(&D8, (size_t)N * S); hipMalloc(&stamps8, (size_t)grid * 4 * kNS * 8);
+        hipMemset(stamps8, 0, (size_t)grid * 4 * kNS * 8);
+        for (int rep = 0; rep < 3; ++rep) {
+            hipEventRecord(e0);
+            const hipError_t e = launch_build_rowpass_images(X, D, N, S, X8, D8, 0);
+            hipEventRecord(e1); hipEventSynchronize(e1);
+            float ms; hipEventElapsedTime(&ms, e0, e1); printf("k_build_rowpass_images %d: %.3f ms  (%s)\n", rep, ms, hipGetErrorString(e));
+        }
+        lds8 = rowpass_v2_lds_bytes(S, n_u, T2, kXS, kPair, kDefer, true);
+        hipFuncSetAttribute((const void*)k_rowpass_v2<3, 4, 4, kXS, kPair, kDefer, kBytes>, hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024);
+        printf("LDS per workgroup: u16 form %zu B, byte form %zu B\n", lds, lds8);
+    }
     for (int rep = 0; rep < (argc > 3 ? atoi(argv[3]) : 3); ++rep) {
         hipEventRecord(e0);
 #ifdef PROBE_NO_STAMPS
@@ -75,12 +102,24 @@ int main(int argc, char** argv) {
 #endif
         hipEventRecord(e1); hipEventSynchronize(e1);
         float ms; hipEventElapsedTime(&ms, e0, e1); printf("launch %d: %.3f ms  (%s)\n", rep, ms, hipGetErrorString(hipGetLastError()));
+        if constexpr (kBytes) {
+            hipEventRecord(e0);
+#ifdef PROBE_NO_STAMPS
+            hipLaunchKernelGGL((k_rowpass_v2<3, 4, 4, kXS, kPair, kDefer, kBytes>), dim3(grid), dim3(256), lds8, 0, V, (const unsigned short*)D8, (const unsigned short*)X8, 256, R, a, u, up, st, N, S, n_c, T2, 0, 1, slab, u2);
+#else
+            hipLaunchKernelGGL((k_rowpass_v2<3, 4, 4, kXS, kPair, kDefer, kBytes>), dim3(grid), dim3(256), lds8, 0, V, (const unsigned short*)D8, (const unsigned short*)X8, 256, R, a, u, up, st, N, S, n_c, T2, 0, 1, slab, u2, stamps8);
+#endif
+            hipEventRecord(e1); hipEventSynchronize(e1);
+            hipEventElapsedTime(&ms, e0, e1); printf("launch %d, byte form: %.3f ms  (%s)\n", rep, ms, hipGetErrorString(hipGetLastError()));
+        }
     }
 #ifdef PROBE_NO_STAMPS
     return 0;
 #endif
     std::vector<unsigned long long> hs((size_t)grid * 4 * kNS);
-    hipMemcpy(hs.data(), stamps, hs.size() * 8, hipMemcpyDeviceToHost);
+  for (int form = 0; form < (kBytes ? 2 : 1); ++form) {
+    if (kBytes) printf("---- %s\n", form == 0 ? "u16 deferred-C form" : "byte form");
+    hipMemcpy(hs.data(), form == 0 ? stamps : stamps8, hs.size() * 8, hipMemcpyDeviceToHost);
     const char* an[16] = {"tile store (vmcnt wait)", "phase A (MFMA)", "partials", "wait X", "phase B / nothing", "wait Y", "phase C", "prefetch issue", "B: partial sums", "B: inner steps", "B: stores", "phase A, 2nd block", "partials, 2nd block", "phase C, 2nd block", "-", "-"};
     double sum[20] = {0}; int cnt = 0;
     for (int b = 0; b < grid; ++b) for (int w = 0; w < 4; ++w) { for (int i = 0; i < kNS; ++i) if (i != 15) sum[i] += (double)hs[((size_t)b * 4 + w) * kNS + i]; ++cnt; }
@@ -115,5 +154,6 @@ int main(int argc, char** argv) {
         adjacent_apart += ok;
     }
     printf("SIMD placement (HW_ID): %d of %d workgroups have their four waves on four SIMDs, %d have waves w, w + 1 apart\n", distinct, grid, adjacent_apart);
+  }
     return 0;
 }
