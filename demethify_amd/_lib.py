@@ -15,6 +15,7 @@ DMF_PTR_DEVICE = 1
 DMF_INIT_IN_UNIT_RANGE = 4
 DMF_SELECT_COUNTS_F32_EXACT, DMF_SELECT_PURITY, DMF_SELECT_ALPHA_OUTSIDE_UNIT, DMF_SELECT_V_UNALIGNED = 1, 2, 4, 8
 DMF_SELECT_X16 = 16
+DMF_SELECT_COUNTS_BYTE, DMF_SELECT_NO_ROWPASS_PAIR, DMF_SELECT_NO_ROWPASS_DEFER_C, DMF_SELECT_NO_ROWPASS_BYTES = 32, 64, 128, 256
 DMF_COUNTS_F64 = 2
 DMF_WLS_TARGET_V, DMF_WLS_TARGET_DV = 0, 1
 DMF_WLS_F64_ARRAYS = 8

@@ -197,7 +197,7 @@ struct dmf_problem {
     dmf_api::DevBuf<unsigned short> X16;
     double x16_dev = 0.0, x16_sum = 0.0;
     // byte images of X16 / D16 ([N16 / 16][SD / 64][1024], dmf_rowpass_image.h) for the row pass's deferred-C schedule: built
-    // (build_rowpass_images) when the problem can run it at all -- X16, every count <= 255, 193..256 samples
+    // (build_rowpass_images) where dmf::rowpass_v2_byte_images_wanted: some plan of the problem reads them
     dmf_api::DevBuf<unsigned char> X8, D8;
     bool d_f32_exact = false;    // every count survives a round trip through f32 (the fused tile stores D as f32)
     dmf_api::DevBuf<double> gb_known;  // [(n_c+1)(n_c+2)/2][S]
@@ -270,9 +270,8 @@ struct dmf_solver {
     bool confirm_stops = false;
     double cf_stream = 0.0;
     long long cf_stream_iter = -1;
-    long long n_rowpass = 0, n_rowpass_pair = 0;  // k_rowpass_v2 launches so far / of them on the pair schedule
-    long long n_rowpass_defer = 0;                // ... / of those with phase C deferred
-    long long n_rowpass_bytes = 0;                // ... / of those from the problem's byte images
+    // k_rowpass_v2 launches so far, by dmf::RowpassSchedule: on that schedule or one built on it ([One]: all of them)
+    long long n_rowpass[dmf::kRowpassSchedules] = {};
     long long n_confirmed = 0, n_unconfirmed = 0;  // stop tests decided on streaming costs / on the Gram form inside the band
     // the iterate and the u phases' scratch as the launch wrappers take them (dmf_internal.h)
     dmf::IterateView iterate() const {

@@ -63,6 +63,10 @@ static int select_key(int64_t N, int64_t S, int64_t n_c, int64_t n_u, int nd, in
     key.rtp_present = true;
     key.v_align = (flags & DMF_SELECT_V_UNALIGNED) ? 8 : 0;
     key.x16 = key.nd > 0 && (flags & DMF_SELECT_X16) != 0;
+    key.x_byte = key.x16 && (flags & DMF_SELECT_COUNTS_BYTE) != 0;
+    key.rowpass_pair = !(flags & DMF_SELECT_NO_ROWPASS_PAIR);
+    key.rowpass_defer_c = !(flags & DMF_SELECT_NO_ROWPASS_DEFER_C);
+    key.rowpass_bytes = !(flags & DMF_SELECT_NO_ROWPASS_BYTES);
     key.rtp_align = 0;
     key.alpha_unit = !(flags & DMF_SELECT_ALPHA_OUTSIDE_UNIT);
     return DMF_OK;
@@ -86,7 +90,7 @@ int dmf_select_describe(int64_t N, int64_t S, int64_t n_c, int64_t n_u, int nd, 
     const dmf::PathSpec spec = dmf::select_path(key);
     if (!spec.supported) return DMF_ERR_UNSUPPORTED;
     const dmf::IterationPlan plan = dmf::plan_iteration(key, spec, (int)n_iter2, (flags & DMF_SELECT_PURITY) != 0);
-    dmf::describe_plan(key, plan, buf, (size_t)cap);
+    dmf::describe_plan(key, plan, (int)n_iter2, buf, (size_t)cap);
     return DMF_OK;
 }
 

@@ -20,13 +20,14 @@ static int alloc_count_copies(dmf_problem* p, int ND, bool x16, bool w16) {
     return DMF_OK;
 }
 
-// The byte images X8 / D8 of the problem's X16 / D16, where the problem can run the row pass's deferred-C schedule at all: X16
-// present, every count (so every x) at most 255, four column groups of which the last is not empty.  Called by
+// The byte images X8 / D8 of the problem's X16 / D16, where some launch plan of the row pass reads them
+// (dmf::rowpass_v2_byte_images_wanted).  Called by
 // problem_finalize once the integer copies and the largest count stand, so for every problem that is created, gathered or
 // masked -- a masked problem's X16 / D16 carry the masked counts, and so do its images.
 static int build_rowpass_images(dmf_problem* p) {
     dmf_context* ctx = p->ctx;
-    if (p->X16 == nullptr || p->D16 == nullptr || !(p->h_consts[kIntCountMax] <= 255.0) || p->S < 193 || p->S > 256) return DMF_OK;
+    const bool x16 = p->X16 != nullptr && p->D16 != nullptr;
+    if (!dmf::rowpass_v2_byte_images_wanted((int)p->S, x16, p->h_consts[kIntCountMax])) return DMF_OK;
     const size_t bytes = (size_t)p->N16 * p->SD;
     HIP_TRY(p->X8.alloc(ctx, bytes));
     HIP_TRY(p->D8.alloc(ctx, bytes));

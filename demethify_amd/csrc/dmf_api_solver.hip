@@ -166,21 +166,13 @@ static int enqueue_outer_iteration(dmf_solver* s, int n_iter2) {
         // Second generation: one read of V (f64) -- or of the u16 methylated read counts X16 -- and of the u16 counts for
         // the u phase and b_u, then the exact
         // integer-matrix-core GEMM for the u-dependent Gram entries on the 8-bit count planes.
-        int grid = 0;
-        bool paired = false, deferred = false, bytes = false;
+        const dmf::RowpassV2Plan rp = dmf::rowpass_v2_plan(s->key, n_iter2);
         {
             FamilyScope scope(ctx, DMF_KERNEL_ROWPASS);
-            dmf::ProblemView pv = p->view();
-            if (!s->key.x16) pv.X16 = nullptr;
-            if (!s->key.rowpass_bytes) pv.X8 = nullptr, pv.D8 = nullptr;
-            HIP_TRY(dmf::launch_rowpass_v2(pv, s->iterate(), n_iter2, s->scratch(), &grid, s->key.rowpass_pair, &paired,
-                                           s->key.rowpass_defer_c && s->key.x_byte, &deferred, &bytes, ctx->stream));
-            ++s->n_rowpass;
-            s->n_rowpass_pair += paired ? 1 : 0;
-            s->n_rowpass_defer += deferred ? 1 : 0;
-            s->n_rowpass_bytes += bytes ? 1 : 0;
+            HIP_TRY(dmf::launch_rowpass_v2(p->view(), s->iterate(), n_iter2, s->scratch(), rp, ctx->stream));
+            for (int i = 0; i <= (int)rp.schedule(); ++i) ++s->n_rowpass[i];  // (each schedule is a form of the one before)
         }
-        return enqueue_gram_i8_tail(s, plan.alpha, n_iter2, grid);
+        return enqueue_gram_i8_tail(s, plan.alpha, n_iter2, rp.grid);
     }
     if (plan.row == dmf::RowKind::CmI8InnerBu) {
         // Wide row groups on u16 counts: c_i / M_i (M_i on the integer matrix cores), then the inner iterations fused with
@@ -330,7 +322,7 @@ static int solver_setup(dmf_solver* s, const double* u0, const double* alpha0, i
     key.rowpass_pair = ctx->rowpass_pair;
     key.rowpass_defer_c = ctx->rowpass_defer_c;
     key.rowpass_bytes = ctx->rowpass_bytes;
-    key.x_byte = key.x16 && p->h_consts[kIntCountMax] <= 255.0;  // (0 <= x <= d for every element of X16)
+    key.x_byte = key.x16 && dmf::rowpass_v2_counts_fit_bytes(p->h_consts[kIntCountMax]);  // (0 <= x <= d for every element of X16)
     key.level = ctx->generic_level;
     key.d_f32_exact = p->d_f32_exact;
     key.rtp_present = n_c == 0 || p->Rtp != nullptr;
@@ -383,7 +375,7 @@ static int solver_setup(dmf_solver* s, const double* u0, const double* alpha0, i
         if (spec > s->slab_doubles) s->slab_doubles = spec;
     }
     if (s->spec.use_v2) {
-        const int64_t bu = (int64_t)dmf::rowpass_v2_grid(N, (int)S) * n_u * S;
+        const int64_t bu = (int64_t)dmf::rowpass_v2_plan(key, dmf::kSizingInnerSteps).grid * n_u * S;  // (the same at every step count)
         if (bu > s->slab_doubles) s->slab_doubles = bu;
     }
     if (s->spec.use_gram_i8) {
@@ -770,7 +762,7 @@ int dmf_solver_destroy(dmf_solver* s) {
 int dmf_solver_describe(const dmf_solver* s, int64_t n_iter2, char* buf, int64_t cap) {
     if (s == nullptr || buf == nullptr || cap < 1 || n_iter2 < 0) return DMF_ERR_BAD_ARG;
     const dmf::IterationPlan plan = dmf::plan_iteration(s->key, s->spec, (int)n_iter2, s->purity != nullptr);
-    dmf::describe_plan(s->key, plan, buf, (size_t)cap);
+    dmf::describe_plan(s->key, plan, (int)n_iter2, buf, (size_t)cap);
     return DMF_OK;
 }
 
@@ -793,23 +785,20 @@ int dmf_solver_stop_info(const dmf_solver* s, int* confirm_stops, int64_t* n_con
 }
 
 int dmf_solver_rowpass_launches(const dmf_solver* s, int64_t* total, int64_t* paired) {
-    if (s == nullptr) return DMF_ERR_BAD_ARG;
-    if (total) *total = s->n_rowpass;
-    if (paired) *paired = s->n_rowpass_pair;
-    return DMF_OK;
+    return dmf_solver_rowpass_schedule_counts(s, total, paired, nullptr);
 }
 
 int dmf_solver_rowpass_schedule_counts(const dmf_solver* s, int64_t* total, int64_t* paired, int64_t* deferred) {
     if (s == nullptr) return DMF_ERR_BAD_ARG;
-    if (total) *total = s->n_rowpass;
-    if (paired) *paired = s->n_rowpass_pair;
-    if (deferred) *deferred = s->n_rowpass_defer;
+    if (total) *total = s->n_rowpass[(int)dmf::RowpassSchedule::One];
+    if (paired) *paired = s->n_rowpass[(int)dmf::RowpassSchedule::Pair];
+    if (deferred) *deferred = s->n_rowpass[(int)dmf::RowpassSchedule::Deferred];
     return DMF_OK;
 }
 
 int dmf_solver_rowpass_byte_launches(const dmf_solver* s, int64_t* bytes) {
     if (s == nullptr || bytes == nullptr) return DMF_ERR_BAD_ARG;
-    *bytes = s->n_rowpass_bytes;
+    *bytes = s->n_rowpass[(int)dmf::RowpassSchedule::Bytes];
     return DMF_OK;
 }
 

@@ -230,12 +230,27 @@ struct UStepDirectPlan : RowLaunch {  // k_u_step_direct, one launch per inner s
     int n_u = 0;
 };
 UStepDirectPlan u_step_direct_plan(int64_t N, int S, int n_c, int n_u);
-// "k_u_phase_mfma<2,3,vec,d16> split nw=2 grid=512 lds=6912 raise=0 blocks/wg=3"
+// The second-generation row pass (dmf_kernels_rowpass2.hip): the same contract, from the solver's ShapeKey -- the plan
+// reads N, S, n_c, n_u, nd, SD, x16, x_byte and the three rowpass_* switches.  supported is checked on the V form's LDS
+// (the X16 forms need less); lds is the launched form's.
+enum class RowpassSchedule { One, Pair, Deferred, Bytes };  // one block per barrier cycle / two / phase C deferred / ... on bytes
+constexpr int kRowpassSchedules = 4;
+struct RowpassV2Plan : RowLaunch {  // k_rowpass_v2<NKC,NU,MAXW,XS,PAIR,DEFER_C,BYTES>; row block = 16 rows
+    int nkc = 0, nu = 0, maxw = 4;
+    bool xs = false, pair = false, defer_c = false, bytes = false;
+    int64_t N = 0;  // the problem and step count it was made for (the launcher takes no other)
+    int S = 0, n_c = 0, SD = 0, nd = 0, n_iter2 = 0;
+    RowpassSchedule schedule() const { return RowpassSchedule(pair + defer_c + bytes); }  // (bytes implies defer_c implies pair)
+};
+RowpassV2Plan rowpass_v2_plan(const ShapeKey& k, int n_iter2);
+// "k_u_phase_mfma<2,3,vec,d16> split nw=2 grid=512 lds=6912 raise=0 blocks/wg=3"; the row pass's plan goes behind its
+// rowpass= text: "maxw=4 bytes nw=4 grid=512 lds=61440 raise=1 blocks/wg=123"
 int describe_row_launch(const UPhaseMfmaPlan& g, char* buf, size_t cap);
 int describe_row_launch(const RowpassFusedPlan& g, char* buf, size_t cap);
 int describe_row_launch(const UPhaseBigPlan& g, char* buf, size_t cap);
 int describe_row_launch(const UPhaseGramPlan& g, char* buf, size_t cap);
 int describe_row_launch(const UStepDirectPlan& g, char* buf, size_t cap);
+int describe_row_launch(const RowpassV2Plan& g, char* buf, size_t cap);
 
 // u phase, Gram form (n_u <= 8): all n_iter2 inner iterations in one launch
 hipError_t launch_u_phase_gram(const ProblemView& p, const IterateView& it, int n_iter2, hipStream_t st);
@@ -371,19 +386,19 @@ hipError_t launch_holdout_weights_f64(const unsigned char* bits, double* W, int6
 constexpr int64_t kMaskDrawMaxS = ((int64_t)1 << 31) - 1, kMaskDrawMaxElements = (int64_t)1 << 60;
 hipError_t launch_mask_draw(unsigned int* key_io, int pos, int64_t N, int64_t S, unsigned long long threshold,
                             unsigned char* bits, unsigned long long* result, hipStream_t st);
-bool rowpass_v2_supported(int S, int n_c, int n_u, int n_iter2);
-int rowpass_v2_grid(int64_t N, int S);
-// u phase + b_u slab (scratch.slab: [grid][n_u][S] doubles) + per-workgroup ||u||^2 shares in one read of V (f64) and
-// D16 -- or, when p.X16 is not null, of X16 and D16 (V is not read).  pair: two blocks per phase B where the X16 form allows
-// it (rowpass_v2_pair_fits); the same results bit for bit.  *paired_out (may be null): whether the pair schedule was launched;
-// defer_c / *deferred_out: the same for its deferred-C form; *bytes_out: whether that read the byte images p.X8 / p.D8
-hipError_t launch_rowpass_v2(const ProblemView& p, const IterateView& it, int n_iter2, const UScratch& scratch, int* grid_out,
-                             bool pair, bool* paired_out, bool defer_c, bool* deferred_out, bool* bytes_out, hipStream_t st);
+// u phase + b_u slab (scratch.slab: [plan.grid][n_u][S] doubles) + per-workgroup ||u||^2 shares in one read of V (f64)
+// and D16 -- or, on the plan's X16 form, of X16 and D16 (V is not read) or of their byte images X8 / D8.  Every schedule of
+// a shape gives the same results bit for bit.  `plan` is rowpass_v2_plan() of this problem, iterate and n_iter2, or
+// hipErrorInvalidValue comes back: N, S, n_c, n_u, SD, ND and n_iter2 equal, X16 present iff plan.xs, X8 / D8 if plan.bytes.
+hipError_t launch_rowpass_v2(const ProblemView& p, const IterateView& it, int n_iter2, const UScratch& scratch,
+                             const RowpassV2Plan& plan, hipStream_t st);
 // the byte images X8 / D8 ([N16 / 16][SD / 64][1024], dmf_rowpass_image.h) of X16 / D16 ([N16][SD], every element <= 255)
 hipError_t launch_build_rowpass_images(const unsigned short* X16, const unsigned short* D16, int64_t N16, int SD,
                                        unsigned char* X8, unsigned char* D8, hipStream_t st);
-// the X16 row pass can run two blocks per phase B at this shape: 2..4 waves, and the grid's workgroups per CU fit the LDS
-bool rowpass_v2_pair_fits(int S, int n_u, int n_iter2);
+// ShapeKey::x_byte: every count of the problem, so every x, fits a byte
+inline bool rowpass_v2_counts_fit_bytes(double max_count) { return max_count <= 255.0; }
+// a problem builds those images: true exactly where some plan of the problem (any n_c, n_u, n_iter2) can have `bytes` set
+bool rowpass_v2_byte_images_wanted(int S, bool x16, double max_count);
 bool gram_i8_supported(int n_c, int n_u, int ND, int64_t N, int SD);
 // What launch_gram_i8 launches for a shape -- the one geometry result that the launcher dispatches on and that
 // describe_gram_i8_plan prints (dmf_gram_i8_describe), so that the text cannot say anything else than what runs.

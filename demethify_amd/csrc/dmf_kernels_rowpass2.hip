@@ -135,9 +135,9 @@ __device__ __forceinline__ void inner_steps_unrolled(double& uu, double& up, dou
 // XS: the problem's methylated read counts x = d v are exact integers (X16, u16, D16's layout; dmf_problem_create checks
 // |fma(v, d, -x)| <= 8 ulp of x): the kernel never needs V itself, only d v -- phase A forms w = d (v - Rt a1) as
 // fma(d, -Rt a1, x), phase C multiplies u by x -- and reads 4 bytes per element instead of 10.  V is not read.
-// PAIR (XS, MAXW = 4, NW >= 2, launched where rowpass_v2_pair_fits): two blocks per barrier cycle, their phases B at the
+// PAIR (XS, MAXW = 4, NW >= 2, launched where rowpass_v2_plan says pair): two blocks per barrier cycle, their phases B at the
 // same time on two waves -- see the block loop.  Each block of a pair has its own tile, slot and ubuf set.
-// DEFER_C (PAIR, four waves, every x <= 255, launched where rowpass_v2_defer_fits): a wave runs phase C only in the barrier
+// DEFER_C (PAIR, four waves, every x <= 255, launched where the plan says defer_c): a wave runs phase C only in the barrier
 // cycles in which it is not one of the two phase-B waves, for the two pairs then pending, between barriers X and Y; x
 // goes from the staging registers into a ring of three pairs per wave as BYTES and is kept nowhere else (phase A reads
 // it there too: no x tile), u waits in ubuf sets of three pairs -- see the block loop.
@@ -879,7 +879,8 @@ hipError_t launch_build_rowpass_images(const unsigned short* X16, const unsigned
     return hipGetLastError();
 }
 
-size_t rowpass_v2_lds_bytes(int S, int n_u, int n_iter2, bool x16, bool pair = false, bool defer_c = false, bool bytes = false) {
+// ---- the launch plan (dmf_internal.h: RowpassV2Plan): every rule about which instance runs, with what grid and LDS, is here
+static size_t rowpass_v2_lds_bytes(int S, int n_u, int n_iter2, bool x16, bool pair = false, bool defer_c = false, bool bytes = false) {
     const int NW = (S + 63) / 64;
     const int maxw = NW <= 4 ? 4 : 8;
     const int nset = pair ? 2 : 1;
@@ -891,84 +892,74 @@ size_t rowpass_v2_lds_bytes(int S, int n_u, int n_iter2, bool x16, bool pair = f
     return doubles * sizeof(double) + (size_t)nset * NW * tile + (defer_c ? (size_t)NW * kRingBytes : 0);
 }
 
-bool rowpass_v2_supported(int S, int n_c, int n_u, int n_iter2) {
-    if (S < 2 || S > 512 || n_c > 16 || n_u < 1 || n_u > 4) return false;
-    // up to 256 samples: two workgroups per CU within 160 KB; beyond: one workgroup of up to eight waves
-    // (checked on the V form: the X16 form's tile is smaller)
-    return rowpass_v2_lds_bytes(S, n_u, n_iter2, false) <= (size_t)(S <= 256 ? 80 : 160) * 1024;
-}
-
-// workgroups per CU the grid is sized for
-static int rowpass_v2_per_cu(int NW) {
-    // two waves per SIMD: NW = 5..8 -> 1, 4 -> 2, 3 -> 2, 2 -> 4, 1 -> 8 workgroups per CU
-    return per_cu_knob("DMF_V2_PER_CU", NW > 4 ? 1 : 8 / NW);
-}
-
-// The pair schedule applies to the X16 form with two to four waves, when the grid's workgroups per CU still fit the CU's
-// 160 KB of LDS with two tile / slot / ubuf sets each: so at two waves (four workgroups per CU) up to three unknowns --
-// four need 44 KB per workgroup, and only three such workgroups would fit a CU: the grid would run in two rounds.
-bool rowpass_v2_pair_fits(int S, int n_u, int n_iter2) {
-    const int NW = (S + 63) / 64;
-    if (NW < 2 || NW > 4) return false;
-    return rowpass_v2_lds_bytes(S, n_u, n_iter2, true, true) * (size_t)rowpass_v2_per_cu(NW) <= (size_t)160 * 1024;
-}
-
-// The deferred-C schedule applies to the pair schedule at four waves when two workgroups, each with the x ring and six
-// ubuf sets, still fit the CU's 160 KB (a workgroup's share counted in whole 2 KB pieces, the coarsest the LDS is handed
-// out in): 70 848 B at n_u = 4 and 20 inner steps -- the ring of three pairs costs 24 KB, the x tiles it replaces 18 KB.
-// The instances <NKC = 4, NU = 3 or 4> (13..16 known types with three or four unknowns) would spill a register on this
-// schedule (tools/kernel_regs.sh --x16): they are not built and keep the pair schedule.
-// The byte form (BYTES) is the same schedule with 1 KB count tiles instead of 2.25 KB: 60 KB at the same shape, so it fits
-// wherever the u16 form does.
+// The instances <NKC = 4, NU = 3 or 4> (13..16 known types with three or four unknowns) would spill a register on the
+// deferred-C schedule (tools/kernel_regs.sh --x16): they are not built and keep the pair schedule.
 constexpr bool rowpass_v2_defer_instance(int nkc, int nu) { return !(nkc == 4 && nu >= 3); }
-bool rowpass_v2_defer_fits(int S, int n_c, int n_u, int n_iter2) {
-    const int NW = (S + 63) / 64;
-    if (NW != 4 || !rowpass_v2_pair_fits(S, n_u, n_iter2) || !rowpass_v2_defer_instance((n_c + 3) / 4, n_u)) return false;
-    const size_t lds = (rowpass_v2_lds_bytes(S, n_u, n_iter2, true, true, true) + 2047) & ~(size_t)2047;
-    return lds * (size_t)rowpass_v2_per_cu(NW) <= (size_t)160 * 1024;
+constexpr int kDeferWaves = 4;  // the deferred-C schedule is written for four waves: 193..256 samples
+
+bool rowpass_v2_byte_images_wanted(int S, bool x16, double max_count) {
+    return x16 && rowpass_v2_counts_fit_bytes(max_count) && (S + 63) / 64 == kDeferWaves;  // (one unknown fits at every step count)
 }
 
-int rowpass_v2_grid(int64_t N, int S) {
-    const int per_cu = rowpass_v2_per_cu((S + 63) / 64);
-    const int64_t nblk = (N + 15) / 16;
-    const int64_t g = 256 * per_cu;
-    return (int)(nblk < g ? nblk : g);
+RowpassV2Plan rowpass_v2_plan(const ShapeKey& k, int n_iter2) {
+    RowpassV2Plan g;
+    const int S = k.S, n_u = k.n_u, NW = (S + 63) / 64;
+    g.N = k.N, g.S = S, g.n_c = k.n_c, g.SD = k.SD, g.nd = k.nd, g.n_iter2 = n_iter2;
+    g.nkc = (k.n_c + 3) / 4, g.nu = n_u, g.xs = k.x16;
+    if (k.N < 1 || S < 2 || S > 512 || k.n_c < 0 || k.n_c > 16 || n_u < 1 || n_u > 4 || n_iter2 < 0 || k.nd < 1 || k.nd > 2 ||
+        k.SD < NW * 64 || (k.SD & 7) != 0)
+        return g;
+    // up to 256 samples: two workgroups per CU within 160 KB; beyond: one workgroup of up to eight waves
+    g.nw = NW, g.maxw = NW <= 4 ? 4 : 8;
+    const size_t wg_cap = (size_t)(g.maxw == 4 ? 80 : 160) * 1024, cu_lds = (size_t)160 * 1024;
+    // (checked on the V form: the X16 form's tile is smaller)
+    if (rowpass_v2_lds_bytes(S, n_u, n_iter2, false) > wg_cap) return g;
+    // workgroups per CU the grid is sized for, two waves per SIMD: NW = 5..8 -> 1, 4 -> 2, 3 -> 2, 2 -> 4, 1 -> 8
+    const int per_cu = per_cu_knob("DMF_V2_PER_CU", NW > 4 ? 1 : 8 / NW);
+    // The pair schedule applies to the X16 form with two to four waves, when the grid's workgroups per CU still fit the
+    // CU's 160 KB of LDS with two tile / slot / ubuf sets each: so at two waves (four workgroups per CU) up to three
+    // unknowns -- four need 44 KB per workgroup, and only three such workgroups would fit a CU: the grid would run in two rounds.
+    g.pair = k.rowpass_pair && k.x16 && NW >= 2 && NW <= 4 &&
+             rowpass_v2_lds_bytes(S, n_u, n_iter2, true, true) * (size_t)per_cu <= cu_lds;
+    // The deferred-C schedule applies to the pair schedule at four waves when every x fits a byte and two workgroups, each
+    // with the x ring and six ubuf sets, still fit the CU's 160 KB (a workgroup's share counted in whole 2 KB pieces, the
+    // coarsest the LDS is handed out in): 70 848 B at n_u = 4 and 20 inner steps -- the ring of three pairs costs 24 KB,
+    // the x tiles it replaces 18 KB.
+    g.defer_c = g.pair && k.rowpass_defer_c && k.x_byte && NW == kDeferWaves && rowpass_v2_defer_instance(g.nkc, n_u) &&
+                ((rowpass_v2_lds_bytes(S, n_u, n_iter2, true, true, true) + 2047) & ~(size_t)2047) * (size_t)per_cu <= cu_lds;
+    // The byte form is the same schedule with 1 KB count tiles instead of 2.25 KB (60 KB at that shape, so it fits wherever
+    // the u16 form does), read from the images every such problem carries (rowpass_v2_byte_images_wanted).
+    g.bytes = g.defer_c && k.rowpass_bytes;
+    g.lds = rowpass_v2_lds_bytes(S, n_u, n_iter2, g.xs, g.pair, g.defer_c, g.bytes);
+    g.raise = g.lds > 48 * 1024;
+    const int64_t nblk = (k.N + 15) / 16, full = 256 * per_cu;
+    g.grid = (int)(nblk < full ? nblk : full);
+    g.blocks_per_wg = (nblk + g.grid - 1) / g.grid;
+    g.supported = g.lds <= wg_cap;
+    return g;
 }
 
-hipError_t launch_rowpass_v2(const ProblemView& p, const IterateView& it, int n_iter2, const UScratch& scratch, int* grid_out,
-                             bool pair, bool* paired_out, bool defer_c, bool* deferred_out, bool* bytes_out, hipStream_t st) {
-    const int S = p.S, NW = (S + 63) / 64;
-    // the pair schedule where it applies (rowpass_v2_pair_fits), else one block per barrier cycle
-    pair = pair && p.X16 != nullptr && rowpass_v2_pair_fits(S, it.n_u, n_iter2);
-    if (paired_out != nullptr) *paired_out = pair;
-    // ... with phase C deferred where that applies (the caller vouches for x <= 255 with `defer_c`)
-    defer_c = defer_c && pair && rowpass_v2_defer_fits(S, p.n_c, it.n_u, n_iter2);
-    if (deferred_out != nullptr) *deferred_out = defer_c;
-    // ... from the byte images where the problem carries them (built only where every count is <= 255 at 193..256 samples)
-    const bool bytes = defer_c && p.X8 != nullptr && p.D8 != nullptr;
-    if (bytes_out != nullptr) *bytes_out = bytes;
-    return dispatch_int<0, 4>((p.n_c + 3) / 4, [&](auto nkc) {
-        return dispatch_bool(p.X16 != nullptr, [&](auto xs) {
-            return dispatch_int<1, 4>(it.n_u, [&](auto nu) {
+hipError_t launch_rowpass_v2(const ProblemView& p, const IterateView& it, int n_iter2, const UScratch& scratch,
+                             const RowpassV2Plan& g, hipStream_t st) {
+    if (!g.supported || g.N != p.N || g.S != p.S || g.n_c != p.n_c || g.nu != it.n_u || g.SD != p.SD || g.nd != p.ND ||
+        g.n_iter2 != n_iter2 || g.xs != (p.X16 != nullptr) || (g.bytes && (p.X8 == nullptr || p.D8 == nullptr)))
+        return hipErrorInvalidValue;
+    return dispatch_int<0, 4>(g.nkc, [&](auto nkc) {
+        return dispatch_bool(g.xs, [&](auto xs) {
+            return dispatch_int<1, 4>(g.nu, [&](auto nu) {
                 const auto launch = [&](auto maxw, auto pair_t, auto defer_t, auto bytes_t) {
-                    constexpr int NU = decltype(nu)::value, MAXW = decltype(maxw)::value;
-                    constexpr bool XS = decltype(xs)::value, PAIR = decltype(pair_t)::value, DEFER_C = decltype(defer_t)::value;
-                    constexpr bool BYTES = decltype(bytes_t)::value;
-                    constexpr auto kernel = k_rowpass_v2<decltype(nkc)::value, NU, MAXW, XS, PAIR, DEFER_C, BYTES>;
-                    const size_t lds = rowpass_v2_lds_bytes(S, NU, n_iter2, XS, PAIR, DEFER_C, BYTES);
-                    constexpr size_t kLdsCap = (size_t)(MAXW == 4 ? 80 : 160) * 1024;
-                    if (NW > MAXW || (MAXW == 8 && NW <= 4) || (PAIR && NW < 2) || (DEFER_C && NW != 4) || lds > kLdsCap || p.N < 1 ||
-                        p.SD < NW * 64 || (p.SD & 7) != 0 || p.ND < 1 || p.ND > 2)
-                        return hipErrorInvalidValue;
-                    if (lds > 48 * 1024) {
-                        const hipError_t e = raise_dynamic_lds<kernel>(kLdsCap);
+                    constexpr int MAXW = decltype(maxw)::value;
+                    constexpr bool PAIR = decltype(pair_t)::value, DEFER_C = decltype(defer_t)::value, BYTES = decltype(bytes_t)::value;
+                    constexpr auto kernel = k_rowpass_v2<decltype(nkc)::value, decltype(nu)::value, MAXW, decltype(xs)::value, PAIR, DEFER_C, BYTES>;
+                    // (a plan that names an instance that is not built ends up here on another one)
+                    if (g.maxw != MAXW || g.pair != PAIR || g.defer_c != DEFER_C || g.bytes != BYTES) return hipErrorInvalidValue;
+                    if (g.raise) {
+                        const hipError_t e = raise_dynamic_lds<kernel>((size_t)(MAXW == 4 ? 80 : 160) * 1024);
                         if (e != hipSuccess) return e;
                     }
-                    const int grid = rowpass_v2_grid(p.N, S);
-                    *grid_out = grid;
-                    hipLaunchKernelGGL(kernel, dim3(grid), dim3(NW * 64), lds, st, p.V, BYTES ? reinterpret_cast<const unsigned short*>(p.D8) : p.D16,
+                    hipLaunchKernelGGL(kernel, dim3(g.grid), dim3(g.nw * 64), g.lds, st, p.V, BYTES ? reinterpret_cast<const unsigned short*>(p.D8) : p.D16,
                                        BYTES ? reinterpret_cast<const unsigned short*>(p.X8) : p.X16, p.SD, p.Rtp, it.alpha,
-                                       it.u, it.u_prev, it.state, p.N, S, p.n_c, n_iter2, it.mode, p.ND, scratch.slab,
+                                       it.u, it.u_prev, it.state, p.N, p.S, p.n_c, n_iter2, it.mode, p.ND, scratch.slab,
                                        scratch.u2_partials
 #ifdef DMF_STAMPS
                                        , (unsigned long long*)nullptr
@@ -976,16 +967,20 @@ hipError_t launch_rowpass_v2(const ProblemView& p, const IterateView& it, int n_
                                        );
                     return hipGetLastError();
                 };
-                // more than 256 samples: one workgroup of up to eight waves; the pair leg only on X16
-                if (S > 256) return launch(std::integral_constant<int, 8>{}, std::false_type{}, std::false_type{}, std::false_type{});
+                // The instances that exist: eight waves run one block at a time; the pair schedule is an X16 form; its
+                // deferred-C forms are built where rowpass_v2_defer_instance says so.
+                constexpr std::integral_constant<int, 4> w4{};
+                constexpr std::true_type yes{};
+                constexpr std::false_type no{};
+                if (g.maxw == 8) return launch(std::integral_constant<int, 8>{}, no, no, no);
                 if constexpr (decltype(xs)::value) {
                     if constexpr (rowpass_v2_defer_instance(decltype(nkc)::value, decltype(nu)::value)) {
-                        if (pair && defer_c && bytes) return launch(std::integral_constant<int, 4>{}, std::true_type{}, std::true_type{}, std::true_type{});
-                        if (pair && defer_c) return launch(std::integral_constant<int, 4>{}, std::true_type{}, std::true_type{}, std::false_type{});
+                        if (g.bytes) return launch(w4, yes, yes, yes);
+                        if (g.defer_c) return launch(w4, yes, yes, no);
                     }
-                    if (pair) return launch(std::integral_constant<int, 4>{}, std::true_type{}, std::false_type{}, std::false_type{});
+                    if (g.pair) return launch(w4, yes, no, no);
                 }
-                return launch(std::integral_constant<int, 4>{}, std::false_type{}, std::false_type{}, std::false_type{});
+                return launch(w4, no, no, no);
             });
         });
     });

@@ -12,6 +12,7 @@ namespace dmf {
 
 // ---- thresholds (each measured; the measurement is cited where the constant is used in dmf_select.hip)
 constexpr int kSplitInnerSteps = 50;        // beyond this many inner steps the split u phase beats the one-launch row pass
+constexpr int kSizingInnerSteps = 20;       // the inner-step count select_path and dmf_solver_create ask the row pass's plan at
 constexpr int kCmI8MinNu = 5;               // wide row groups: k_cm_i8 from this many unknowns on
 constexpr int kSplitMinNu = 7;              // k_u_phase_mfma: split form from this many unknowns on (5 with known types)
 constexpr int kGramI8MinFp64Acc = 48;       // integer Gram route instead of k_gram_u from this many FP64 accumulators on
@@ -68,13 +69,14 @@ struct IterationPlan {
 PathSpec select_path(const ShapeKey& k);
 IterationPlan plan_iteration(const ShapeKey& k, const PathSpec& s, int n_iter2, bool purity);
 // "rowpass=... gram=... alpha=..." (what dmf_solver_describe reports and the parity tests assert)
-int describe_plan(const ShapeKey& k, const IterationPlan& plan, char* buf, size_t cap);
+int describe_plan(const ShapeKey& k, const IterationPlan& plan, int n_iter2, char* buf, size_t cap);
 // the PathSpec behind a u phase that runs as a kernel of its own (dmf_update_u): no one-launch row pass, no integer Gram
 PathSpec standalone_spec(PathSpec s);
 // The u phase alone, with what its launcher launches (dmf_u_phase_describe).  standalone: the u phase of dmf_update_u
 // instead of the solver's loop.  For the first-generation FP64 row kernels the text is the launcher's own plan
-// (dmf_internal.h: "k_u_phase_mfma<2,3,vec,d16> split nw=2 grid=512 lds=6912 raise=0 blocks/wg=3"); for the others it is
-// the rowpass= part of describe_plan.
+// (dmf_internal.h: "k_u_phase_mfma<2,3,vec,d16> split nw=2 grid=512 lds=6912 raise=0 blocks/wg=3"); for the second
+// generation it is the rowpass= part of describe_plan followed by the launcher's plan (k_rowpass_v2: RowpassV2Plan, which
+// names the schedule; k_cm_i8: CmI8Plan).
 int describe_u_phase(const ShapeKey& k, const PathSpec& s, int n_iter2, bool purity, bool standalone, char* buf, size_t cap);
 
 // ---- the streaming cost (cost_f_w, deconvolution.py:15-17; the kernels and the plan: dmf_kernels_stream.hip).  Like the

@@ -23,7 +23,7 @@ PathSpec select_path(const ShapeKey& k) {
     // ---- second generation: one-launch row pass on u16 counts + integer-matrix-core Gram (level 0 only)
     // (on X16 the row pass does not read V: its alignment does not matter)
     s.use_v2 = k.level == 0 && ints && (n_c == 0 || k.rtp_present) && (k.v_align == 0 || k.x16) && k.rtp_align == 0 &&
-               rowpass_v2_supported(S, n_c, n_u, 20) && gram_i8_supported(n_c, n_u, k.nd, k.N, k.SD);
+               rowpass_v2_plan(k, kSizingInnerSteps).supported && gram_i8_supported(n_c, n_u, k.nd, k.N, k.SD);
 
     // ---- wide row groups (5..32 unknowns; narrow ones beyond the row pass's 512 samples or 16 known types): the split u
     // phase with the integer-matrix-core producer.  Measured at 5e5 x 128 against what ran before: DESIGN.md section 5.
@@ -66,7 +66,7 @@ IterationPlan plan_iteration(const ShapeKey& k, const PathSpec& s, int n_iter2, 
     // The fixed-point features of the integer Gram need u inside [0, 1]: the u phase's clip puts it there -- after at
     // least one inner step.  With none, u is still the caller's array and the FP64 kernels run.
     const bool clipped = n_iter2 >= 1;
-    if (s.use_v2 && clipped && n_iter2 <= kSplitInnerSteps && rowpass_v2_supported(S, n_c, n_u, n_iter2)) {
+    if (s.use_v2 && clipped && n_iter2 <= kSplitInnerSteps && rowpass_v2_plan(k, n_iter2).supported) {
         plan.row = RowKind::RowpassV2;
         plan.gram = GramKind::I8;
     } else if (s.use_cm_i8 && s.use_gram_i8 && clipped && u_inner_bu_supported(k.v_align, S, k.SD, n_u, n_iter2)) {
@@ -102,12 +102,12 @@ IterationPlan plan_iteration(const ShapeKey& k, const PathSpec& s, int n_iter2, 
 }
 
 // the rowpass= part of describe_plan
-static void describe_row(const ShapeKey& k, RowKind kind, char* row, size_t cap) {
+static void describe_row(const ShapeKey& k, RowKind kind, int n_iter2, char* row, size_t cap) {
     const int S = k.S, n_c = k.n_c, n_u = k.n_u;
     switch (kind) {
         case RowKind::RowpassV2:
             snprintf(row, cap, "k_rowpass_v2<%d,%d> nw=%d grid=%d tail=%d%s", (n_c + 3) / 4, n_u, (S + 63) / 64,
-                     rowpass_v2_grid(k.N, S), (int)(k.N & 15), k.x16 ? " x16" : "");
+                     rowpass_v2_plan(k, n_iter2).grid, (int)(k.N & 15), k.x16 ? " x16" : "");
             break;
         case RowKind::RowpassFused:
             snprintf(row, cap, "k_rowpass_fused<%d,%d> nw=%d grid=%d tail=%d", (n_c + 3) / 4, n_u, (S + 63) / 64,
@@ -123,9 +123,9 @@ static void describe_row(const ShapeKey& k, RowKind kind, char* row, size_t cap)
     }
 }
 
-int describe_plan(const ShapeKey& k, const IterationPlan& plan, char* buf, size_t cap) {
+int describe_plan(const ShapeKey& k, const IterationPlan& plan, int n_iter2, char* buf, size_t cap) {
     char row[160], gram[64];
-    describe_row(k, plan.row, row, sizeof(row));
+    describe_row(k, plan.row, n_iter2, row, sizeof(row));
     switch (plan.gram) {
         case GramKind::InRowPass: snprintf(gram, sizeof(gram), "fused"); break;
         case GramKind::I8: snprintf(gram, sizeof(gram), "k_gram_i8<nd=%d>/w8", k.nd); break;
@@ -183,6 +183,14 @@ int describe_row_launch(const UStepDirectPlan& g, char* buf, size_t cap) {
     return snprintf(buf, cap, "k_u_step_direct n_u=%d %s", g.n_u, tail);
 }
 
+// (behind the rowpass= text, which names the kernel, NKC, NU and the form)
+int describe_row_launch(const RowpassV2Plan& g, char* buf, size_t cap) {
+    static const char* const schedule[kRowpassSchedules] = {"one", "pair", "deferred", "bytes"};
+    char tail[96];
+    describe_launch_tail(g, tail, sizeof(tail));
+    return snprintf(buf, cap, "maxw=%d %s %s", g.maxw, schedule[(int)g.schedule()], tail);
+}
+
 PathSpec standalone_spec(PathSpec s) {
     s.use_v2 = false;  // (plan_iteration then names the split / fall-back u phase of this shape)
     s.use_fused = false;
@@ -211,18 +219,14 @@ int describe_u_phase(const ShapeKey& k, const PathSpec& s, int n_iter2, bool pur
             describe_row_launch(u_step_direct_plan(k.N, k.S, k.n_c, k.n_u), head, sizeof(head));
             return snprintf(buf, cap, "%s launches=%d", head, n_iter2);
         }
-        case RowKind::CmI8InnerRows:
-        case RowKind::CmI8InnerBu: {
-            // the rowpass= text, then the producer's launch plan (the one launch_cm_i8 dispatches on)
-            char rowtext[160], plan[2048];
-            describe_row(k, row, rowtext, sizeof(rowtext));
-            describe_cm_i8_plan(cm_i8_plan(k.N, k.S, k.n_c, k.n_u, k.nd), plan, sizeof(plan));
-            return snprintf(buf, cap, "%s %s", rowtext, plan);
-        }
         default: {
-            char rowtext[160];
-            describe_row(k, row, rowtext, sizeof(rowtext));
-            return snprintf(buf, cap, "%s", rowtext);
+            // the second generation: the rowpass= text, then the launch plan that launch_rowpass_v2 or (for the producer
+            // of the two k_cm_i8 kinds) launch_cm_i8 dispatches on
+            char rowtext[160], plan[2048];
+            describe_row(k, row, n_iter2, rowtext, sizeof(rowtext));
+            if (row == RowKind::RowpassV2) describe_row_launch(rowpass_v2_plan(k, n_iter2), plan, sizeof(plan));
+            else describe_cm_i8_plan(cm_i8_plan(k.N, k.S, k.n_c, k.n_u, k.nd), plan, sizeof(plan));
+            return snprintf(buf, cap, "%s %s", rowtext, plan);
         }
     }
 }

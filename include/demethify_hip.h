@@ -53,7 +53,12 @@ enum {
     DMF_SELECT_PURITY = 2,             /* a purity vector is set (Frank-Wolfe alpha phase)               */
     DMF_SELECT_ALPHA_OUTSIDE_UNIT = 4, /* the starting alpha does not lie inside [0, 1]                  */
     DMF_SELECT_V_UNALIGNED = 8,        /* meth_frequency starts 8 bytes off a 16-byte boundary           */
-    DMF_SELECT_X16 = 16                /* the problem carries X16: every v d is an exact count (with nd > 0) */
+    DMF_SELECT_X16 = 16,               /* the problem carries X16: every v d is an exact count (with nd > 0) */
+    /* what only the row pass's launch plan reads (dmf_u_phase_describe; dmf_select_describe's text does not change) */
+    DMF_SELECT_COUNTS_BYTE = 32,           /* every count is at most 255                                 */
+    DMF_SELECT_NO_ROWPASS_PAIR = 64,       /* dmf_context_set_rowpass_pair is off                        */
+    DMF_SELECT_NO_ROWPASS_DEFER_C = 128,   /* dmf_context_set_rowpass_defer_c is off                     */
+    DMF_SELECT_NO_ROWPASS_BYTES = 256      /* dmf_context_set_rowpass_bytes is off                       */
 };
 
 /* solver variants */
@@ -424,8 +429,12 @@ int dmf_select_describe(int64_t N, int64_t S, int64_t n_c, int64_t n_u, int nd, 
  *    grid=.. blocks/wave=1 | col0=256 sp=44 k_cm_i8<1,1,2,s4> tpl=5 .."
  * k_cm_i8<NKC,ND,NCGX,s4|pairs>; tiles: 16-pair tiles of M_i, tpl of them per launch; ctiles: 16-unknown tiles of c; lds, grid
  * and blocks/wave (32-row blocks of the busiest wave) are the first launch's -- where the last launch holds fewer tiles,
- * " last: tiles=.. lds=.. grid=.. blocks/wave=.." follows.  (2 KB hold every such text.)  For every other u phase it is the
- * rowpass= part of dmf_select_describe.  DMF_ERR_UNSUPPORTED where no kernel takes the shape. */
+ * " last: tiles=.. lds=.. grid=.. blocks/wave=.." follows.  (2 KB hold every such text.)  For the one-launch row pass
+ * k_rowpass_v2 it is the rowpass= part of dmf_select_describe, then the plan launch_rowpass_v2 dispatches on -- template
+ * argument MAXW, the schedule (one | pair | deferred | bytes: one block per barrier cycle, two, phase C deferred, the same
+ * from the byte images) and the launch as above:
+ *   "k_rowpass_v2<3,4> nw=4 grid=512 tail=0 x16 maxw=4 bytes nw=4 grid=512 lds=.. raise=1 blocks/wg=123"
+ * so a test knows, before any launch, which schedule a solver runs.  DMF_ERR_UNSUPPORTED where no kernel takes the shape. */
 enum { DMF_ROUTE_SOLVER = 0, DMF_ROUTE_UPDATE_U = 1 };
 int dmf_u_phase_describe(int64_t N, int64_t S, int64_t n_c, int64_t n_u, int nd, int level, int64_t n_iter2, int flags, int route,
                          char* buf, int64_t cap);

@@ -14,32 +14,102 @@ asserts what the hand-over rests on:
   * every wave meets the same number of barriers.
 
 A wrong hand-over on the device is a hang or silent garbage; here it is an assertion.  Plain Python, no GPU.
-`blocks_per_workgroup(N, S)` is the grid rule (rowpass_v2_grid) for the GPU tests that pick their row counts by it."""
+
+The module is also the one Python statement of the row pass's launch rule (rowpass_v2_plan, dmf_kernels_rowpass2.hip), written
+from the rules alone: `plan(...)` answers wave count, grid, blocks per workgroup, LDS bytes and schedule, `plan_text(...)` what
+dmf_u_phase_describe must say of it (tests/test_rowpass_plan_host.py holds the two together over a grid of shapes), and the
+GPU tests ask `schedule`, `runs_deferred`, `blocks_per_workgroup` and `expected_counts` instead of restating any of it."""
 
 NW = 4           # waves of a workgroup on this schedule
 RING_PAIRS = 3   # pairs of blocks a wave's x ring holds
 UBUF_PAIRS = 3   # pairs of blocks the ubuf sets hold
 
+SCHEDULES = ("one", "pair", "deferred", "bytes")  # each a form of the one before
+CU_LDS, CUS = 160 * 1024, 256
+TILE_V, TILE_COUNTS, TILE_BYTES = 16 * 66 * 8, 16 * 72 * 2, 1024  # a column group of a block: V (f64), u16 counts (padded rows), the byte image
+RING = 2 * RING_PAIRS * 16 * 64                                   # a wave's x ring on the deferred-C schedule
+
+
+def lds_bytes(S, n_u, n_iter2, x16, schedule="one"):
+    """Dynamic LDS of a workgroup: the momentum table, the ubuf sets, the partial-sum slots and the wave sums, then per wave
+    its tile sets (V and counts; x and counts on X16; counts alone, x in the ring, with phase C deferred)."""
+    nw = (S + 63) // 64
+    maxw = 4 if nw <= 4 else 8
+    level = SCHEDULES.index(schedule)
+    nset = 2 if level >= 1 else 1
+    nub = 2 * UBUF_PAIRS if level >= 2 else nset
+    nv = n_u * ((n_u + 2) & ~1)
+    doubles = ((n_iter2 + 1) & ~1) + nub * 16 * n_u + nset * maxw * nv * 16 + maxw
+    tile = TILE_BYTES if level == 3 else TILE_COUNTS if level == 2 else 2 * TILE_COUNTS if x16 else TILE_V + TILE_COUNTS
+    return 8 * doubles + nset * nw * tile + (nw * RING if level >= 2 else 0)
+
+
+def plan(N, S, n_c, n_u, n_iter2=20, x16=True, max_count=255, pair=True, defer_c=True, bytes_=True):
+    """The launch plan of k_rowpass_v2 for a problem with integer count copies, or None where the kernel does not take the
+    shape.  pair / defer_c / bytes_: the context's three switches."""
+    nw = (S + 63) // 64
+    if not (N >= 1 and 2 <= S <= 512 and 0 <= n_c <= 16 and 1 <= n_u <= 4):
+        return None
+    maxw = 4 if nw <= 4 else 8
+    wg_cap = (80 if maxw == 4 else 160) * 1024
+    if lds_bytes(S, n_u, n_iter2, False) > wg_cap:   # (asked of the V form, the largest)
+        return None
+    per_cu = 1 if nw > 4 else 8 // nw                # two waves per SIMD
+    schedule = "one"
+    if pair and x16 and 2 <= nw <= 4 and per_cu * lds_bytes(S, n_u, n_iter2, True, "pair") <= CU_LDS:
+        schedule = "pair"
+        spills = (n_c + 3) // 4 == 4 and n_u >= 3    # the two instances that are not built
+        whole = (lds_bytes(S, n_u, n_iter2, True, "deferred") + 2047) & ~2047   # the LDS is handed out in 2 KB pieces
+        if defer_c and max_count <= 255 and nw == NW and not spills and per_cu * whole <= CU_LDS:
+            schedule = "bytes" if bytes_ else "deferred"
+    nblk = (N + 15) // 16
+    grid = min(nblk, CUS * per_cu)
+    lds = lds_bytes(S, n_u, n_iter2, x16, schedule)
+    return {"nkc": (n_c + 3) // 4, "nw": nw, "maxw": maxw, "grid": grid, "lds": lds, "raise": int(lds > 48 * 1024),
+            "blocks": (nblk // grid, (nblk + grid - 1) // grid), "schedule": schedule, "x16": x16, "tail": N % 16}
+
+
+def plan_text(N, S, n_c, n_u, n_iter2=20, **kw):
+    """What dmf_u_phase_describe (route solver) answers where the row pass runs: the rowpass= text of dmf_select_describe,
+    then the plan.  None where plan() is."""
+    g = plan(N, S, n_c, n_u, n_iter2, **kw)
+    if g is None:
+        return None
+    return (f"k_rowpass_v2<{g['nkc']},{n_u}> nw={g['nw']} grid={g['grid']} tail={g['tail']}{' x16' if g['x16'] else ''} "
+            f"maxw={g['maxw']} {g['schedule']} nw={g['nw']} grid={g['grid']} lds={g['lds']} raise={g['raise']} "
+            f"blocks/wg={g['blocks'][1]}")
+
+
+def schedule(S, n_c, n_u, n_iter2=20, **kw):
+    return plan(16, S, n_c, n_u, n_iter2, **kw)["schedule"]
+
+
+def schedule_in_text(text):
+    """The schedule word of a u_phase_describe text, None where the text is not the row pass's."""
+    return text.split(" maxw=")[1].split()[1] if text.startswith("k_rowpass_v2<") else None
+
+
+def expected_counts(word, total):
+    """(launches, paired, deferred, from bytes) as the solver's counters must show them after `total` launches on the schedule
+    `word` (None: the row pass does not run at all)."""
+    if word is None:
+        return (0, 0, 0, 0)
+    return tuple(total if SCHEDULES.index(word) >= i else 0 for i in range(4))
+
+
+def byte_images_wanted(S, x16, max_count):
+    """Whether a problem carries the byte images (rowpass_v2_byte_images_wanted): where some plan of it can read them."""
+    return x16 and max_count <= 255 and (S + 63) // 64 == NW
+
 
 def blocks_per_workgroup(N, S):
     """(fewest, most) blocks a workgroup of the row pass owns: block b goes to workgroup b % grid."""
-    nw = (S + 63) // 64
-    per_cu = 1 if nw > 4 else 8 // nw
-    nblk = (N + 15) // 16
-    grid = min(nblk, 256 * per_cu)
-    return nblk // grid, (nblk + grid - 1) // grid
+    return plan(N, S, 0, 1)["blocks"]
 
 
 def runs_deferred(S, n_c, n_u, n_iter2, max_count, x16=True, pair=True, defer_c=True):
-    """Whether a solver's row pass runs the deferred-C schedule (launch_rowpass_v2, rowpass_v2_defer_fits): four waves, X16,
-    every count at most 255, not the two kernel instances that would spill, and two workgroups' LDS within a CU."""
-    nw = (S + 63) // 64
-    if not (x16 and pair and defer_c) or nw != 4 or max_count > 255 or ((n_c + 3) // 4 == 4 and n_u >= 3):
-        return False
-    nv = n_u * ((n_u + 2) & ~1)
-    doubles = ((n_iter2 + 1) & ~1) + 6 * 16 * n_u + 2 * 4 * nv * 16 + 4
-    lds = doubles * 8 + 2 * nw * 16 * 72 * 2 + nw * 6 * 16 * 64  # count tiles, the x ring
-    return 2 * ((lds + 2047) & ~2047) <= 160 * 1024
+    """Whether a solver's row pass runs the deferred-C schedule, on u16 counts or on bytes."""
+    return schedule(S, n_c, n_u, n_iter2, x16=x16, max_count=max_count, pair=pair, defer_c=defer_c) in ("deferred", "bytes")
 
 
 def wave_program(nk, wave):

@@ -192,17 +192,21 @@ def test_supported_boundaries():
 
 def test_second_generation_kernels_keep_their_row_text():
     """For a u phase that is not one of the five kernels the accessor answers the rowpass= part of dmf_select_describe --
-    followed, for the integer producer k_cm_i8, by that producer's launch plan (tests/cm_exact.py writes it down)."""
+    followed by the launch plan of the kernel it names: the integer producer k_cm_i8's (tests/cm_exact.py writes it down) or
+    the one-launch row pass k_rowpass_v2's (tests/rowpass_schedule_model.py; the flags do not say that every count fits a byte)."""
     import cm_exact as cm
+    import rowpass_schedule_model as rp
 
     flags = F32 | L.DMF_SELECT_X16
-    for key, producer in (((1000, 64, 6, 2, 1, 0, 20), False), ((1000, 640, 6, 2, 1, 0, 20), True), ((1000, 64, 0, 12, 1, 0, 20), True)):
+    for key, producer in (((1000, 64, 6, 2, 1, 0, 20), False), ((1000, 640, 6, 2, 1, 0, 20), True), ((1000, 64, 0, 12, 1, 0, 20), True),
+                          ((5000, 256, 12, 4, 1, 0, 20), False)):
         st, sel = _select(*key, flags)
         assert st == L.DMF_OK
         N, S, n_c, n_u, nd = key[:5]
-        plan = " " + cm.plan_text(N, S, n_c, n_u, nd) if producer else ""
-        assert ("k_cm_i8<" in sel) == producer
-        assert "rowpass=" + u_phase_describe(*key, flags) == sel.split(" gram=")[0] + plan
+        plan = cm.plan_text(N, S, n_c, n_u, nd) if producer else rp.plan_text(N, S, n_c, n_u, 20, max_count=256).split(" x16 ")[1]
+        assert ("k_cm_i8<" in sel) == producer and ("k_rowpass_v2<" in sel) == (not producer)
+        assert plan.startswith("panels=" if producer else "maxw=4 one nw=1 " if S == 64 else "maxw=4 pair nw=4 ")
+        assert "rowpass=" + u_phase_describe(*key, flags) == sel.split(" gram=")[0] + " " + plan
 
 
 def test_describe_argument_checks():

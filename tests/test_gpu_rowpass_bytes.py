@@ -34,13 +34,16 @@ def _run(ctx, V, D, Rt, u0, a0, n_iter2, rowpass_bytes, x16=True, derive=None):
             try:
                 with Solver(p, u0, a0, mode) as s:
                     desc = s.describe(n_iter2)
+                    word = model.schedule_in_text(s.u_phase_describe(n_iter2))  # the plan's schedule, before any launch
                     s.step(K_ITERS, n_iter2, 0.0)
                     u, alpha = s.get()[:2]
                     mom = s.momentum_state()
                     gram = s.gram("last")[0]
                     out = {"u": u, "alpha": alpha, "u_prev": mom["u_prev"], "alpha_prev": mom["alpha_prev"], "gram": gram,
                            "direct_cost": np.float64(s.direct_cost())}
-                    return out, desc, s.rowpass_schedule_counts(), s.rowpass_byte_launches(), p.has_byte_images()
+                    counts = s.rowpass_schedule_counts() + (s.rowpass_byte_launches(),)
+                    assert counts == model.expected_counts(word, counts[0]), (word, counts)  # ... is what the launches ran
+                    return out, desc, counts[:3], counts[3], p.has_byte_images()
             finally:
                 if p is not full:
                     p.close()

@@ -47,12 +47,15 @@ def _run(ctx, V, D, Rt, u0, a0, n_iter2, defer_c, x16=True, derive=None):
             try:
                 with Solver(p, u0, a0, mode) as s:
                     desc = s.describe(n_iter2)
+                    word = model.schedule_in_text(s.u_phase_describe(n_iter2))  # the plan's schedule, before any launch
                     s.step(K_ITERS, n_iter2, 0.0)
                     u, alpha = s.get()[:2]
                     mom = s.momentum_state()
                     gram = s.gram("last")[0]
+                    counts = s.rowpass_schedule_counts()
+                    assert counts == model.expected_counts(word, counts[0])[:3], (word, counts)  # ... is what the launches ran
                     return {"u": u, "alpha": alpha, "u_prev": mom["u_prev"], "alpha_prev": mom["alpha_prev"], "gram": gram,
-                            "direct_cost": np.float64(s.direct_cost())}, desc, s.rowpass_schedule_counts(), s.rowpass_launches()
+                            "direct_cost": np.float64(s.direct_cost())}, desc, counts, s.rowpass_launches()
             finally:
                 if p is not full:
                     p.close()

@@ -32,6 +32,7 @@ import pytest
 
 from oracle import solver as osol
 
+import rowpass_schedule_model as model
 from conftest import rel_err
 from test_gpu_rowpass_pair import _run
 
@@ -53,26 +54,21 @@ def _nw(S):
 
 
 def _grid(nw):
-    """The row pass's workgroups (rowpass_v2_grid) for rows enough to fill it."""
-    return 256 * (8 // nw if nw <= 4 else 1)
+    """The row pass's workgroups for rows enough to fill it (tests/rowpass_schedule_model.py: the launch plan's rule)."""
+    return model.plan(10 ** 7, 64 * nw, 0, 1)["grid"]
 
 
 def _legs(S):
     return FOUR_LEGS if 2 <= _nw(S) <= 4 else OTHER_LEGS
 
 
-def _pairs(S, n_u):
-    """Whether the pair schedule applies (rowpass_v2_pair_fits, up to 50 inner steps): two to four waves, except two
-    waves with four unknowns."""
-    return 2 <= _nw(S) <= 4 and not (_nw(S) == 2 and n_u == 4)
-
-
-def _instance(S, n_c, n_u, leg, x16=None):
-    """(NKC, NU, MAXW, form, schedule) of the k_rowpass_v2 instance a leg runs; x16: whether the problem takes X16 (by
-    default: with the leg's switch)."""
+def _instance(S, n_c, n_u, leg, x16=None, n_iter2=50):
+    """(NKC, NU, MAXW, form, schedule) of the k_rowpass_v2 instance a leg runs, by the launch plan's rule; x16: whether the
+    problem takes X16 (by default: with the leg's switch).  Schedule: "pair" for the pair schedule and the forms built on it
+    (the 100 instances of this file are told apart by PAIR, and the launch counter these legs read counts them all)."""
     x16 = leg[1] if x16 is None else x16
-    sched = "pair" if x16 and leg[2] and _pairs(S, n_u) else "one"
-    return ((n_c + 3) // 4, n_u, 4 if _nw(S) <= 4 else 8, "x16" if x16 else "v", sched)
+    g = model.plan(16, S, n_c, n_u, n_iter2, x16=x16, pair=leg[2])
+    return (g["nkc"], n_u, g["maxw"], "x16" if x16 else "v", "one" if g["schedule"] == "one" else "pair")
 
 
 def _matrix():
@@ -156,7 +152,7 @@ def _legs_against_oracle(ctx, record_property, data, n_iter2, legs, x16=None):
     for leg in legs:
         name = leg[0]
         desc, trail, direct, launches = _run(ctx, V, D, Rt, u0, a0, n_iter2, T1, leg[2], x16=leg[1])
-        nkc, _, _, form, sched = _instance(S, n_c, n_u, leg, x16=None if x16 is None else leg[1] and x16)
+        nkc, _, _, form, sched = _instance(S, n_c, n_u, leg, x16=None if x16 is None else leg[1] and x16, n_iter2=n_iter2)
         assert f"rowpass=k_rowpass_v2<{nkc},{n_u}> nw={_nw(S)} " in desc, (name, desc)
         assert f" tail={N % 16} " in desc and f"gram=k_gram_i8<nd={nd}>" in desc, (name, desc)
         assert (" x16 " in desc) if form == "x16" else ("x16" not in desc), (name, desc)
@@ -194,7 +190,7 @@ def test_every_instance_is_in_the_matrix():
     for cid, c in MATRIX:
         nd = 2 if c.depth > 127 else 1
         for leg in _legs(c.S):
-            nkc, nu, maxw, form, sched = inst = _instance(c.S, c.n_c, c.n_u, leg)
+            nkc, nu, maxw, form, sched = inst = _instance(c.S, c.n_c, c.n_u, leg, n_iter2=c.n_iter2)
             flags = L.DMF_SELECT_COUNTS_F32_EXACT | (L.DMF_SELECT_X16 if form == "x16" else 0)
             buf = C.create_string_buffer(512)
             assert lib.dmf_select_describe(c.N, c.S, c.n_c, c.n_u, nd, 0, c.n_iter2, flags, buf, len(buf)) == L.DMF_OK

@@ -11,6 +11,7 @@ import pytest
 
 from oracle import solver as osol
 
+import rowpass_schedule_model as model
 from conftest import rel_err
 
 pytestmark = pytest.mark.gpu
@@ -31,11 +32,14 @@ def _run(ctx, V, D, Rt, u0, a0, n_iter2, n_calls, pair, x16=True):
     try:
         with Problem(ctx, V, D, Rt) as p, Solver(p, u0, a0, mode) as s:
             desc = s.describe(n_iter2)
+            word = model.schedule_in_text(s.u_phase_describe(n_iter2))  # the plan's schedule, before any launch
             trail = []
             for _ in range(n_calls):
                 s.step(1, n_iter2, 0.0)
                 trail.append(s.get())
-            return desc, trail, s.direct_cost(), s.rowpass_launches()
+            launches = s.rowpass_launches()
+            assert launches == model.expected_counts(word, launches[0])[:2], (word, launches)  # ... is what the launches ran
+            return desc, trail, s.direct_cost(), launches
     finally:
         ctx.set_rowpass_pair(True)
         ctx.set_x16(True)
@@ -52,7 +56,8 @@ def _problem(N, S, n_c, n_u, depth, seed=0):
 
 
 # (N, S, n_c, n_u, n_iter2, depth, paired, why).  Row pass grid: min(blocks, 512) workgroups at 3-4 waves, min(blocks,
-# 1024) at 2.  paired: whether the pair schedule applies (dmf's rowpass_v2_pair_fits).
+# 1024) at 2.  paired: whether the pair schedule applies (the launch plan's rule: tests/rowpass_schedule_model.py, which
+# tests/test_rowpass_plan_host.py holds this column to).
 CASES = [
     (40_000, 256, 12, 4, 20, 50, True, "the bench's shape in everything but the row count; 4-5 blocks per workgroup"),
     (8192 + 3, 255, 12, 4, 19, 50, True, "odd S, ragged last column group and last block, odd step count"),
