@@ -137,6 +137,8 @@ SIGNATURES = {
     "dmf_solve_small": (C.c_int, [_p, _p, _i64, _p, _p, _p, _i64, C.c_int, _i64, _i64, C.c_double, _i64, C.c_int, _p, _p, _p, _p]),
     "dmf_solve_small_purity": (C.c_int, [_p, _p, _i64, _p, _p, _p, _p, _i64, C.c_int, _i64, _i64, C.c_double, _i64, C.c_int, _p, _p,
                                          _p, _p]),
+    "dmf_solve_small_masked": (C.c_int, [_p, _p, _i64, _p, _p, _p, _i64, C.c_int, _i64, _i64, C.c_double, _i64, C.c_int, _p, _p, _p,
+                                         _p, _p, _p]),
 }
 
 _lib = None

@@ -1,5 +1,5 @@
 // C-ABI of libdemethify_hip.so, part 7: many independent small solves of one resident problem per launch
-// (dmf_solve_small, dmf_solve_small_purity; the kernel is dmf_kernels_small.hip).
+// (dmf_solve_small, dmf_solve_small_purity, dmf_solve_small_masked; the kernels are in dmf_kernels_small.hip).
 #include <algorithm>
 
 #include "dmf_api.h"
@@ -7,15 +7,20 @@
 
 using namespace dmf_api;
 
-// The body of both entries.  with_purity: `purity` (S doubles) selects the purity variant of the kernel.
+// The body of the three entries.  with_purity: `purity` (S doubles) selects the purity variant of the kernel.  with_mask:
+// `train_bits` (B x N x ceil(S / 8) bytes) gives every solve a train mask, and the hold-out error of every final iterate goes
+// to out_holdout_sum_sq / out_n_test.
 static int solve_small(dmf_context* ctx, const dmf_problem* p, int64_t B, const int64_t* idx, const double* u0, const double* alpha0,
                        int64_t n_u, int mode, int64_t n_iter1, int64_t n_iter2, double tol, int64_t iters_per_launch, int flags,
                        bool with_purity, const double* purity, double* out_u, double* out_alpha, double* out_cost,
-                       int64_t* out_iters) {
+                       int64_t* out_iters, bool with_mask = false, const uint8_t* train_bits = nullptr,
+                       double* out_holdout_sum_sq = nullptr, int64_t* out_n_test = nullptr) {
     if (ctx == nullptr || p == nullptr || B < 1 || B > 0x7fffffff || u0 == nullptr || alpha0 == nullptr || out_u == nullptr ||
         out_alpha == nullptr || out_cost == nullptr || out_iters == nullptr || n_iter1 < 0 || n_iter2 < 0 || iters_per_launch < 0)
         return DMF_ERR_BAD_ARG;
     if (p->ctx != ctx || p->mask_bits != nullptr) return DMF_ERR_BAD_ARG;  // (a masked problem's held-out zeros are not data)
+    if (with_mask && (train_bits == nullptr || out_holdout_sum_sq == nullptr || out_n_test == nullptr || idx != nullptr))
+        return DMF_ERR_BAD_ARG;
     if (with_purity && (purity == nullptr || p->n_c < 1)) return DMF_ERR_BAD_ARG;  // (no known block to hold at that mass)
     if (with_purity && mode != DMF_MODE_PARTIAL) return DMF_ERR_UNSUPPORTED;
     if (!dmf::small_supported(p->N, p->S, p->n_c, n_u, mode)) return DMF_ERR_UNSUPPORTED;
@@ -35,6 +40,22 @@ static int solve_small(dmf_context* ctx, const dmf_problem* p, int64_t B, const 
         HIP_TRY(hipMemcpyAsync(&h_bad, d_bad, sizeof(h_bad), hipMemcpyDeviceToHost, ctx->stream));
         HIP_TRY(hipStreamSynchronize(ctx->stream));
         if (h_bad != 0) return DMF_ERR_BAD_ARG;
+    }
+    DevBuf<uint8_t> d_bits;
+    std::vector<long long> h_train;
+    if (with_mask) {
+        // every solve's kept elements are counted on the device before the first launch: a fold that keeps none (upstream
+        // skips it, ic.py:71; here d would be 0 and l_w a division by zero) is refused while no solve has started
+        const size_t nb = (size_t)(S + 7) / 8;
+        DMF_TRY(import_array(ctx, train_bits, (size_t)B * N * nb, flags, d_bits));
+        DevBuf<long long> d_train;
+        h_train.assign((size_t)B, 0);
+        HIP_TRY(d_train.alloc(ctx, (size_t)B));
+        HIP_TRY(dmf::launch_small_mask_count(d_bits, B, N, (int)S, d_train, ctx->stream));
+        HIP_TRY(hipMemcpyAsync(h_train.data(), d_train, (size_t)B * sizeof(long long), hipMemcpyDeviceToHost, ctx->stream));
+        HIP_TRY(hipStreamSynchronize(ctx->stream));
+        for (int64_t b = 0; b < B; ++b)
+            if (h_train[(size_t)b] < 1) return DMF_ERR_BAD_ARG;
     }
     DMF_TRY(import_array(ctx, u0, un, flags, d_u0));
     DMF_TRY(import_array(ctx, alpha0, an, flags, d_a0));
@@ -64,6 +85,7 @@ static int solve_small(dmf_context* ctx, const dmf_problem* p, int64_t B, const 
     a.u = w_u, a.u_prev = w_up, a.alpha = w_a, a.alpha_prev = w_ap, a.gk = w_gk, a.ratio = w_ratio, a.scal = w_scal;
     a.iters = w_iters, a.done = w_done;
     if (with_purity) a.purity = d_purity;
+    if (with_mask) a.mask = d_bits;
 
     const int64_t per_launch = iters_per_launch > 0 ? std::min<int64_t>(iters_per_launch, 1 << 20)
                                                       : dmf::small_default_iters_per_launch(N, S, with_purity);
@@ -82,6 +104,16 @@ static int solve_small(dmf_context* ctx, const dmf_problem* p, int64_t B, const 
         if (all) break;
     }
 
+    // the hold-out error of every final iterate, taken where it lives (ic.py:80 before the division)
+    DevBuf<double> d_hold;
+    std::vector<double> h_hold;
+    if (with_mask) {
+        h_hold.assign((size_t)B, 0.0);
+        HIP_TRY(d_hold.alloc(ctx, (size_t)B));
+        HIP_TRY(dmf::launch_small_holdout(p->V, p->Rt, w_u, w_a, d_bits, B, N, (int)S, (int)p->n_c, (int)n_u, d_hold, ctx->stream));
+        HIP_TRY(hipMemcpyAsync(h_hold.data(), d_hold, (size_t)B * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    }
+
     // out_cost[b] = cost_f_w of the final iterate (the loop's own streaming cost), out_iters[b] = its outer iterations
     std::vector<double> h_scal((size_t)B * dmf::kSmallScalars);
     static_assert(sizeof(long long) == sizeof(int64_t), "out_iters is copied as long long");
@@ -91,6 +123,8 @@ static int solve_small(dmf_context* ctx, const dmf_problem* p, int64_t B, const 
     if (!(flags & DMF_PTR_DEVICE)) HIP_TRY(hipMemcpyAsync(out_u, w_u, un * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(hipStreamSynchronize(ctx->stream));
     for (int64_t b = 0; b < B; ++b) out_cost[b] = h_scal[(size_t)b * dmf::kSmallScalars + dmf::kSmCf];
+    if (with_mask)
+        for (int64_t b = 0; b < B; ++b) out_holdout_sum_sq[b] = h_hold[(size_t)b], out_n_test[b] = N * S - h_train[(size_t)b];
     return DMF_OK;
 }
 
@@ -113,6 +147,14 @@ int dmf_solve_small_purity(dmf_context* ctx, const dmf_problem* p, int64_t B, co
                            int64_t* out_iters) {
     return solve_small(ctx, p, B, idx, u0, alpha0, n_u, mode, n_iter1, n_iter2, tol, iters_per_launch, flags, true, purity, out_u,
                        out_alpha, out_cost, out_iters);
+}
+
+int dmf_solve_small_masked(dmf_context* ctx, const dmf_problem* p, int64_t B, const uint8_t* train_bits, const double* u0,
+                           const double* alpha0, int64_t n_u, int mode, int64_t n_iter1, int64_t n_iter2, double tol,
+                           int64_t iters_per_launch, int flags, double* out_u, double* out_alpha, double* out_cost,
+                           int64_t* out_iters, double* out_holdout_sum_sq, int64_t* out_n_test) {
+    return solve_small(ctx, p, B, nullptr, u0, alpha0, n_u, mode, n_iter1, n_iter2, tol, iters_per_launch, flags, false, nullptr,
+                       out_u, out_alpha, out_cost, out_iters, true, train_bits, out_holdout_sum_sq, out_n_test);
 }
 
 }  // extern "C"

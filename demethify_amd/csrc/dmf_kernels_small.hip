@@ -30,6 +30,13 @@
 // replaces the alpha phase by n_iter2 Frank-Wolfe steps per sample (frank_wolfe_nmf, :280-302) on the same G_s, b_s: one
 // sample per 16-lane row, lane k owning row k of G_s in registers, the 16 rows of the workgroup taking samples r, r + 16, ...
 // There is no a2, no l_h and no alpha_; the purity vector is an input, not state.
+//
+// The masked variant (MASK; a bi-cross-validation fold, ic.py:58-89) gives solve b a train mask of its own, packed as
+// dmf_problem_mask packs it: wherever the kernel reads a count d_is -- the set-up maximum, the known Gram block, c_i and M_i,
+// gram_jobs, stream_cost and so the stop test -- it is 0 where the bit is 0 (upstream's counts * train_mask); v of a held-out
+// element is still read and only ever multiplied by that 0.  The bits are read from memory, not kept in LDS.  MASK is a
+// template parameter: the instances without it are the code they were.  k_small_mask_count (before the first launch) counts a
+// solve's kept elements, k_small_holdout (after the last) takes the squared error on the held-out ones.
 #include "dmf_small.h"
 #include "dmf_rowlanes.h"
 
@@ -97,13 +104,17 @@ struct Rows {
     const double* Rt;
     const long long* idx;  // null: the identity
     const double* u;       // this solve's current u
+    const uint8_t* mask;   // this solve's train mask (the MASK instances): nb bytes per row
     int64_t N;
-    int S, n_c, n_u, K, SP, R;
+    int S, n_c, n_u, K, SP, R, nb;
     __device__ __forceinline__ int64_t row(int64_t i) const { return idx != nullptr ? (int64_t)idx[i] : i; }
+    // is element (i, s) kept?  The bits are read from memory (at most 128 KB per solve: they stay in L2)
+    __device__ __forceinline__ bool kept(int64_t i, int s) const { return (mask[i * nb + (s >> 3)] >> (s & 7)) & 1; }
 };
 
 // Jobs [j0, j1) of the job tables: gb[jd][s] = sum_i d_is x_k x_l over the solve's rows.  Threads as (slice r, sample s);
-// slice r adds rows r, r + R, ... in rising order, the slices are added in rising order.
+// slice r adds rows r, r + R, ... in rising order, the slices are added in rising order.  MASK: d is 0 where the solve's bit is.
+template <bool MASK>
 __device__ void gram_jobs(const Rows& p, const Lds& m, int j0, int j1) {
     const int t = threadIdx.x;
     const int s = t & (p.SP - 1), r = t / p.SP;
@@ -125,7 +136,8 @@ __device__ void gram_jobs(const Rows& p, const Lds& m, int j0, int j1) {
                     const int64_t iq = i + (int64_t)q * p.R;
                     const bool in = iq < p.N;
                     const int64_t ic = in ? iq : i, g = p.row(ic);
-                    d[q] = in ? p.D[g * p.S + s] : 0.0;
+                    if constexpr (MASK) d[q] = in && p.kept(g, s) ? p.D[g * p.S + s] : 0.0;
+                    else d[q] = in ? p.D[g * p.S + s] : 0.0;
                     v[q] = p.V[g * p.S + s];
                     rt[q] = p.Rt + g * p.n_c;
                     ui[q] = p.u + ic * p.n_u;
@@ -157,7 +169,8 @@ __device__ void gram_jobs(const Rows& p, const Lds& m, int j0, int j1) {
     }
 }
 
-// sum_i sum_s d (v - [Rt | u] alpha)^2 over the solve's rows with alpha from LDS (deconvolution.py:15-17)
+// sum_i sum_s d (v - [Rt | u] alpha)^2 over the solve's rows with alpha from LDS (deconvolution.py:15-17); MASK as above
+template <bool MASK>
 __device__ double stream_cost(const Rows& p, const Lds& m) {
     const int t = threadIdx.x;
     const int s = t & (p.SP - 1), r = t / p.SP;
@@ -172,7 +185,8 @@ __device__ double stream_cost(const Rows& p, const Lds& m) {
                 const int64_t iq = i + (int64_t)q * p.R;
                 const bool in = iq < p.N;
                 const int64_t ic = in ? iq : i, g = p.row(ic);
-                d[q] = in ? p.D[g * p.S + s] : 0.0;
+                if constexpr (MASK) d[q] = in && p.kept(g, s) ? p.D[g * p.S + s] : 0.0;
+                else d[q] = in ? p.D[g * p.S + s] : 0.0;
                 resid[q] = p.V[g * p.S + s];
                 rt[q] = p.Rt + g * p.n_c;
                 ui[q] = p.u + ic * p.n_u;
@@ -281,8 +295,9 @@ __device__ void frank_wolfe_rows(const Lds& m, const double* __restrict__ purity
 
 }  // namespace
 
-template <int NU, bool PURITY>
+template <int NU, bool PURITY, bool MASK>
 __global__ __launch_bounds__(kSmallThreads) void k_solve_small(SmallArgs a) {
+    static_assert(!(PURITY && MASK), "a purity run with a mask is not built");
     constexpr int NP = NU * (NU + 1) / 2;
     const int64_t b = blockIdx.x;
     if (!a.first && a.done[b]) return;  // a finished solve's workgroup returns at once
@@ -318,6 +333,8 @@ __global__ __launch_bounds__(kSmallThreads) void k_solve_small(SmallArgs a) {
     p.idx = a.idx != nullptr ? a.idx + b * N : nullptr;
     p.u = u;
     p.N = N, p.S = S, p.n_c = n_c, p.n_u = NU, p.K = K, p.SP = SP, p.R = kSmallThreads / SP;
+    p.nb = (S + 7) / 8;
+    p.mask = MASK ? a.mask + b * N * p.nb : nullptr;
 
     // job tables: the known block (pairs of R_trunc columns in packed order, then their products with v), then what
     // involves u (the packed rows l >= n_c, then b_u)
@@ -357,7 +374,13 @@ __global__ __launch_bounds__(kSmallThreads) void k_solve_small(SmallArgs a) {
         {
             const int s = t & (SP - 1), r = t / SP;
             if (s < S)
-                for (int64_t i = r; i < N; i += p.R) dmax = fmax(dmax, p.D[p.row(i) * S + s]);
+                for (int64_t i = r; i < N; i += p.R) {
+                    if constexpr (MASK) {  // the maximum over the kept elements (D.max() of counts * train_mask)
+                        if (p.kept(i, s)) dmax = fmax(dmax, p.D[i * S + s]);
+                    } else {
+                        dmax = fmax(dmax, p.D[p.row(i) * S + s]);
+                    }
+                }
         }
         dmax = block_max(dmax, m.red);
         dsq = dmax * dmax;
@@ -372,12 +395,12 @@ __global__ __launch_bounds__(kSmallThreads) void k_solve_small(SmallArgs a) {
         l_h = l_h_prev = (rt_norm2 + u2) * dsq;
         a1 = a2 = 1.0;
         iters = 0;
-        gram_jobs(p, m, 0, n_known);
+        gram_jobs<MASK>(p, m, 0, n_known);
         for (int e = t; e < n_known * S; e += kSmallThreads) {
             const int j = e / S, s = e - j * S;
             gk[e] = m.gb[(int)m.jd[j] * SP + s];
         }
-        cf = stream_cost(p, m);
+        cf = stream_cost<MASK>(p, m);
     } else {
         for (int e = t; e < K * S; e += kSmallThreads) {
             const int k = e / S, s = e - k * S;
@@ -428,9 +451,13 @@ __global__ __launch_bounds__(kSmallThreads) void k_solve_small(SmallArgs a) {
             for (int q = 0; q < NP; ++q) M[q] = 0.0;
             const double* Vr = p.V + g * S;
             const double* Dr = p.D + g * S;
+            unsigned long long bits = 0;  // the row's train bits, sample s in bit s (S <= 64)
+            if constexpr (MASK)
+                for (int q = 0; q < p.nb; ++q) bits |= (unsigned long long)p.mask[g * p.nb + q] << (8 * q);
 #pragma unroll 4
             for (int s = 0; s < S; ++s) {
-                const double d = Dr[s];
+                double d = Dr[s];
+                if constexpr (MASK) d = (bits >> s) & 1 ? d : 0.0;
                 double x = Vr[s];
 #pragma unroll
                 for (int k = 0; k < kSmallMaxK - 1; ++k)
@@ -478,7 +505,7 @@ __global__ __launch_bounds__(kSmallThreads) void k_solve_small(SmallArgs a) {
         if constexpr (!PURITY) l_h = (rt_norm2 + u2) * dsq;  // :212
 
         // ---- the u-dependent entries of the per-sample Grams
-        gram_jobs(p, m, n_known, n_jobs);
+        gram_jobs<MASK>(p, m, n_known, n_jobs);
 
         // ---- alpha phase: Frank-Wolfe under the purity constraint (:280-302), else (:93-102) thread s owns column s
         if constexpr (PURITY) {
@@ -515,7 +542,7 @@ __global__ __launch_bounds__(kSmallThreads) void k_solve_small(SmallArgs a) {
 
         // ---- cost and stop test (:218-220)
         const double cf_0 = cf;
-        cf = stream_cost(p, m);
+        cf = stream_cost<MASK>(p, m);
         ++iters;
         if (fabs(cf - cf_0) < a.tol) {
             done = 1;
@@ -537,6 +564,72 @@ __global__ __launch_bounds__(kSmallThreads) void k_solve_small(SmallArgs a) {
     }
 }
 
+// n_train[b] = the set bits among the N x S real positions of mask b: thread t counts rows t, t + 256, ..., the 256 integer
+// partials are added by one fixed tree.  Bits of samples >= S in a row's last byte are padding and not counted.
+__global__ __launch_bounds__(kSmallThreads) void k_small_mask_count(const uint8_t* __restrict__ mask, int64_t N, int S,
+                                                                    long long* __restrict__ n_train) {
+    __shared__ long long part[kSmallThreads];
+    const int t = threadIdx.x, nb = (S + 7) / 8;
+    const uint8_t* mb = mask + (int64_t)blockIdx.x * N * nb;
+    const unsigned int last = (S & 7) ? (1u << (S & 7)) - 1u : 0xFFu;  // the real bits of a row's last byte
+    long long n = 0;
+    for (int64_t i = t; i < N; i += kSmallThreads)
+        for (int q = 0; q < nb; ++q) n += __popc((unsigned int)mb[i * nb + q] & (q == nb - 1 ? last : 0xFFu));
+    part[t] = n;
+    __syncthreads();
+    for (int off = kSmallThreads / 2; off > 0; off >>= 1) {
+        if (t < off) part[t] += part[t + off];
+        __syncthreads();
+    }
+    if (t == 0) n_train[blockIdx.x] = part[0];
+}
+
+// sum_sq[b] = sum over the held-out elements (bit 0) of (v - [Rt | u_b] alpha_b)^2 on the problem's full V: threads as
+// (row slice r, sample s) like stream_cost, a thread adds its rows in rising order, the partials go through block_sum's tree.
+__global__ __launch_bounds__(kSmallThreads) void k_small_holdout(const double* __restrict__ V, const double* __restrict__ Rt,
+                                                                 const double* __restrict__ u, const double* __restrict__ alpha,
+                                                                 const uint8_t* __restrict__ mask, int64_t N, int S, int n_c,
+                                                                 int n_u, double* __restrict__ sum_sq) {
+    __shared__ double al[kSmallMaxK * kSmallMaxS];
+    __shared__ double red[kSmallThreads];
+    const int64_t b = blockIdx.x;
+    const int t = threadIdx.x, K = n_c + n_u, SP = pow2_at_least(S), nb = (S + 7) / 8, R = kSmallThreads / SP;
+    for (int e = t; e < K * S; e += kSmallThreads) al[e] = alpha[b * K * S + e];
+    __syncthreads();
+    const double* ub = u + b * N * n_u;
+    const uint8_t* mb = mask + b * N * nb;
+    const int s = t & (SP - 1), r = t / SP;
+    double acc = 0.0;
+    if (s < S) {
+        for (int64_t i = r; i < N; i += R) {
+            if ((mb[i * nb + (s >> 3)] >> (s & 7)) & 1) continue;
+            double resid = V[i * S + s];
+            for (int k = 0; k < n_c; ++k) resid = fma(-Rt[i * n_c + k], al[k * S + s], resid);
+            for (int j = 0; j < n_u; ++j) resid = fma(-ub[i * n_u + j], al[(n_c + j) * S + s], resid);
+            acc = fma(resid, resid, acc);
+        }
+    }
+    const double total = block_sum(acc, red);
+    if (t == 0) sum_sq[b] = total;
+}
+
+hipError_t launch_small_mask_count(const uint8_t* mask, int64_t B, int64_t N, int S, long long* n_train, hipStream_t st) {
+    if (mask == nullptr || n_train == nullptr || B < 1 || B > 0x7fffffff || N < 1 || S < 1 || S > kSmallMaxS)
+        return hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_small_mask_count, dim3((unsigned)B), dim3(kSmallThreads), 0, st, mask, N, S, n_train);
+    return hipGetLastError();
+}
+
+hipError_t launch_small_holdout(const double* V, const double* Rt, const double* u, const double* alpha, const uint8_t* mask,
+                                int64_t B, int64_t N, int S, int n_c, int n_u, double* sum_sq, hipStream_t st) {
+    if (V == nullptr || u == nullptr || alpha == nullptr || mask == nullptr || sum_sq == nullptr || B < 1 || B > 0x7fffffff ||
+        !small_supported(N, S, n_c, n_u, DMF_MODE_PARTIAL) || (n_c > 0 && Rt == nullptr))
+        return hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_small_holdout, dim3((unsigned)B), dim3(kSmallThreads), 0, st, V, Rt, u, alpha, mask, N, S, n_c, n_u,
+                       sum_sq);
+    return hipGetLastError();
+}
+
 bool small_supported(int64_t N, int64_t S, int64_t n_c, int64_t n_u, int mode) {
     if (mode != DMF_MODE_PARTIAL && mode != DMF_MODE_UNSUPERVISED) return false;
     if (N < 1 || S < 1 || S > kSmallMaxS || n_c < 0 || n_u < 1 || n_u > kSmallMaxNu || n_c + n_u > kSmallMaxK) return false;
@@ -549,16 +642,16 @@ size_t small_lds_bytes(int S, int K) {
     return doubles * sizeof(double) + (kJobShorts * sizeof(short) + 7) / 8 * 8;
 }
 
-template <int NU, bool PURITY>
+template <int NU, bool PURITY, bool MASK = false>
 static hipError_t launch_nu(const SmallArgs& a, int64_t B, size_t lds, hipStream_t st) {
     static bool raised = false;  // more than 64 KB of dynamic LDS need the kernel's limit raised, once
     if (lds > 64 * 1024 && !raised) {
-        const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_solve_small<NU, PURITY>),
+        const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_solve_small<NU, PURITY, MASK>),
                                                  hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
         if (e != hipSuccess) return e;
         raised = true;
     }
-    hipLaunchKernelGGL((k_solve_small<NU, PURITY>), dim3((unsigned)B), dim3(kSmallThreads), lds, st, a);
+    hipLaunchKernelGGL((k_solve_small<NU, PURITY, MASK>), dim3((unsigned)B), dim3(kSmallThreads), lds, st, a);
     return hipGetLastError();
 }
 
@@ -566,12 +659,21 @@ hipError_t launch_solve_small(const SmallArgs& a, int64_t B, hipStream_t st) {
     if (!small_supported(a.N, a.S, a.n_c, a.n_u, a.mode) || B < 1 || B > 0x7fffffff) return hipErrorInvalidValue;
     const size_t lds = small_lds_bytes(a.S, a.n_c + a.n_u);
     if (a.purity != nullptr) {  // the purity variant: partial mode with a known block to hold at that mass
-        if (a.mode != DMF_MODE_PARTIAL || a.n_c < 1) return hipErrorInvalidValue;
+        if (a.mode != DMF_MODE_PARTIAL || a.n_c < 1 || a.mask != nullptr) return hipErrorInvalidValue;
         switch (a.n_u) {
             case 1: return launch_nu<1, true>(a, B, lds, st);
             case 2: return launch_nu<2, true>(a, B, lds, st);
             case 3: return launch_nu<3, true>(a, B, lds, st);
             default: return launch_nu<4, true>(a, B, lds, st);
+        }
+    }
+    if (a.mask != nullptr) {  // a train mask per solve: neither a row list nor the purity variant goes with it
+        if (a.idx != nullptr) return hipErrorInvalidValue;
+        switch (a.n_u) {
+            case 1: return launch_nu<1, false, true>(a, B, lds, st);
+            case 2: return launch_nu<2, false, true>(a, B, lds, st);
+            case 3: return launch_nu<3, false, true>(a, B, lds, st);
+            default: return launch_nu<4, false, true>(a, B, lds, st);
         }
     }
     switch (a.n_u) {

@@ -66,7 +66,17 @@ struct SmallArgs {
     // S doubles or null.  Not null: the purity variant (mdwbssmf_deconv_p, deconvolution.py:306-337), whose alpha phase is
     // Frank-Wolfe with mass purity[s] on the known block of sample s; alpha_prev and the second half of ratio are unused.
     const double* purity = nullptr;
+    // B x N x ceil(S / 8) bytes or null.  Not null: solve b has its own train mask (a bi-cross-validation fold, ic.py:58-89)
+    // in dmf_problem_mask's layout -- row-major, sample s in bit (s & 7) of byte (s >> 3), 1 = kept, padding bits ignored --
+    // and sees the count of an element as 0 where its bit is 0.  Not together with idx or purity.
+    const uint8_t* mask = nullptr;
 };
 hipError_t launch_solve_small(const SmallArgs& a, int64_t B, hipStream_t st);
+// n_train[b] = the set bits among the N x S real positions of mask b (grid B; an integer sum in a fixed tree)
+hipError_t launch_small_mask_count(const uint8_t* mask, int64_t B, int64_t N, int S, long long* n_train, hipStream_t st);
+// sum_sq[b] = sum over the elements whose bit is 0 of (v - [Rt | u_b] alpha_b)^2 on the problem's full V, with (u, alpha) the
+// B x N x n_u and B x K x S iterates of the workspace (grid B; ic.py:80 before the division)
+hipError_t launch_small_holdout(const double* V, const double* Rt, const double* u, const double* alpha, const uint8_t* mask,
+                                int64_t B, int64_t N, int S, int n_c, int n_u, double* sum_sq, hipStream_t st);
 
 }  // namespace dmf

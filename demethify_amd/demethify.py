@@ -20,7 +20,9 @@ Deliberate differences from upstream, all flagged at run time:
     problem are solved many per kernel launch, one workgroup each, when the case is eligible
     (bootstrap.batched_ineligible) and N x S is at most bootstrap.SMALL_BATCH_MAX_ELEMENTS (with ``--purity``:
     bootstrap.SMALL_BATCH_PURITY_MAX_ELEMENTS, the purity variant of the kernel); otherwise a one-line note says
-    why not and the run takes the per-solve path.
+    why not and the run takes the per-solve path.  With ``--ic`` the sweep's restarts (CCC) and folds (BCV) go the same
+    way (evaluate_best_ic(batched=True)) for the criteria of ic.SMALL_BATCH_IC_CRITERIA up to
+    ic.SMALL_BATCH_IC_MAX_ELEMENTS elements; a candidate outside the kernel's envelope takes the per-solve path inside it.
   * ``--ic NAME [n [lo hi]]``: upstream sweeps the hard-coded range 1..25 (ic.py:171); two more values after the
     restart count restrict the sweep to lo..hi unknown types (``--ic BIC 5 2 12``).  Without them: 1..25, as upstream.
 """
@@ -223,10 +225,29 @@ def main(argv=None):
     elif args.confidence and n_u < 1:
         sys.exit(f'Invalid number of unknown value! : "{args.nbunknown}" ')
 
+    def ic_batch_route():
+        """DEMETHIFY_BATCH=1 with --ic: does the sweep go through evaluate_best_ic(batched=True)?  Candidates outside the
+        kernel's envelope take the per-solve path inside it; the size gate is the measured one of ic.py."""
+        if batch_env != "1":
+            return False
+        from . import ic as ic_mod
+
+        reason = None
+        if args.ic not in ic_mod.SMALL_BATCH_IC_CRITERIA:
+            reason = f"{args.ic} was not measured faster through the batch (ic.SMALL_BATCH_IC_CRITERIA)"
+        elif meth_f.size > ic_mod.SMALL_BATCH_IC_MAX_ELEMENTS:
+            reason = (f"{meth_f.shape[0]} x {meth_f.shape[1]} elements are more than SMALL_BATCH_IC_MAX_ELEMENTS = "
+                      f"{ic_mod.SMALL_BATCH_IC_MAX_ELEMENTS}")
+        if reason is not None and rank == 0:
+            print(f"Note: DEMETHIFY_BATCH=1 is not used for --ic: {reason}; taking the per-solve path.")
+        return reason is None
+
     if args.ic:
+        # (the keyword is passed only when the route is taken: without the switch the call is what it was)
+        ic_kw = {"batched": True} if ic_batch_route() else {}
         ref_estimate, proportions, ic_n_u, _scores = evaluate_best_ic(
             meth_f, ref, counts, args.init, args.ic, args.seed, iter1=args.iterations[0], iter2=args.iterations[1],
-            tol=args.termination, n_restarts=nb_r, n_u_values=ic_range)
+            tol=args.termination, n_restarts=nb_r, n_u_values=ic_range, **ic_kw)
         unknown_header = ["unknown_cell_" + str(i + 1) for i in range(ic_n_u)]
         header = header + unknown_header
     elif (not args.ref) or (n_u > 0 and meth_f.shape[1] >= 1):

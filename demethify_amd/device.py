@@ -694,6 +694,47 @@ class Problem:
                                           _ptr(alpha), _ptr(cost), _ptr(iters)), "dmf_solve_small")
         return u, alpha, cost, iters
 
+    def solve_many_masked(self, u0s, alpha0s, train_masks, mode, n_iter1, n_iter2, tol, iters_per_launch=0):
+        """B independent solves of this problem, each on its own hold-out mask, in one call (dmf_solve_small_masked: the
+        folds of a bi-cross-validation, ic.py:58-89) -> (u[B, N, n_u], alpha[B, K, S], cost[B], iters[B],
+        holdout_sum_sq[B], n_test[B]).  ``train_masks``: a bool array of shape (B, N, S), True = kept, or the masks as
+        ``pack_mask`` packs them, uint8 of shape (B, N, ceil(S / 8)).  Solve b sees the count of an element as 0 where its
+        mask is False; ``cost[b]`` is cost_f_w on those masked data, ``holdout_sum_sq[b]`` the squared error of the final
+        iterate on the held-out elements of the full data and ``n_test[b]`` their number (the fold's error is their
+        quotient).  Everything else is ``solve_many``'s.  Shape errors raise ValueError before any device call; a mask that
+        keeps no element is refused by the library (DMF_ERR_BAD_ARG) before any solve starts."""
+        u0s = np.ascontiguousarray(u0s, dtype=np.float64)
+        alpha0s = np.ascontiguousarray(alpha0s, dtype=np.float64)
+        if u0s.ndim != 3 or u0s.shape[1] != self.N:
+            raise ValueError(f"u0s is B x {self.N} x n_u, got shape {u0s.shape}")
+        B, _, n_u = u0s.shape
+        K = self.n_c + n_u
+        if alpha0s.shape != (B, K, self.S):
+            raise ValueError(f"alpha0s shape {alpha0s.shape} != {(B, K, self.S)}")
+        nb = (self.S + 7) // 8
+        m = np.asarray(train_masks)
+        if m.dtype == np.bool_:
+            if m.shape != (B, self.N, self.S):
+                raise ValueError(f"train_masks shape {m.shape} != {(B, self.N, self.S)}")
+            bits = np.packbits(m, axis=2, bitorder="little")  # (pack_mask's layout, one mask after the other)
+        elif m.dtype == np.uint8:
+            if m.shape != (B, self.N, nb):
+                raise ValueError(f"packed train_masks shape {m.shape} != {(B, self.N, nb)} (ceil(S / 8) bytes per row)")
+            bits = np.ascontiguousarray(m)
+        else:
+            raise ValueError("train_masks must be a bool (B, N, S) array or packed uint8 bits (B, N, ceil(S / 8))")
+        u = np.empty((B, self.N, n_u), dtype=np.float64)
+        alpha = np.empty((B, K, self.S), dtype=np.float64)
+        cost = np.empty(B, dtype=np.float64)
+        iters = np.empty(B, dtype=np.int64)
+        sum_sq = np.empty(B, dtype=np.float64)
+        n_test = np.empty(B, dtype=np.int64)
+        L.check(self._lib.dmf_solve_small_masked(self.ctx._h, self._h, B, _ptr(bits), _ptr(u0s), _ptr(alpha0s), n_u, int(mode),
+                                                 int(n_iter1), int(n_iter2), float(tol), int(iters_per_launch), 0, _ptr(u),
+                                                 _ptr(alpha), _ptr(cost), _ptr(iters), _ptr(sum_sq), _ptr(n_test)),
+                "dmf_solve_small_masked")
+        return u, alpha, cost, iters, sum_sq, n_test
+
     def update_u(self, u, u_prev, alpha, n_iter2, a1, l_w_prev, l_w, mode=L.DMF_MODE_PARTIAL):
         u = np.ascontiguousarray(u, dtype=np.float64).reshape(self.N, -1)
         u_prev = np.ascontiguousarray(u_prev, dtype=np.float64).reshape(u.shape)

@@ -22,7 +22,7 @@ from .staging import Prefetcher
 from .init_func import wls_intercept
 
 __all__ = ["compute_bic", "compute_aic", "compute_consensus_matrix", "compute_ccc", "run_deconvolution",
-           "bicross_validation", "evaluate_best_ic"]
+           "bicross_validation", "evaluate_best_ic", "batched_ic_ineligible", "SMALL_BATCH_IC_MAX_ELEMENTS"]
 
 
 def _n_free(n_u, n_cpg, n_ct, n_samples):
@@ -176,8 +176,63 @@ class _DeviceFolds:
         return test_error, factors
 
 
+# The number of elements N x S up to which the command line (DEMETHIFY_BATCH=1) sends an --ic sweep through
+# evaluate_best_ic(batched=True): the largest measured size at which the batched leg wins for BCV and CCC there and at every
+# smaller measured size.  Measured (tools/small_ic_bench.py, profiles/small_batch_ic_bench.txt; candidates n_u = 1..4, medians
+# of five, per-solve against batched): 350 x 10 with 20 folds of BCV 646 ms against 213 ms and with 20 restarts of CCC 441 ms
+# against 210 ms, 1 000 x 16 BCV 515 ms against 305 ms and CCC 358 ms against 270 ms -- and 10 000 x 64 with 5 folds of BCV
+# 0.22 s against 12.9 s: there one workgroup per fold loses, as for the restarts (bootstrap.SMALL_BATCH_MAX_ELEMENTS), so the
+# gate sits at 1 000 x 16.
+SMALL_BATCH_IC_MAX_ELEMENTS = 16000
+# The criteria the command line sends through the batch below that gate.  AIC / BIC are not among them: their one solve
+# per candidate as a batch of one is ONE workgroup on one CU, measured slower on the 350 x 10 example (22 ms against 125 ms for
+# the four candidates), so the command line leaves them on the per-solve path; evaluate_best_ic(batched=True) takes them.
+SMALL_BATCH_IC_CRITERIA = ("CCC", "BCV")
+
+
+def batched_ic_ineligible(n_u, n_rows, n_samples, n_ct, mode):
+    """Why a candidate ``n_u`` of a model-selection sweep cannot go through ``Problem.solve_many`` /
+    ``Problem.solve_many_masked``, as a sentence, or None when it can.  The batched kernel's envelope only (nothing else
+    stands between a sweep and the batch: every initialiser runs on host arrays before the call).  Touches no device."""
+    from .device import small_solve_supported
+
+    if n_u < 1:
+        return "there is no unknown cell type to solve for"
+    if not small_solve_supported(n_rows, n_samples, n_ct, n_u, mode):
+        return (f"the shape {n_rows} x {n_samples} with {n_ct} + {n_u} cell types is outside the batched kernel's envelope "
+                f"(n_u <= {L.SMALL_MAX_NU}, K <= {L.SMALL_MAX_K}, S <= {L.SMALL_MAX_S}, N S <= {L.SMALL_MAX_ELEMENTS})")
+    return None
+
+
+def _bcv_batched(meth_f, n_u, counts, iter1, iter2, tol, n_folds, seed, ref, init_option, fraction, problem):
+    """bicross_validation(batched=True): every fold is drawn first, on the host and in the reference's order (the draws do
+    not depend on the solves, so the generator's stream is the serial one), the folds upstream skips are dropped, the rest
+    are solved by ``problem.solve_many_masked`` in chunks, and ic.py:80-86 is replayed in fold order."""
+    from .bootstrap import batch_chunk
+
+    folds = []
+    for _ in range(n_folds):
+        fold = _bcv_draw_fold(meth_f, counts, ref, n_u, init_option, seed, fraction)
+        if fold is not None:
+            folds.append(fold)
+    mode = L.DMF_MODE_PARTIAL if ref is not None else L.DMF_MODE_UNSUPERVISED
+    chunk = batch_chunk(meth_f.shape[0], n_u)
+    total_press, best_u, best_alpha, min_error = 0, None, None, float("inf")
+    for c0 in range(0, len(folds), chunk):
+        part = folds[c0:c0 + chunk]
+        u, alpha, _, _, sum_sq, n_test = problem.solve_many_masked(
+            np.stack([np.asarray(f[1], dtype=np.float64).reshape(meth_f.shape[0], n_u) for f in part]),
+            np.stack([f[2] for f in part]), np.stack([f[0] for f in part]), mode, iter1, iter2, tol)
+        for b in range(len(part)):
+            test_error = sum_sq[b] / n_test[b]
+            total_press += test_error
+            if test_error < min_error:
+                min_error, best_u, best_alpha = test_error, u[b], alpha[b]
+    return total_press, best_u, best_alpha
+
+
 def bicross_validation(meth_f, n_u, counts, iter1, iter2, tol, n_folds=10, seed=None, ref=None,
-                       init_option="uniform_", fraction=0.3, problem=None, _fold_solver=None):
+                       init_option="uniform_", fraction=0.3, problem=None, _fold_solver=None, batched=False):
     """ic.py:58-89: random-mask hold-out error (returns the SUM over folds, as upstream).
 
     The data are uploaded once (``problem``: a resident upload of (meth_f, counts, ref) to reuse; created here when
@@ -186,7 +241,26 @@ def bicross_validation(meth_f, n_u, counts, iter1, iter2, tol, n_folds=10, seed=
     thread (numpy's global generator), one fold ahead of the GPU; above the gate of _bcv_draw_fold that thread has the
     device continue the generator's stream for the mask (``solve.draw``) and takes the generator up behind it.
     ``_fold_solver(fold, best) -> (test_error, (u, alpha) or None)`` replaces the device half (tests drive the draw order
-    through it without a GPU); its ``stage`` and ``draw`` attributes, where it has them, are picked up like _DeviceFolds'."""
+    through it without a GPU); its ``stage`` and ``draw`` attributes, where it has them, are picked up like _DeviceFolds'.
+
+    ``batched``: the folds go through ``Problem.solve_many_masked``, one workgroup per fold with its mask read in the kernel
+    and the hold-out error taken where the iterates live, instead of one masked problem and one solver
+    per fold.  Draws, skipped folds, the running sum and the first strict minimum are the serial route's.  Only inside the
+    kernel's envelope (``batched_ic_ineligible``): any other shape raises ValueError before any device work."""
+    if batched:
+        reason = batched_ic_ineligible(n_u, meth_f.shape[0], meth_f.shape[1], 0 if ref is None else ref.shape[1],
+                                       L.DMF_MODE_UNSUPERVISED if ref is None else L.DMF_MODE_PARTIAL)
+        if reason is not None:
+            raise ValueError(f"bicross_validation(batched=True): {reason}")
+        np.random.seed(seed)
+        own = problem is None
+        if own:
+            problem = Problem(get_context(), meth_f, counts, ref)
+        try:
+            return _bcv_batched(meth_f, n_u, counts, iter1, iter2, tol, n_folds, seed, ref, init_option, fraction, problem)
+        finally:
+            if own:
+                problem.close()
     np.random.seed(seed)
     total_press, best_u, best_alpha, min_error = 0, None, None, float("inf")
     own = problem is None and _fold_solver is None
@@ -216,12 +290,37 @@ def bicross_validation(meth_f, n_u, counts, iter1, iter2, tol, n_folds=10, seed=
     return total_press, best_u, best_alpha
 
 
+def _note_per_solve(candidates, rank):
+    if candidates and rank == 0:
+        print(f"note: candidates n_u = {candidates} are outside the batched kernel's envelope (n_u <= {L.SMALL_MAX_NU}, "
+              f"K <= {L.SMALL_MAX_K}, S <= {L.SMALL_MAX_S}, N S <= {L.SMALL_MAX_ELEMENTS}): they take the per-solve path")
+
+
+def _solve_many_chunked(problem, inits, mode, iter1, iter2, tol, n_u):
+    """``problem.solve_many`` on a list of (u0, alpha0), at most bootstrap.batch_chunk solves per call -> (u, alpha, cost)."""
+    from .bootstrap import batch_chunk
+
+    chunk = batch_chunk(problem.N, n_u)
+    parts = []
+    for c0 in range(0, len(inits), chunk):
+        part = inits[c0:c0 + chunk]
+        parts.append(problem.solve_many(np.stack([np.asarray(u0, dtype=np.float64).reshape(problem.N, n_u) for u0, _ in part]),
+                                        np.stack([a0 for _, a0 in part]), mode, iter1, iter2, tol)[:3])
+    return tuple(np.concatenate([part[j] for part in parts]) for j in range(3))
+
+
 def evaluate_best_ic(meth_f, ref, counts, init_option, ic, seed, iter1, iter2, tol, n_restarts=5,
-                     n_u_values=None):
+                     n_u_values=None, batched=False):
     """ic.py:169-218 -> (u, alpha, n_u, list of criterion values).
 
     ``n_u_values`` defaults to upstream's hard-coded ``range(1, 26)`` (ic.py:171).  AIC / BIC sweeps
     are sharded across the ranks of an initialised torch.distributed job; CCC and BCV run serially.
+
+    ``batched``: a candidate inside the batched kernel's envelope (``batched_ic_ineligible``) is solved through
+    ``Problem.solve_many`` -- the restarts of CCC in one call, the one solve of AIC / BIC as a batch of one, whose cost is
+    the cost_f_w the formula takes -- or, for BCV, through ``bicross_validation(batched=True)``.  Any other candidate takes the
+    per-solve path inside the same sweep, and one note on rank 0 lists which did.  Initialisers, seeds, the order of the
+    candidates and the rank sharding of AIC / BIC are the same either way.
     """
     default_range = n_u_values is None
     if default_range:
@@ -236,11 +335,21 @@ def evaluate_best_ic(meth_f, ref, counts, init_option, ic, seed, iter1, iter2, t
 
     if ic in ("CCC", "BCV"):
         best_ic, best = float("inf"), (None, None, None)
-        scores = []
+        scores, per_solve = [], []
+        mode = L.DMF_MODE_PARTIAL if ref is not None else L.DMF_MODE_UNSUPERVISED
         # one resident upload for the whole sweep: every restart (CCC) and every fold (BCV) of every candidate solves on it
         with Problem(get_context(), meth_f, counts, ref) as problem:
             for n_u in n_u_values:
-                if ic == "CCC":
+                in_batch = batched and batched_ic_ineligible(n_u, n_cpg, n_samples, n_ct, mode) is None
+                if batched and not in_batch:
+                    per_solve.append(n_u)
+                if ic == "CCC" and in_batch:
+                    inits = [_init_on(problem, meth_f, counts, ref, n_u, init_option, seed + restart)
+                             for restart in range(n_restarts)]
+                    us, alphas, _ = _solve_many_chunked(problem, inits, mode, iter1, iter2, tol, n_u)
+                    u, alpha = us[-1], alphas[-1]  # (the serial loop leaves its last restart's factors behind)
+                    score = -compute_ccc(list(alphas))
+                elif ic == "CCC":
                     runs = []
                     for restart in range(n_restarts):
                         u, _, alpha = run_deconvolution(meth_f, counts, ref, n_u, init_option, seed + restart, iter1,
@@ -250,10 +359,11 @@ def evaluate_best_ic(meth_f, ref, counts, init_option, ic, seed, iter1, iter2, t
                 else:
                     score, u, alpha = bicross_validation(meth_f, n_u, counts, iter1, iter2, tol, fraction=0.3,
                                                          n_folds=n_restarts, seed=seed, ref=ref,
-                                                         init_option=init_option, problem=problem)
+                                                         init_option=init_option, problem=problem, batched=in_batch)
                 scores.append(score)
                 if score < best_ic:
                     best_ic, best = score, (u, alpha, n_u)
+        _note_per_solve(per_solve, 0)
         return best[0], best[1], best[2], scores
 
     # AIC / BIC: one solve per candidate; candidates dealt to ranks longest-first (cost grows with n_u)
@@ -291,12 +401,22 @@ def evaluate_best_ic(meth_f, ref, counts, init_option, ic, seed, iter1, iter2, t
         return None if on_device(n_u) else _init_on(None, meth_f, counts, ref, n_u, init_option, seed)
 
     mode = L.DMF_MODE_PARTIAL if ref is not None else L.DMF_MODE_UNSUPERVISED
+    if batched:  # (every rank sees the same list: eligibility is a function of the shape)
+        _note_per_solve([n for n in n_u_values if batched_ic_ineligible(n, n_cpg, n_samples, n_ct, mode) is not None], rank)
     with Problem(get_context(), meth_f, counts, ref) as problem:
         feed = Prefetcher(mine, draw, depth=1, workers=1)
         try:
             for i, drawn in feed:
                 n_u = n_u_values[i]
                 u0, a0 = drawn if drawn is not None else _init_on(problem, meth_f, counts, ref, n_u, init_option, seed)
+                if batched and batched_ic_ineligible(n_u, n_cpg, n_samples, n_ct, mode) is None:
+                    # a batch of one: out_cost is cost_f_w(meth_f, R, alpha, counts) of the final iterate (ic.py:206)
+                    us, alphas, costs = _solve_many_chunked(problem, [(u0, a0)], mode, iter1, iter2, tol, n_u)
+                    score = float(formula(costs[0], n_u, n_cpg, n_ct, n_samples))
+                    local.append((i, score))
+                    if score < (keep[0] if keep else float("inf")) or (keep and score == keep[0] and i < keep[1]):
+                        keep = (score, i, us[0], alphas[0])
+                    continue
                 with Solver(problem, u0, a0, mode) as s:
                     s.step(iter1, iter2, tol)
                     cost = s.direct_cost()  # cost_f_w(meth_f, R, alpha, counts), ic.py:206, where the iterate lives

@@ -502,6 +502,25 @@ int dmf_solve_small_purity(dmf_context* ctx, const dmf_problem* p, int64_t B, co
                            const double* alpha0, const double* purity, int64_t n_u, int mode, int64_t n_iter1,
                            int64_t n_iter2, double tol, int64_t iters_per_launch, int flags, double* out_u,
                            double* out_alpha, double* out_cost, int64_t* out_iters);
+/* dmf_solve_small_masked: the same B solves, each on its own hold-out mask -- the folds of a bi-cross-validation
+ * (demethify/ic.py:58-89) in one call.  train_bits: B x N x ceil(S / 8) bytes in dmf_problem_mask's layout (row-major, sample s
+ * in bit (s & 7) of byte (s >> 3), 1 = kept, 0 = held out, padding bits ignored); a host array, or a device array with
+ * DMF_PTR_DEVICE in flags.  Solve b sees the count of an element as 0 where its bit is 0 (`counts * train_mask`, ic.py:75)
+ * in every place the kernel reads a count: d = max(counts)^2 is the maximum over the kept elements, the known Gram block,
+ * the u phase, the Gram, the streaming cost and therefore the stop test.  v of a held-out element is only ever multiplied
+ * by that 0 (`meth_f * train_mask`: V is finite).  out_cost[b] is cost_f_w of the final iterate on the masked data.  After the
+ * last launch the hold-out error is taken where the iterates live: out_holdout_sum_sq[b] = sum over the held-out elements of
+ * (v - [R_trunc | u_b] alpha_b)^2 on the problem's full V (ic.py:80 before the division), out_n_test[b] = N S minus the
+ * number of kept elements (B host doubles, B host int64).  A mask that holds out nothing is valid: 0.0 and 0.
+ * Arguments, conventions, envelope, workspace and determinism are dmf_solve_small's: a solve's results do not depend on B, on
+ * its slot, on the other solves' masks or on iters_per_launch, bit for bit; an all-ones mask gives dmf_solve_small's results
+ * bit for bit.  There is no idx and no purity here.  DMF_ERR_UNSUPPORTED outside the envelope, before the context is touched.
+ * DMF_ERR_BAD_ARG: a null train_bits, a masked p, a solve whose mask keeps no element (upstream skips such a fold, ic.py:71;
+ * d would be 0) -- the kept elements are counted on the device before any solve starts, and the outputs stay untouched. */
+int dmf_solve_small_masked(dmf_context* ctx, const dmf_problem* p, int64_t B, const uint8_t* train_bits, const double* u0,
+                           const double* alpha0, int64_t n_u, int mode, int64_t n_iter1, int64_t n_iter2, double tol,
+                           int64_t iters_per_launch, int flags, double* out_u, double* out_alpha, double* out_cost,
+                           int64_t* out_iters, double* out_holdout_sum_sq, int64_t* out_n_test);
 
 /* ---- input tables (host side) ---------------------------------------------------------------
  * demethify/demethify.py:103-143 reads each sample file with pandas.read_csv and stacks its `percent_modified` and
