@@ -39,6 +39,8 @@ DMF_MODE_UNSUPERVISED = 1
 MAX_K = 64  # dmf::kMaxK: largest n_c + n_u the kernels are built for (DMF_ERR_UNSUPPORTED beyond)
 # dmf::kSmallMax*: the envelope of dmf_solve_small (S, n_c + n_u, n_u, N * S)
 SMALL_MAX_S, SMALL_MAX_K, SMALL_MAX_NU, SMALL_MAX_ELEMENTS = 64, 16, 4, 1 << 20
+# dmf::kMidMax*: the envelope of dmf_solve_mid, and the most workgroups it gives one solve
+MID_MAX_S, MID_MAX_K, MID_MAX_NU, MID_MAX_ELEMENTS, MID_MAX_W = 64, 16, 4, 1 << 23, 64
 SVD_MAX_S, SVD_MAX_NC, SVD_MAX_RANK, SVD_MAX_LDS = 512, 64, 64, 160 * 1024  # dmf::kSvdMax*: what the SVD initialiser's kernels take
 
 
@@ -139,6 +141,10 @@ SIGNATURES = {
                                          _p, _p]),
     "dmf_solve_small_masked": (C.c_int, [_p, _p, _i64, _p, _p, _p, _i64, C.c_int, _i64, _i64, C.c_double, _i64, C.c_int, _p, _p, _p,
                                          _p, _p, _p]),
+    "dmf_solve_mid_supported": (C.c_int, [_i64, _i64, _i64, _i64, C.c_int]),
+    "dmf_solve_mid_plan": (C.c_int, [_i64, _i64, _i64, C.POINTER(_i64), C.POINTER(_i64), C.POINTER(_i64)]),
+    "dmf_solve_mid": (C.c_int, [_p, _p, _i64, _p, _p, _p, _i64, C.c_int, _i64, _i64, C.c_double, _i64, _i64, C.c_int, _p, _p, _p,
+                                _p]),
 }
 
 _lib = None

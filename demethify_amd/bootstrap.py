@@ -83,21 +83,36 @@ SMALL_BATCH_MAX_ELEMENTS = 16000
 # against 67 ms.  The batched leg wins at every measured size, so the gate is the largest of them; nothing larger has been
 # measured under purity (without it the batched leg loses at 10 000 x 64, above).
 SMALL_BATCH_PURITY_MAX_ELEMENTS = 16000
+# The range of N x S in which the command line (DEMETHIFY_BATCH_MID=1) sends bootstrap replicates and restarts through
+# Problem.solve_many_mid (several workgroups per solve): the contiguous range of MEASURED sizes at
+# which the mid-size leg beats both the per-solve leg and the one-launch batch (tools/mid_batch_bench.py,
+# profiles/mid_batch_bench.txt).  MIN > MAX would be a closed gate.  Measured (medians of five; per-solve on the commit
+# before / solve_many / solve_many_mid), 64 restarts of at most 200 outer iterations: 1 000 x 16 (6 + 2) 194 / 40 / 28 ms,
+# 4 000 x 16 (6 + 2) 296 / 183 / 67 ms, 10 000 x 64 (12 + 4) 609 / 4 050 / 719 ms, 32 768 x 64 829 / - / 2 083 ms,
+# 131 072 x 64 1 048 / - / 9 124 ms; bt_ci with 500 replicates at 10 000 x 64 (6 + 2) 4 556 / 4 064 / 2 306 ms.  The mid-size
+# leg wins at 16 000 and 64 000 elements; at 640 000 it wins the bootstrap and loses the restarts, so that size stays out.
+MID_BATCH_MIN_ELEMENTS, MID_BATCH_MAX_ELEMENTS = 16000, 64000
 
 
 def batched_ineligible(n_u, n_rows, n_samples, n_ct, init_option, purity, mode, observe=None, align=False,
-                       profile_rows="position", purity_batched=False):
+                       profile_rows="position", purity_batched=False, kernel="small"):
     """Why a loop of solves cannot go through ``Problem.solve_many`` (one launch for many solves), as a sentence, or None
     when it can: at least one unknown type, no purity constraint, nobody watching single replicates, no component
     alignment, profile rows by position, an initialiser that does not read the data (``uniform_``, ``beta``, or the silent
     replacement by ``uniform_`` when there are more unknown types than samples) and a shape the kernel takes.
     ``purity_batched``: the caller has asked for the purity variant of the kernel (``solve_many(purity=...)``), so a purity
-    vector passes where there is a reference to hold at that mass.  Touches no device."""
-    from .device import small_solve_supported
+    vector passes where there is a reference to hold at that mass.  ``kernel``: "small" (``Problem.solve_many``, the default)
+    or "mid" (``Problem.solve_many_mid``, several workgroups per solve): the mid-size batch has an envelope of its own and no
+    purity variant, whatever ``purity_batched`` says.  Touches no device."""
+    from .device import mid_solve_supported, small_solve_supported
 
+    if kernel not in ("small", "mid"):
+        raise ValueError(f'kernel must be "small" or "mid", got {kernel!r}')
     if n_u < 1:
         return "there is no unknown cell type to solve for"
     if purity is not None and np.size(purity) > 0:
+        if kernel == "mid":
+            return "the purity-constrained alpha phase is not part of the mid-size batch"
         if not purity_batched:
             return ("the purity-constrained alpha phase is not part of the batched kernel unless it is asked for "
                     "(bt_ci(..., batched_purity=True), batched_ineligible(..., purity_batched=True))")
@@ -112,6 +127,11 @@ def batched_ineligible(n_u, n_rows, n_samples, n_ct, init_option, purity, mode, 
     option = "uniform_" if (init_option != "uniform_" and n_u > n_samples) else init_option
     if option not in ("uniform_", "beta"):
         return f"the initialiser {init_option!r} reads the resampled data"
+    if kernel == "mid":
+        if not mid_solve_supported(n_rows, n_samples, n_ct, n_u, mode):
+            return (f"the shape {n_rows} x {n_samples} with {n_ct} + {n_u} cell types is outside the mid-size batch's envelope "
+                    f"(n_u <= {L.MID_MAX_NU}, K <= {L.MID_MAX_K}, S <= {L.MID_MAX_S}, N S <= {L.MID_MAX_ELEMENTS})")
+        return None
     if not small_solve_supported(n_rows, n_samples, n_ct, n_u, mode):
         return (f"the shape {n_rows} x {n_samples} with {n_ct} + {n_u} cell types is outside the batched kernel's envelope "
                 f"(n_u <= {L.SMALL_MAX_NU}, K <= {L.SMALL_MAX_K}, S <= {L.SMALL_MAX_S}, N S <= {L.SMALL_MAX_ELEMENTS})")
@@ -124,9 +144,23 @@ def batch_chunk(n_rows, n_u):
     return int(max(1, min(1024, (1 << 25) // max(1, n_rows * n_u))))
 
 
+def mid_batch_chunk(n_rows, n_samples, n_ct, n_u):
+    """How many solves one ``solve_many_mid`` call of the drivers takes: as many as keep the slab workspace (W workgroups per
+    solve, each with the larger of the known and the u-dependent Gram jobs times S doubles) and the stack of profiles
+    together within 256 MB, at least 1 and at most 1024."""
+    from .device import mid_solve_plan
+
+    _, n_slabs, _ = mid_solve_plan(n_rows, n_samples)
+    K = n_ct + n_u
+    known = n_ct * (n_ct + 1) // 2 + n_ct
+    jobs = max(known, K * (K + 1) // 2 + K - known)
+    per_solve = 8 * (n_slabs * jobs * n_samples + n_rows * n_u)
+    return int(max(1, min(1024, (1 << 28) // per_solve)))
+
+
 def bt_ci(confidence_level, n_bootstrap, n_u, meth_f, counts, ref, init_option, n_iter1, n_iter2, tol, header,
           outdir, samples, purity, seed, materialize=True, _observe=None, anchor=None, align_unknown=None,
-          profile_rows="position", batched=False, batched_purity=False):
+          profile_rows="position", batched=False, batched_purity=False, batch_kernel="small"):
     """bootstrap.py:10-93 -> [proportions CI DataFrame, (profile CI DataFrame)]; writes the two CSVs.
     materialize=False (the CLI, which ignores the return value) skips building the N-row DataFrame of tuples for the
     profile intervals: the CSV is written by the library and the second result is the (lower, upper) array pair.
@@ -155,10 +189,24 @@ def bt_ci(confidence_level, n_bootstrap, n_u, meth_f, counts, ref, init_option, 
     from seed_i in the reference's order, exactly as without it.  Only for the cases ``batched_ineligible`` accepts; any
     other raises ValueError naming the reason before any device work.  A purity vector is among those reasons unless
     ``batched_purity`` is set as well: the replicates then run the purity variant of the kernel (``solve_many(purity=p / 100)``)
-    from ``init_BSSMF_md_p``'s starting points.  (Two switches because ``batched=True`` alone is pinned to refuse purity.)"""
+    from ``init_BSSMF_md_p``'s starting points.  (Two switches because ``batched=True`` alone is pinned to refuse purity.)
+
+    ``batch_kernel``: which batch ``batched=True`` means.  "small" (the default): ``Problem.solve_many``, as above.  "mid":
+    ``Problem.solve_many_mid``, several workgroups per replicate (DESIGN.md section 6.3), in chunks of ``mid_batch_chunk``;
+    eligibility is ``batched_ineligible(..., kernel="mid")``, which has no purity variant.  Any other value raises
+    ValueError."""
     if profile_rows not in ("position", "cpg"):
         raise ValueError(f'profile_rows must be "position" or "cpg", got {profile_rows!r}')
-    if batched:
+    if batch_kernel not in ("small", "mid"):
+        raise ValueError(f'batch_kernel must be "small" or "mid", got {batch_kernel!r}')
+    if batched and batch_kernel == "mid":
+        will_align = bool(ref is None if align_unknown is None else align_unknown) and n_u >= 2
+        reason = batched_ineligible(n_u, meth_f.shape[0], meth_f.shape[1], 0 if ref is None else ref.shape[1], init_option,
+                                    purity, L.DMF_MODE_UNSUPERVISED if ref is None else L.DMF_MODE_PARTIAL, _observe,
+                                    will_align, profile_rows, kernel="mid")
+        if reason is not None:
+            raise ValueError(f'bt_ci(batched=True, batch_kernel="mid"): {reason}')
+    elif batched:
         will_align = bool(ref is None if align_unknown is None else align_unknown) and n_u >= 2
         reason = batched_ineligible(n_u, meth_f.shape[0], meth_f.shape[1], 0 if ref is None else ref.shape[1], init_option,
                                     purity, L.DMF_MODE_UNSUPERVISED if ref is None else L.DMF_MODE_PARTIAL, _observe,
@@ -221,7 +269,8 @@ def bt_ci(confidence_level, n_bootstrap, n_u, meth_f, counts, ref, init_option, 
         u_stack = None
         mine = shard.my_items(n_bootstrap, rank, world)
         shape_f = np.broadcast_to(meth_f[:1], meth_f.shape)
-        chunk = batch_chunk(n_rows, n_u)
+        mid = batch_kernel == "mid"
+        chunk = mid_batch_chunk(n_rows, n_samples, n_ct, n_u) if mid else batch_chunk(n_rows, n_u)
         with Problem(get_context(), meth_f, counts, ref) as full:
             for c0 in range(0, len(mine), chunk):
                 part = mine[c0:c0 + chunk]
@@ -240,8 +289,12 @@ def bt_ci(confidence_level, n_bootstrap, n_u, meth_f, counts, ref, init_option, 
                                                   np.broadcast_to(ref[:1], ref.shape), n_u, rb_alg=wls_intercept, seed=seeds[i],
                                                   _stack=False)
                         inits.append((u0, a0))
-                us, alphas, _, _ = full.solve_many(np.stack([u0 for u0, _ in inits]), np.stack([a0 for _, a0 in inits]),
-                                                   mode, n_iter1, n_iter2, tol, idx=idx, purity=purity_frac)
+                if mid:
+                    us, alphas, _, _ = full.solve_many_mid(np.stack([u0 for u0, _ in inits]), np.stack([a0 for _, a0 in inits]),
+                                                           mode, n_iter1, n_iter2, tol, idx=idx)
+                else:
+                    us, alphas, _, _ = full.solve_many(np.stack([u0 for u0, _ in inits]), np.stack([a0 for _, a0 in inits]),
+                                                       mode, n_iter1, n_iter2, tol, idx=idx, purity=purity_frac)
                 local.extend((i, (us[j], alphas[j])) for j, i in enumerate(part))
     else:
         # The host work of the replicates ahead (MT19937 index draw of N rows; uniform N x n_u + Dirichlet init: ~10 + ~13 ms

@@ -23,6 +23,11 @@ Deliberate differences from upstream, all flagged at run time:
     why not and the run takes the per-solve path.  With ``--ic`` the sweep's restarts (CCC) and folds (BCV) go the same
     way (evaluate_best_ic(batched=True)) for the criteria of ic.SMALL_BATCH_IC_CRITERIA up to
     ic.SMALL_BATCH_IC_MAX_ELEMENTS elements; a candidate outside the kernel's envelope takes the per-solve path inside it.
+  * ``DEMETHIFY_BATCH_MID=1`` (environment; default ``0``): where the route above was not taken, ``--confidence`` replicates
+    and ``--restart`` restarts go through ``Problem.solve_many_mid`` (several workgroups per solve) when the case is eligible
+    (bootstrap.batched_ineligible(kernel="mid")) and N x S lies within [bootstrap.MID_BATCH_MIN_ELEMENTS,
+    bootstrap.MID_BATCH_MAX_ELEMENTS]; otherwise a one-line note says why and the per-solve path runs.  ``--ic`` sweeps and
+    ``--purity`` runs are not wired to it.
   * ``--ic NAME [n [lo hi]]``: upstream sweeps the hard-coded range 1..25 (ic.py:171); two more values after the
     restart count restrict the sweep to lo..hi unknown types (``--ic BIC 5 2 12``).  Without them: 1..25, as upstream.
 """
@@ -161,6 +166,12 @@ def main(argv=None):
     if batch_env not in ("0", "1"):
         sys.stderr.write(f'Error: DEMETHIFY_BATCH must be "0" or "1", got "{batch_env}".\n')
         sys.exit(1)
+    # DEMETHIFY_BATCH_MID=1: where DEMETHIFY_BATCH's own route is not taken, replicates and restarts of mid-size problems go
+    # through Problem.solve_many_mid (several workgroups per solve), where eligible
+    batch_mid_env = os.environ.get("DEMETHIFY_BATCH_MID", "0")
+    if batch_mid_env not in ("0", "1"):
+        sys.stderr.write(f'Error: DEMETHIFY_BATCH_MID must be "0" or "1", got "{batch_mid_env}".\n')
+        sys.exit(1)
     if args.plot:
         sys.stderr.write("Note: --plot is ignored, plotting (seaborn/colorcet) is outside this build's scope.\n")
 
@@ -213,8 +224,31 @@ def main(argv=None):
             print(f"Note: DEMETHIFY_BATCH=1 is not used for {what}: {reason}; taking the per-solve path.")
         return reason is None
 
+    def batch_mid_route(what, align=False, profile_rows="position"):
+        """DEMETHIFY_BATCH_MID=1, asked after DEMETHIFY_BATCH's own route was not taken: does `what` go through
+        Problem.solve_many_mid?  A one-line note says why not."""
+        if batch_mid_env != "1":
+            return False
+        n_rows, n_samples = meth_f.shape
+        reason = bootstrap_mod.batched_ineligible(
+            n_u, n_rows, n_samples, ref.shape[1] if args.ref else 0, args.init, args.purity,
+            L.DMF_MODE_PARTIAL if args.ref else L.DMF_MODE_UNSUPERVISED, None, align, profile_rows, kernel="mid")
+        lo, hi = bootstrap_mod.MID_BATCH_MIN_ELEMENTS, bootstrap_mod.MID_BATCH_MAX_ELEMENTS
+        if reason is None and not lo <= n_rows * n_samples <= hi:
+            reason = (f"{n_rows} x {n_samples} elements are outside [MID_BATCH_MIN_ELEMENTS, MID_BATCH_MAX_ELEMENTS] = "
+                      f"[{lo}, {hi}]" + (" (the gate is closed)" if lo > hi else ""))
+        if reason is not None and rank == 0:
+            print(f"Note: DEMETHIFY_BATCH_MID=1 is not used for {what}: {reason}; taking the per-solve path.")
+        return reason is None
+
     def bootstrap(anchor=None):
-        batched = batch_route("--confidence", align=not args.ref and n_u >= 2, profile_rows=ci_rows)
+        align = not args.ref and n_u >= 2
+        batched = batch_route("--confidence", align=align, profile_rows=ci_rows)
+        if not batched and batch_mid_route("--confidence", align=align, profile_rows=ci_rows):
+            bt_ci(args.confidence[0], args.confidence[1], n_u, meth_f, counts, ref, args.init, args.iterations[0],
+                  args.iterations[1], args.termination, header if args.ref else [], outdir, args.methfreq, args.purity,
+                  args.seed, materialize=False, anchor=anchor, profile_rows=ci_rows, batched=True, batch_kernel="mid")
+            return
         bt_ci(args.confidence[0], args.confidence[1], n_u, meth_f, counts, ref, args.init, args.iterations[0],
               args.iterations[1], args.termination, header if args.ref else [], outdir, args.methfreq, args.purity,
               args.seed, materialize=False, anchor=anchor, profile_rows=ci_rows, batched=batched,
@@ -258,8 +292,9 @@ def main(argv=None):
         if args.restart > 1 and rank == 0:
             print(f"restart k > 0 uses seed + k (upstream repeats the same seed); {args.restart} restarts")
         batch_restarts = args.restart > 1 and batch_route("--restart")
+        mid_restarts = args.restart > 1 and not batch_restarts and batch_mid_route("--restart")
         with Problem(get_context(), meth_f, counts, None if unsupervised else ref) as problem:
-            if args.restart > 1 and not batch_restarts:
+            if args.restart > 1 and not batch_restarts and not mid_restarts:
                 staging.reserve(((meth_f.shape[0], n_u), (K, meth_f.shape[1])), count=2)
 
             # --init uniform on a large problem: u0 is drawn on the host as init_BSSMF_md / init_BSSMF_md_p draw it (set_seed,
@@ -315,10 +350,14 @@ def main(argv=None):
                     u, alpha, _, _ = s.get()
                 return u, alpha, cost
 
-            def solve_batch(ks):
-                # this rank's restarts, one workgroup each: the initialisers are drawn one after the other, as prepare draws them
+            def solve_batch(ks, mid=False):
+                # this rank's restarts, one workgroup each (mid: several each, Problem.solve_many_mid): the initialisers are
+                # drawn one after the other, as prepare draws them
                 mode = L.DMF_MODE_UNSUPERVISED if unsupervised else L.DMF_MODE_PARTIAL
-                chunk = bootstrap_mod.batch_chunk(meth_f.shape[0], n_u)
+                if mid:
+                    chunk = bootstrap_mod.mid_batch_chunk(meth_f.shape[0], meth_f.shape[1], K - n_u, n_u)
+                else:
+                    chunk = bootstrap_mod.batch_chunk(meth_f.shape[0], n_u)
                 parts = []
                 for c0 in range(0, len(ks), chunk):
                     inits = []
@@ -334,6 +373,10 @@ def main(argv=None):
                             u0, _, a0 = init_BSSMF_md(args.init, meth_f, counts, ref, n_u, rb_alg=wls_intercept, seed=seed_k,
                                                       _stack=False)
                             inits.append((u0, a0))
+                    if mid:
+                        parts.append(problem.solve_many_mid(np.stack([u0 for u0, _ in inits]), np.stack([a0 for _, a0 in inits]),
+                                                            mode, args.iterations[0], args.iterations[1], args.termination)[:3])
+                        continue
                     parts.append(problem.solve_many(np.stack([u0 for u0, _ in inits]), np.stack([a0 for _, a0 in inits]), mode,
                                                     args.iterations[0], args.iterations[1], args.termination,
                                                     purity=None if unsupervised else purity)[:3])
@@ -342,6 +385,9 @@ def main(argv=None):
             shapes = ((meth_f.shape[0], n_u), (K, meth_f.shape[1]))
             if batch_restarts:
                 ref_estimate, proportions, _best, _costs = shard.sharded_restarts_batched(args.restart, solve_batch, shapes)
+            elif mid_restarts:
+                ref_estimate, proportions, _best, _costs = shard.sharded_restarts_batched(
+                    args.restart, lambda ks: solve_batch(ks, mid=True), shapes)
             else:
                 ref_estimate, proportions, _best, _costs = shard.sharded_restarts(
                     args.restart, solve_one, shapes, prepare=prepare, solve_end=solve_end)

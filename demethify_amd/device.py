@@ -245,6 +245,26 @@ def small_solve_supported(N, S, n_c, n_u, mode=L.DMF_MODE_PARTIAL) -> bool:
     return bool(L.load().dmf_solve_small_supported(int(N), int(S), int(n_c), int(n_u), int(mode)))
 
 
+def mid_solve_supported(N, S, n_c, n_u, mode=L.DMF_MODE_PARTIAL) -> bool:
+    """dmf_solve_mid_supported: does ``Problem.solve_many_mid`` take the shape?  Modes partial and unsupervised,
+    1 <= n_u <= 4, n_c + n_u <= 16, S <= 64, N * S <= 2**23.  A pure function of its arguments: no GPU is touched."""
+    return bool(L.load().dmf_solve_mid_supported(int(N), int(S), int(n_c), int(n_u), int(mode)))
+
+
+def mid_solve_plan(N, S, rows_per_workgroup=0):
+    """dmf_solve_mid_plan -> (rows, W, check_every): ``Problem.solve_many_mid`` cuts the N rows of a solve into W slabs of
+    ``rows`` rows (a multiple of 256, W <= 64, the last slab may be ragged), one workgroup each, and the host reads the stop
+    flags every ``check_every`` outer iterations.  ``rows_per_workgroup`` 0: the default, a function of (N, S) alone; any
+    other value must be a positive multiple of 256 that gives W <= 64 (ValueError).  No GPU is touched."""
+    rows, W, every = C.c_int64(), C.c_int64(), C.c_int64()
+    st = L.load().dmf_solve_mid_plan(int(N), int(S), int(rows_per_workgroup), C.byref(rows), C.byref(W), C.byref(every))
+    if st == L.DMF_ERR_BAD_ARG:
+        raise ValueError(f"no plan for {N} x {S} with rows_per_workgroup = {rows_per_workgroup}: N and S are at least 1, "
+                         f"rows_per_workgroup is 0 or a positive multiple of 256 that gives at most {L.MID_MAX_W} workgroups")
+    L.check(st, "dmf_solve_mid_plan")
+    return rows.value, W.value, every.value
+
+
 class Problem:
     """dmf_problem: meth_frequency (N x S), counts (N x S), R_trunc (N x n_c or None)."""
 
@@ -692,6 +712,34 @@ class Problem:
         L.check(self._lib.dmf_solve_small(self.ctx._h, self._h, B, _ptr(idx), _ptr(u0s), _ptr(alpha0s), n_u, int(mode),
                                           int(n_iter1), int(n_iter2), float(tol), int(iters_per_launch), 0, _ptr(u),
                                           _ptr(alpha), _ptr(cost), _ptr(iters)), "dmf_solve_small")
+        return u, alpha, cost, iters
+
+    def solve_many_mid(self, u0s, alpha0s, mode, n_iter1, n_iter2, tol, idx=None, rows_per_workgroup=0, check_every=0):
+        """B independent solves of this problem in one call, several workgroups per solve (dmf_solve_mid; DESIGN.md section
+        6.3) -> (u[B, N, n_u], alpha[B, K, S], cost[B], iters[B]).  Arguments, shapes, errors and results are
+        ``solve_many``'s; the shapes taken are those of ``mid_solve_supported`` (N * S up to 2**23), anything else raises
+        (DMF_ERR_UNSUPPORTED): there is no fall-back.  ``rows_per_workgroup``: rows per slab, 0 = the default of
+        ``mid_solve_plan``; it orders the sums over rows and so may change the last bits.  ``check_every``: outer iterations
+        between two reads of the stop flags, 0 = the default; the results do not depend on it.  No purity, no masks."""
+        u0s = np.ascontiguousarray(u0s, dtype=np.float64)
+        alpha0s = np.ascontiguousarray(alpha0s, dtype=np.float64)
+        if u0s.ndim != 3 or u0s.shape[1] != self.N:
+            raise ValueError(f"u0s is B x {self.N} x n_u, got shape {u0s.shape}")
+        B, _, n_u = u0s.shape
+        K = self.n_c + n_u
+        if alpha0s.shape != (B, K, self.S):
+            raise ValueError(f"alpha0s shape {alpha0s.shape} != {(B, K, self.S)}")
+        if idx is not None:
+            idx = np.ascontiguousarray(idx, dtype=np.int64)
+            if idx.shape != (B, self.N):
+                raise ValueError(f"idx shape {idx.shape} != {(B, self.N)}")
+        u = np.empty((B, self.N, n_u), dtype=np.float64)
+        alpha = np.empty((B, K, self.S), dtype=np.float64)
+        cost = np.empty(B, dtype=np.float64)
+        iters = np.empty(B, dtype=np.int64)
+        L.check(self._lib.dmf_solve_mid(self.ctx._h, self._h, B, _ptr(idx), _ptr(u0s), _ptr(alpha0s), n_u, int(mode),
+                                        int(n_iter1), int(n_iter2), float(tol), int(rows_per_workgroup), int(check_every), 0,
+                                        _ptr(u), _ptr(alpha), _ptr(cost), _ptr(iters)), "dmf_solve_mid")
         return u, alpha, cost, iters
 
     def solve_many_masked(self, u0s, alpha0s, train_masks, mode, n_iter1, n_iter2, tol, iters_per_launch=0):

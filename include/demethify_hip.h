@@ -522,6 +522,41 @@ int dmf_solve_small_masked(dmf_context* ctx, const dmf_problem* p, int64_t B, co
                            int64_t iters_per_launch, int flags, double* out_u, double* out_alpha, double* out_cost,
                            int64_t* out_iters, double* out_holdout_sum_sq, int64_t* out_n_test);
 
+/* ---- mid-size problems: B independent solves of one resident problem, W >= 1 workgroups per solve, three launches per
+ * outer iteration for all B solves.  The arithmetic is dmf_solve_small's and therefore the reference's: mdwbssmf_deconv
+ * (demethify/deconvolution.py:190-223, DMF_MODE_PARTIAL) or unsupervised_deconv (:107-184, DMF_MODE_UNSUPERVISED) -- set-up as
+ * :192-204, the row-local u phase (:81-90; the gradient at u_temp in partial mode, at the previous iterate in unsupervised
+ * mode, :163), l_h (:212), the alpha phase with the sort-based projection (:93-102, :21-37), l_w (:216), the streaming cost
+ * (:15-17) and the stop test fabs(cf - cf_0) < tol on it (:218-220); no Gram-form cost, no confirmation of stops.  Only the
+ * orders of the sums over rows differ: a solve's rows are cut into W slabs of `rows` rows (a multiple of 256, the last slab
+ * may be ragged, W <= 64), one workgroup per slab, and a sum over rows is a sum per slab followed by the sum of the slab
+ * partials in rising slab order.  Workgroups meet at launch boundaries only; there are no atomics; every order depends on
+ * (N, S, n_c, n_u, rows) alone.
+ * dmf_solve_mid_supported: 1 where the kernels take the shape, else 0 -- the two modes, 1 <= n_u <= 4, n_c + n_u <= 16,
+ * S <= 64, N S <= 2^23 (that bounds the workspace; it is not a measured cross-over).  Pure: no context, no GPU.
+ * dmf_solve_mid_plan: the plan of an N x S solve -- *out_rows rows per workgroup, *out_W workgroups per solve with
+ * (W - 1) rows < N <= W rows, *out_check_every outer iterations between two reads of the stop flags.  rows_per_workgroup 0:
+ * the default, the smallest multiple of 256 with W <= 64; the default check_every is 2^22 / (N S) within [4, 16].  Both are
+ * functions of (N, S) alone.  DMF_ERR_BAD_ARG: N or S below 1, a rows_per_workgroup that is not a positive multiple of 256 or
+ * that gives W > 64, a null pointer.  Pure: no context, no GPU.
+ * dmf_solve_mid: dmf_solve_small's contract -- B, idx (B x N int64 or NULL; a bootstrap replicate, demethify/bootstrap.py:28,
+ * d being the maximum over the drawn rows), u0, alpha0, DMF_PTR_DEVICE in flags, out_u / out_alpha / out_cost / out_iters,
+ * out_cost[b] = cost_f_w of the final iterate (demethify/demethify.py:199), out_iters[b] its outer iterations, inputs never
+ * written -- with rows_per_workgroup (0: the default) and check_every (0: the default) in the place of iters_per_launch.
+ * The host enqueues check_every outer iterations, reads the B stop flags and ends when every solve has stopped or n_iter1
+ * is reached; the launches of a stopped solve return at once and its iterate is never touched again.  A solve's results do
+ * not depend on B, on its slot, on the other solves or on check_every, bit for bit; rows_per_workgroup changes the order of
+ * the sums over rows and with it the last bits.  DMF_ERR_UNSUPPORTED outside the envelope, before the context is touched.
+ * DMF_ERR_BAD_ARG: B < 1, a null array, a negative count, a bad rows_per_workgroup (as above), a masked problem, an index
+ * outside [0, N) -- every index is checked on the device before any solve starts.  No purity and no hold-out masks here. */
+int dmf_solve_mid_supported(int64_t N, int64_t S, int64_t n_c, int64_t n_u, int mode);
+int dmf_solve_mid_plan(int64_t N, int64_t S, int64_t rows_per_workgroup, int64_t* out_rows, int64_t* out_W,
+                       int64_t* out_check_every);
+int dmf_solve_mid(dmf_context* ctx, const dmf_problem* p, int64_t B, const int64_t* idx, const double* u0,
+                  const double* alpha0, int64_t n_u, int mode, int64_t n_iter1, int64_t n_iter2, double tol,
+                  int64_t rows_per_workgroup, int64_t check_every, int flags, double* out_u, double* out_alpha,
+                  double* out_cost, int64_t* out_iters);
+
 /* ---- input tables (host side) ---------------------------------------------------------------
  * demethify/demethify.py:103-143 reads each sample file with pandas.read_csv and stacks its `percent_modified` and
  * `valid_coverage` columns.  dmf_table_scan finds the two columns by header name and counts the data rows;

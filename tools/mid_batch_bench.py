@@ -1,0 +1,167 @@
+#!/usr/bin/env python3
+"""Mid-size problems: many solves per call with several workgroups per solve (Problem.solve_many_mid) against one solve at a
+time and against the one-launch batch (Problem.solve_many, one workgroup per solve).
+
+   python tools/mid_batch_bench.py per-solve|small|mid [repetition [case]]   one timing of every case on one leg
+   python tools/mid_batch_bench.py summary FILE                              medians and validity of a file of such output
+
+Cases (tol 1e-2, 20 inner steps, initialiser uniform_; restarts run at most 200 outer iterations):
+  1000x16 restart 64     synthetic_problem(1000, 16, 6, 2), 64 restarts
+  4000x16 restart 64     synthetic_problem(4000, 16, 6, 2), 64 restarts
+  10000x64 restart 64    synthetic_problem(10000, 64, 12, 4), 64 restarts
+  32768x64 restart 64    synthetic_problem(32768, 64, 12, 4), 64 restarts
+  131072x64 restart 64   synthetic_problem(131072, 64, 12, 4), 64 restarts
+  10000x64 bt_ci 500     bt_ci(95, 500) on synthetic_problem(10000, 64, 6, 2)
+Legs: `per-solve` is the command line's own restart loop (initialisers drawn and uploaded one restart ahead by a worker
+thread, the streaming cost taken while the next restart is set up) and plain bt_ci; it uses nothing the mid-size batch
+added, so the same file runs on a checkout of the commit before it -- which is where it is meant to run.  `small` draws the
+same initialisers and goes through solve_many / bt_ci(batched=True); a case outside that kernel's envelope is skipped.  `mid`
+goes through solve_many_mid / bt_ci(batched=True, batch_kernel="mid").
+
+Method: run the legs in turn, one process each, five times, append the output to one file, then `summary`.  A timing is a
+host clock around work that ends in a device synchronise (every call returns host arrays), after a warm-up of the same
+code on two restarts (eight replicates).  Every timing is a line "launch <repetition>: <ms> ms   (check <value>)" under its
+"== <case> | <leg>" heading; the check is the winning cost of the restarts (for bt_ci: the sum of the lower profile
+bounds).  `summary` prints per case the median of each leg and marks the case INVALID unless every timing of every leg
+shows the same check to ten digits."""
+import sys
+import tempfile
+import time
+from pathlib import Path
+
+ROOT = Path(__file__).resolve().parent.parent
+sys.path.insert(0, str(ROOT))
+sys.path.insert(0, str(ROOT / "tests"))
+
+TOL, T2, MAX_OUTER = 1e-2, 20, 200
+RESTART_SHAPES = ((1000, 16, 6, 2), (4000, 16, 6, 2), (10000, 64, 12, 4), (32768, 64, 12, 4), (131072, 64, 12, 4))
+LEGS = ("per-solve", "small", "mid")
+
+
+def run_legs(leg, repetition, only=""):
+    import numpy as np
+
+    from demethify_amd import _lib as L
+    from demethify_amd import bootstrap, shard, staging
+    from demethify_amd.bootstrap import bt_ci
+    from demethify_amd.deconvolution import init_BSSMF_md
+    from demethify_amd.device import Problem, Solver, get_context, small_solve_supported
+    from oracle.solver import synthetic_problem
+
+    ctx = get_context()
+
+    def restarts_per_solve(problem, V, D, Rt, n_u, n_restarts, n_iter1):
+        """demethify.main's restart loop (prepare / solve_one / solve_end through shard.sharded_restarts)."""
+        shapes = ((V.shape[0], n_u), (Rt.shape[1] + n_u, V.shape[1]))
+
+        def prepare(k):
+            u0, _, a0 = init_BSSMF_md("uniform_", V, D, Rt, n_u, seed=shard.restart_seed(1, k), _stack=False)
+            return staging.to_device((u0, a0), problem.ctx)
+
+        def solve_one(k, best_cost, prepared):
+            s = Solver(problem, prepared[0], prepared[1], L.DMF_MODE_PARTIAL)
+            try:
+                s.step(n_iter1, T2, TOL)
+                s.cost_begin()
+            except BaseException:
+                s.close()
+                raise
+            return s
+
+        def solve_end(s, best_cost):
+            with s:
+                cost = s.cost_end()
+                if not cost < best_cost:
+                    return None, None, cost
+                u, alpha, _, _ = s.get()
+            return u, alpha, cost
+
+        staging.reserve(shapes, count=2)
+        return shard.sharded_restarts(n_restarts, solve_one, shapes, prepare=prepare, solve_end=solve_end)
+
+    def restarts_batched(problem, V, D, Rt, n_u, n_restarts, n_iter1):
+        mid = leg == "mid"
+        if mid:
+            chunk = bootstrap.mid_batch_chunk(V.shape[0], V.shape[1], Rt.shape[1], n_u)
+        else:
+            chunk = bootstrap.batch_chunk(V.shape[0], n_u)
+        solve = problem.solve_many_mid if mid else problem.solve_many
+
+        def solve_batch(ks):
+            parts = []
+            for c0 in range(0, len(ks), chunk):
+                inits = [init_BSSMF_md("uniform_", V, D, Rt, n_u, seed=shard.restart_seed(1, k), _stack=False)
+                         for k in ks[c0:c0 + chunk]]
+                parts.append(solve(np.stack([i[0] for i in inits]), np.stack([i[2] for i in inits]), L.DMF_MODE_PARTIAL,
+                                   n_iter1, T2, TOL)[:3])
+            return tuple(np.concatenate([part[j] for part in parts]) for j in range(3))
+
+        return shard.sharded_restarts_batched(n_restarts, solve_batch, ((V.shape[0], n_u), (Rt.shape[1] + n_u, V.shape[1])))
+
+    def restart_case(V, D, Rt, n_u, n_restarts, n_iter1):
+        with Problem(ctx, V, D, Rt) as p:
+            fn = restarts_per_solve if leg == "per-solve" else restarts_batched
+            _, _, best, costs = fn(p, V, D, Rt, n_u, n_restarts, n_iter1)
+        return float(costs[best])
+
+    def bt_ci_case(V, D, Rt, n_u, n):
+        kw = {"per-solve": {}, "small": {"batched": True}, "mid": {"batched": True, "batch_kernel": "mid"}}[leg]
+        with tempfile.TemporaryDirectory() as d:
+            out = bt_ci(95, n, n_u, V, D, Rt, "uniform_", 10000, T2, TOL, [f"c{k}" for k in range(Rt.shape[1])], d,
+                        [f"s{i}" for i in range(V.shape[1])], None, 1, materialize=False, **kw)
+        return float(np.sum(out[1][0]))
+
+    cases = []
+    for N, S, n_c, n_u in RESTART_SHAPES:
+        name = f"{N}x{S} restart 64"
+        if only not in name or (leg == "small" and not small_solve_supported(N, S, n_c, n_u, L.DMF_MODE_PARTIAL)):
+            continue
+        a = synthetic_problem(N, S, n_c, n_u, seed=5, depth=30) + (n_u,)
+        cases.append((name, lambda a=a: restart_case(*a, 64, MAX_OUTER), lambda a=a: restart_case(*a, 2, 3)))
+    if only in "10000x64 bt_ci 500":
+        b = synthetic_problem(10000, 64, 6, 2, seed=5, depth=30) + (2,)
+        cases.append(("10000x64 bt_ci 500", lambda: bt_ci_case(*b, 500), lambda: bt_ci_case(*b, 8)))
+    for name, timed, warm in cases:
+        warm()  # code objects, pools, pinned buffers
+        ctx.synchronize()
+        t0 = time.perf_counter()
+        check = timed()
+        ms = (time.perf_counter() - t0) * 1e3
+        print(f"== {name} | {leg}")
+        print(f"launch {repetition}: {ms:.3f} ms   (check {check:.9e})", flush=True)
+
+
+def summary(path):
+    import re
+    import statistics
+
+    times, checks, order = {}, {}, []
+    head = None
+    for line in Path(path).read_text().splitlines():
+        m = re.match(r"== (.+) \| (.+)$", line)
+        if m:
+            head = (m.group(1), m.group(2))
+            if head[0] not in order:
+                order.append(head[0])
+            continue
+        m = re.match(r"launch \d+: ([0-9.]+) ms\s+\(check (\S+)\)", line)
+        if m and head is not None:
+            times.setdefault(head, []).append(float(m.group(1)))
+            checks.setdefault(head[0], set()).add(m.group(2))
+    for case in order:
+        med = {leg: statistics.median(times[(case, leg)]) for leg in LEGS if (case, leg) in times}
+        n = {leg: len(times[(case, leg)]) for leg in med}
+        text = "   ".join(f"{leg} {med[leg]:.1f} ms (n = {n[leg]})" for leg in med)
+        valid = len(checks[case]) == 1
+        wins = valid and "mid" in med and all(med["mid"] < v for leg, v in med.items() if leg != "mid")
+        print(f"{case}: {text}   {'valid, check ' + next(iter(checks[case])) if valid else 'INVALID: checks ' + ', '.join(sorted(checks[case]))}"
+              f"   {'mid wins' if wins else 'mid does not win'}")
+
+
+if __name__ == "__main__":
+    if len(sys.argv) >= 3 and sys.argv[1] == "summary":
+        summary(sys.argv[2])
+    elif len(sys.argv) >= 2 and sys.argv[1] in LEGS:
+        run_legs(sys.argv[1], int(sys.argv[2]) if len(sys.argv) > 2 else 0, sys.argv[3] if len(sys.argv) > 3 else "")
+    else:
+        sys.exit(__doc__)
