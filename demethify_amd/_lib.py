@@ -145,6 +145,8 @@ SIGNATURES = {
     "dmf_solve_mid_plan": (C.c_int, [_i64, _i64, _i64, C.POINTER(_i64), C.POINTER(_i64), C.POINTER(_i64)]),
     "dmf_solve_mid": (C.c_int, [_p, _p, _i64, _p, _p, _p, _i64, C.c_int, _i64, _i64, C.c_double, _i64, _i64, C.c_int, _p, _p, _p,
                                 _p]),
+    "dmf_solve_mid_purity": (C.c_int, [_p, _p, _i64, _p, _p, _p, _p, _i64, C.c_int, _i64, _i64, C.c_double, _i64, _i64, C.c_int, _p,
+                                       _p, _p, _p]),
 }
 
 _lib = None

@@ -92,18 +92,28 @@ SMALL_BATCH_PURITY_MAX_ELEMENTS = 16000
 # 131 072 x 64 1 048 / - / 9 124 ms; bt_ci with 500 replicates at 10 000 x 64 (6 + 2) 4 556 / 4 064 / 2 306 ms.  The mid-size
 # leg wins at 16 000 and 64 000 elements; at 640 000 it wins the bootstrap and loses the restarts, so that size stays out.
 MID_BATCH_MIN_ELEMENTS, MID_BATCH_MAX_ELEMENTS = 16000, 64000
+# The same range for purity-constrained runs (--purity with DEMETHIFY_BATCH_MID_PURITY=1; Problem.solve_many_mid(purity=...),
+# dmf_solve_mid_purity), by the same rule, from tools/mid_batch_purity_bench.py (profiles/mid_batch_purity_bench.txt).
+# Measured (medians of five, 100 x 500 iterations; per-solve on the commit before / solve_many(purity) /
+# solve_many_mid(purity)), 64 restarts: 1 000 x 16 (6 + 2) 1 631 / 67 / 42 ms, 4 000 x 16 (6 + 2) 1 431 / 227 / 67 ms,
+# 10 000 x 64 (12 + 4) 3 154 / 2 595 / 414 ms, 32 768 x 64 (12 + 4) 3 419 / - / 1 185 ms; bt_ci with 500 replicates at
+# 10 000 x 64 (6 + 2) 19 136 / 1 944 / 1 366 ms.  The mid-size leg wins every case at every measured size, 16 000, 64 000,
+# 640 000 and 2 097 152 elements, so the gate is that whole range; nothing larger and nothing smaller was measured.
+MID_BATCH_PURITY_MIN_ELEMENTS, MID_BATCH_PURITY_MAX_ELEMENTS = 16000, 2097152
 
 
 def batched_ineligible(n_u, n_rows, n_samples, n_ct, init_option, purity, mode, observe=None, align=False,
-                       profile_rows="position", purity_batched=False, kernel="small"):
+                       profile_rows="position", purity_batched=False, kernel="small", mid_purity=False):
     """Why a loop of solves cannot go through ``Problem.solve_many`` (one launch for many solves), as a sentence, or None
     when it can: at least one unknown type, no purity constraint, nobody watching single replicates, no component
     alignment, profile rows by position, an initialiser that does not read the data (``uniform_``, ``beta``, or the silent
     replacement by ``uniform_`` when there are more unknown types than samples) and a shape the kernel takes.
     ``purity_batched``: the caller has asked for the purity variant of the kernel (``solve_many(purity=...)``), so a purity
     vector passes where there is a reference to hold at that mass.  ``kernel``: "small" (``Problem.solve_many``, the default)
-    or "mid" (``Problem.solve_many_mid``, several workgroups per solve): the mid-size batch has an envelope of its own and no
-    purity variant, whatever ``purity_batched`` says.  Touches no device."""
+    or "mid" (``Problem.solve_many_mid``, several workgroups per solve): the mid-size batch has an envelope of its own, and
+    it refuses a purity vector whatever ``purity_batched`` says unless ``mid_purity`` is set (a switch of its own, because
+    the refusal without it is pinned): then ``solve_many_mid(purity=...)`` takes the vector where there is a reference to
+    hold at that mass.  Touches no device."""
     from .device import mid_solve_supported, small_solve_supported
 
     if kernel not in ("small", "mid"):
@@ -111,9 +121,9 @@ def batched_ineligible(n_u, n_rows, n_samples, n_ct, init_option, purity, mode, 
     if n_u < 1:
         return "there is no unknown cell type to solve for"
     if purity is not None and np.size(purity) > 0:
-        if kernel == "mid":
+        if kernel == "mid" and not mid_purity:
             return "the purity-constrained alpha phase is not part of the mid-size batch"
-        if not purity_batched:
+        if kernel == "small" and not purity_batched:
             return ("the purity-constrained alpha phase is not part of the batched kernel unless it is asked for "
                     "(bt_ci(..., batched_purity=True), batched_ineligible(..., purity_batched=True))")
         if mode != L.DMF_MODE_PARTIAL or n_ct < 1:
@@ -147,7 +157,8 @@ def batch_chunk(n_rows, n_u):
 def mid_batch_chunk(n_rows, n_samples, n_ct, n_u):
     """How many solves one ``solve_many_mid`` call of the drivers takes: as many as keep the slab workspace (W workgroups per
     solve, each with the larger of the known and the u-dependent Gram jobs times S doubles) and the stack of profiles
-    together within 256 MB, at least 1 and at most 1024."""
+    together within 256 MB, at least 1 and at most 1024.  The purity variant (``solve_many_mid(purity=...)``) has the same
+    workspace -- it adds nothing per slab or per solve, only the S purities per call -- so the bound holds for it as it is."""
     from .device import mid_solve_plan
 
     _, n_slabs, _ = mid_solve_plan(n_rows, n_samples)
@@ -160,7 +171,7 @@ def mid_batch_chunk(n_rows, n_samples, n_ct, n_u):
 
 def bt_ci(confidence_level, n_bootstrap, n_u, meth_f, counts, ref, init_option, n_iter1, n_iter2, tol, header,
           outdir, samples, purity, seed, materialize=True, _observe=None, anchor=None, align_unknown=None,
-          profile_rows="position", batched=False, batched_purity=False, batch_kernel="small"):
+          profile_rows="position", batched=False, batched_purity=False, batch_kernel="small", batched_mid_purity=False):
     """bootstrap.py:10-93 -> [proportions CI DataFrame, (profile CI DataFrame)]; writes the two CSVs.
     materialize=False (the CLI, which ignores the return value) skips building the N-row DataFrame of tuples for the
     profile intervals: the CSV is written by the library and the second result is the (lower, upper) array pair.
@@ -193,8 +204,9 @@ def bt_ci(confidence_level, n_bootstrap, n_u, meth_f, counts, ref, init_option, 
 
     ``batch_kernel``: which batch ``batched=True`` means.  "small" (the default): ``Problem.solve_many``, as above.  "mid":
     ``Problem.solve_many_mid``, several workgroups per replicate (DESIGN.md section 6.3), in chunks of ``mid_batch_chunk``;
-    eligibility is ``batched_ineligible(..., kernel="mid")``, which has no purity variant.  Any other value raises
-    ValueError."""
+    eligibility is ``batched_ineligible(..., kernel="mid")``, which refuses a purity vector whatever ``batched_purity`` says.
+    ``batched_mid_purity`` (looked at only with ``batched=True, batch_kernel="mid"``) opens it: the purity replicates then go
+    through ``solve_many_mid(purity=p / 100)`` in the same chunks.  Any other ``batch_kernel`` raises ValueError."""
     if profile_rows not in ("position", "cpg"):
         raise ValueError(f'profile_rows must be "position" or "cpg", got {profile_rows!r}')
     if batch_kernel not in ("small", "mid"):
@@ -203,7 +215,7 @@ def bt_ci(confidence_level, n_bootstrap, n_u, meth_f, counts, ref, init_option, 
         will_align = bool(ref is None if align_unknown is None else align_unknown) and n_u >= 2
         reason = batched_ineligible(n_u, meth_f.shape[0], meth_f.shape[1], 0 if ref is None else ref.shape[1], init_option,
                                     purity, L.DMF_MODE_UNSUPERVISED if ref is None else L.DMF_MODE_PARTIAL, _observe,
-                                    will_align, profile_rows, kernel="mid")
+                                    will_align, profile_rows, kernel="mid", mid_purity=bool(batched_mid_purity))
         if reason is not None:
             raise ValueError(f'bt_ci(batched=True, batch_kernel="mid"): {reason}')
     elif batched:
@@ -291,7 +303,7 @@ def bt_ci(confidence_level, n_bootstrap, n_u, meth_f, counts, ref, init_option, 
                         inits.append((u0, a0))
                 if mid:
                     us, alphas, _, _ = full.solve_many_mid(np.stack([u0 for u0, _ in inits]), np.stack([a0 for _, a0 in inits]),
-                                                           mode, n_iter1, n_iter2, tol, idx=idx)
+                                                           mode, n_iter1, n_iter2, tol, idx=idx, purity=purity_frac)
                 else:
                     us, alphas, _, _ = full.solve_many(np.stack([u0 for u0, _ in inits]), np.stack([a0 for _, a0 in inits]),
                                                        mode, n_iter1, n_iter2, tol, idx=idx, purity=purity_frac)

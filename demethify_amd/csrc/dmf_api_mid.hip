@@ -1,5 +1,6 @@
 // C-ABI of libdemethify_hip.so, part 8: many independent mid-size solves of one resident problem, several workgroups per
-// solve (dmf_solve_mid, dmf_solve_mid_plan, dmf_solve_mid_supported; the kernels are in dmf_kernels_mid.hip).
+// solve (dmf_solve_mid, dmf_solve_mid_purity, dmf_solve_mid_plan, dmf_solve_mid_supported; the kernels are in
+// dmf_kernels_mid.hip).
 #include <algorithm>
 
 #include "dmf_api.h"
@@ -7,30 +8,18 @@
 
 using namespace dmf_api;
 
-extern "C" {
-
-int dmf_solve_mid_supported(int64_t N, int64_t S, int64_t n_c, int64_t n_u, int mode) {
-    return dmf::mid_supported(N, S, n_c, n_u, mode) ? 1 : 0;
-}
-
-int dmf_solve_mid_plan(int64_t N, int64_t S, int64_t rows_per_workgroup, int64_t* out_rows, int64_t* out_W,
-                       int64_t* out_check_every) {
-    dmf::MidPlan plan;
-    if (out_rows == nullptr || out_W == nullptr || out_check_every == nullptr || N > ((int64_t)1 << 40) ||
-        !dmf::mid_plan(N, S, rows_per_workgroup, &plan))
-        return DMF_ERR_BAD_ARG;
-    *out_rows = plan.rows, *out_W = plan.W, *out_check_every = plan.check_every;
-    return DMF_OK;
-}
-
-int dmf_solve_mid(dmf_context* ctx, const dmf_problem* p, int64_t B, const int64_t* idx, const double* u0, const double* alpha0,
-                  int64_t n_u, int mode, int64_t n_iter1, int64_t n_iter2, double tol, int64_t rows_per_workgroup,
-                  int64_t check_every, int flags, double* out_u, double* out_alpha, double* out_cost, int64_t* out_iters) {
+// The body of the two solve entries.  with_purity: `purity` (S doubles) selects the Frank-Wolfe alpha launch.
+static int solve_mid(dmf_context* ctx, const dmf_problem* p, int64_t B, const int64_t* idx, const double* u0, const double* alpha0,
+                     int64_t n_u, int mode, int64_t n_iter1, int64_t n_iter2, double tol, int64_t rows_per_workgroup,
+                     int64_t check_every, int flags, bool with_purity, const double* purity, double* out_u, double* out_alpha,
+                     double* out_cost, int64_t* out_iters) {
     if (ctx == nullptr || p == nullptr || B < 1 || B > 0x7fffffff || u0 == nullptr || alpha0 == nullptr || out_u == nullptr ||
         out_alpha == nullptr || out_cost == nullptr || out_iters == nullptr || n_iter1 < 0 || n_iter2 < 0 ||
         rows_per_workgroup < 0 || check_every < 0)
         return DMF_ERR_BAD_ARG;
     if (p->ctx != ctx || p->mask_bits != nullptr) return DMF_ERR_BAD_ARG;  // (a masked problem's held-out zeros are not data)
+    if (with_purity && (purity == nullptr || p->n_c < 1)) return DMF_ERR_BAD_ARG;  // (no known block to hold at that mass)
+    if (with_purity && mode != DMF_MODE_PARTIAL) return DMF_ERR_UNSUPPORTED;
     if (!dmf::mid_supported(p->N, p->S, p->n_c, n_u, mode)) return DMF_ERR_UNSUPPORTED;
     dmf::MidPlan plan;
     if (!dmf::mid_plan(p->N, p->S, rows_per_workgroup, &plan) || B > 0x7fffffff / plan.W) return DMF_ERR_BAD_ARG;
@@ -53,8 +42,11 @@ int dmf_solve_mid(dmf_context* ctx, const dmf_problem* p, int64_t B, const int64
     }
     DMF_TRY(import_array(ctx, u0, un, flags, d_u0));
     DMF_TRY(import_array(ctx, alpha0, an, flags, d_a0));
+    DevBuf<double> d_purity;
+    if (with_purity) DMF_TRY(import_array(ctx, purity, (size_t)S, flags, d_purity));
+    const double* fw_purity = with_purity ? (const double*)d_purity : nullptr;
 
-    // the workspace: all per-solve state and the slab partials
+    // the workspace: all per-solve state and the slab partials (the purity variant uses the same, less alpha_, a2 and l_h)
     const int n_pj = dmf::mid_slab_jobs((int)p->n_c, (int)n_u);
     DevBuf<double> w_u, w_up, w_a, w_ap, w_gk, w_ratio, w_scal, w_pg, w_ps, w_pc, w_cost;
     DevBuf<long long> w_iters;
@@ -88,7 +80,7 @@ int dmf_solve_mid(dmf_context* ctx, const dmf_problem* p, int64_t B, const int64
     std::vector<int> h_done((size_t)B);
     for (int64_t ran = 0; ran < n_iter1;) {
         const int64_t n_run = std::min<int64_t>(every, n_iter1 - ran);
-        for (int64_t it = 0; it < n_run; ++it) HIP_TRY(dmf::launch_mid_iteration(a, B, ctx->stream));
+        for (int64_t it = 0; it < n_run; ++it) HIP_TRY(dmf::launch_mid_iteration(a, B, ctx->stream, fw_purity));
         ran += n_run;
         if (ran >= n_iter1) break;
         HIP_TRY(dmf::launch_mid_finish(a, B, ctx->stream));
@@ -108,6 +100,37 @@ int dmf_solve_mid(dmf_context* ctx, const dmf_problem* p, int64_t B, const int64
     if (!(flags & DMF_PTR_DEVICE)) HIP_TRY(hipMemcpyAsync(out_u, w_u, un * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(hipStreamSynchronize(ctx->stream));
     return DMF_OK;
+}
+
+extern "C" {
+
+int dmf_solve_mid_supported(int64_t N, int64_t S, int64_t n_c, int64_t n_u, int mode) {
+    return dmf::mid_supported(N, S, n_c, n_u, mode) ? 1 : 0;
+}
+
+int dmf_solve_mid_plan(int64_t N, int64_t S, int64_t rows_per_workgroup, int64_t* out_rows, int64_t* out_W,
+                       int64_t* out_check_every) {
+    dmf::MidPlan plan;
+    if (out_rows == nullptr || out_W == nullptr || out_check_every == nullptr || N > ((int64_t)1 << 40) ||
+        !dmf::mid_plan(N, S, rows_per_workgroup, &plan))
+        return DMF_ERR_BAD_ARG;
+    *out_rows = plan.rows, *out_W = plan.W, *out_check_every = plan.check_every;
+    return DMF_OK;
+}
+
+int dmf_solve_mid(dmf_context* ctx, const dmf_problem* p, int64_t B, const int64_t* idx, const double* u0, const double* alpha0,
+                  int64_t n_u, int mode, int64_t n_iter1, int64_t n_iter2, double tol, int64_t rows_per_workgroup,
+                  int64_t check_every, int flags, double* out_u, double* out_alpha, double* out_cost, int64_t* out_iters) {
+    return solve_mid(ctx, p, B, idx, u0, alpha0, n_u, mode, n_iter1, n_iter2, tol, rows_per_workgroup, check_every, flags, false,
+                     nullptr, out_u, out_alpha, out_cost, out_iters);
+}
+
+int dmf_solve_mid_purity(dmf_context* ctx, const dmf_problem* p, int64_t B, const int64_t* idx, const double* u0,
+                         const double* alpha0, const double* purity, int64_t n_u, int mode, int64_t n_iter1, int64_t n_iter2,
+                         double tol, int64_t rows_per_workgroup, int64_t check_every, int flags, double* out_u, double* out_alpha,
+                         double* out_cost, int64_t* out_iters) {
+    return solve_mid(ctx, p, B, idx, u0, alpha0, n_u, mode, n_iter1, n_iter2, tol, rows_per_workgroup, check_every, flags, true,
+                     purity, out_u, out_alpha, out_cost, out_iters);
 }
 
 }  // extern "C"

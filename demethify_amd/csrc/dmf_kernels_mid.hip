@@ -27,7 +27,14 @@
 // state), so a solve's result is a function of its own inputs and of (N, S, n_c, n_u, rows) alone -- not of B, its slot,
 // what else is resident, or how often the host looks.  A solve that has stopped leaves every later launch at the prologue:
 // its partials and scal[kMdCf] no longer change, so the decision is the same each time.
+//
+// The purity-constrained solve (dmf_solve_mid_purity; mdwbssmf_deconv_p, :306-337) runs the same launches with
+// k_mid_alpha_fw in k_mid_alpha's place: the same G_s, b_s from the same slab partials, then n_iter2 Frank-Wolfe steps per
+// sample (frank_wolfe_nmf, :280-302) with every sample on a 16-lane row of its own, all samples stepping at once in one
+// workgroup of 64 ceil(S / 4) threads.  There is no a2, no l_h and no alpha_; the purity vector is an input shared by the B
+// solves.  Every other kernel is launched as it is.
 #include "dmf_mid.h"
+#include "dmf_rowlanes.h"
 
 #include "../../include/demethify_hip.h"
 
@@ -254,6 +261,24 @@ __device__ __forceinline__ void load_alpha(const double* ws_alpha, double* al, i
         const int k = e / S, s = e - k * S;
         al[k * SP + s] = ws_alpha[e];
     }
+}
+
+// ---- the Frank-Wolfe device helpers of k_solve_small's purity variant (dmf_kernels_small.hip), copied like the row helpers
+// above; the lane moves and the argmin butterfly are dmf_rowlanes.h's
+// g4[l % 4] += G[l] a[lane l of the row] for l = L .. 15, in this order (row_newbcast:l; four chains)
+template <int L = 0>
+__device__ __forceinline__ void gram_row_times_a(double (&g4)[4], double a, const double (&G)[16]) {
+    if constexpr (L < 16) {
+        g4[L & 3] = fma(G[L], row_mov<0x150 + L>(a), g4[L & 3]);
+        gram_row_times_a<L + 1>(g4, a, G);
+    }
+}
+
+// a = (1 - gamma) a + gamma vertex as numpy evaluates it: two products and a sum, each rounded (:299-300)
+__device__ __forceinline__ double frank_wolfe_update(double a, double gamma, double vertex) {
+#pragma clang fp contract(off)
+    const double keep = (1.0 - gamma) * a, move = gamma * vertex;
+    return keep + move;
 }
 
 }  // namespace
@@ -535,6 +560,117 @@ __global__ __launch_bounds__(kMidThreads) void k_mid_alpha(MidArgs a) {
     if (t == 64) scal[kMdA2] = fill_ratios(a2, ratio_h, T2);  // (after the barriers behind the alpha phase, which read it)
 }
 
+// ---- the alpha launch of a purity-constrained outer iteration (grid B, 64 ceil(S / 4) threads): k_mid_alpha's Grams, then
+// the Frank-Wolfe steps of deconvolution.py:280-302 as k_solve_small's purity variant takes them -- sample s on the 16-lane
+// row s of the workgroup, lane k holding row k of G_s in registers, grad = G a - b, the argmin of each block with the lowest
+// index first among equal minima (np.argmin), step 2 / (k + 2), vertex mass purity[s] on the known block and 1 - purity[s]
+// on the unknown one.  All samples step at once; n_iter2 is the only bound of the loop the DPP moves sit in, so every wave
+// finds its four rows complete (rows past S run on sample S - 1's numbers and write nothing).
+__global__ __launch_bounds__(kMidFwMaxThreads) void k_mid_alpha_fw(MidArgs a, const double* __restrict__ purity) {
+    const int64_t b = blockIdx.x;
+    if (a.done[b]) return;  // (recorded by slab 0 of this iteration's row launch, or by k_mid_finish)
+    extern __shared__ double mid_lds[];
+    const int t = threadIdx.x, nt = blockDim.x;
+    const int S = a.S, n_c = a.n_c, n_u = a.n_u, K = n_c + n_u, SP = pow2_at_least(S), W = a.W;
+    const int n_pairs = K * (K + 1) / 2;
+    double* gb = mid_lds;                  // [K (K + 1) / 2 + K][SP]: packed G, then b
+    double* al = gb + (n_pairs + K) * SP;  // [K][SP] alpha
+    double* red = al + K * SP;             // [kMidThreads]: the squares of the unknown block, then their tree
+    short* jk = reinterpret_cast<short*>(red + kMidThreads);
+    short* jl = jk + kMaxJobs;
+    short* jdk = jl + kMaxJobs;   // rows of gb of the known jobs
+    short* jdu = jdk + kMaxJobs;  // ... and of the u jobs
+    double* ws_alpha = a.alpha + b * K * S;
+    double* scal = a.scal + b * kMidScalars;
+    const int n_known = mid_known_jobs(n_c), n_uj = mid_u_jobs(n_c, n_u);
+    if (t == 0) {
+        fill_jobs(jk, jl, jdk, n_c, K, true);
+        fill_jobs(jk, jl, jdu, n_c, K, false);
+    }
+    for (int e = t; e < K * S; e += nt) {
+        const int k = e / S, s = e - k * S;
+        al[k * SP + s] = ws_alpha[e];
+    }
+    const double cf = cost_of_partials(a, b);  // the cost of the iterate this iteration started from
+    const double l_w_old = scal[kMdLw], dsq = scal[kMdDsq], a1 = scal[kMdA1];
+    const int64_t T2 = a.n_iter2;
+    __syncthreads();
+    const double* gk = a.gk + b * (int64_t)n_known * S;
+    for (int e = t; e < n_known * S; e += nt) {
+        const int j = e / S, s = e - j * S;
+        gb[(int)jdk[j] * SP + s] = gk[e];
+    }
+    const double* pg = a.part_g + b * W * (int64_t)a.n_pj * S;
+    for (int e = t; e < n_uj * S; e += nt) {
+        const int j = e / S, s = e - j * S;
+        double sum = 0.0;
+        for (int w = 0; w < W; ++w) sum += pg[(int64_t)w * a.n_pj * S + e];
+        gb[(int)jdu[j] * SP + s] = sum;
+    }
+    __syncthreads();
+
+    // ---- Frank-Wolfe: lane k of row s
+    {
+        const int k = t & 15, s = t >> 4;
+        const bool row_ok = k < K, known = k < n_c, unknown = row_ok && !known;
+        const bool col_ok = s < S;
+        const int kc = row_ok ? k : K - 1, sc = col_ok ? s : S - 1;
+        double Grow[16];
+#pragma unroll
+        for (int l = 0; l < 16; ++l) {
+            const int lc = l < K ? l : K - 1;
+            const int lo = kc < lc ? kc : lc, hi = kc < lc ? lc : kc;
+            const double v = gb[(hi * (hi + 1) / 2 + lo) * SP + sc];
+            Grow[l] = (row_ok && l < K) ? v : 0.0;
+        }
+        const double bk = row_ok ? gb[(n_pairs + kc) * SP + sc] : 0.0;
+        const double pur = purity[sc];
+        const double mass = known ? pur : 1.0 - pur;  // what this lane's vertex would put on row k
+        double x = row_ok ? al[kc * SP + sc] : 0.0;
+        __syncthreads();  // (every lane has read its alpha before any is replaced)
+        for (int64_t it = 0; it < T2; ++it) {
+            double g4[4] = {-bk, 0.0, 0.0, 0.0};
+            gram_row_times_a(g4, x, Grow);
+            const double grad = (g4[0] + g4[1]) + (g4[2] + g4[3]);
+            double v1 = known ? grad : INFINITY, v2 = unknown ? grad : INFINITY;
+            int i1 = k, i2 = k;
+            argmin_step<1>(v1, i1, k); argmin_step<2>(v1, i1, k); argmin_step<4>(v1, i1, k); argmin_step<8>(v1, i1, k);
+            argmin_step<1>(v2, i2, k); argmin_step<2>(v2, i2, k); argmin_step<4>(v2, i2, k); argmin_step<8>(v2, i2, k);
+            const double gamma = 2.0 / (double)(it + 2);
+            const bool at_vertex = (known && k == i1) || (unknown && k == i2);
+            x = frank_wolfe_update(x, gamma, at_vertex ? mass : 0.0);
+        }
+        if (col_ok && row_ok) al[k * SP + s] = x;
+    }
+    __syncthreads();
+
+    // ---- l_w = ||alpha[n_c:]||^2 d (:327): the n_u S <= 256 squares, zero-padded to 256, through one fixed tree
+    for (int e = t; e < kMidThreads; e += nt) {
+        const int j = e / S, s = e - j * S;
+        const double x = e < n_u * S ? al[(n_c + j) * SP + s] : 0.0;
+        red[e] = x * x;
+    }
+    __syncthreads();
+    for (int off = kMidThreads / 2; off > 0; off >>= 1) {
+        for (int e = t; e < off; e += nt) red[e] += red[e + off];
+        __syncthreads();
+    }
+    const double l_w = red[0] * dsq;
+
+    // everything the next launches (or the host) read
+    for (int e = t; e < K * S; e += nt) {
+        const int k = e / S, s = e - k * S;
+        ws_alpha[e] = al[k * SP + s];
+    }
+    if (t == 0) {
+        scal[kMdA1] = fill_ratios(a1, a.ratio + b * 2 * a.n_iter2, T2);
+        scal[kMdLw] = l_w;
+        if (T2 > 0) scal[kMdLwPrev] = l_w_old;
+        scal[kMdCf] = cf;
+        a.iters[b] += 1;
+    }
+}
+
 // ---- the cost launch (grid W x B): the slab's partial of the streaming cost of the current iterate
 __global__ __launch_bounds__(kMidThreads) void k_mid_cost(MidArgs a) {
     __shared__ double al[kMidMaxK * kMidMaxS];
@@ -584,6 +720,12 @@ size_t mid_alpha_lds_bytes(int S, int K) {
     return doubles * sizeof(double) + (4 * kMaxJobs * sizeof(short) + 7) / 8 * 8;
 }
 
+size_t mid_alpha_fw_lds_bytes(int S, int K) {
+    const int SP = pow2_at_least(S);
+    const size_t doubles = (size_t)(K * (K + 1) / 2 + K) * SP + (size_t)K * SP + kMidThreads;
+    return doubles * sizeof(double) + (4 * kMaxJobs * sizeof(short) + 7) / 8 * 8;
+}
+
 static bool mid_args_ok(const MidArgs& a, int64_t B) {
     if (!mid_supported(a.N, a.S, a.n_c, a.n_u, a.mode) || B < 1) return false;
     if (a.rows < kMidThreads || a.rows % kMidThreads != 0 || a.W < 1 || a.W > kMidMaxW) return false;
@@ -605,23 +747,35 @@ static void launch_rows(const MidArgs& a, int64_t B, hipStream_t st) {
     hipLaunchKernelGGL((k_mid_rows<NU>), dim3((unsigned)(B * a.W)), dim3(kMidThreads), 0, st, a);
 }
 
-hipError_t launch_mid_iteration(const MidArgs& a, int64_t B, hipStream_t st) {
-    if (!mid_args_ok(a, B)) return hipErrorInvalidValue;
-    const size_t lds = mid_alpha_lds_bytes(a.S, a.n_c + a.n_u);
-    static bool raised = false;  // more than 64 KB of dynamic LDS need the kernel's limit raised, once
-    if (lds > 64 * 1024 && !raised) {
-        const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_mid_alpha),
-                                                 hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+static hipError_t raise_lds_limit(const void* kernel, size_t lds, bool* raised) {
+    if (lds > 64 * 1024 && !*raised) {  // more than 64 KB of dynamic LDS need the kernel's limit raised, once
+        const hipError_t e = hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
         if (e != hipSuccess) return e;
-        raised = true;
+        *raised = true;
     }
+    return hipSuccess;
+}
+
+hipError_t launch_mid_iteration(const MidArgs& a, int64_t B, hipStream_t st, const double* purity) {
+    if (!mid_args_ok(a, B)) return hipErrorInvalidValue;
+    // the purity variant: partial mode with a known block to hold at that mass
+    if (purity != nullptr && (a.mode != DMF_MODE_PARTIAL || a.n_c < 1)) return hipErrorInvalidValue;
+    const int K = a.n_c + a.n_u;
+    const size_t lds = purity != nullptr ? mid_alpha_fw_lds_bytes(a.S, K) : mid_alpha_lds_bytes(a.S, K);
+    static bool raised = false, raised_fw = false;
+    const hipError_t e = purity != nullptr ? raise_lds_limit(reinterpret_cast<const void*>(&k_mid_alpha_fw), lds, &raised_fw)
+                                           : raise_lds_limit(reinterpret_cast<const void*>(&k_mid_alpha), lds, &raised);
+    if (e != hipSuccess) return e;
     switch (a.n_u) {
         case 1: launch_rows<1>(a, B, st); break;
         case 2: launch_rows<2>(a, B, st); break;
         case 3: launch_rows<3>(a, B, st); break;
         default: launch_rows<4>(a, B, st); break;
     }
-    hipLaunchKernelGGL(k_mid_alpha, dim3((unsigned)B), dim3(kMidThreads), lds, st, a);
+    if (purity != nullptr)  // a 16-lane row per sample, four rows to a wave
+        hipLaunchKernelGGL(k_mid_alpha_fw, dim3((unsigned)B), dim3((unsigned)(64 * ((a.S + 3) / 4))), lds, st, a, purity);
+    else
+        hipLaunchKernelGGL(k_mid_alpha, dim3((unsigned)B), dim3(kMidThreads), lds, st, a);
     hipLaunchKernelGGL(k_mid_cost, dim3((unsigned)(B * a.W)), dim3(kMidThreads), 0, st, a);
     return hipGetLastError();
 }

@@ -11,6 +11,7 @@ namespace dmf {
 constexpr int kMidMaxS = 64, kMidMaxK = 16, kMidMaxNu = 4;
 constexpr int64_t kMidMaxElements = (int64_t)1 << 23;  // N S: bounds the workspace, not a cross-over
 constexpr int kMidThreads = 256;
+constexpr int kMidFwMaxThreads = 1024;  // k_mid_alpha_fw: 64 ceil(S / 4) threads, a 16-lane row per sample
 constexpr int kMidChunk = 16;     // Gram accumulators per pass over a slab's rows
 constexpr int kMidMaxW = 64;      // slabs (workgroups) per solve
 constexpr int kMidSlabScalars = 4;  // per (solve, slab): ||u||^2, ||R_trunc||^2, max(D), spare
@@ -44,6 +45,7 @@ inline int mid_slab_jobs(int n_c, int n_u) {
     return a > b ? a : b;
 }
 size_t mid_alpha_lds_bytes(int S, int K);
+size_t mid_alpha_fw_lds_bytes(int S, int K);  // k_mid_alpha_fw: G and b, alpha, 256 doubles, the job tables
 
 // What the launches of one call work on.  The problem's arrays and the caller's (idx, u0, alpha0) are read only; all
 // per-solve state lives in the workspace arrays, indexed by the solve b and, where it says so, the slab w.
@@ -76,7 +78,8 @@ struct MidArgs {
     int* done = nullptr;           // B
 };
 hipError_t launch_mid_setup(const MidArgs& a, int64_t B, hipStream_t st);      // set-up, then the first cost partials
-hipError_t launch_mid_iteration(const MidArgs& a, int64_t B, hipStream_t st);  // k_mid_rows, k_mid_alpha, k_mid_cost
+// k_mid_rows, k_mid_alpha, k_mid_cost; with `purity` (S doubles on the device) k_mid_alpha_fw takes k_mid_alpha's place
+hipError_t launch_mid_iteration(const MidArgs& a, int64_t B, hipStream_t st, const double* purity = nullptr);
 hipError_t launch_mid_finish(const MidArgs& a, int64_t B, hipStream_t st);     // cost[b], done[b]
 
 }  // namespace dmf

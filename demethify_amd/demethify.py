@@ -26,8 +26,13 @@ Deliberate differences from upstream, all flagged at run time:
   * ``DEMETHIFY_BATCH_MID=1`` (environment; default ``0``): where the route above was not taken, ``--confidence`` replicates
     and ``--restart`` restarts go through ``Problem.solve_many_mid`` (several workgroups per solve) when the case is eligible
     (bootstrap.batched_ineligible(kernel="mid")) and N x S lies within [bootstrap.MID_BATCH_MIN_ELEMENTS,
-    bootstrap.MID_BATCH_MAX_ELEMENTS]; otherwise a one-line note says why and the per-solve path runs.  ``--ic`` sweeps and
-    ``--purity`` runs are not wired to it.
+    bootstrap.MID_BATCH_MAX_ELEMENTS]; otherwise a one-line note says why and the per-solve path runs.  ``--ic`` sweeps are
+    not wired to it, and a ``--purity`` run is refused by it with a note.
+  * ``DEMETHIFY_BATCH_MID_PURITY=1`` (environment; default ``0``): asked after the two above, for ``--purity`` runs only:
+    ``--confidence`` replicates and ``--restart`` restarts go through ``Problem.solve_many_mid(purity=...)`` (the Frank-Wolfe
+    alpha launch of the mid-size batch) when the case is eligible (bootstrap.batched_ineligible(kernel="mid",
+    mid_purity=True)) and N x S lies within [bootstrap.MID_BATCH_PURITY_MIN_ELEMENTS,
+    bootstrap.MID_BATCH_PURITY_MAX_ELEMENTS]; otherwise a one-line note says why and the per-solve path runs.
   * ``--ic NAME [n [lo hi]]``: upstream sweeps the hard-coded range 1..25 (ic.py:171); two more values after the
     restart count restrict the sweep to lo..hi unknown types (``--ic BIC 5 2 12``).  Without them: 1..25, as upstream.
 """
@@ -172,6 +177,12 @@ def main(argv=None):
     if batch_mid_env not in ("0", "1"):
         sys.stderr.write(f'Error: DEMETHIFY_BATCH_MID must be "0" or "1", got "{batch_mid_env}".\n')
         sys.exit(1)
+    # DEMETHIFY_BATCH_MID_PURITY=1: where neither route above is taken, --purity replicates and restarts of mid-size problems go
+    # through Problem.solve_many_mid(purity=...), where eligible and inside a gate of its own
+    batch_mid_purity_env = os.environ.get("DEMETHIFY_BATCH_MID_PURITY", "0")
+    if batch_mid_purity_env not in ("0", "1"):
+        sys.stderr.write(f'Error: DEMETHIFY_BATCH_MID_PURITY must be "0" or "1", got "{batch_mid_purity_env}".\n')
+        sys.exit(1)
     if args.plot:
         sys.stderr.write("Note: --plot is ignored, plotting (seaborn/colorcet) is outside this build's scope.\n")
 
@@ -227,7 +238,7 @@ def main(argv=None):
     def batch_mid_route(what, align=False, profile_rows="position"):
         """DEMETHIFY_BATCH_MID=1, asked after DEMETHIFY_BATCH's own route was not taken: does `what` go through
         Problem.solve_many_mid?  A one-line note says why not."""
-        if batch_mid_env != "1":
+        if batch_mid_env != "1" or (args.purity and batch_mid_purity_env == "1"):  # (the purity route speaks for itself)
             return False
         n_rows, n_samples = meth_f.shape
         reason = bootstrap_mod.batched_ineligible(
@@ -241,6 +252,23 @@ def main(argv=None):
             print(f"Note: DEMETHIFY_BATCH_MID=1 is not used for {what}: {reason}; taking the per-solve path.")
         return reason is None
 
+    def batch_mid_purity_route(what, align=False, profile_rows="position"):
+        """DEMETHIFY_BATCH_MID_PURITY=1, asked last and for --purity runs only: does `what` go through
+        Problem.solve_many_mid(purity=...)?  A one-line note says why not."""
+        if batch_mid_purity_env != "1" or not args.purity:
+            return False
+        n_rows, n_samples = meth_f.shape
+        reason = bootstrap_mod.batched_ineligible(
+            n_u, n_rows, n_samples, ref.shape[1] if args.ref else 0, args.init, args.purity,
+            L.DMF_MODE_PARTIAL if args.ref else L.DMF_MODE_UNSUPERVISED, None, align, profile_rows, kernel="mid", mid_purity=True)
+        lo, hi = bootstrap_mod.MID_BATCH_PURITY_MIN_ELEMENTS, bootstrap_mod.MID_BATCH_PURITY_MAX_ELEMENTS
+        if reason is None and not lo <= n_rows * n_samples <= hi:
+            reason = (f"{n_rows} x {n_samples} elements are outside [MID_BATCH_PURITY_MIN_ELEMENTS, "
+                      f"MID_BATCH_PURITY_MAX_ELEMENTS] = [{lo}, {hi}]" + (" (the gate is closed)" if lo > hi else ""))
+        if reason is not None and rank == 0:
+            print(f"Note: DEMETHIFY_BATCH_MID_PURITY=1 is not used for {what}: {reason}; taking the per-solve path.")
+        return reason is None
+
     def bootstrap(anchor=None):
         align = not args.ref and n_u >= 2
         batched = batch_route("--confidence", align=align, profile_rows=ci_rows)
@@ -248,6 +276,12 @@ def main(argv=None):
             bt_ci(args.confidence[0], args.confidence[1], n_u, meth_f, counts, ref, args.init, args.iterations[0],
                   args.iterations[1], args.termination, header if args.ref else [], outdir, args.methfreq, args.purity,
                   args.seed, materialize=False, anchor=anchor, profile_rows=ci_rows, batched=True, batch_kernel="mid")
+            return
+        if not batched and batch_mid_purity_route("--confidence", align=align, profile_rows=ci_rows):
+            bt_ci(args.confidence[0], args.confidence[1], n_u, meth_f, counts, ref, args.init, args.iterations[0],
+                  args.iterations[1], args.termination, header if args.ref else [], outdir, args.methfreq, args.purity,
+                  args.seed, materialize=False, anchor=anchor, profile_rows=ci_rows, batched=True, batch_kernel="mid",
+                  batched_mid_purity=True)
             return
         bt_ci(args.confidence[0], args.confidence[1], n_u, meth_f, counts, ref, args.init, args.iterations[0],
               args.iterations[1], args.termination, header if args.ref else [], outdir, args.methfreq, args.purity,
@@ -292,7 +326,8 @@ def main(argv=None):
         if args.restart > 1 and rank == 0:
             print(f"restart k > 0 uses seed + k (upstream repeats the same seed); {args.restart} restarts")
         batch_restarts = args.restart > 1 and batch_route("--restart")
-        mid_restarts = args.restart > 1 and not batch_restarts and batch_mid_route("--restart")
+        mid_restarts = args.restart > 1 and not batch_restarts and (batch_mid_route("--restart")
+                                                                    or batch_mid_purity_route("--restart"))
         with Problem(get_context(), meth_f, counts, None if unsupervised else ref) as problem:
             if args.restart > 1 and not batch_restarts and not mid_restarts:
                 staging.reserve(((meth_f.shape[0], n_u), (K, meth_f.shape[1])), count=2)
@@ -374,8 +409,11 @@ def main(argv=None):
                                                       _stack=False)
                             inits.append((u0, a0))
                     if mid:
+                        # (a purity vector is passed only on the purity route: without it the call is what it was)
+                        purity_kw = {} if unsupervised or purity is None else {"purity": purity}
                         parts.append(problem.solve_many_mid(np.stack([u0 for u0, _ in inits]), np.stack([a0 for _, a0 in inits]),
-                                                            mode, args.iterations[0], args.iterations[1], args.termination)[:3])
+                                                            mode, args.iterations[0], args.iterations[1], args.termination,
+                                                            **purity_kw)[:3])
                         continue
                     parts.append(problem.solve_many(np.stack([u0 for u0, _ in inits]), np.stack([a0 for _, a0 in inits]), mode,
                                                     args.iterations[0], args.iterations[1], args.termination,

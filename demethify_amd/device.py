@@ -714,13 +714,18 @@ class Problem:
                                           _ptr(alpha), _ptr(cost), _ptr(iters)), "dmf_solve_small")
         return u, alpha, cost, iters
 
-    def solve_many_mid(self, u0s, alpha0s, mode, n_iter1, n_iter2, tol, idx=None, rows_per_workgroup=0, check_every=0):
+    def solve_many_mid(self, u0s, alpha0s, mode, n_iter1, n_iter2, tol, idx=None, rows_per_workgroup=0, check_every=0,
+                       purity=None):
         """B independent solves of this problem in one call, several workgroups per solve (dmf_solve_mid; DESIGN.md section
         6.3) -> (u[B, N, n_u], alpha[B, K, S], cost[B], iters[B]).  Arguments, shapes, errors and results are
         ``solve_many``'s; the shapes taken are those of ``mid_solve_supported`` (N * S up to 2**23), anything else raises
         (DMF_ERR_UNSUPPORTED): there is no fall-back.  ``rows_per_workgroup``: rows per slab, 0 = the default of
         ``mid_solve_plan``; it orders the sums over rows and so may change the last bits.  ``check_every``: outer iterations
-        between two reads of the stop flags, 0 = the default; the results do not depend on it.  No purity, no masks."""
+        between two reads of the stop flags, 0 = the default; the results do not depend on it.  No masks.
+
+        ``purity`` (S fractions, shared by the B solves; None = no constraint, the call as it is without the keyword): the
+        purity-constrained solve (dmf_solve_mid_purity, ``mdwbssmf_deconv_p``), checked as ``solve_many`` checks it -- a vector
+        of S values, partial mode, a problem with a reference, anything else raises ValueError before any device call."""
         u0s = np.ascontiguousarray(u0s, dtype=np.float64)
         alpha0s = np.ascontiguousarray(alpha0s, dtype=np.float64)
         if u0s.ndim != 3 or u0s.shape[1] != self.N:
@@ -733,10 +738,24 @@ class Problem:
             idx = np.ascontiguousarray(idx, dtype=np.int64)
             if idx.shape != (B, self.N):
                 raise ValueError(f"idx shape {idx.shape} != {(B, self.N)}")
+        if purity is not None:
+            purity = np.ascontiguousarray(purity, dtype=np.float64)
+            if purity.shape != (self.S,):
+                raise ValueError(f"purity needs one value per sample ({self.S}), got shape {purity.shape}")
+            if int(mode) != L.DMF_MODE_PARTIAL:
+                raise ValueError("a purity constraint needs the partial-reference mode (DMF_MODE_PARTIAL)")
+            if self.n_c < 1:
+                raise ValueError("a purity constraint needs a reference: there is no known block to hold at that mass")
         u = np.empty((B, self.N, n_u), dtype=np.float64)
         alpha = np.empty((B, K, self.S), dtype=np.float64)
         cost = np.empty(B, dtype=np.float64)
         iters = np.empty(B, dtype=np.int64)
+        if purity is not None:
+            L.check(self._lib.dmf_solve_mid_purity(self.ctx._h, self._h, B, _ptr(idx), _ptr(u0s), _ptr(alpha0s), _ptr(purity), n_u,
+                                                   int(mode), int(n_iter1), int(n_iter2), float(tol), int(rows_per_workgroup),
+                                                   int(check_every), 0, _ptr(u), _ptr(alpha), _ptr(cost), _ptr(iters)),
+                    "dmf_solve_mid_purity")
+            return u, alpha, cost, iters
         L.check(self._lib.dmf_solve_mid(self.ctx._h, self._h, B, _ptr(idx), _ptr(u0s), _ptr(alpha0s), n_u, int(mode),
                                         int(n_iter1), int(n_iter2), float(tol), int(rows_per_workgroup), int(check_every), 0,
                                         _ptr(u), _ptr(alpha), _ptr(cost), _ptr(iters)), "dmf_solve_mid")

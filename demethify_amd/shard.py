@@ -258,7 +258,8 @@ def sharded_restarts(n_restarts, solve_one, shapes, prepare=None, solve_end=None
 def sharded_restarts_batched(n_restarts, solve_many, shapes):
     """``sharded_restarts`` with this rank's restarts solved in ONE call: solve_many(ks) -> (u[B], alpha[B], cost[B]) for
     the restarts ``ks`` this rank owns (Problem.solve_many behind it: one workgroup per restart; or a callable built on
-    Problem.solve_many_mid: several workgroups per restart).  The pick is the same:
+    Problem.solve_many_mid: several workgroups per restart; a purity vector travels inside the
+    callable, to either kernel's ``purity=``).  The pick is the same:
     strict '<' keeps the first minimum locally, one all-reduce(min) over the cost vector, the winner's iterate to every
     rank.  Returns (u, alpha, best_k, cost_vector)."""
     rank, world, _ = dist_state()

@@ -548,7 +548,8 @@ int dmf_solve_small_masked(dmf_context* ctx, const dmf_problem* p, int64_t B, co
  * not depend on B, on its slot, on the other solves or on check_every, bit for bit; rows_per_workgroup changes the order of
  * the sums over rows and with it the last bits.  DMF_ERR_UNSUPPORTED outside the envelope, before the context is touched.
  * DMF_ERR_BAD_ARG: B < 1, a null array, a negative count, a bad rows_per_workgroup (as above), a masked problem, an index
- * outside [0, N) -- every index is checked on the device before any solve starts.  No purity and no hold-out masks here. */
+ * outside [0, N) -- every index is checked on the device before any solve starts.  The purity-constrained solve is
+ * dmf_solve_mid_purity, below; there are no hold-out masks here. */
 int dmf_solve_mid_supported(int64_t N, int64_t S, int64_t n_c, int64_t n_u, int mode);
 int dmf_solve_mid_plan(int64_t N, int64_t S, int64_t rows_per_workgroup, int64_t* out_rows, int64_t* out_W,
                        int64_t* out_check_every);
@@ -556,6 +557,22 @@ int dmf_solve_mid(dmf_context* ctx, const dmf_problem* p, int64_t B, const int64
                   const double* alpha0, int64_t n_u, int mode, int64_t n_iter1, int64_t n_iter2, double tol,
                   int64_t rows_per_workgroup, int64_t check_every, int flags, double* out_u, double* out_alpha,
                   double* out_cost, int64_t* out_iters);
+/* dmf_solve_mid_purity: the same B solves under the purity constraint -- mdwbssmf_deconv_p (demethify/deconvolution.py:306-337)
+ * with the Frank-Wolfe alpha phase frank_wolfe_nmf (:280-302), the arithmetic of dmf_solve_small_purity: no a2, no l_h, no
+ * alpha_; per outer iteration the u phase, then per sample n_iter2 Frank-Wolfe steps restarting at k = 0 from the current alpha
+ * (grad = G_s a - b_s, the first-index argmin over the known rows and over the unknown rows, mass purity[s] on the known
+ * vertex and 1 - purity[s] on the unknown one, gamma = 2 / (k + 2), every product and the sum rounded), l_w, the streaming
+ * cost and the stop test.  The launches are dmf_solve_mid's with one alpha launch of its own (one workgroup per solve, a
+ * 16-lane row per sample, all samples stepping at once); the workspace is dmf_solve_mid's and gains nothing per slab.
+ * purity: S doubles shared by all B solves, a host array, or a device array with DMF_PTR_DEVICE in flags.  Everything else is
+ * dmf_solve_mid's: arguments, plan, idx, determinism, the envelope dmf_solve_mid_supported in DMF_MODE_PARTIAL with n_c >= 1.
+ * DMF_ERR_UNSUPPORTED, before the context is touched: outside the envelope; DMF_MODE_UNSUPERVISED on a problem with a
+ * reference.  DMF_ERR_BAD_ARG: a null purity, a problem without a reference (n_c < 1), a masked problem, and every refusal of
+ * dmf_solve_mid.  Inputs are never written. */
+int dmf_solve_mid_purity(dmf_context* ctx, const dmf_problem* p, int64_t B, const int64_t* idx, const double* u0,
+                         const double* alpha0, const double* purity, int64_t n_u, int mode, int64_t n_iter1,
+                         int64_t n_iter2, double tol, int64_t rows_per_workgroup, int64_t check_every, int flags,
+                         double* out_u, double* out_alpha, double* out_cost, int64_t* out_iters);
 
 /* ---- input tables (host side) ---------------------------------------------------------------
  * demethify/demethify.py:103-143 reads each sample file with pandas.read_csv and stacks its `percent_modified` and
