@@ -1,9 +1,7 @@
 // C-ABI of libdemethify_hip.so, part 8: many independent mid-size solves of one resident problem, several workgroups per
 // solve (dmf_solve_mid, dmf_solve_mid_purity, dmf_solve_mid_plan, dmf_solve_mid_supported; the kernels are in
 // dmf_kernels_mid.hip).
-#include <algorithm>
-
-#include "dmf_api.h"
+#include "dmf_api_batch.h"
 #include "dmf_mid.h"
 
 using namespace dmf_api;
@@ -20,84 +18,50 @@ static int solve_mid(dmf_context* ctx, const dmf_problem* p, int64_t B, const in
     if (p->ctx != ctx || p->mask_bits != nullptr) return DMF_ERR_BAD_ARG;  // (a masked problem's held-out zeros are not data)
     if (with_purity && (purity == nullptr || p->n_c < 1)) return DMF_ERR_BAD_ARG;  // (no known block to hold at that mass)
     if (with_purity && mode != DMF_MODE_PARTIAL) return DMF_ERR_UNSUPPORTED;
-    if (!dmf::mid_supported(p->N, p->S, p->n_c, n_u, mode)) return DMF_ERR_UNSUPPORTED;
+    if (!dmf::batch_supported(p->N, p->S, p->n_c, n_u, mode, dmf::kMidMaxElements)) return DMF_ERR_UNSUPPORTED;
     dmf::MidPlan plan;
     if (!dmf::mid_plan(p->N, p->S, rows_per_workgroup, &plan) || B > 0x7fffffff / plan.W) return DMF_ERR_BAD_ARG;
     DMF_TRY(check_ctx(ctx));
     const int64_t N = p->N, S = p->S, K = p->n_c + n_u, W = plan.W;
     const size_t un = (size_t)B * N * n_u, an = (size_t)B * K * S;
 
-    DevBuf<long long> d_idx;
-    DevBuf<double> d_u0, d_a0;
-    if (idx != nullptr) {
-        DMF_TRY(import_array(ctx, idx, (size_t)B * N, flags, d_idx));
-        // every index is checked on the device before the first launch: no solve has started when one is refused
-        DevBuf<unsigned int> d_bad;
-        unsigned int h_bad = 1;
-        HIP_TRY(d_bad.alloc(ctx, 1));
-        HIP_TRY(dmf::launch_index_range_check(d_idx, B * N, N, d_bad, ctx->stream));
-        HIP_TRY(hipMemcpyAsync(&h_bad, d_bad, sizeof(h_bad), hipMemcpyDeviceToHost, ctx->stream));
-        HIP_TRY(hipStreamSynchronize(ctx->stream));
-        if (h_bad != 0) return DMF_ERR_BAD_ARG;
-    }
-    DMF_TRY(import_array(ctx, u0, un, flags, d_u0));
-    DMF_TRY(import_array(ctx, alpha0, an, flags, d_a0));
-    DevBuf<double> d_purity;
-    if (with_purity) DMF_TRY(import_array(ctx, purity, (size_t)S, flags, d_purity));
-    const double* fw_purity = with_purity ? (const double*)d_purity : nullptr;
+    BatchInputs in;
+    DMF_TRY(in.import_idx(ctx, idx, B, N, flags));
+    DMF_TRY(in.import_starts(ctx, u0, alpha0, with_purity ? purity : nullptr, S, un, an, flags));
+    const double* fw_purity = with_purity ? (const double*)in.purity : nullptr;
 
     // the workspace: all per-solve state and the slab partials (the purity variant uses the same, less alpha_, a2 and l_h)
     const int n_pj = dmf::mid_slab_jobs((int)p->n_c, (int)n_u);
-    DevBuf<double> w_u, w_up, w_a, w_ap, w_gk, w_ratio, w_scal, w_pg, w_ps, w_pc, w_cost;
-    DevBuf<long long> w_iters;
-    DevBuf<int> w_done;
-    if (flags & DMF_PTR_DEVICE) w_u.borrow(out_u);  // (the iterate lives in the caller's result array)
-    else HIP_TRY(w_u.alloc(ctx, un));
-    HIP_TRY(w_up.alloc(ctx, un));
-    HIP_TRY(w_a.alloc(ctx, an));
-    HIP_TRY(w_ap.alloc(ctx, an));
-    HIP_TRY(w_gk.alloc(ctx, (size_t)B * (size_t)std::max<int64_t>(dmf::mid_known_jobs((int)p->n_c) * S, 1)));
-    HIP_TRY(w_ratio.alloc(ctx, (size_t)B * 2 * (size_t)std::max<int64_t>(n_iter2, 1)));
-    HIP_TRY(w_scal.alloc(ctx, (size_t)B * dmf::kMidScalars));
+    BatchWorkspace w;
+    DevBuf<double> w_pg, w_ps, w_pc, w_cost;
+    DMF_TRY(w.alloc(ctx, B, un, an, p->n_c, S, n_iter2, flags, out_u));
     HIP_TRY(w_pg.alloc(ctx, (size_t)B * W * n_pj * S));
     HIP_TRY(w_ps.alloc(ctx, (size_t)B * W * dmf::kMidSlabScalars));
     HIP_TRY(w_pc.alloc(ctx, (size_t)B * W));
     HIP_TRY(w_cost.alloc(ctx, (size_t)B));
-    HIP_TRY(w_iters.alloc(ctx, (size_t)B));
-    HIP_TRY(w_done.alloc(ctx, (size_t)B));
 
     dmf::MidArgs a;
-    a.V = p->V, a.D = p->D, a.Rt = p->Rt;
-    a.idx = d_idx, a.u0 = d_u0, a.alpha0 = d_a0;
-    a.N = N, a.S = (int)S, a.n_c = (int)p->n_c, a.n_u = (int)n_u, a.mode = mode;
-    a.n_iter2 = n_iter2, a.tol = tol;
+    w.fill(a, p, in, n_u, mode, n_iter2, tol);
     a.rows = plan.rows, a.W = plan.W, a.n_pj = n_pj;
-    a.u = w_u, a.u_prev = w_up, a.alpha = w_a, a.alpha_prev = w_ap, a.gk = w_gk, a.ratio = w_ratio, a.scal = w_scal;
-    a.part_g = w_pg, a.part_s = w_ps, a.part_cf = w_pc, a.cost = w_cost, a.iters = w_iters, a.done = w_done;
+    a.part_g = w_pg, a.part_s = w_ps, a.part_cf = w_pc, a.cost = w_cost;
 
     HIP_TRY(dmf::launch_mid_setup(a, B, ctx->stream));
     const int64_t every = check_every > 0 ? std::min<int64_t>(check_every, 1 << 20) : plan.check_every;
-    std::vector<int> h_done((size_t)B);
     for (int64_t ran = 0; ran < n_iter1;) {
         const int64_t n_run = std::min<int64_t>(every, n_iter1 - ran);
         for (int64_t it = 0; it < n_run; ++it) HIP_TRY(dmf::launch_mid_iteration(a, B, ctx->stream, fw_purity));
         ran += n_run;
         if (ran >= n_iter1) break;
         HIP_TRY(dmf::launch_mid_finish(a, B, ctx->stream));
-        HIP_TRY(hipMemcpyAsync(h_done.data(), w_done, (size_t)B * sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
-        HIP_TRY(hipStreamSynchronize(ctx->stream));
-        bool all = true;
-        for (int64_t b = 0; b < B && all; ++b) all = h_done[(size_t)b] != 0;
+        bool all = false;
+        DMF_TRY(w.all_done(ctx, B, &all));
         if (all) break;
     }
 
     // out_cost[b] = cost_f_w of the final iterate (the loop's own streaming cost), out_iters[b] = its outer iterations
     HIP_TRY(dmf::launch_mid_finish(a, B, ctx->stream));
-    static_assert(sizeof(long long) == sizeof(int64_t), "out_iters is copied as long long");
     HIP_TRY(hipMemcpyAsync(out_cost, w_cost, (size_t)B * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(hipMemcpyAsync(out_iters, w_iters, (size_t)B * sizeof(long long), hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(hipMemcpyAsync(out_alpha, w_a, an * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-    if (!(flags & DMF_PTR_DEVICE)) HIP_TRY(hipMemcpyAsync(out_u, w_u, un * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    DMF_TRY(w.copy_out(ctx, B, un, an, flags, out_u, out_alpha, out_iters));
     HIP_TRY(hipStreamSynchronize(ctx->stream));
     return DMF_OK;
 }
@@ -105,7 +69,7 @@ static int solve_mid(dmf_context* ctx, const dmf_problem* p, int64_t B, const in
 extern "C" {
 
 int dmf_solve_mid_supported(int64_t N, int64_t S, int64_t n_c, int64_t n_u, int mode) {
-    return dmf::mid_supported(N, S, n_c, n_u, mode) ? 1 : 0;
+    return dmf::batch_supported(N, S, n_c, n_u, mode, dmf::kMidMaxElements) ? 1 : 0;
 }
 
 int dmf_solve_mid_plan(int64_t N, int64_t S, int64_t rows_per_workgroup, int64_t* out_rows, int64_t* out_W,

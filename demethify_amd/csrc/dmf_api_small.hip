@@ -1,8 +1,6 @@
 // C-ABI of libdemethify_hip.so, part 7: many independent small solves of one resident problem per launch
 // (dmf_solve_small, dmf_solve_small_purity, dmf_solve_small_masked; the kernels are in dmf_kernels_small.hip).
-#include <algorithm>
-
-#include "dmf_api.h"
+#include "dmf_api_batch.h"
 #include "dmf_small.h"
 
 using namespace dmf_api;
@@ -23,24 +21,13 @@ static int solve_small(dmf_context* ctx, const dmf_problem* p, int64_t B, const 
         return DMF_ERR_BAD_ARG;
     if (with_purity && (purity == nullptr || p->n_c < 1)) return DMF_ERR_BAD_ARG;  // (no known block to hold at that mass)
     if (with_purity && mode != DMF_MODE_PARTIAL) return DMF_ERR_UNSUPPORTED;
-    if (!dmf::small_supported(p->N, p->S, p->n_c, n_u, mode)) return DMF_ERR_UNSUPPORTED;
+    if (!dmf::batch_supported(p->N, p->S, p->n_c, n_u, mode, dmf::kSmallMaxElements)) return DMF_ERR_UNSUPPORTED;
     DMF_TRY(check_ctx(ctx));
     const int64_t N = p->N, S = p->S, K = p->n_c + n_u;
     const size_t un = (size_t)B * N * n_u, an = (size_t)B * K * S;
 
-    DevBuf<long long> d_idx;
-    DevBuf<double> d_u0, d_a0;
-    if (idx != nullptr) {
-        DMF_TRY(import_array(ctx, idx, (size_t)B * N, flags, d_idx));
-        // every index is checked on the device before the first launch: no solve has started when one is refused
-        DevBuf<unsigned int> d_bad;
-        unsigned int h_bad = 1;
-        HIP_TRY(d_bad.alloc(ctx, 1));
-        HIP_TRY(dmf::launch_index_range_check(d_idx, B * N, N, d_bad, ctx->stream));
-        HIP_TRY(hipMemcpyAsync(&h_bad, d_bad, sizeof(h_bad), hipMemcpyDeviceToHost, ctx->stream));
-        HIP_TRY(hipStreamSynchronize(ctx->stream));
-        if (h_bad != 0) return DMF_ERR_BAD_ARG;
-    }
+    BatchInputs in;
+    DMF_TRY(in.import_idx(ctx, idx, B, N, flags));
     DevBuf<uint8_t> d_bits;
     std::vector<long long> h_train;
     if (with_mask) {
@@ -57,39 +44,16 @@ static int solve_small(dmf_context* ctx, const dmf_problem* p, int64_t B, const 
         for (int64_t b = 0; b < B; ++b)
             if (h_train[(size_t)b] < 1) return DMF_ERR_BAD_ARG;
     }
-    DMF_TRY(import_array(ctx, u0, un, flags, d_u0));
-    DMF_TRY(import_array(ctx, alpha0, an, flags, d_a0));
-    DevBuf<double> d_purity;
-    if (with_purity) DMF_TRY(import_array(ctx, purity, (size_t)S, flags, d_purity));
-
-    // the workspace: all per-solve state, so that the next launch continues where this one stopped
-    DevBuf<double> w_u, w_up, w_a, w_ap, w_gk, w_ratio, w_scal;
-    DevBuf<long long> w_iters;
-    DevBuf<int> w_done;
-    if (flags & DMF_PTR_DEVICE) w_u.borrow(out_u);  // (the iterate lives in the caller's result array)
-    else HIP_TRY(w_u.alloc(ctx, un));
-    HIP_TRY(w_up.alloc(ctx, un));
-    HIP_TRY(w_a.alloc(ctx, an));
-    HIP_TRY(w_ap.alloc(ctx, an));
-    HIP_TRY(w_gk.alloc(ctx, (size_t)B * (size_t)std::max<int64_t>(dmf::small_known_jobs((int)p->n_c) * S, 1)));
-    HIP_TRY(w_ratio.alloc(ctx, (size_t)B * 2 * (size_t)std::max<int64_t>(n_iter2, 1)));
-    HIP_TRY(w_scal.alloc(ctx, (size_t)B * dmf::kSmallScalars));
-    HIP_TRY(w_iters.alloc(ctx, (size_t)B));
-    HIP_TRY(w_done.alloc(ctx, (size_t)B));
-
+    DMF_TRY(in.import_starts(ctx, u0, alpha0, with_purity ? purity : nullptr, S, un, an, flags));
+    BatchWorkspace w;
+    DMF_TRY(w.alloc(ctx, B, un, an, p->n_c, S, n_iter2, flags, out_u));
     dmf::SmallArgs a;
-    a.V = p->V, a.D = p->D, a.Rt = p->Rt;
-    a.idx = d_idx, a.u0 = d_u0, a.alpha0 = d_a0;
-    a.N = N, a.S = (int)S, a.n_c = (int)p->n_c, a.n_u = (int)n_u, a.mode = mode;
-    a.n_iter2 = n_iter2, a.tol = tol;
-    a.u = w_u, a.u_prev = w_up, a.alpha = w_a, a.alpha_prev = w_ap, a.gk = w_gk, a.ratio = w_ratio, a.scal = w_scal;
-    a.iters = w_iters, a.done = w_done;
-    if (with_purity) a.purity = d_purity;
+    w.fill(a, p, in, n_u, mode, n_iter2, tol);
+    if (with_purity) a.purity = in.purity;
     if (with_mask) a.mask = d_bits;
 
     const int64_t per_launch = iters_per_launch > 0 ? std::min<int64_t>(iters_per_launch, 1 << 20)
                                                       : dmf::small_default_iters_per_launch(N, S, with_purity);
-    std::vector<int> h_done((size_t)B);
     int64_t ran = 0;  // outer iterations every unfinished solve has run
     for (bool first = true;; first = false) {
         a.first = first ? 1 : 0;
@@ -97,10 +61,8 @@ static int solve_small(dmf_context* ctx, const dmf_problem* p, int64_t B, const 
         HIP_TRY(dmf::launch_solve_small(a, B, ctx->stream));
         ran += a.n_run;
         if (ran >= n_iter1) break;
-        HIP_TRY(hipMemcpyAsync(h_done.data(), w_done, (size_t)B * sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
-        HIP_TRY(hipStreamSynchronize(ctx->stream));
-        bool all = true;
-        for (int64_t b = 0; b < B && all; ++b) all = h_done[(size_t)b] != 0;
+        bool all = false;
+        DMF_TRY(w.all_done(ctx, B, &all));
         if (all) break;
     }
 
@@ -110,19 +72,16 @@ static int solve_small(dmf_context* ctx, const dmf_problem* p, int64_t B, const 
     if (with_mask) {
         h_hold.assign((size_t)B, 0.0);
         HIP_TRY(d_hold.alloc(ctx, (size_t)B));
-        HIP_TRY(dmf::launch_small_holdout(p->V, p->Rt, w_u, w_a, d_bits, B, N, (int)S, (int)p->n_c, (int)n_u, d_hold, ctx->stream));
+        HIP_TRY(dmf::launch_small_holdout(p->V, p->Rt, w.u, w.alpha, d_bits, B, N, (int)S, (int)p->n_c, (int)n_u, d_hold, ctx->stream));
         HIP_TRY(hipMemcpyAsync(h_hold.data(), d_hold, (size_t)B * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
     }
 
     // out_cost[b] = cost_f_w of the final iterate (the loop's own streaming cost), out_iters[b] = its outer iterations
-    std::vector<double> h_scal((size_t)B * dmf::kSmallScalars);
-    static_assert(sizeof(long long) == sizeof(int64_t), "out_iters is copied as long long");
-    HIP_TRY(hipMemcpyAsync(h_scal.data(), w_scal, h_scal.size() * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(hipMemcpyAsync(out_iters, w_iters, (size_t)B * sizeof(long long), hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(hipMemcpyAsync(out_alpha, w_a, an * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-    if (!(flags & DMF_PTR_DEVICE)) HIP_TRY(hipMemcpyAsync(out_u, w_u, un * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    std::vector<double> h_scal((size_t)B * dmf::kBatchScalars);
+    HIP_TRY(hipMemcpyAsync(h_scal.data(), w.scal, h_scal.size() * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    DMF_TRY(w.copy_out(ctx, B, un, an, flags, out_u, out_alpha, out_iters));
     HIP_TRY(hipStreamSynchronize(ctx->stream));
-    for (int64_t b = 0; b < B; ++b) out_cost[b] = h_scal[(size_t)b * dmf::kSmallScalars + dmf::kSmCf];
+    for (int64_t b = 0; b < B; ++b) out_cost[b] = h_scal[(size_t)b * dmf::kBatchScalars + dmf::kBsCf];
     if (with_mask)
         for (int64_t b = 0; b < B; ++b) out_holdout_sum_sq[b] = h_hold[(size_t)b], out_n_test[b] = N * S - h_train[(size_t)b];
     return DMF_OK;
@@ -131,7 +90,7 @@ static int solve_small(dmf_context* ctx, const dmf_problem* p, int64_t B, const 
 extern "C" {
 
 int dmf_solve_small_supported(int64_t N, int64_t S, int64_t n_c, int64_t n_u, int mode) {
-    return dmf::small_supported(N, S, n_c, n_u, mode) ? 1 : 0;
+    return dmf::batch_supported(N, S, n_c, n_u, mode, dmf::kSmallMaxElements) ? 1 : 0;
 }
 
 int dmf_solve_small(dmf_context* ctx, const dmf_problem* p, int64_t B, const int64_t* idx, const double* u0, const double* alpha0,

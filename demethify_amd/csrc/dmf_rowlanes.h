@@ -1,5 +1,5 @@
 // Cross-lane moves inside a 16-lane DPP row, and the argmin butterfly built on them.  Shared by the alpha kernels
-// (dmf_kernels_alpha.hip) and the Frank-Wolfe phase of k_solve_small (dmf_kernels_small.hip).
+// (dmf_kernels_alpha.hip) and the Frank-Wolfe lane of the two batched solver families (dmf_batch.h).
 #pragma once
 #include <hip/hip_runtime.h>
 

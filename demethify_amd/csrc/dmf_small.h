@@ -2,14 +2,12 @@
 // (dmf_kernels_small.hip, dmf_api_small.hip).  Shared by the kernel's translation unit and the
 // C-ABI layer; nothing else includes it.
 #pragma once
-#include <hip/hip_runtime.h>
-#include <stdint.h>
+#include "dmf_batch.h"
 
 namespace dmf {
 
-// the envelope of k_solve_small (dmf_solve_small_supported)
-constexpr int kSmallMaxS = 64, kSmallMaxK = 16, kSmallMaxNu = 4;
-constexpr int64_t kSmallMaxElements = (int64_t)1 << 20;  // N S: bounds how long one launch can run, not a cross-over
+// the envelope of k_solve_small (dmf_solve_small_supported): the batch envelope with this bound on N S
+constexpr int64_t kSmallMaxElements = (int64_t)1 << 20;  // bounds how long one launch can run, not a cross-over
 // Outer iterations per launch when the caller passes 0: as many as keep (iterations x N S) within kSmallLaunchElements,
 // at least kSmallMinItersPerLaunch and at most kSmallMaxItersPerLaunch.  Measured on an MI355X at the envelope's largest
 // shapes (N S = 2^20, 12 + 4 types, 20 inner steps; tools/small_batch_bench.py envelope, profiles/small_batch_bench.txt): one
@@ -30,27 +28,11 @@ inline int small_default_iters_per_launch(int64_t N, int64_t S, bool purity = fa
     const int64_t lo = purity ? 1 : kSmallMinItersPerLaunch;
     return (int)(q < lo ? lo : (q > kSmallMaxItersPerLaunch ? kSmallMaxItersPerLaunch : q));
 }
-constexpr int kSmallThreads = 256;
-constexpr int kSmallChunk = 16;  // Gram accumulators per pass over the rows
-enum SmallScalar { kSmA1, kSmA2, kSmLw, kSmLwPrev, kSmLh, kSmLhPrev, kSmDsq, kSmRtNorm2, kSmCf, kSmallScalars = 16 };
-
-bool small_supported(int64_t N, int64_t S, int64_t n_c, int64_t n_u, int mode);
 size_t small_lds_bytes(int S, int K);
-// jobs of the known block per sample: the pairs of R_trunc columns and their products with v
-__host__ __device__ inline int64_t small_known_jobs(int n_c) { return (int64_t)n_c * (n_c + 1) / 2 + n_c; }
 
-// What one launch of k_solve_small works on.  The problem's arrays and the caller's (idx, u0, alpha0) are read only; all
-// per-solve state lives in the workspace arrays, indexed by the solve b = blockIdx.x.
-struct SmallArgs {
-    const double* V = nullptr;        // N_src x S
-    const double* D = nullptr;        // N_src x S
-    const double* Rt = nullptr;       // N_src x n_c
-    const long long* idx = nullptr;   // B x N row indices into the problem, or null: the problem's own rows
-    const double* u0 = nullptr;       // B x N x n_u
-    const double* alpha0 = nullptr;   // B x K x S
-    int64_t N = 0;
-    int S = 0, n_c = 0, n_u = 0, mode = 0;
-    int64_t n_iter2 = 0;
+// What one launch of k_solve_small works on.  All per-solve state lives in the workspace arrays, indexed by the solve
+// b = blockIdx.x.
+struct SmallArgs : BatchArgs {
     int n_run = 0;    // outer iterations this launch may run per solve
     int first = 0;    // the launch that sets the solves up (deconvolution.py:192-204)
     double tol = 0.0;
@@ -58,9 +40,9 @@ struct SmallArgs {
     double* u_prev = nullptr;      // B x N x n_u
     double* alpha = nullptr;       // B x K x S
     double* alpha_prev = nullptr;  // B x K x S
-    double* gk = nullptr;          // B x small_known_jobs(n_c) x S: the known block of the per-sample Grams
+    double* gk = nullptr;          // B x known_jobs(n_c) x S: the known block of the per-sample Grams
     double* ratio = nullptr;       // B x 2 x n_iter2: (a_{t-1} - 1) / a_t of the u phase and of the alpha phase
-    double* scal = nullptr;        // B x kSmallScalars
+    double* scal = nullptr;        // B x kBatchScalars
     long long* iters = nullptr;    // B
     int* done = nullptr;           // B
     // S doubles or null.  Not null: the purity variant (mdwbssmf_deconv_p, deconvolution.py:306-337), whose alpha phase is
