@@ -147,6 +147,8 @@ SIGNATURES = {
                                 _p]),
     "dmf_solve_mid_purity": (C.c_int, [_p, _p, _i64, _p, _p, _p, _p, _i64, C.c_int, _i64, _i64, C.c_double, _i64, _i64, C.c_int, _p,
                                        _p, _p, _p]),
+    "dmf_solve_mid_masked": (C.c_int, [_p, _p, _i64, _p, _p, _p, _i64, C.c_int, _i64, _i64, C.c_double, _i64, _i64, C.c_int, _p, _p,
+                                       _p, _p, _p, _p]),
 }
 
 _lib = None

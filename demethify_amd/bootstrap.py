@@ -154,11 +154,13 @@ def batch_chunk(n_rows, n_u):
     return int(max(1, min(1024, (1 << 25) // max(1, n_rows * n_u))))
 
 
-def mid_batch_chunk(n_rows, n_samples, n_ct, n_u):
+def mid_batch_chunk(n_rows, n_samples, n_ct, n_u, masked=False):
     """How many solves one ``solve_many_mid`` call of the drivers takes: as many as keep the slab workspace (W workgroups per
     solve, each with the larger of the known and the u-dependent Gram jobs times S doubles) and the stack of profiles
     together within 256 MB, at least 1 and at most 1024.  The purity variant (``solve_many_mid(purity=...)``) has the same
-    workspace -- it adds nothing per slab or per solve, only the S purities per call -- so the bound holds for it as it is."""
+    workspace -- it adds nothing per slab or per solve, only the S purities per call -- so the bound holds for it as it is.
+    ``masked``: a ``solve_many_mid_masked`` call, which adds a solve's train mask (N x ceil(S / 8) bytes) and its W count and
+    W hold-out partials (8 bytes each) to what the bound counts."""
     from .device import mid_solve_plan
 
     _, n_slabs, _ = mid_solve_plan(n_rows, n_samples)
@@ -166,6 +168,8 @@ def mid_batch_chunk(n_rows, n_samples, n_ct, n_u):
     known = n_ct * (n_ct + 1) // 2 + n_ct
     jobs = max(known, K * (K + 1) // 2 + K - known)
     per_solve = 8 * (n_slabs * jobs * n_samples + n_rows * n_u)
+    if masked:
+        per_solve += n_rows * ((n_samples + 7) // 8) + 16 * n_slabs
     return int(max(1, min(1024, (1 << 28) // per_solve)))
 
 

@@ -1,6 +1,6 @@
 // Private to the C-ABI layer of the two batched solver families (dmf_api_small.hip, dmf_api_mid.hip): the steps both entry
-// bodies take the same way -- the checked import of the caller's batch inputs, the workspace both families keep per solve,
-// the poll of the stop flags and the copy-out of the results.
+// bodies take the same way -- the checked import of the caller's batch inputs and of the train masks of a masked call, the
+// workspace both families keep per solve, the poll of the stop flags and the copy-out of the results.
 #pragma once
 #include <algorithm>
 
@@ -33,6 +33,33 @@ struct BatchInputs {
         DMF_TRY(import_array(ctx, h_u0, un, flags, u0));
         DMF_TRY(import_array(ctx, h_alpha0, an, flags, alpha0));
         if (h_purity != nullptr) DMF_TRY(import_array(ctx, h_purity, (size_t)S, flags, purity));
+        return DMF_OK;
+    }
+};
+
+// The train masks of a masked call (B x N x ceil(S / 8) bytes) as a device array, and every solve's kept elements.
+struct BatchMasks {
+    DevBuf<uint8_t> bits;
+    std::vector<long long> n_train;  // B: the set bits among the N x S real positions of mask b
+    // The checked import: every solve's kept elements are counted on the device before the first launch, and a fold that
+    // keeps none (upstream skips it, ic.py:71; here d would be 0 and l_w a division by zero) is refused while no solve has
+    // started.  count(bits, n_part) enqueues the family's count launch, which writes `parts` integer partials per solve.
+    template <class Count>
+    int import_counted(dmf_context* ctx, const uint8_t* h_bits, int64_t B, int64_t N, int64_t S, int flags, int64_t parts,
+                       const Count& count) {
+        const size_t nb = (size_t)(S + 7) / 8;
+        DMF_TRY(import_array(ctx, h_bits, (size_t)B * N * nb, flags, bits));
+        DevBuf<long long> d_part;
+        std::vector<long long> h_part((size_t)(B * parts), 0);
+        HIP_TRY(d_part.alloc(ctx, h_part.size()));
+        HIP_TRY(count((const uint8_t*)bits, (long long*)d_part));
+        HIP_TRY(hipMemcpyAsync(h_part.data(), d_part, h_part.size() * sizeof(long long), hipMemcpyDeviceToHost, ctx->stream));
+        HIP_TRY(hipStreamSynchronize(ctx->stream));
+        n_train.assign((size_t)B, 0);
+        for (int64_t b = 0; b < B; ++b) {
+            for (int64_t w = 0; w < parts; ++w) n_train[(size_t)b] += h_part[(size_t)(b * parts + w)];
+            if (n_train[(size_t)b] < 1) return DMF_ERR_BAD_ARG;
+        }
         return DMF_OK;
     }
 };

@@ -28,29 +28,18 @@ static int solve_small(dmf_context* ctx, const dmf_problem* p, int64_t B, const 
 
     BatchInputs in;
     DMF_TRY(in.import_idx(ctx, idx, B, N, flags));
-    DevBuf<uint8_t> d_bits;
-    std::vector<long long> h_train;
-    if (with_mask) {
-        // every solve's kept elements are counted on the device before the first launch: a fold that keeps none (upstream
-        // skips it, ic.py:71; here d would be 0 and l_w a division by zero) is refused while no solve has started
-        const size_t nb = (size_t)(S + 7) / 8;
-        DMF_TRY(import_array(ctx, train_bits, (size_t)B * N * nb, flags, d_bits));
-        DevBuf<long long> d_train;
-        h_train.assign((size_t)B, 0);
-        HIP_TRY(d_train.alloc(ctx, (size_t)B));
-        HIP_TRY(dmf::launch_small_mask_count(d_bits, B, N, (int)S, d_train, ctx->stream));
-        HIP_TRY(hipMemcpyAsync(h_train.data(), d_train, (size_t)B * sizeof(long long), hipMemcpyDeviceToHost, ctx->stream));
-        HIP_TRY(hipStreamSynchronize(ctx->stream));
-        for (int64_t b = 0; b < B; ++b)
-            if (h_train[(size_t)b] < 1) return DMF_ERR_BAD_ARG;
-    }
+    BatchMasks masks;
+    if (with_mask)  // (a mask that keeps nothing is refused here, while no solve has started)
+        DMF_TRY(masks.import_counted(ctx, train_bits, B, N, S, flags, 1, [&](const uint8_t* bits, long long* n_train) {
+            return dmf::launch_small_mask_count(bits, B, N, (int)S, n_train, ctx->stream);
+        }));
     DMF_TRY(in.import_starts(ctx, u0, alpha0, with_purity ? purity : nullptr, S, un, an, flags));
     BatchWorkspace w;
     DMF_TRY(w.alloc(ctx, B, un, an, p->n_c, S, n_iter2, flags, out_u));
     dmf::SmallArgs a;
     w.fill(a, p, in, n_u, mode, n_iter2, tol);
     if (with_purity) a.purity = in.purity;
-    if (with_mask) a.mask = d_bits;
+    if (with_mask) a.mask = masks.bits;
 
     const int64_t per_launch = iters_per_launch > 0 ? std::min<int64_t>(iters_per_launch, 1 << 20)
                                                       : dmf::small_default_iters_per_launch(N, S, with_purity);
@@ -72,7 +61,7 @@ static int solve_small(dmf_context* ctx, const dmf_problem* p, int64_t B, const 
     if (with_mask) {
         h_hold.assign((size_t)B, 0.0);
         HIP_TRY(d_hold.alloc(ctx, (size_t)B));
-        HIP_TRY(dmf::launch_small_holdout(p->V, p->Rt, w.u, w.alpha, d_bits, B, N, (int)S, (int)p->n_c, (int)n_u, d_hold, ctx->stream));
+        HIP_TRY(dmf::launch_small_holdout(p->V, p->Rt, w.u, w.alpha, masks.bits, B, N, (int)S, (int)p->n_c, (int)n_u, d_hold, ctx->stream));
         HIP_TRY(hipMemcpyAsync(h_hold.data(), d_hold, (size_t)B * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
     }
 
@@ -83,7 +72,7 @@ static int solve_small(dmf_context* ctx, const dmf_problem* p, int64_t B, const 
     HIP_TRY(hipStreamSynchronize(ctx->stream));
     for (int64_t b = 0; b < B; ++b) out_cost[b] = h_scal[(size_t)b * dmf::kBatchScalars + dmf::kBsCf];
     if (with_mask)
-        for (int64_t b = 0; b < B; ++b) out_holdout_sum_sq[b] = h_hold[(size_t)b], out_n_test[b] = N * S - h_train[(size_t)b];
+        for (int64_t b = 0; b < B; ++b) out_holdout_sum_sq[b] = h_hold[(size_t)b], out_n_test[b] = N * S - masks.n_train[(size_t)b];
     return DMF_OK;
 }
 

@@ -33,19 +33,31 @@
 // sample (frank_wolfe_nmf, :280-302) with every sample on a 16-lane row of its own, all samples stepping at once in one
 // workgroup of 64 ceil(S / 4) threads.  There is no a2, no l_h and no alpha_; the purity vector is an input shared by the B
 // solves.  Every other kernel is launched as it is.
+//
+// The masked solve (dmf_solve_mid_masked; a bi-cross-validation fold, ic.py:58-89) gives solve b a train mask of its own
+// (MidArgs::mask, dmf_problem_mask's packing) and runs the MASK instances of k_mid_setup_rows, k_mid_rows and k_mid_cost: the
+// count of an element is 0 where its bit is 0 in the slab's maximum count (taken over the kept elements; -inf from a slab that
+// keeps none), the known and the u-dependent Gram jobs, c_i / M_i and the streaming cost, as in k_solve_small<.., MASK>.
+// MASK is a template parameter: the instances without it are the code they were.  k_mid_setup_fin, k_mid_alpha and
+// k_mid_finish are launched as they are; neither idx nor purity goes with a mask.  Two passes frame the call, a workgroup per
+// slab each: k_mid_mask_count before the first launch (a solve's kept elements), k_mid_holdout after the last (the squared
+// error on the held-out ones).
 #include "dmf_mid.h"
 
 namespace dmf {
 
 namespace {
 
-// rows [w rows, (w + 1) rows) of solve b, cut off at N: what the workgroup of slab w reads
+// rows [w rows, (w + 1) rows) of solve b, cut off at N: what the workgroup of slab w reads.  MASK: with solve b's train mask
+// (rows of the solve are rows of the problem there: a masked call has no row list)
+template <bool MASK = false>
 __device__ __forceinline__ RowRange make_slab(const MidArgs& a, int64_t b, int w, const double* u) {
     RowRange p;
     p.V = a.V, p.D = a.D, p.Rt = a.Rt;
     p.idx = a.idx != nullptr ? a.idx + b * a.N : nullptr;
     p.u = u;
-    p.mask = nullptr, p.nb = 0;  // (no masks in this family)
+    if constexpr (MASK) p.nb = (a.S + 7) / 8, p.mask = a.mask + b * a.N * p.nb;
+    else p.mask = nullptr, p.nb = 0;
     p.lo = (int64_t)w * a.rows;
     p.hi = p.lo + a.rows < a.N ? p.lo + a.rows : a.N;
     p.S = a.S, p.n_c = a.n_c, p.n_u = a.n_u, p.K = a.n_c + a.n_u;
@@ -95,13 +107,20 @@ __device__ __forceinline__ void assemble_grams(const MidArgs& a, int64_t b, doub
     }
 }
 
+// k_mid_setup_rows' packed-row table: fill_jobs writes it, the slab partials do not go by it.  At namespace scope, so that both
+// instances of the template drop it as the kernel did before it was one (a template's own __shared__ arrays are kept whether
+// read or not: 304 B more static LDS)
+__shared__ short setup_rows_jd[kBatchMaxJobs];
+
 }  // namespace
 
 // ---- set-up, part 1 (grid W x B): the slab's rows of u and u_, its partials of max(D), ||R_trunc||^2, ||u0||^2 and of the
-// known Gram jobs
+// known Gram jobs.  MASK: the maximum over the slab's KEPT elements (-inf where it keeps none: k_mid_setup_fin's fmax over the
+// slabs is then the solve's kept maximum), the Gram jobs with d = 0 where the bit is
+template <bool MASK>
 __global__ __launch_bounds__(kBatchThreads) void k_mid_setup_rows(MidArgs a) {
     __shared__ double red[kBatchChunk * kBatchThreads];
-    __shared__ short jk[kBatchMaxJobs], jl[kBatchMaxJobs], jd[kBatchMaxJobs];
+    __shared__ short jk[kBatchMaxJobs], jl[kBatchMaxJobs];
     const int t = threadIdx.x;
     const int64_t b = blockIdx.x / a.W;
     const int w = (int)(blockIdx.x - b * a.W);
@@ -110,8 +129,8 @@ __global__ __launch_bounds__(kBatchThreads) void k_mid_setup_rows(MidArgs a) {
     double* u = a.u + b * N * n_u;
     double* u_prev = a.u_prev + b * N * n_u;
     const double* u0 = a.u0 + b * N * n_u;
-    const RowRange p = make_slab(a, b, w, u);
-    if (t == 0) fill_jobs(jk, jl, jd, n_c, p.K, true);
+    const RowRange p = make_slab<MASK>(a, b, w, u);
+    if (t == 0) fill_jobs(jk, jl, setup_rows_jd, n_c, p.K, true);
     double u2 = 0.0, rt2 = 0.0, dmax = -INFINITY;
     for (int64_t i = p.lo + t; i < p.hi; i += kBatchThreads) {
         for (int j = 0; j < n_u; ++j) {
@@ -125,14 +144,20 @@ __global__ __launch_bounds__(kBatchThreads) void k_mid_setup_rows(MidArgs a) {
     {
         const int s = t & (p.SP - 1), r = t / p.SP;
         if (s < S)
-            for (int64_t i = p.lo + r; i < p.hi; i += p.R) dmax = fmax(dmax, p.D[p.row(i) * S + s]);
+            for (int64_t i = p.lo + r; i < p.hi; i += p.R) {
+                if constexpr (MASK) {  // (D.max() of counts * train_mask, as k_solve_small<.., MASK> takes it)
+                    if (p.kept(i, s)) dmax = fmax(dmax, p.D[i * S + s]);
+                } else {
+                    dmax = fmax(dmax, p.D[p.row(i) * S + s]);
+                }
+            }
     }
     dmax = block_max(dmax, red);
     rt2 = block_sum(rt2, red);
     u2 = block_sum(u2, red);  // (its barriers also publish the job tables)
     double* ps = a.part_s + (b * a.W + w) * kMidSlabScalars;
     if (t == 0) ps[0] = u2, ps[1] = rt2, ps[2] = dmax, ps[3] = 0.0;
-    gram_rows<false>(p, jk, jl, 0, known_jobs(n_c), red, slab_partials(a, b, w));
+    gram_rows<MASK>(p, jk, jl, 0, known_jobs(n_c), red, slab_partials(a, b, w));
 }
 
 // ---- set-up, part 2 (grid B; deconvolution.py:192-204): a1 = a2 = 1, alpha_ = alpha = alpha0, d = max(D)^2, l_w, l_h, the
@@ -179,8 +204,8 @@ __global__ __launch_bounds__(kBatchThreads) void k_mid_setup_fin(MidArgs a) {
     if (t == 64) scal[kBsA2] = fill_ratios(1.0, ratio_u + a.n_iter2, a.n_iter2);
 }
 
-// ---- the row launch of an outer iteration (grid W x B)
-template <int NU>
+// ---- the row launch of an outer iteration (grid W x B).  MASK: c_i, M_i and the Gram jobs with d = 0 where the bit is
+template <int NU, bool MASK>
 __global__ __launch_bounds__(kBatchThreads) void k_mid_rows(MidArgs a) {
     __shared__ double al[kBatchMaxK * kBatchMaxS];
     __shared__ double red[kBatchChunk * kBatchThreads];
@@ -198,7 +223,7 @@ __global__ __launch_bounds__(kBatchThreads) void k_mid_rows(MidArgs a) {
     const int S = a.S, n_c = a.n_c, K = n_c + NU;
     double* u = a.u + b * N * NU;
     double* u_prev = a.u_prev + b * N * NU;
-    const RowRange p = make_slab(a, b, w, u);
+    const RowRange p = make_slab<MASK>(a, b, w, u);
     const int SP = p.SP;
     load_alpha(a.alpha + b * K * S, al, K, S, SP);
     if (t == 0) fill_jobs(jk, jl, jd, n_c, K, false);
@@ -211,12 +236,12 @@ __global__ __launch_bounds__(kBatchThreads) void k_mid_rows(MidArgs a) {
     const double cap_w = 0.9999 * sqrt(l_w_prev / l_w);
     double u2 = 0.0;
     for (int64_t i = p.lo + t; i < p.hi; i += kBatchThreads)
-        u2 = u_phase_row<NU, false>(p, i, al, ratio_u, T2, cap_w, l_w, a.mode, u, u_prev, u2);
+        u2 = u_phase_row<NU, MASK>(p, i, al, ratio_u, T2, cap_w, l_w, a.mode, u, u_prev, u2);
     u2 = block_sum(u2, red);  // (its barriers publish the slab's u to the workgroup)
     if (t == 0) a.part_s[(b * a.W + w) * kMidSlabScalars] = u2;
 
     // ---- the slab's partial of the u-dependent entries of the per-sample Grams
-    gram_rows<false>(p, jk, jl, 0, u_jobs(n_c, NU), red, slab_partials(a, b, w));
+    gram_rows<MASK>(p, jk, jl, 0, u_jobs(n_c, NU), red, slab_partials(a, b, w));
 }
 
 // ---- the alpha launch of an outer iteration (grid B)
@@ -355,7 +380,9 @@ __global__ __launch_bounds__(kMidFwMaxThreads) void k_mid_alpha_fw(MidArgs a, co
     }
 }
 
-// ---- the cost launch (grid W x B): the slab's partial of the streaming cost of the current iterate
+// ---- the cost launch (grid W x B): the slab's partial of the streaming cost of the current iterate (MASK: on the kept
+// elements, hence the stop test on them)
+template <bool MASK>
 __global__ __launch_bounds__(kBatchThreads) void k_mid_cost(MidArgs a) {
     __shared__ double al[kBatchMaxK * kBatchMaxS];
     __shared__ double red[kBatchThreads];
@@ -363,11 +390,65 @@ __global__ __launch_bounds__(kBatchThreads) void k_mid_cost(MidArgs a) {
     const int w = (int)(blockIdx.x - b * a.W);
     if (a.done[b]) return;
     const int K = a.n_c + a.n_u;
-    const RowRange p = make_slab(a, b, w, a.u + b * a.N * a.n_u);
+    const RowRange p = make_slab<MASK>(a, b, w, a.u + b * a.N * a.n_u);
     load_alpha(a.alpha + b * K * a.S, al, K, a.S, p.SP);
     __syncthreads();
-    const double cf = stream_cost<false>(p, al, red);
+    const double cf = stream_cost<MASK>(p, al, red);
     if (threadIdx.x == 0) a.part_cf[b * a.W + w] = cf;
+}
+
+// ---- the two framing passes of a masked call (grid W x B each, a workgroup per slab like every row launch).
+// n_part[b W + w] = the set bits among the real S positions of slab w's rows of mask b: thread t counts rows lo + t,
+// lo + t + 256, ..., the 256 integer partials go through one tree.  Bits of samples >= S in a row's last byte are padding and
+// not counted.  Integers: the host adds a solve's W partials in any order.
+__global__ __launch_bounds__(kBatchThreads) void k_mid_mask_count(const uint8_t* __restrict__ mask, int64_t N, int S, int64_t rows,
+                                                                  int W, long long* __restrict__ n_part) {
+    __shared__ long long part[kBatchThreads];
+    const int t = threadIdx.x, nb = (S + 7) / 8;
+    const int64_t b = blockIdx.x / W;
+    const int w = (int)(blockIdx.x - b * W);
+    const int64_t lo = (int64_t)w * rows, hi = lo + rows < N ? lo + rows : N;
+    const uint8_t* mb = mask + b * N * nb;
+    const unsigned int last = (S & 7) ? (1u << (S & 7)) - 1u : 0xFFu;  // the real bits of a row's last byte
+    long long n = 0;
+    for (int64_t i = lo + t; i < hi; i += kBatchThreads)
+        for (int q = 0; q < nb; ++q) n += __popc((unsigned int)mb[i * nb + q] & (q == nb - 1 ? last : 0xFFu));
+    part[t] = n;
+    __syncthreads();
+    for (int off = kBatchThreads / 2; off > 0; off >>= 1) {
+        if (t < off) part[t] += part[t + off];
+        __syncthreads();
+    }
+    if (t == 0) n_part[blockIdx.x] = part[0];
+}
+
+// part_h[b W + w] = the slab's partial of the sum over the held-out elements (bit 0) of (v - [R_trunc | u_b] alpha_b)^2 on the
+// problem's full V with the workspace's iterate (ic.py:80 before the division): threads as (row slice r, sample s) like
+// stream_cost, a thread adds its rows in rising order, the partials go through block_sum's tree.  The caller adds a solve's W
+// partials in rising slab order.
+__global__ __launch_bounds__(kBatchThreads) void k_mid_holdout(MidArgs a, double* __restrict__ part_h) {
+    __shared__ double al[kBatchMaxK * kBatchMaxS];
+    __shared__ double red[kBatchThreads];
+    const int64_t b = blockIdx.x / a.W;
+    const int w = (int)(blockIdx.x - b * a.W);
+    const int t = threadIdx.x, S = a.S, n_c = a.n_c, n_u = a.n_u, K = n_c + n_u;
+    const RowRange p = make_slab<true>(a, b, w, a.u + b * a.N * n_u);
+    const int SP = p.SP;
+    load_alpha(a.alpha + b * K * S, al, K, S, SP);
+    __syncthreads();
+    const int s = t & (SP - 1), r = t / SP;
+    double acc = 0.0;
+    if (s < S) {
+        for (int64_t i = p.lo + r; i < p.hi; i += p.R) {
+            if (p.kept(i, s)) continue;
+            double resid = p.V[i * S + s];
+            for (int k = 0; k < n_c; ++k) resid = fma(-p.Rt[i * n_c + k], al[k * SP + s], resid);
+            for (int j = 0; j < n_u; ++j) resid = fma(-p.u[i * n_u + j], al[(n_c + j) * SP + s], resid);
+            acc = fma(resid, resid, acc);
+        }
+    }
+    const double total = block_sum(acc, red);
+    if (t == 0) part_h[blockIdx.x] = total;
 }
 
 // ---- cost[b] = the cost of solve b's current iterate, done[b] = its stop test (a thread per solve)
@@ -409,26 +490,32 @@ static bool mid_args_ok(const MidArgs& a, int64_t B) {
     if (a.rows < kBatchThreads || a.rows % kBatchThreads != 0 || a.W < 1 || a.W > kMidMaxW) return false;
     if ((int64_t)(a.W - 1) * a.rows >= a.N || (int64_t)a.W * a.rows < a.N) return false;  // the slabs cover the rows exactly
     if (a.n_pj != mid_slab_jobs(a.n_c, a.n_u) || a.n_iter2 < 0) return false;
+    if (a.mask != nullptr && a.idx != nullptr) return false;  // a train mask per solve: no row list goes with it
     return B <= 0x7fffffff / a.W;
 }
 
 hipError_t launch_mid_setup(const MidArgs& a, int64_t B, hipStream_t st) {
     if (!mid_args_ok(a, B)) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(k_mid_setup_rows, dim3((unsigned)(B * a.W)), dim3(kBatchThreads), 0, st, a);
-    hipLaunchKernelGGL(k_mid_setup_fin, dim3((unsigned)B), dim3(kBatchThreads), 0, st, a);
-    hipLaunchKernelGGL(k_mid_cost, dim3((unsigned)(B * a.W)), dim3(kBatchThreads), 0, st, a);
+    const dim3 slabs((unsigned)(B * a.W)), threads(kBatchThreads);
+    if (a.mask != nullptr) hipLaunchKernelGGL(k_mid_setup_rows<true>, slabs, threads, 0, st, a);
+    else hipLaunchKernelGGL(k_mid_setup_rows<false>, slabs, threads, 0, st, a);
+    hipLaunchKernelGGL(k_mid_setup_fin, dim3((unsigned)B), threads, 0, st, a);
+    if (a.mask != nullptr) hipLaunchKernelGGL(k_mid_cost<true>, slabs, threads, 0, st, a);
+    else hipLaunchKernelGGL(k_mid_cost<false>, slabs, threads, 0, st, a);
     return hipGetLastError();
 }
 
 template <int NU>
 static void launch_rows(const MidArgs& a, int64_t B, hipStream_t st) {
-    hipLaunchKernelGGL((k_mid_rows<NU>), dim3((unsigned)(B * a.W)), dim3(kBatchThreads), 0, st, a);
+    const dim3 slabs((unsigned)(B * a.W)), threads(kBatchThreads);
+    if (a.mask != nullptr) hipLaunchKernelGGL((k_mid_rows<NU, true>), slabs, threads, 0, st, a);
+    else hipLaunchKernelGGL((k_mid_rows<NU, false>), slabs, threads, 0, st, a);
 }
 
 hipError_t launch_mid_iteration(const MidArgs& a, int64_t B, hipStream_t st, const double* purity) {
     if (!mid_args_ok(a, B)) return hipErrorInvalidValue;
     // the purity variant: partial mode with a known block to hold at that mass
-    if (purity != nullptr && (a.mode != DMF_MODE_PARTIAL || a.n_c < 1)) return hipErrorInvalidValue;
+    if (purity != nullptr && (a.mode != DMF_MODE_PARTIAL || a.n_c < 1 || a.mask != nullptr)) return hipErrorInvalidValue;
     const int K = a.n_c + a.n_u;
     const size_t lds = purity != nullptr ? mid_alpha_fw_lds_bytes(a.S, K) : mid_alpha_lds_bytes(a.S, K);
     static bool raised = false, raised_fw = false;
@@ -445,7 +532,23 @@ hipError_t launch_mid_iteration(const MidArgs& a, int64_t B, hipStream_t st, con
         hipLaunchKernelGGL(k_mid_alpha_fw, dim3((unsigned)B), dim3((unsigned)(64 * ((a.S + 3) / 4))), lds, st, a, purity);
     else
         hipLaunchKernelGGL(k_mid_alpha, dim3((unsigned)B), dim3(kBatchThreads), lds, st, a);
-    hipLaunchKernelGGL(k_mid_cost, dim3((unsigned)(B * a.W)), dim3(kBatchThreads), 0, st, a);
+    if (a.mask != nullptr) hipLaunchKernelGGL(k_mid_cost<true>, dim3((unsigned)(B * a.W)), dim3(kBatchThreads), 0, st, a);
+    else hipLaunchKernelGGL(k_mid_cost<false>, dim3((unsigned)(B * a.W)), dim3(kBatchThreads), 0, st, a);
+    return hipGetLastError();
+}
+
+hipError_t launch_mid_mask_count(const uint8_t* mask, int64_t B, int64_t N, int S, int64_t rows, int W, long long* n_part,
+                                 hipStream_t st) {
+    if (mask == nullptr || n_part == nullptr || B < 1 || N < 1 || S < 1 || S > kBatchMaxS || rows < kBatchThreads || W < 1 ||
+        W > kMidMaxW || (int64_t)(W - 1) * rows >= N || (int64_t)W * rows < N || B > 0x7fffffff / W)
+        return hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_mid_mask_count, dim3((unsigned)(B * W)), dim3(kBatchThreads), 0, st, mask, N, S, rows, W, n_part);
+    return hipGetLastError();
+}
+
+hipError_t launch_mid_holdout(const MidArgs& a, int64_t B, double* part_h, hipStream_t st) {
+    if (!mid_args_ok(a, B) || a.mask == nullptr || part_h == nullptr) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_mid_holdout, dim3((unsigned)(B * a.W)), dim3(kBatchThreads), 0, st, a, part_h);
     return hipGetLastError();
 }
 

@@ -54,10 +54,22 @@ struct MidArgs : BatchArgs {
     double* cost = nullptr;        // B: the sum of part_cf (k_mid_finish)
     long long* iters = nullptr;    // B
     int* done = nullptr;           // B
+    // B x N x ceil(S / 8) bytes or null.  Not null: solve b has its own train mask (a bi-cross-validation fold, ic.py:58-89) in
+    // dmf_problem_mask's layout -- row-major, sample s in bit (s & 7) of byte (s >> 3), 1 = kept, padding bits ignored -- and
+    // the MASK instances of the slab kernels run, which see the count of an element as 0 where its bit is 0.  Not together with
+    // idx or purity.  The last field: every other one keeps its place (dmf_batch.h on why that matters).
+    const uint8_t* mask = nullptr;
 };
 hipError_t launch_mid_setup(const MidArgs& a, int64_t B, hipStream_t st);      // set-up, then the first cost partials
 // k_mid_rows, k_mid_alpha, k_mid_cost; with `purity` (S doubles on the device) k_mid_alpha_fw takes k_mid_alpha's place
 hipError_t launch_mid_iteration(const MidArgs& a, int64_t B, hipStream_t st, const double* purity = nullptr);
 hipError_t launch_mid_finish(const MidArgs& a, int64_t B, hipStream_t st);     // cost[b], done[b]
+// the framing passes of a masked call, a workgroup per slab of the plan (rows, W):
+// n_part[b W + w] = the set bits among the real positions of slab w's rows of mask b (integers: add them in any order)
+hipError_t launch_mid_mask_count(const uint8_t* mask, int64_t B, int64_t N, int S, int64_t rows, int W, long long* n_part,
+                                 hipStream_t st);
+// part_h[b W + w] = slab w's partial of the sum over the held-out elements of (v - [Rt | u_b] alpha_b)^2 on the problem's full V
+// with the workspace's iterate; a solve's hold-out sum is its W partials added in rising slab order
+hipError_t launch_mid_holdout(const MidArgs& a, int64_t B, double* part_h, hipStream_t st);
 
 }  // namespace dmf

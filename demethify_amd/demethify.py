@@ -26,13 +26,20 @@ Deliberate differences from upstream, all flagged at run time:
   * ``DEMETHIFY_BATCH_MID=1`` (environment; default ``0``): where the route above was not taken, ``--confidence`` replicates
     and ``--restart`` restarts go through ``Problem.solve_many_mid`` (several workgroups per solve) when the case is eligible
     (bootstrap.batched_ineligible(kernel="mid")) and N x S lies within [bootstrap.MID_BATCH_MIN_ELEMENTS,
-    bootstrap.MID_BATCH_MAX_ELEMENTS]; otherwise a one-line note says why and the per-solve path runs.  ``--ic`` sweeps are
-    not wired to it, and a ``--purity`` run is refused by it with a note.
+    bootstrap.MID_BATCH_MAX_ELEMENTS]; otherwise a one-line note says why and the per-solve path runs.  ``--ic`` sweeps have
+    a switch of their own (``DEMETHIFY_BATCH_MID_IC``, below): this one leaves them on the per-solve path.  A ``--purity`` run
+    is refused by it with a note.
   * ``DEMETHIFY_BATCH_MID_PURITY=1`` (environment; default ``0``): asked after the two above, for ``--purity`` runs only:
     ``--confidence`` replicates and ``--restart`` restarts go through ``Problem.solve_many_mid(purity=...)`` (the Frank-Wolfe
     alpha launch of the mid-size batch) when the case is eligible (bootstrap.batched_ineligible(kernel="mid",
     mid_purity=True)) and N x S lies within [bootstrap.MID_BATCH_PURITY_MIN_ELEMENTS,
     bootstrap.MID_BATCH_PURITY_MAX_ELEMENTS]; otherwise a one-line note says why and the per-solve path runs.
+  * ``DEMETHIFY_BATCH_MID_IC=1`` (environment; default ``0``): asked for ``--ic`` sweeps after ``DEMETHIFY_BATCH``'s own
+    ``--ic`` route was not taken: the sweep goes through evaluate_best_ic(batched=True, batch_kernel="mid") -- CCC restarts and
+    the AIC / BIC solve through ``Problem.solve_many_mid``, BCV folds through ``Problem.solve_many_mid_masked`` (a hold-out
+    mask per solve, several workgroups per solve) -- when the criterion is in ic.MID_BATCH_IC_CRITERIA and N x S lies within
+    [ic.MID_BATCH_IC_MIN_ELEMENTS, ic.MID_BATCH_IC_MAX_ELEMENTS]; otherwise a one-line note says why and the per-solve path
+    runs.  A candidate outside the mid-size batch's envelope takes the per-solve path inside the sweep.
   * ``--ic NAME [n [lo hi]]``: upstream sweeps the hard-coded range 1..25 (ic.py:171); two more values after the
     restart count restrict the sweep to lo..hi unknown types (``--ic BIC 5 2 12``).  Without them: 1..25, as upstream.
 """
@@ -183,6 +190,12 @@ def main(argv=None):
     if batch_mid_purity_env not in ("0", "1"):
         sys.stderr.write(f'Error: DEMETHIFY_BATCH_MID_PURITY must be "0" or "1", got "{batch_mid_purity_env}".\n')
         sys.exit(1)
+    # DEMETHIFY_BATCH_MID_IC=1: where DEMETHIFY_BATCH's own --ic route is not taken, an --ic sweep of a mid-size problem goes
+    # through evaluate_best_ic(batched=True, batch_kernel="mid"), for the measured criteria and inside a gate of its own
+    batch_mid_ic_env = os.environ.get("DEMETHIFY_BATCH_MID_IC", "0")
+    if batch_mid_ic_env not in ("0", "1"):
+        sys.stderr.write(f'Error: DEMETHIFY_BATCH_MID_IC must be "0" or "1", got "{batch_mid_ic_env}".\n')
+        sys.exit(1)
     if args.plot:
         sys.stderr.write("Note: --plot is ignored, plotting (seaborn/colorcet) is outside this build's scope.\n")
 
@@ -310,9 +323,30 @@ def main(argv=None):
             print(f"Note: DEMETHIFY_BATCH=1 is not used for --ic: {reason}; taking the per-solve path.")
         return reason is None
 
+    def ic_batch_mid_route():
+        """DEMETHIFY_BATCH_MID_IC=1 with --ic, asked after DEMETHIFY_BATCH's own --ic route was not taken: does the sweep go
+        through evaluate_best_ic(batched=True, batch_kernel="mid")?  Candidates outside the mid-size batch's envelope take
+        the per-solve path inside it; the criteria and the size range are the measured ones of ic.py."""
+        if batch_mid_ic_env != "1":
+            return False
+        from . import ic as ic_mod
+
+        reason = None
+        lo, hi = ic_mod.MID_BATCH_IC_MIN_ELEMENTS, ic_mod.MID_BATCH_IC_MAX_ELEMENTS
+        if args.ic not in ic_mod.MID_BATCH_IC_CRITERIA:
+            reason = f"{args.ic} was not measured faster through the mid-size batch (ic.MID_BATCH_IC_CRITERIA)"
+        elif not lo <= meth_f.size <= hi:
+            reason = (f"{meth_f.shape[0]} x {meth_f.shape[1]} elements are outside [MID_BATCH_IC_MIN_ELEMENTS, "
+                      f"MID_BATCH_IC_MAX_ELEMENTS] = [{lo}, {hi}]" + (" (the gate is closed)" if lo > hi else ""))
+        if reason is not None and rank == 0:
+            print(f"Note: DEMETHIFY_BATCH_MID_IC=1 is not used for --ic: {reason}; taking the per-solve path.")
+        return reason is None
+
     if args.ic:
-        # (the keyword is passed only when the route is taken: without the switch the call is what it was)
+        # (a keyword is passed only when its route is taken: without the switches the call is what it was)
         ic_kw = {"batched": True} if ic_batch_route() else {}
+        if not ic_kw and ic_batch_mid_route():
+            ic_kw = {"batched": True, "batch_kernel": "mid"}
         ref_estimate, proportions, ic_n_u, _scores = evaluate_best_ic(
             meth_f, ref, counts, args.init, args.ic, args.seed, iter1=args.iterations[0], iter2=args.iterations[1],
             tol=args.termination, n_restarts=nb_r, n_u_values=ic_range, **ic_kw)

@@ -721,7 +721,8 @@ class Problem:
         ``solve_many``'s; the shapes taken are those of ``mid_solve_supported`` (N * S up to 2**23), anything else raises
         (DMF_ERR_UNSUPPORTED): there is no fall-back.  ``rows_per_workgroup``: rows per slab, 0 = the default of
         ``mid_solve_plan``; it orders the sums over rows and so may change the last bits.  ``check_every``: outer iterations
-        between two reads of the stop flags, 0 = the default; the results do not depend on it.  No masks.
+        between two reads of the stop flags, 0 = the default; the results do not depend on it.  A hold-out mask per solve:
+        ``solve_many_mid_masked``.
 
         ``purity`` (S fractions, shared by the B solves; None = no constraint, the call as it is without the keyword): the
         purity-constrained solve (dmf_solve_mid_purity, ``mdwbssmf_deconv_p``), checked as ``solve_many`` checks it -- a vector
@@ -778,18 +779,7 @@ class Problem:
         K = self.n_c + n_u
         if alpha0s.shape != (B, K, self.S):
             raise ValueError(f"alpha0s shape {alpha0s.shape} != {(B, K, self.S)}")
-        nb = (self.S + 7) // 8
-        m = np.asarray(train_masks)
-        if m.dtype == np.bool_:
-            if m.shape != (B, self.N, self.S):
-                raise ValueError(f"train_masks shape {m.shape} != {(B, self.N, self.S)}")
-            bits = np.packbits(m, axis=2, bitorder="little")  # (pack_mask's layout, one mask after the other)
-        elif m.dtype == np.uint8:
-            if m.shape != (B, self.N, nb):
-                raise ValueError(f"packed train_masks shape {m.shape} != {(B, self.N, nb)} (ceil(S / 8) bytes per row)")
-            bits = np.ascontiguousarray(m)
-        else:
-            raise ValueError("train_masks must be a bool (B, N, S) array or packed uint8 bits (B, N, ceil(S / 8))")
+        bits = self._packed_train_masks(train_masks, B)
         u = np.empty((B, self.N, n_u), dtype=np.float64)
         alpha = np.empty((B, K, self.S), dtype=np.float64)
         cost = np.empty(B, dtype=np.float64)
@@ -800,6 +790,50 @@ class Problem:
                                                  int(n_iter1), int(n_iter2), float(tol), int(iters_per_launch), 0, _ptr(u),
                                                  _ptr(alpha), _ptr(cost), _ptr(iters), _ptr(sum_sq), _ptr(n_test)),
                 "dmf_solve_small_masked")
+        return u, alpha, cost, iters, sum_sq, n_test
+
+    def _packed_train_masks(self, train_masks, B):
+        """The train masks of B solves as the masked batch entries take them: uint8 (B, N, ceil(S / 8)) in ``pack_mask``'s
+        layout, from a bool (B, N, S) array or from such bits.  Anything else raises ValueError."""
+        nb = (self.S + 7) // 8
+        m = np.asarray(train_masks)
+        if m.dtype == np.bool_:
+            if m.shape != (B, self.N, self.S):
+                raise ValueError(f"train_masks shape {m.shape} != {(B, self.N, self.S)}")
+            return np.packbits(m, axis=2, bitorder="little")  # (pack_mask's layout, one mask after the other)
+        if m.dtype == np.uint8:
+            if m.shape != (B, self.N, nb):
+                raise ValueError(f"packed train_masks shape {m.shape} != {(B, self.N, nb)} (ceil(S / 8) bytes per row)")
+            return np.ascontiguousarray(m)
+        raise ValueError("train_masks must be a bool (B, N, S) array or packed uint8 bits (B, N, ceil(S / 8))")
+
+    def solve_many_mid_masked(self, u0s, alpha0s, train_masks, mode, n_iter1, n_iter2, tol, rows_per_workgroup=0,
+                              check_every=0):
+        """B independent solves of this problem, each on its own hold-out mask, several workgroups per solve
+        (dmf_solve_mid_masked) -> (u[B, N, n_u], alpha[B, K, S], cost[B], iters[B],
+        holdout_sum_sq[B], n_test[B]).  ``train_masks``, what a solve sees of a held-out element and the results are
+        ``solve_many_masked``'s; ``rows_per_workgroup``, ``check_every`` and the shapes taken are ``solve_many_mid``'s.  No
+        ``idx`` and no ``purity``.  Shape errors raise ValueError before any device call; a mask that keeps no element is
+        refused by the library (DMF_ERR_BAD_ARG) before any solve starts."""
+        u0s = np.ascontiguousarray(u0s, dtype=np.float64)
+        alpha0s = np.ascontiguousarray(alpha0s, dtype=np.float64)
+        if u0s.ndim != 3 or u0s.shape[1] != self.N:
+            raise ValueError(f"u0s is B x {self.N} x n_u, got shape {u0s.shape}")
+        B, _, n_u = u0s.shape
+        K = self.n_c + n_u
+        if alpha0s.shape != (B, K, self.S):
+            raise ValueError(f"alpha0s shape {alpha0s.shape} != {(B, K, self.S)}")
+        bits = self._packed_train_masks(train_masks, B)
+        u = np.empty((B, self.N, n_u), dtype=np.float64)
+        alpha = np.empty((B, K, self.S), dtype=np.float64)
+        cost = np.empty(B, dtype=np.float64)
+        iters = np.empty(B, dtype=np.int64)
+        sum_sq = np.empty(B, dtype=np.float64)
+        n_test = np.empty(B, dtype=np.int64)
+        L.check(self._lib.dmf_solve_mid_masked(self.ctx._h, self._h, B, _ptr(bits), _ptr(u0s), _ptr(alpha0s), n_u, int(mode),
+                                               int(n_iter1), int(n_iter2), float(tol), int(rows_per_workgroup),
+                                               int(check_every), 0, _ptr(u), _ptr(alpha), _ptr(cost), _ptr(iters), _ptr(sum_sq),
+                                               _ptr(n_test)), "dmf_solve_mid_masked")
         return u, alpha, cost, iters, sum_sq, n_test
 
     def update_u(self, u, u_prev, alpha, n_iter2, a1, l_w_prev, l_w, mode=L.DMF_MODE_PARTIAL):

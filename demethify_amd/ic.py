@@ -22,7 +22,8 @@ from .staging import Prefetcher
 from .init_func import wls_intercept
 
 __all__ = ["compute_bic", "compute_aic", "compute_consensus_matrix", "compute_ccc", "run_deconvolution",
-           "bicross_validation", "evaluate_best_ic", "batched_ic_ineligible", "SMALL_BATCH_IC_MAX_ELEMENTS"]
+           "bicross_validation", "evaluate_best_ic", "batched_ic_ineligible", "SMALL_BATCH_IC_MAX_ELEMENTS",
+           "MID_BATCH_IC_MIN_ELEMENTS", "MID_BATCH_IC_MAX_ELEMENTS", "MID_BATCH_IC_CRITERIA"]
 
 
 def _n_free(n_u, n_cpg, n_ct, n_samples):
@@ -190,25 +191,50 @@ SMALL_BATCH_IC_MAX_ELEMENTS = 16000
 SMALL_BATCH_IC_CRITERIA = ("CCC", "BCV")
 
 
-def batched_ic_ineligible(n_u, n_rows, n_samples, n_ct, mode):
+# The range of N x S in which the command line (DEMETHIFY_BATCH_MID_IC=1) sends an --ic sweep through
+# evaluate_best_ic(batched=True, batch_kernel="mid"), and the criteria it sends: by the rule of bootstrap.MID_BATCH_*, the
+# contiguous range of MEASURED sizes at which the mid-size leg beats both the per-solve leg and the one-launch batch in every
+# gated criterion, and the criteria that won (tools/mid_ic_bench.py, profiles/mid_batch_ic_bench.txt).  MIN > MAX is a closed
+# gate.  Measured (candidates n_u = 1..4, at most 200 outer iterations, medians of five; per-solve on the commit before /
+# one-launch batch / mid-size batch): 1 000 x 16 (6 + 2) BCV with 20 folds 515 / 305 / 196 ms, CCC with 20 restarts
+# 355 / 271 / 181 ms, AIC 21 / 220 / 144 ms; 4 000 x 16 (6 + 2) BCV 590 / 864 / 255 ms, CCC 469 / 789 / 239 ms, AIC
+# 25 / 648 / 178 ms; 10 000 x 64 (12 + 4) BCV with 5 folds 221 / 12 770 / 818 ms, CCC 672 / 10 756 / 1 097 ms, AIC
+# 36 / 9 247 / 647 ms; 32 768 x 64 (12 + 4) BCV 331 / - / 1 466 ms, CCC 996 / - / 2 253 ms, AIC 48 / - / 1 054 ms.  The mid-size
+# leg wins BCV and CCC at 16 000 and 64 000 elements and loses both from 640 000 on; AIC (one solve per candidate: a batch of
+# one) loses at every size and stays out, so BIC, the same single solve, stays out with it.
+MID_BATCH_IC_MIN_ELEMENTS, MID_BATCH_IC_MAX_ELEMENTS = 16000, 64000
+MID_BATCH_IC_CRITERIA = ("CCC", "BCV")
+
+
+def batched_ic_ineligible(n_u, n_rows, n_samples, n_ct, mode, kernel="small"):
     """Why a candidate ``n_u`` of a model-selection sweep cannot go through ``Problem.solve_many`` /
     ``Problem.solve_many_masked``, as a sentence, or None when it can.  The batched kernel's envelope only (nothing else
-    stands between a sweep and the batch: every initialiser runs on host arrays before the call).  Touches no device."""
-    from .device import small_solve_supported
+    stands between a sweep and the batch: every initialiser runs on host arrays before the call).  ``kernel``: "small" (the
+    default) or "mid" -- ``Problem.solve_many_mid`` / ``Problem.solve_many_mid_masked``, several workgroups per solve, with
+    an envelope of their own.  Touches no device."""
+    from .device import mid_solve_supported, small_solve_supported
 
+    if kernel not in ("small", "mid"):
+        raise ValueError(f'kernel must be "small" or "mid", got {kernel!r}')
     if n_u < 1:
         return "there is no unknown cell type to solve for"
+    if kernel == "mid":
+        if not mid_solve_supported(n_rows, n_samples, n_ct, n_u, mode):
+            return (f"the shape {n_rows} x {n_samples} with {n_ct} + {n_u} cell types is outside the mid-size batch's envelope "
+                    f"(n_u <= {L.MID_MAX_NU}, K <= {L.MID_MAX_K}, S <= {L.MID_MAX_S}, N S <= {L.MID_MAX_ELEMENTS})")
+        return None
     if not small_solve_supported(n_rows, n_samples, n_ct, n_u, mode):
         return (f"the shape {n_rows} x {n_samples} with {n_ct} + {n_u} cell types is outside the batched kernel's envelope "
                 f"(n_u <= {L.SMALL_MAX_NU}, K <= {L.SMALL_MAX_K}, S <= {L.SMALL_MAX_S}, N S <= {L.SMALL_MAX_ELEMENTS})")
     return None
 
 
-def _bcv_batched(meth_f, n_u, counts, iter1, iter2, tol, n_folds, seed, ref, init_option, fraction, problem):
+def _bcv_batched(meth_f, n_u, counts, iter1, iter2, tol, n_folds, seed, ref, init_option, fraction, problem, batch_kernel):
     """bicross_validation(batched=True): every fold is drawn first, on the host and in the reference's order (the draws do
     not depend on the solves, so the generator's stream is the serial one), the folds upstream skips are dropped, the rest
-    are solved by ``problem.solve_many_masked`` in chunks, and ic.py:80-86 is replayed in fold order."""
-    from .bootstrap import batch_chunk
+    are solved by ``problem.solve_many_masked`` (``batch_kernel`` "mid": ``problem.solve_many_mid_masked``) in chunks, and
+    ic.py:80-86 is replayed in fold order."""
+    from .bootstrap import batch_chunk, mid_batch_chunk
 
     folds = []
     for _ in range(n_folds):
@@ -216,11 +242,16 @@ def _bcv_batched(meth_f, n_u, counts, iter1, iter2, tol, n_folds, seed, ref, ini
         if fold is not None:
             folds.append(fold)
     mode = L.DMF_MODE_PARTIAL if ref is not None else L.DMF_MODE_UNSUPERVISED
-    chunk = batch_chunk(meth_f.shape[0], n_u)
+    if batch_kernel == "mid":
+        chunk = mid_batch_chunk(meth_f.shape[0], meth_f.shape[1], 0 if ref is None else ref.shape[1], n_u, masked=True)
+        solve_many_masked = problem.solve_many_mid_masked
+    else:
+        chunk = batch_chunk(meth_f.shape[0], n_u)
+        solve_many_masked = problem.solve_many_masked
     total_press, best_u, best_alpha, min_error = 0, None, None, float("inf")
     for c0 in range(0, len(folds), chunk):
         part = folds[c0:c0 + chunk]
-        u, alpha, _, _, sum_sq, n_test = problem.solve_many_masked(
+        u, alpha, _, _, sum_sq, n_test = solve_many_masked(
             np.stack([np.asarray(f[1], dtype=np.float64).reshape(meth_f.shape[0], n_u) for f in part]),
             np.stack([f[2] for f in part]), np.stack([f[0] for f in part]), mode, iter1, iter2, tol)
         for b in range(len(part)):
@@ -232,7 +263,8 @@ def _bcv_batched(meth_f, n_u, counts, iter1, iter2, tol, n_folds, seed, ref, ini
 
 
 def bicross_validation(meth_f, n_u, counts, iter1, iter2, tol, n_folds=10, seed=None, ref=None,
-                       init_option="uniform_", fraction=0.3, problem=None, _fold_solver=None, batched=False):
+                       init_option="uniform_", fraction=0.3, problem=None, _fold_solver=None, batched=False,
+                       batch_kernel="small"):
     """ic.py:58-89: random-mask hold-out error (returns the SUM over folds, as upstream).
 
     The data are uploaded once (``problem``: a resident upload of (meth_f, counts, ref) to reuse; created here when
@@ -246,10 +278,15 @@ def bicross_validation(meth_f, n_u, counts, iter1, iter2, tol, n_folds=10, seed=
     ``batched``: the folds go through ``Problem.solve_many_masked``, one workgroup per fold with its mask read in the kernel
     and the hold-out error taken where the iterates live, instead of one masked problem and one solver
     per fold.  Draws, skipped folds, the running sum and the first strict minimum are the serial route's.  Only inside the
-    kernel's envelope (``batched_ic_ineligible``): any other shape raises ValueError before any device work."""
+    kernel's envelope (``batched_ic_ineligible``): any other shape raises ValueError before any device work.
+    ``batch_kernel`` (with ``batched``): "small", the default, or "mid" -- the folds go through
+    ``Problem.solve_many_mid_masked``, several workgroups per fold (DESIGN.md section 6.3), inside that family's envelope;
+    any other value raises ValueError."""
+    if batch_kernel not in ("small", "mid"):
+        raise ValueError(f'batch_kernel must be "small" or "mid", got {batch_kernel!r}')
     if batched:
         reason = batched_ic_ineligible(n_u, meth_f.shape[0], meth_f.shape[1], 0 if ref is None else ref.shape[1],
-                                       L.DMF_MODE_UNSUPERVISED if ref is None else L.DMF_MODE_PARTIAL)
+                                       L.DMF_MODE_UNSUPERVISED if ref is None else L.DMF_MODE_PARTIAL, kernel=batch_kernel)
         if reason is not None:
             raise ValueError(f"bicross_validation(batched=True): {reason}")
         np.random.seed(seed)
@@ -257,7 +294,8 @@ def bicross_validation(meth_f, n_u, counts, iter1, iter2, tol, n_folds=10, seed=
         if own:
             problem = Problem(get_context(), meth_f, counts, ref)
         try:
-            return _bcv_batched(meth_f, n_u, counts, iter1, iter2, tol, n_folds, seed, ref, init_option, fraction, problem)
+            return _bcv_batched(meth_f, n_u, counts, iter1, iter2, tol, n_folds, seed, ref, init_option, fraction, problem,
+                                batch_kernel)
         finally:
             if own:
                 problem.close()
@@ -290,27 +328,34 @@ def bicross_validation(meth_f, n_u, counts, iter1, iter2, tol, n_folds=10, seed=
     return total_press, best_u, best_alpha
 
 
-def _note_per_solve(candidates, rank):
-    if candidates and rank == 0:
+def _note_per_solve(candidates, rank, kernel="small"):
+    if candidates and rank == 0 and kernel == "mid":
+        print(f"note: candidates n_u = {candidates} are outside the mid-size batch's envelope (n_u <= {L.MID_MAX_NU}, "
+              f"K <= {L.MID_MAX_K}, S <= {L.MID_MAX_S}, N S <= {L.MID_MAX_ELEMENTS}): they take the per-solve path")
+    elif candidates and rank == 0:
         print(f"note: candidates n_u = {candidates} are outside the batched kernel's envelope (n_u <= {L.SMALL_MAX_NU}, "
               f"K <= {L.SMALL_MAX_K}, S <= {L.SMALL_MAX_S}, N S <= {L.SMALL_MAX_ELEMENTS}): they take the per-solve path")
 
 
-def _solve_many_chunked(problem, inits, mode, iter1, iter2, tol, n_u):
-    """``problem.solve_many`` on a list of (u0, alpha0), at most bootstrap.batch_chunk solves per call -> (u, alpha, cost)."""
-    from .bootstrap import batch_chunk
+def _solve_many_chunked(problem, inits, mode, iter1, iter2, tol, n_u, kernel="small"):
+    """``problem.solve_many`` on a list of (u0, alpha0), at most bootstrap.batch_chunk solves per call -> (u, alpha, cost);
+    ``kernel`` "mid": ``problem.solve_many_mid``, at most bootstrap.mid_batch_chunk solves per call."""
+    from .bootstrap import batch_chunk, mid_batch_chunk
 
-    chunk = batch_chunk(problem.N, n_u)
+    if kernel == "mid":
+        chunk, solve_many = mid_batch_chunk(problem.N, problem.S, problem.n_c, n_u), problem.solve_many_mid
+    else:
+        chunk, solve_many = batch_chunk(problem.N, n_u), problem.solve_many
     parts = []
     for c0 in range(0, len(inits), chunk):
         part = inits[c0:c0 + chunk]
-        parts.append(problem.solve_many(np.stack([np.asarray(u0, dtype=np.float64).reshape(problem.N, n_u) for u0, _ in part]),
+        parts.append(solve_many(np.stack([np.asarray(u0, dtype=np.float64).reshape(problem.N, n_u) for u0, _ in part]),
                                         np.stack([a0 for _, a0 in part]), mode, iter1, iter2, tol)[:3])
     return tuple(np.concatenate([part[j] for part in parts]) for j in range(3))
 
 
 def evaluate_best_ic(meth_f, ref, counts, init_option, ic, seed, iter1, iter2, tol, n_restarts=5,
-                     n_u_values=None, batched=False):
+                     n_u_values=None, batched=False, batch_kernel="small"):
     """ic.py:169-218 -> (u, alpha, n_u, list of criterion values).
 
     ``n_u_values`` defaults to upstream's hard-coded ``range(1, 26)`` (ic.py:171).  AIC / BIC sweeps
@@ -321,7 +366,13 @@ def evaluate_best_ic(meth_f, ref, counts, init_option, ic, seed, iter1, iter2, t
     the cost_f_w the formula takes -- or, for BCV, through ``bicross_validation(batched=True)``.  Any other candidate takes the
     per-solve path inside the same sweep, and one note on rank 0 lists which did.  Initialisers, seeds, the order of the
     candidates and the rank sharding of AIC / BIC are the same either way.
+
+    ``batch_kernel`` (with ``batched``): "small", the default, or "mid" -- the mid-size batch and
+    its envelope in the place of the one-launch batch: CCC restarts and the AIC / BIC solve through
+    ``Problem.solve_many_mid``, BCV folds through ``Problem.solve_many_mid_masked``.  Any other value raises ValueError.
     """
+    if batch_kernel not in ("small", "mid"):
+        raise ValueError(f'batch_kernel must be "small" or "mid", got {batch_kernel!r}')
     default_range = n_u_values is None
     if default_range:
         n_u_values = range(1, 25 + 1)
@@ -340,13 +391,13 @@ def evaluate_best_ic(meth_f, ref, counts, init_option, ic, seed, iter1, iter2, t
         # one resident upload for the whole sweep: every restart (CCC) and every fold (BCV) of every candidate solves on it
         with Problem(get_context(), meth_f, counts, ref) as problem:
             for n_u in n_u_values:
-                in_batch = batched and batched_ic_ineligible(n_u, n_cpg, n_samples, n_ct, mode) is None
+                in_batch = batched and batched_ic_ineligible(n_u, n_cpg, n_samples, n_ct, mode, batch_kernel) is None
                 if batched and not in_batch:
                     per_solve.append(n_u)
                 if ic == "CCC" and in_batch:
                     inits = [_init_on(problem, meth_f, counts, ref, n_u, init_option, seed + restart)
                              for restart in range(n_restarts)]
-                    us, alphas, _ = _solve_many_chunked(problem, inits, mode, iter1, iter2, tol, n_u)
+                    us, alphas, _ = _solve_many_chunked(problem, inits, mode, iter1, iter2, tol, n_u, batch_kernel)
                     u, alpha = us[-1], alphas[-1]  # (the serial loop leaves its last restart's factors behind)
                     score = -compute_ccc(list(alphas))
                 elif ic == "CCC":
@@ -359,11 +410,12 @@ def evaluate_best_ic(meth_f, ref, counts, init_option, ic, seed, iter1, iter2, t
                 else:
                     score, u, alpha = bicross_validation(meth_f, n_u, counts, iter1, iter2, tol, fraction=0.3,
                                                          n_folds=n_restarts, seed=seed, ref=ref,
-                                                         init_option=init_option, problem=problem, batched=in_batch)
+                                                         init_option=init_option, problem=problem, batched=in_batch,
+                                                         batch_kernel=batch_kernel)
                 scores.append(score)
                 if score < best_ic:
                     best_ic, best = score, (u, alpha, n_u)
-        _note_per_solve(per_solve, 0)
+        _note_per_solve(per_solve, 0, batch_kernel)
         return best[0], best[1], best[2], scores
 
     # AIC / BIC: one solve per candidate; candidates dealt to ranks longest-first (cost grows with n_u)
@@ -402,16 +454,17 @@ def evaluate_best_ic(meth_f, ref, counts, init_option, ic, seed, iter1, iter2, t
 
     mode = L.DMF_MODE_PARTIAL if ref is not None else L.DMF_MODE_UNSUPERVISED
     if batched:  # (every rank sees the same list: eligibility is a function of the shape)
-        _note_per_solve([n for n in n_u_values if batched_ic_ineligible(n, n_cpg, n_samples, n_ct, mode) is not None], rank)
+        _note_per_solve([n for n in n_u_values if batched_ic_ineligible(n, n_cpg, n_samples, n_ct, mode, batch_kernel) is not None],
+                        rank, batch_kernel)
     with Problem(get_context(), meth_f, counts, ref) as problem:
         feed = Prefetcher(mine, draw, depth=1, workers=1)
         try:
             for i, drawn in feed:
                 n_u = n_u_values[i]
                 u0, a0 = drawn if drawn is not None else _init_on(problem, meth_f, counts, ref, n_u, init_option, seed)
-                if batched and batched_ic_ineligible(n_u, n_cpg, n_samples, n_ct, mode) is None:
+                if batched and batched_ic_ineligible(n_u, n_cpg, n_samples, n_ct, mode, batch_kernel) is None:
                     # a batch of one: out_cost is cost_f_w(meth_f, R, alpha, counts) of the final iterate (ic.py:206)
-                    us, alphas, costs = _solve_many_chunked(problem, [(u0, a0)], mode, iter1, iter2, tol, n_u)
+                    us, alphas, costs = _solve_many_chunked(problem, [(u0, a0)], mode, iter1, iter2, tol, n_u, batch_kernel)
                     score = float(formula(costs[0], n_u, n_cpg, n_ct, n_samples))
                     local.append((i, score))
                     if score < (keep[0] if keep else float("inf")) or (keep and score == keep[0] and i < keep[1]):

@@ -549,7 +549,7 @@ int dmf_solve_small_masked(dmf_context* ctx, const dmf_problem* p, int64_t B, co
  * the sums over rows and with it the last bits.  DMF_ERR_UNSUPPORTED outside the envelope, before the context is touched.
  * DMF_ERR_BAD_ARG: B < 1, a null array, a negative count, a bad rows_per_workgroup (as above), a masked problem, an index
  * outside [0, N) -- every index is checked on the device before any solve starts.  The purity-constrained solve is
- * dmf_solve_mid_purity, below; there are no hold-out masks here. */
+ * dmf_solve_mid_purity, the one with a hold-out mask per solve dmf_solve_mid_masked, both below. */
 int dmf_solve_mid_supported(int64_t N, int64_t S, int64_t n_c, int64_t n_u, int mode);
 int dmf_solve_mid_plan(int64_t N, int64_t S, int64_t rows_per_workgroup, int64_t* out_rows, int64_t* out_W,
                        int64_t* out_check_every);
@@ -573,6 +573,25 @@ int dmf_solve_mid_purity(dmf_context* ctx, const dmf_problem* p, int64_t B, cons
                          const double* alpha0, const double* purity, int64_t n_u, int mode, int64_t n_iter1,
                          int64_t n_iter2, double tol, int64_t rows_per_workgroup, int64_t check_every, int flags,
                          double* out_u, double* out_alpha, double* out_cost, int64_t* out_iters);
+/* dmf_solve_mid_masked: the same B solves, each on its own hold-out mask -- the folds of a bi-cross-validation
+ * (demethify/ic.py:58-89) in one call, several workgroups per fold.  train_bits, what a solve sees of a held-out element,
+ * out_cost, out_holdout_sum_sq and out_n_test are dmf_solve_small_masked's: B x N x ceil(S / 8) bytes in dmf_problem_mask's
+ * layout (sample s in bit (s & 7) of byte (s >> 3), 1 = kept, padding bits ignored), a host array or a device array with
+ * DMF_PTR_DEVICE; the count of an element is 0 where its bit is 0 in the maximum count (taken over the kept elements), the
+ * known Gram block, the u phase, the Gram, the streaming cost and therefore the stop test; out_cost[b] = cost_f_w of the final
+ * iterate on the masked data, out_holdout_sum_sq[b] = the sum over the held-out elements of (v - [R_trunc | u_b] alpha_b)^2 on
+ * the problem's full V, out_n_test[b] = N S minus the kept elements.  The launches are dmf_solve_mid's, in their masked
+ * instances, between two passes of a workgroup per slab: the kept elements are counted before any solve starts, the hold-out
+ * error is taken after the last iteration (per slab, the slab partials added in rising slab order).  Everything else is
+ * dmf_solve_mid's: arguments, plan, determinism -- a solve's results do not depend on B, on its slot, on the other solves'
+ * masks or on check_every, bit for bit, and an all-ones mask gives dmf_solve_mid's results bit for bit.  There is no idx and
+ * no purity here.  DMF_ERR_UNSUPPORTED outside dmf_solve_mid_supported, before the context is touched.  DMF_ERR_BAD_ARG: a null
+ * train_bits, a masked p, a solve whose mask keeps no element (the outputs stay untouched), and every refusal of
+ * dmf_solve_mid. */
+int dmf_solve_mid_masked(dmf_context* ctx, const dmf_problem* p, int64_t B, const uint8_t* train_bits, const double* u0,
+                         const double* alpha0, int64_t n_u, int mode, int64_t n_iter1, int64_t n_iter2, double tol,
+                         int64_t rows_per_workgroup, int64_t check_every, int flags, double* out_u, double* out_alpha,
+                         double* out_cost, int64_t* out_iters, double* out_holdout_sum_sq, int64_t* out_n_test);
 
 /* ---- input tables (host side) ---------------------------------------------------------------
  * demethify/demethify.py:103-143 reads each sample file with pandas.read_csv and stacks its `percent_modified` and
