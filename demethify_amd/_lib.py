@@ -41,6 +41,7 @@ MAX_K = 64  # dmf::kMaxK: largest n_c + n_u the kernels are built for (DMF_ERR_U
 SMALL_MAX_S, SMALL_MAX_K, SMALL_MAX_NU, SMALL_MAX_ELEMENTS = 64, 16, 4, 1 << 20
 # dmf::kMidMax*: the envelope of dmf_solve_mid, and the most workgroups it gives one solve
 MID_MAX_S, MID_MAX_K, MID_MAX_NU, MID_MAX_ELEMENTS, MID_MAX_W = 64, 16, 4, 1 << 23, 64
+MASK_DRAW_MAX_SEGMENTS = 1024  # DMF_MASK_DRAW_MAX_SEGMENTS: the most segments (workgroups) of a mask draw
 SVD_MAX_S, SVD_MAX_NC, SVD_MAX_RANK, SVD_MAX_LDS = 512, 64, 64, 160 * 1024  # dmf::kSvdMax*: what the SVD initialiser's kernels take
 
 
@@ -133,6 +134,10 @@ SIGNATURES = {
     "dmf_stage_download": (C.c_int, [_p, _p, C.c_size_t, _p]),
     "dmf_mask_draw": (C.c_int, [_p, _p, C.POINTER(C.c_int), _i64, _i64, C.c_uint64, C.POINTER(C.c_void_p),
                                 C.POINTER(_i64)]),
+    "dmf_mask_draw_plan": (C.c_int, [_i64, _i64, C.POINTER(_i64), C.POINTER(_i64)]),
+    "dmf_mask_draw_segments": (C.c_int, [_p, _p, C.POINTER(C.c_int), _i64, _i64, C.c_uint64, _i64, C.POINTER(C.c_void_p),
+                                         C.POINTER(_i64)]),
+    "dmf_mt_jump": (C.c_int, [_p, C.POINTER(C.c_int), C.c_uint64]),
     "dmf_solve": (C.c_int, [_p, _p, _p, _p, _i64, C.c_int, _i64, _i64, C.c_double, C.c_int, _p, _p,
                             _dbl_p, C.POINTER(_i64)]),
     "dmf_solve_small_supported": (C.c_int, [_i64, _i64, _i64, _i64, C.c_int]),

@@ -71,6 +71,13 @@ struct dmf_context {
                                         // (hipHostMalloc / hipHostFree cost ~0.1 ms each: a restart loop makes one per restart)
     hipStream_t copy_stream = nullptr;  // dmf_stage_upload: uploads beside the kernels of `stream` (created on first use)
     std::mutex copy_mutex;
+    // dmf_mask_draw, under copy_mutex: the jump rounds of the last segmented draw's plan (segments of mask_jump_c blocks,
+    // mask_jump_w of them) on the device -- the job table, then from byte mask_jump_terms_at on the polynomials' term lists --
+    // and per launch { first job, number of jobs }: a sweep draws one shape
+    char* mask_jump_table = nullptr;
+    size_t mask_jump_terms_at = 0;
+    int64_t mask_jump_c = 0, mask_jump_w = 0;
+    std::vector<std::pair<size_t, size_t>> mask_jump_rounds;
     dmf_api::FamilyClock clocks[DMF_KERNEL_FAMILIES];
 };
 

@@ -1,6 +1,7 @@
 // C-ABI of libdemethify_hip.so, part 1: the context -- errors, the per-family HIP-event timers, the memory pool that every
 // device buffer of the library comes from, and the upload staging of the restart loops.
 #include "dmf_api.h"
+#include "dmf_mt_jump.h"
 
 namespace dmf_api {
 
@@ -115,6 +116,121 @@ int check_ctx(dmf_context* ctx) {
     return DMF_OK;
 }
 
+// The keys of W >= 2 segments of c blocks, made on the device from row 0 of keys[W][624], the caller's key (block 0): row
+// s >= 1 is the key of block c s - 1 (see k_mask_draw_segments).  By rounds of radix R = kJumpRadix, one launch each with a
+// workgroup per key and no workgroup waiting for another: the first makes rows 1..min(R, W - 1) from row 0 (jumps of c s - 1
+// blocks); then, with rows [1, d] at hand, a round makes rows src + k d (k = 1..R - 1, src in [1, d]) by jumps of c d k blocks
+// and multiplies d by R -- ceil(log_R (W - 1)) launches (two for 1024 segments) on at most 2 R - 1 polynomials.  The job
+// table and the term lists of the last (c, W) stay on the device.  Under copy_mutex, on the copy stream.
+constexpr int64_t kJumpRadix = 32;
+int mask_jump_keys(dmf_context* ctx, unsigned int* keys, int64_t c, int64_t W, hipStream_t st) {
+    if (ctx->mask_jump_table == nullptr || ctx->mask_jump_c != c || ctx->mask_jump_w != W) {
+        std::vector<unsigned short> terms;
+        std::vector<dmf::MtJumpJob> jobs;
+        std::vector<std::pair<size_t, size_t>> rounds;
+        std::unordered_map<uint64_t, std::pair<int, int>> placed;  // blocks -> { first, n_terms } in `terms`
+        auto add = [&](int64_t src, int64_t dst, uint64_t blocks) {
+            auto it = placed.find(blocks);
+            if (it == placed.end()) {
+                const std::vector<uint16_t>& t = dmf::mt_jump_terms(blocks);
+                it = placed.emplace(blocks, std::make_pair((int)terms.size(), (int)t.size())).first;
+                terms.insert(terms.end(), t.begin(), t.end());
+            }
+            jobs.push_back({(int)src, (int)dst, it->second.first, it->second.second});
+        };
+        int64_t d = kJumpRadix < W - 1 ? kJumpRadix : W - 1;
+        for (int64_t s = 1; s <= d; ++s) add(0, s, (uint64_t)c * (uint64_t)s - 1);
+        rounds.push_back({0, jobs.size()});
+        while (d < W - 1) {
+            const size_t first = jobs.size();
+            for (int64_t k = 1; k < kJumpRadix && k * d + 1 <= W - 1; ++k)
+                for (int64_t src = 1; src <= d && src + k * d <= W - 1; ++src)
+                    add(src, src + k * d, (uint64_t)c * (uint64_t)d * (uint64_t)k);
+            rounds.push_back({first, jobs.size() - first});
+            d = kJumpRadix * d < W - 1 ? kJumpRadix * d : W - 1;
+        }
+        if (ctx->mask_jump_table != nullptr) (void)hipFree(ctx->mask_jump_table);  // (no draw is in flight: each waits for its own)
+        ctx->mask_jump_table = nullptr;
+        const size_t job_bytes = jobs.size() * sizeof(dmf::MtJumpJob), term_bytes = terms.size() * sizeof(unsigned short);
+        char* table = nullptr;
+        HIP_TRY(hipMalloc((void**)&table, job_bytes + term_bytes));
+        hipError_t e = hipMemcpyAsync(table, jobs.data(), job_bytes, hipMemcpyHostToDevice, st);
+        e = e != hipSuccess ? e : hipMemcpyAsync(table + job_bytes, terms.data(), term_bytes, hipMemcpyHostToDevice, st);
+        e = e != hipSuccess ? e : hipStreamSynchronize(st);
+        if (e != hipSuccess) {
+            (void)hipFree(table);
+            return hip_fail(e, "mask_jump_keys", __FILE_NAME__, __LINE__);
+        }
+        ctx->mask_jump_table = table, ctx->mask_jump_terms_at = job_bytes, ctx->mask_jump_c = c, ctx->mask_jump_w = W;
+        ctx->mask_jump_rounds = std::move(rounds);
+    }
+    const dmf::MtJumpJob* jobs = reinterpret_cast<const dmf::MtJumpJob*>(ctx->mask_jump_table);
+    const unsigned short* terms = reinterpret_cast<const unsigned short*>(ctx->mask_jump_table + ctx->mask_jump_terms_at);
+    for (const auto& round : ctx->mask_jump_rounds)
+        HIP_TRY(dmf::launch_mt_jump(keys, jobs + round.first, (int64_t)round.second, terms, st));
+    return DMF_OK;
+}
+
+static_assert(dmf::kMaskDrawMaxSegments == DMF_MASK_DRAW_MAX_SEGMENTS, "the header's constant is the kernels'");
+
+// dmf_mask_draw and dmf_mask_draw_segments.  blocks_per_segment: 0 the plan's choice, -1 one workgroup, >= 1 as given.
+int mask_draw(dmf_context* ctx, uint32_t key[624], int* pos, int64_t N, int64_t S, uint64_t threshold,
+              int64_t blocks_per_segment, void** out_bits, int64_t* n_kept) {
+    if (ctx == nullptr || key == nullptr || pos == nullptr || out_bits == nullptr || n_kept == nullptr) return DMF_ERR_BAD_ARG;
+    *out_bits = nullptr;
+    if (*pos < 0 || *pos > 624 || N < 1 || S < 1 || threshold > ((uint64_t)1 << 53) || blocks_per_segment < -1)
+        return DMF_ERR_BAD_ARG;
+    if (S > dmf::kMaskDrawMaxS || N > dmf::kMaskDrawMaxElements / S) return DMF_ERR_UNSUPPORTED;
+    int64_t c = blocks_per_segment;  // below: -1 = the one-workgroup kernel
+    if (c == 0) {
+        int64_t segments = 0;
+        dmf::mask_draw_plan(N, S, &segments, &c);
+        if (segments == 1) c = -1;
+    } else if (c >= 1 && (dmf::mask_draw_blocks(N, S) + c - 1) / c > dmf::kMaskDrawMaxSegments) {
+        return DMF_ERR_BAD_ARG;
+    }
+    // the segments in use, W: up to the block of the last word, which the position moves by at most one; keys are made for
+    // all the W_keys >= W segments of the shape, so that the folds of a sweep share one set of polynomials
+    const int64_t W = c < 1 ? 1 : (int64_t)(((uint64_t)*pos + 2 * (uint64_t)N * (uint64_t)S - 1) / 624 / (uint64_t)c) + 1;
+    const int64_t W_keys = c < 1 ? 1 : (dmf::mask_draw_blocks(N, S) + c - 1) / c;
+    HIP_TRY(hipSetDevice(ctx->device));  // (the current device is per thread)
+    std::lock_guard<std::mutex> lock(ctx->copy_mutex);
+    if (ctx->copy_stream == nullptr) HIP_TRY(hipStreamCreateWithFlags(&ctx->copy_stream, hipStreamNonBlocking));
+    const hipStream_t st = ctx->copy_stream;
+    // the key, then { ones, position } as two u64 (8-byte aligned: 624 is even), then the ones per segment
+    const size_t state_words = 624 + 4 + (c < 1 ? 0 : 2 * (size_t)W_keys);
+    DevBuf<unsigned char> bits;
+    DevBuf<uint32_t> state, keys;
+    HIP_TRY(bits.alloc_staged(ctx, (size_t)N * (size_t)((S + 7) / 8), st));
+    HIP_TRY(state.alloc_staged(ctx, state_words, st));
+    std::vector<uint32_t> h_state(state_words, 0);
+    unsigned long long* d_result = reinterpret_cast<unsigned long long*>(state + 624);
+    if (c < 1) {
+        std::memcpy(h_state.data(), key, 624 * sizeof(uint32_t));
+        HIP_TRY(hipMemcpyAsync(state, h_state.data(), (624 + 4) * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+        HIP_TRY(dmf::launch_mask_draw(state, *pos, N, S, threshold, bits, d_result, st));
+    } else {
+        HIP_TRY(keys.alloc_staged(ctx, 624 * (size_t)W_keys, st));
+        HIP_TRY(hipMemcpyAsync(keys, key, 624 * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+        if (W_keys >= 2) DMF_TRY(mask_jump_keys(ctx, keys, c, W_keys, st));
+        HIP_TRY(dmf::launch_mask_draw_segments(keys, state, *pos, c, N, S, threshold, bits, d_result, d_result + 2, st));
+    }
+    HIP_TRY(hipMemcpyAsync(h_state.data(), state, state_words * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    std::vector<unsigned long long> result((state_words - 624) / 2);
+    std::memcpy(result.data(), h_state.data() + 624, result.size() * sizeof(unsigned long long));
+    unsigned long long ones = result[0];
+    if (c >= 1) {
+        ones = 0;
+        for (int64_t s = 0; s < W; ++s) ones += result[2 + (size_t)s];  // (integers, segment by segment)
+    }
+    std::memcpy(key, h_state.data(), 624 * sizeof(uint32_t));
+    *pos = (int)result[1];
+    *n_kept = (int64_t)ones;
+    *out_bits = bits.release();
+    return DMF_OK;
+}
+
 }  // namespace dmf_api
 
 using namespace dmf_api;
@@ -211,6 +327,7 @@ int dmf_context_destroy(dmf_context* ctx) {
         hipStreamSynchronize(ctx->copy_stream);
         hipStreamDestroy(ctx->copy_stream);
     }
+    if (ctx->mask_jump_table != nullptr) (void)hipFree(ctx->mask_jump_table);
     if (ctx->pool != nullptr) (void)hipMemPoolDestroy(ctx->pool);  // hands the cached buffers back to the driver
     if (ctx->own_stream) hipStreamDestroy(ctx->stream);
     delete ctx;
@@ -248,36 +365,24 @@ int dmf_stage_download(dmf_context* ctx, const void* dev, size_t bytes, void* ho
 }
 
 /* The hold-out mask of a bi-cross-validation fold (ic.py:68, `np.random.rand(*meth_f.shape) < fraction`) drawn where it
- * is used: numpy's MT19937 stream is continued by one persistent workgroup (dmf_kernels_rng.hip) on the copy stream, under
- * dmf_stage_upload's threading contract.  No kernel-family clock: a FamilyScope records on `stream`, which another thread
+ * is used: numpy's MT19937 stream is continued on the copy stream (dmf_kernels_rng.hip), under dmf_stage_upload's threading
+ * contract -- by one persistent workgroup where the plan says one segment, else by one workgroup per segment, on keys that
+ * jump-ahead rounds make from the caller's.  No kernel-family clock: a FamilyScope records on `stream`, which another thread
  * drives. */
 int dmf_mask_draw(dmf_context* ctx, uint32_t key[624], int* pos, int64_t N, int64_t S, uint64_t threshold, void** out_bits,
                   int64_t* n_kept) {
-    if (ctx == nullptr || key == nullptr || pos == nullptr || out_bits == nullptr || n_kept == nullptr) return DMF_ERR_BAD_ARG;
-    *out_bits = nullptr;
-    if (*pos < 0 || *pos > 624 || N < 1 || S < 1 || threshold > ((uint64_t)1 << 53)) return DMF_ERR_BAD_ARG;
+    return mask_draw(ctx, key, pos, N, S, threshold, 0, out_bits, n_kept);
+}
+
+int dmf_mask_draw_segments(dmf_context* ctx, uint32_t key[624], int* pos, int64_t N, int64_t S, uint64_t threshold,
+                           int64_t blocks_per_segment, void** out_bits, int64_t* n_kept) {
+    return mask_draw(ctx, key, pos, N, S, threshold, blocks_per_segment, out_bits, n_kept);
+}
+
+int dmf_mask_draw_plan(int64_t N, int64_t S, int64_t* segments, int64_t* blocks_per_segment) {
+    if (segments == nullptr || blocks_per_segment == nullptr || N < 1 || S < 1) return DMF_ERR_BAD_ARG;
     if (S > dmf::kMaskDrawMaxS || N > dmf::kMaskDrawMaxElements / S) return DMF_ERR_UNSUPPORTED;
-    HIP_TRY(hipSetDevice(ctx->device));  // (the current device is per thread)
-    std::lock_guard<std::mutex> lock(ctx->copy_mutex);
-    if (ctx->copy_stream == nullptr) HIP_TRY(hipStreamCreateWithFlags(&ctx->copy_stream, hipStreamNonBlocking));
-    const hipStream_t st = ctx->copy_stream;
-    constexpr size_t kStateWords = 624 + 4;  // the key, then { ones, position } as two u64 (8-byte aligned: 624 is even)
-    DevBuf<unsigned char> bits;
-    DevBuf<uint32_t> state;
-    HIP_TRY(bits.alloc_staged(ctx, (size_t)N * (size_t)((S + 7) / 8), st));
-    HIP_TRY(state.alloc_staged(ctx, kStateWords, st));
-    uint32_t h_state[kStateWords] = {};
-    std::memcpy(h_state, key, 624 * sizeof(uint32_t));
-    HIP_TRY(hipMemcpyAsync(state, h_state, sizeof(h_state), hipMemcpyHostToDevice, st));
-    HIP_TRY(dmf::launch_mask_draw(state, *pos, N, S, threshold, bits, reinterpret_cast<unsigned long long*>(state + 624), st));
-    HIP_TRY(hipMemcpyAsync(h_state, state, sizeof(h_state), hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    unsigned long long result[2];
-    std::memcpy(result, h_state + 624, sizeof(result));
-    std::memcpy(key, h_state, 624 * sizeof(uint32_t));
-    *pos = (int)result[1];
-    *n_kept = (int64_t)result[0];
-    *out_bits = bits.release();
+    dmf::mask_draw_plan(N, S, segments, blocks_per_segment);
     return DMF_OK;
 }
 

@@ -386,6 +386,33 @@ hipError_t launch_holdout_weights_f64(const unsigned char* bits, double* W, int6
 constexpr int64_t kMaskDrawMaxS = ((int64_t)1 << 31) - 1, kMaskDrawMaxElements = (int64_t)1 << 60;
 hipError_t launch_mask_draw(unsigned int* key_io, int pos, int64_t N, int64_t S, unsigned long long threshold,
                             unsigned char* bits, unsigned long long* result, hipStream_t st);
+// ... cut into segments of `c` 624-word blocks on numpy's grid, one workgroup each (block 0 = the caller's key, used from word
+// pos).  The plan is a function of the shape alone: `segments` of `blocks_per_segment` blocks cover the 2 N S + 624 words a
+// draw can reach; one segment means launch_mask_draw.  Measured (profiles/r14_mask_draw_segments.txt): segments of about 64
+// blocks are the fastest cut while there are workgroups to give (shorter ones cost more in jumps than they save in
+// regenerations), and a round of jumps costs what some 200 regenerations do, so a draw is cut from 512 blocks on.
+constexpr int64_t kMaskDrawMaxSegments = 1024, kMaskDrawMinBlocks = 64, kMaskDrawCutFrom = 512;
+inline int64_t mask_draw_blocks(int64_t N, int64_t S) { return (2 * N * S + 624 + 623) / 624; }
+inline void mask_draw_plan(int64_t N, int64_t S, int64_t* segments, int64_t* blocks_per_segment) {
+    const int64_t blocks = mask_draw_blocks(N, S), by_length = blocks / kMaskDrawMinBlocks;
+    const int64_t w = blocks < kMaskDrawCutFrom ? 1 : by_length > kMaskDrawMaxSegments ? kMaskDrawMaxSegments : by_length;
+    *segments = w, *blocks_per_segment = (blocks + w - 1) / w;
+}
+// keys[W][624] (device), W = (pos + 2 N S - 1) / 624 / c + 1 <= kMaskDrawMaxSegments: row 0 the caller's key, row s >= 1 the key
+// of block c s - 1.  key_out[624] <- the key as of the last regeneration, result[1] <- the position after the last word used,
+// counts[W] <- the ones per segment (result[0] is not written: the caller adds them up).  Every byte of bits is written, by
+// the one workgroup whose segment holds the byte's first element.
+hipError_t launch_mask_draw_segments(const unsigned int* keys, unsigned int* key_out, int pos, int64_t c, int64_t N, int64_t S,
+                                     unsigned long long threshold, unsigned char* bits, unsigned long long* result,
+                                     unsigned long long* counts, hipStream_t st);
+// One jump per job, a workgroup each: row dst of keys[..][624] (device) <- row src carried forward by the jump polynomial with
+// the non-zero terms terms[first .. first + n_terms) (dmf_mt_jump.h; exponents <= 19937).  The jobs of one launch write rows
+// that none of them reads.
+struct MtJumpJob {
+    int src, dst, first, n_terms;
+};
+hipError_t launch_mt_jump(unsigned int* keys, const MtJumpJob* jobs, int64_t n_jobs, const unsigned short* terms,
+                          hipStream_t st);
 // u phase + b_u slab (scratch.slab: [plan.grid][n_u][S] doubles) + per-workgroup ||u||^2 shares in one read of V (f64)
 // and D16 -- or, on the plan's X16 form, of X16 and D16 (V is not read) or of their byte images X8 / D8.  Every schedule of
 // a shape gives the same results bit for bit.  `plan` is rowpass_v2_plan() of this problem, iterate and n_iter2, or

@@ -7,7 +7,9 @@
 //     i in [0, 227):    new[i] = old[i + 397] ^ tw(old[i], old[i + 1])
 //     i in [227, 454):  new[i] = new[i - 227] ^ tw(old[i], old[i + 1])
 //     i in [454, 623):  new[i] = new[i - 227] ^ tw(old[i], old[i + 1]);  new[623] = new[396] ^ tw(old[623], new[0])
-// which is as far as the recurrence parallelises without a jump-ahead: ONE workgroup of 256 threads walks the stream, the
+// which is as far as the recurrence itself parallelises.  Beyond that the stream is cut into segments whose starting keys
+// come from the caller's by polynomial jump-ahead (k_mt_jump, dmf_mt_jump.hip), one workgroup per segment
+// (k_mask_draw_segments); a draw of one segment is k_mask_draw.  Either way a workgroup of 256 threads walks its stream, the
 // key ping-ponging between two LDS arrays (old is read while new is written), a barrier after each group.  random_sample
 // makes a double from two consecutive tempered words, k / 2^53 with k = (a >> 5) 2^26 + (b >> 6), so `x < fraction` is the
 // integer compare k < T with the host's T = ceil(fraction 2^53): no floating point here.
@@ -23,7 +25,9 @@
 // stretch t runs between the first two barriers of regeneration t + 1, which saves it a barrier of its own.
 #include <cstdint>
 
+#include "dmf_batch.h"
 #include "dmf_internal.h"
+#include "dmf_mt_jump.h"
 
 namespace dmf {
 
@@ -78,33 +82,38 @@ __device__ __forceinline__ void emit_bytes(const unsigned long long* ring, unsig
     done.row = row_c, done.col = s_c >> 3;
 }
 
-}  // namespace
+// The first element at or behind double j that begins a byte, as (row, sample): (N, 0) from N S on.
+__device__ __forceinline__ void byte_start(unsigned long long j, unsigned long long N, unsigned long long S,
+                                           unsigned long long& row, unsigned int& s) {
+    if (j >= N * S) {
+        row = N, s = 0;
+        return;
+    }
+    row = j / S;
+    unsigned long long r = (j - row * S + 7) & ~7ull;
+    if (r >= S) ++row, r = 0;
+    s = (unsigned int)r;
+}
 
-// key_io[624]: the generator's key, in and out (the key as of the last regeneration); p = position % 624 of the first word
-// to use, regen_first: the position was 624.  bits <- the packed N x S mask (every byte written), result[0] <- number of
-// ones, result[1] <- the position after the last word used (1..624).  Launched as ONE workgroup of 256 threads.
-__global__ __launch_bounds__(256) void k_mask_draw(unsigned int* __restrict__ key_io, int p, int regen_first,
-                                                   unsigned long long N, unsigned long long S, unsigned long long T,
-                                                   unsigned char* __restrict__ bits,
-                                                   unsigned long long* __restrict__ result) {
-    __shared__ unsigned int key[2][kMtN];
-    __shared__ unsigned long long ring[kRingSlots];
-    __shared__ unsigned long long wave_kept[4];
+// The stretch loop of one workgroup of 256 threads over the blocks t_first..t_last of the stream (block t = the words
+// [624 t, 624 t + 624), the stream's word p the first that makes a double).  key[0] holds the key of block t_first, or with
+// regen_first the key before it; ring is zero.  Drawn and stored are the doubles from element (row_c, s_c) up to j_end, a
+// range that begins and ends where a byte does (or is empty).  Returns the LDS array that holds the key of block t_last;
+// kept: this thread's share of the ones.
+__device__ __forceinline__ int draw_stretches(unsigned int (*key)[kMtN], unsigned long long* ring, int p, bool regen_first,
+                                              unsigned long long t_first, unsigned long long t_last,
+                                              unsigned long long row_c, unsigned int s_c, unsigned long long j_end,
+                                              unsigned long long S, unsigned long long T,
+                                              unsigned char* __restrict__ bits, unsigned long long& kept) {
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
-    const unsigned long long M = N * S, last_word = (unsigned long long)p + 2 * M - 1, t_last = last_word / kMtN;
     const unsigned int nb = (unsigned int)((S + 7) / 8);
-    for (int i = tid; i < kMtN; i += 256) key[0][i] = key_io[i];
-    if (tid < kRingSlots) ring[tid] = 0;
-    __syncthreads();
-
     int cur = 0;  // the LDS array that holds the key of the stretch in hand
-    unsigned long long kept = 0;
-    unsigned long long row_c = 0;  // (row_c, s_c): the first element not drawn yet
-    unsigned int s_c = 0;
-    unsigned long long jb = 0;  // = row_c S + s_c
+    // (row_c, s_c): the first element not drawn yet
+    unsigned long long jb = row_c * S + s_c;
     Emitted done;
-    for (unsigned long long t = 0; t <= t_last; ++t) {
-        if (t > 0 || regen_first) {
+    done.row = row_c, done.col = s_c >> 3;
+    for (unsigned long long t = t_first; t <= t_last; ++t) {
+        if (t > t_first || regen_first) {
             const unsigned int* __restrict__ o = key[cur];
             unsigned int* __restrict__ n = key[cur ^ 1];
             if (tid < 227) n[tid] = o[tid + kMtM] ^ mt_twist(o[tid], o[tid + 1]);
@@ -122,7 +131,8 @@ __global__ __launch_bounds__(256) void k_mask_draw(unsigned int* __restrict__ ke
         // the doubles this stretch completes: [ja, jb_new), double j from the words p + 2 j and p + 2 j + 1 of the stream
         const unsigned long long first = t * kMtN, ja = jb;
         unsigned long long jb_new = ((t + 1) * kMtN - (unsigned long long)p) / 2;
-        jb_new = jb_new < M ? jb_new : M;
+        jb_new = jb_new < j_end ? jb_new : j_end;
+        jb_new = jb_new > ja ? jb_new : ja;  // (a range that begins behind this stretch)
         const int rel0 = (int)((long long)((unsigned long long)p + 2 * ja) - (long long)first);  // `a` of double ja: -1 = straddles
         const unsigned long long base = ja & ~63ull;
         const unsigned int* __restrict__ k_cur = key[cur];
@@ -157,16 +167,141 @@ __global__ __launch_bounds__(256) void k_mask_draw(unsigned int* __restrict__ ke
         jb = jb_new;
     }
     __syncthreads();
-    emit_bytes(ring, bits, S, nb, row_c, s_c, done, kept);  // (jb = M: row_c = N, s_c = 0 -- every byte is out)
+    emit_bytes(ring, bits, S, nb, row_c, s_c, done, kept);  // (jb = j_end: every byte of the range is out)
+    return cur;
+}
 
-    for (int i = tid; i < kMtN; i += 256) key_io[i] = key[cur][i];
+// The workgroup's ones, summed wave by wave in a fixed order; the value is thread 0's.
+__device__ __forceinline__ unsigned long long sum_kept(unsigned long long kept, unsigned long long* wave_kept) {
+    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
 #pragma unroll
     for (int off = 32; off > 0; off >>= 1) kept += __shfl_xor(kept, off, 64);
     if (lane == 0) wave_kept[wave] = kept;
     __syncthreads();
+    return wave_kept[0] + wave_kept[1] + wave_kept[2] + wave_kept[3];
+}
+
+}  // namespace
+
+// key_io[624]: the generator's key, in and out (the key as of the last regeneration); p = position % 624 of the first word
+// to use, regen_first: the position was 624.  bits <- the packed N x S mask (every byte written), result[0] <- number of
+// ones, result[1] <- the position after the last word used (1..624).  Launched as ONE workgroup of 256 threads.
+__global__ __launch_bounds__(256) void k_mask_draw(unsigned int* __restrict__ key_io, int p, int regen_first,
+                                                   unsigned long long N, unsigned long long S, unsigned long long T,
+                                                   unsigned char* __restrict__ bits,
+                                                   unsigned long long* __restrict__ result) {
+    __shared__ unsigned int key[2][kMtN];
+    __shared__ unsigned long long ring[kRingSlots];
+    __shared__ unsigned long long wave_kept[4];
+    const int tid = threadIdx.x;
+    const unsigned long long M = N * S, last_word = (unsigned long long)p + 2 * M - 1, t_last = last_word / kMtN;
+    for (int i = tid; i < kMtN; i += 256) key[0][i] = key_io[i];
+    if (tid < kRingSlots) ring[tid] = 0;
+    __syncthreads();
+
+    unsigned long long kept = 0;
+    const int cur = draw_stretches(key, ring, p, regen_first != 0, 0, t_last, 0, 0, M, S, T, bits, kept);
+
+    for (int i = tid; i < kMtN; i += 256) key_io[i] = key[cur][i];
+    const unsigned long long ones = sum_kept(kept, wave_kept);
     if (tid == 0) {
-        result[0] = wave_kept[0] + wave_kept[1] + wave_kept[2] + wave_kept[3];
+        result[0] = ones;
         result[1] = last_word % kMtN + 1;
+    }
+}
+
+// The same draw cut into segments of c blocks on numpy's own 624-word grid, one workgroup of 256 threads per segment: block
+// 0 is the caller's key (used from word p = the position, 0..624), segment s the blocks [c s, c s + c).  keys[s][624]: for
+// s = 0 the caller's key, for s >= 1 the key of block c s - 1 -- the block BEFORE the segment, which the workgroup
+// regenerates once: with p odd the first double of a segment has its `a` in word 623 of that block.  A double belongs to
+// the block of its second word, and a byte to the segment that holds its first element: the workgroup skips the leading
+// doubles of a byte begun before its segment and draws the (at most 7) doubles behind its segment that finish its last
+// byte, so every byte is stored by exactly one workgroup.  counts[s] <- the ones of the bytes it stored; the workgroup whose
+// segment holds the last word used hands back key_out[624] (the key of that block) and result[1] (the position behind that
+// word, 1..624).  The grid is last block / c + 1 workgroups.
+__global__ __launch_bounds__(256) void k_mask_draw_segments(const unsigned int* __restrict__ keys,
+                                                            unsigned int* __restrict__ key_out, int p,
+                                                            unsigned long long c, unsigned long long N,
+                                                            unsigned long long S, unsigned long long T,
+                                                            unsigned char* __restrict__ bits,
+                                                            unsigned long long* __restrict__ result,
+                                                            unsigned long long* __restrict__ counts) {
+    __shared__ unsigned int key[2][kMtN];
+    __shared__ unsigned long long ring[kRingSlots];
+    __shared__ unsigned long long wave_kept[4];
+    const int tid = threadIdx.x;
+    const unsigned long long seg = blockIdx.x;
+    const unsigned long long M = N * S, last_word = (unsigned long long)p + 2 * M - 1, t_end = last_word / kMtN;
+    const unsigned long long t0 = c * seg, t1 = c * (seg + 1) < t_end + 1 ? c * (seg + 1) : t_end + 1;
+    // the doubles the segment's blocks complete, [j0, j1), and the bytes that begin among them, [j_first, j_end)
+    unsigned long long j0 = seg == 0 ? 0 : (t0 * kMtN - (unsigned long long)p) / 2, j1 = (t1 * kMtN - (unsigned long long)p) / 2;
+    j0 = j0 < M ? j0 : M, j1 = j1 < M ? j1 : M;
+    unsigned long long row_first, row_end;
+    unsigned int s_first, s_end;
+    byte_start(j0, N, S, row_first, s_first);
+    byte_start(j1, N, S, row_end, s_end);
+    const unsigned long long j_first = row_first * S + s_first, j_end = row_end * S + s_end;
+    unsigned long long t_last = t1 - 1;  // the last block to regenerate: the segment's, or the one that finishes its last byte
+    if (j_end > j_first) {
+        const unsigned long long t_byte = ((unsigned long long)p + 2 * j_end - 1) / kMtN;
+        t_last = t_byte > t_last ? t_byte : t_last;
+    }
+    const unsigned int* __restrict__ mine = keys + seg * kMtN;
+    for (int i = tid; i < kMtN; i += 256) key[0][i] = mine[i];
+    if (tid < kRingSlots) ring[tid] = 0;
+    __syncthreads();
+
+    unsigned long long kept = 0;
+    const int cur = draw_stretches(key, ring, p, seg > 0, t0, t_last, row_first, s_first, j_end, S, T, bits, kept);
+
+    const bool holds_last = t_end >= t0 && t_end < t1;  // (then j_end = N S and t_last = t_end)
+    if (holds_last)
+        for (int i = tid; i < kMtN; i += 256) key_out[i] = key[cur][i];
+    const unsigned long long ones = sum_kept(kept, wave_kept);
+    if (tid == 0) {
+        counts[seg] = ones;
+        if (holds_last) result[1] = last_word % kMtN + 1;
+    }
+}
+
+// One workgroup of 640 threads per job: row job.dst of keys[..][624] <- row job.src carried forward by the polynomial whose
+// non-zero terms are terms[job.first .. job.first + job.n_terms) (ascending exponents <= 19937; dmf_mt_jump.hip).  No job of a
+// launch reads a row that a job of the same launch writes.  The raw sequence that follows the source key -- 32 regenerations
+// by the three-group scheme above, each written behind the block it reads -- is laid out in (dynamic) LDS, x[0 .. 33 * 624);
+// result word m is the XOR of x[i + m] over the terms i: one thread per word, the term list read by all of them alike, no
+// barrier between terms.
+__global__ __launch_bounds__(640) void k_mt_jump(unsigned int* keys, const MtJumpJob* __restrict__ jobs,
+                                                 const unsigned short* __restrict__ all_terms) {
+    extern __shared__ unsigned int x[];
+    const int tid = threadIdx.x;
+    const MtJumpJob job = jobs[blockIdx.x];
+    const unsigned short* __restrict__ terms = all_terms + job.first;
+    const int n_terms = job.n_terms;
+    const unsigned int* k = keys + (size_t)job.src * kMtN;
+    if (tid < kMtN) x[tid] = k[tid];
+    __syncthreads();
+    for (int b = 0; b + 1 < kMtJumpBlocks; ++b) {
+        const unsigned int* o = x + b * kMtN;
+        unsigned int* n = x + (b + 1) * kMtN;
+        if (tid < 227) n[tid] = o[tid + kMtM] ^ mt_twist(o[tid], o[tid + 1]);
+        __syncthreads();
+        if (tid < 227) n[tid + 227] = n[tid] ^ mt_twist(o[tid + 227], o[tid + 228]);
+        __syncthreads();
+        if (tid < 169) n[tid + 454] = n[tid + 227] ^ mt_twist(o[tid + 454], o[tid + 455]);
+        if (tid == 169) n[623] = n[396] ^ mt_twist(o[623], n[0]);
+        __syncthreads();
+    }
+    if (tid < kMtN) {
+        unsigned int acc = 0;
+        int i = 0;
+        for (; i + 8 <= n_terms; i += 8) {
+            unsigned int v = 0;
+#pragma unroll
+            for (int u = 0; u < 8; ++u) v ^= x[(int)terms[i + u] + tid];  // (<= 19937 + 623 < 33 * 624)
+            acc ^= v;
+        }
+        for (; i < n_terms; ++i) acc ^= x[(int)terms[i] + tid];
+        keys[(size_t)job.dst * kMtN + tid] = acc;
     }
 }
 
@@ -177,6 +312,32 @@ hipError_t launch_mask_draw(unsigned int* key_io, int pos, int64_t N, int64_t S,
         return hipErrorInvalidValue;
     hipLaunchKernelGGL(k_mask_draw, dim3(1), dim3(256), 0, st, key_io, pos % kMtN, pos == kMtN ? 1 : 0,
                        (unsigned long long)N, (unsigned long long)S, threshold, bits, result);
+    return hipGetLastError();
+}
+
+hipError_t launch_mask_draw_segments(const unsigned int* keys, unsigned int* key_out, int pos, int64_t c, int64_t N, int64_t S,
+                                     unsigned long long threshold, unsigned char* bits, unsigned long long* result,
+                                     unsigned long long* counts, hipStream_t st) {
+    if (keys == nullptr || key_out == nullptr || bits == nullptr || result == nullptr || counts == nullptr || pos < 0 ||
+        pos > kMtN || c < 1 || N < 1 || S < 1 || S > kMaskDrawMaxS || N > kMaskDrawMaxElements / S)
+        return hipErrorInvalidValue;
+    const unsigned long long t_end = ((unsigned long long)pos + 2ull * (unsigned long long)N * (unsigned long long)S - 1) / kMtN;
+    const unsigned long long W = t_end / (unsigned long long)c + 1;
+    if (W > (unsigned long long)kMaskDrawMaxSegments) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_mask_draw_segments, dim3((unsigned)W), dim3(256), 0, st, keys, key_out, pos, (unsigned long long)c,
+                       (unsigned long long)N, (unsigned long long)S, threshold, bits, result, counts);
+    return hipGetLastError();
+}
+
+hipError_t launch_mt_jump(unsigned int* keys, const MtJumpJob* jobs, int64_t n_jobs, const unsigned short* terms,
+                          hipStream_t st) {
+    if (keys == nullptr || jobs == nullptr || terms == nullptr || n_jobs < 1 || n_jobs > kMaskDrawMaxSegments)
+        return hipErrorInvalidValue;
+    static bool raised = false;
+    constexpr size_t lds = (size_t)kMtJumpWords * sizeof(unsigned int);  // 82 368 bytes: above the 64 KB a kernel gets unasked
+    const hipError_t e = raise_lds_limit(reinterpret_cast<const void*>(&k_mt_jump), lds, &raised);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(k_mt_jump, dim3((unsigned)n_jobs), dim3(640), lds, st, keys, jobs, terms);
     return hipGetLastError();
 }
 

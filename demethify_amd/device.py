@@ -59,6 +59,19 @@ def mask_threshold(fraction) -> int:
     return math.ceil(f * 9007199254740992.0)
 
 
+def mt_jump(state, n_words: int):
+    """The state tuple of numpy's legacy generator (``np.random.get_state()``) after ``n_words`` further 32-bit words --
+    what ``np.random.bytes(4 * n_words)`` leaves behind -- by polynomial jump-ahead on the host (dmf_mt_jump): no word in
+    between is generated, so 2**60 words cost what 2**10 do.  The Gaussian cache fields are passed through."""
+    name, key, pos, *rest = state
+    if name != "MT19937" or not 0 <= int(n_words) < 1 << 64:
+        raise ValueError("mt_jump takes a legacy MT19937 state and a number of words in [0, 2**64)")
+    key = np.ascontiguousarray(key, dtype=np.uint32).copy()
+    pos_io = C.c_int(int(pos))
+    L.check(L.load().dmf_mt_jump(key.ctypes.data_as(C.c_void_p), C.byref(pos_io), int(n_words)), "dmf_mt_jump")
+    return (name, key, pos_io.value, *rest)
+
+
 class Context:
     """dmf_context: a GPU, a HIP stream and the kernel-family clocks."""
 

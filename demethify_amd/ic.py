@@ -97,9 +97,9 @@ def run_deconvolution(meth_f, counts, ref, n_u, init_option, seed, iter1, iter2,
 
 # The number of elements N x S from which a fold's mask is drawn on the device (staging.draw_mask) instead of on the host:
 # the smallest measured size from which the device leg is the faster one at every larger measured size.  Measured
-# (profiles/r13_mask_draw.txt: 350 x 10 to 1e6 x 256) it is the faster one at none -- 0.940 s against 0.881 s at 1e6 x 256 --
-# so the gate sits above them all and the host draws.
-DEVICE_MASK_MIN_ELEMENTS = 1 << 62
+# (profiles/r14_mask_draw_segments.txt, the segmented draw against the host leg: 350 x 10, 1e4 x 64, 1e5 x 64, 1e6 x 256) the
+# host is the faster one at 350 x 10 alone, where the plan is one workgroup, and the device from 1e4 x 64 on.
+DEVICE_MASK_MIN_ELEMENTS = 640_000
 
 
 def _bcv_draw_fold(meth_f, counts, ref, n_u, init_option, seed, fraction, stage=None, draw=None):

@@ -180,12 +180,14 @@ def mask_to_device(bits, ctx):
     return out
 
 
-def draw_mask(shape, fraction, ctx):
+def draw_mask(shape, fraction, ctx, blocks_per_segment=0):
     """``pack_mask(np.random.rand(*shape) < fraction)`` of numpy's global generator, drawn on the context's GPU
     (dmf_mask_draw) and left there: the generator's key and position go to the device, the stream is continued by the
     kernel, and the advanced key and position are put back -- the Gaussian cache fields as they were -- so that whatever
     draws next sees the stream exactly where the host draw would have left it.  Returns (DeviceArray carrying
-    ``packed_mask``, number of ones).  Meant for the ONE thread that owns the global generator (see ic.bicross_validation)."""
+    ``packed_mask``, number of ones).  ``blocks_per_segment``: how the stream is cut into workgroups (dmf_mask_draw_segments) --
+    0 the plan's choice for the shape, -1 one workgroup, n >= 1 segments of n 624-word blocks; the results are the same bit for
+    bit.  Meant for the ONE thread that owns the global generator (see ic.bicross_validation)."""
     import ctypes as C
 
     from . import _lib as L
@@ -195,8 +197,9 @@ def draw_mask(shape, fraction, ctx):
     name, key, pos, has_gauss, cached = np.random.get_state()
     key = np.ascontiguousarray(key, dtype=np.uint32).copy()
     pos_io, dev, kept = C.c_int(int(pos)), C.c_void_p(), C.c_int64()
-    L.check(ctx._lib.dmf_mask_draw(ctx._h, key.ctypes.data_as(C.c_void_p), C.byref(pos_io), n, s,
-                                   mask_threshold(fraction), C.byref(dev), C.byref(kept)), "dmf_mask_draw")
+    L.check(ctx._lib.dmf_mask_draw_segments(ctx._h, key.ctypes.data_as(C.c_void_p), C.byref(pos_io), n, s,
+                                            mask_threshold(fraction), int(blocks_per_segment), C.byref(dev), C.byref(kept)),
+            "dmf_mask_draw_segments")
     out = DeviceArray(ctx, dev.value, (n, (s + 7) // 8))
     out.packed_mask = out.shape
     np.random.set_state((name, key, pos_io.value, has_gauss, cached))

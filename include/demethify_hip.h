@@ -638,13 +638,38 @@ int dmf_stage_download(dmf_context* ctx, const void* dev, size_t bytes, void* ho
  * threshold: x < fraction as an integer compare on x 2^53: 0 for fraction <= 0 or NaN, 2^53 for fraction >= 1, else
  * ceil(fraction 2^53) (the product is exact).  *out_bits: a new device buffer of N ceil(S / 8) bytes, every byte written,
  * padding bits zero -- what dmf_problem_mask takes with DMF_PTR_DEVICE -- released with dmf_stage_free; *n_kept: the number of
- * ones.  One persistent workgroup walks the stream (the recurrence allows no more without a jump-ahead).
+ * ones.  Where dmf_mask_draw_plan says one segment, one persistent workgroup walks the stream (the recurrence itself allows
+ * no more); else the stream is cut into segments, their keys come from the caller's by jump-ahead, and one workgroup per
+ * segment draws -- the same results either way.
  * Threading as dmf_stage_upload: it runs on the context's copy stream, may be called from a worker thread while the
  * context's stream iterates, and returns when the mask and the three results are complete.  DMF_ERR_BAD_ARG: a position
  * outside [0, 624], N or S below 1, a threshold above 2^53, a null pointer; DMF_ERR_UNSUPPORTED: S >= 2^31 or more than 2^60
  * elements.  After an error nothing stays allocated and key / *pos are untouched. */
 int dmf_mask_draw(dmf_context* ctx, uint32_t key[624], int* pos, int64_t N, int64_t S,
                   uint64_t threshold, void** out_bits, int64_t* n_kept);
+
+/* The segmented draw.  The stream is cut on numpy's own grid of 624-word blocks -- block 0 the caller's key, used from word
+ * *pos -- into segments of blocks_per_segment blocks.  A segment's starting key is the caller's carried forward by a
+ * polynomial: with phi the characteristic polynomial of MT19937 and g = t^J mod (t phi), word m of the key J words on is the
+ * XOR of the raw words x[i + m] over the non-zero terms i of g (modulo t phi, not phi: the low 31 bits of word 0 of an
+ * arbitrary key are output but are no part of the state, and a remainder divisible by t never reads them).  The keys are
+ * made on the device in rounds that multiply their number by 32 (two launches for 1024 segments); the polynomials are computed on the host at first
+ * use and kept per process.  Every byte of the mask is written by exactly one workgroup, the one whose segment holds the
+ * byte's first element.
+ * dmf_mask_draw_plan: what dmf_mask_draw does for a shape, a function of (N, S) alone and no GPU touched: *segments <=
+ * DMF_MASK_DRAW_MAX_SEGMENTS of *blocks_per_segment blocks, together at least the 2 N S + 624 words a draw can reach; one
+ * segment is the one-workgroup kernel.  DMF_ERR_BAD_ARG: N or S below 1, a null pointer; DMF_ERR_UNSUPPORTED as above.
+ * dmf_mask_draw_segments: dmf_mask_draw with the segment length given -- blocks_per_segment 0: the plan's choice (that is
+ * dmf_mask_draw), -1: one workgroup, >= 1: segments of that many blocks, DMF_ERR_BAD_ARG if the shape would need more than
+ * DMF_MASK_DRAW_MAX_SEGMENTS of them (or below -1).  Results, threading and errors as dmf_mask_draw.
+ * dmf_mt_jump: host only, no context.  Advances numpy's legacy state (key, *pos) exactly as consuming n_words 32-bit words
+ * would: the key comes back as of the last regeneration on numpy's grid, *pos as numpy would report it; n_words = 0 leaves
+ * both untouched.  DMF_ERR_BAD_ARG: a null pointer, *pos outside [0, 624].  Thread-safe. */
+#define DMF_MASK_DRAW_MAX_SEGMENTS 1024
+int dmf_mask_draw_plan(int64_t N, int64_t S, int64_t* segments, int64_t* blocks_per_segment);
+int dmf_mask_draw_segments(dmf_context* ctx, uint32_t key[624], int* pos, int64_t N, int64_t S, uint64_t threshold,
+                           int64_t blocks_per_segment, void** out_bits, int64_t* n_kept);
+int dmf_mt_jump(uint32_t key[624], int* pos, uint64_t n_words);
 
 #ifdef __cplusplus
 }
