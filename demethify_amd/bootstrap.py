@@ -17,6 +17,7 @@ import pandas as pd
 
 from . import _lib as L
 from . import init_func, shard
+from .batch import batch_chunk, family, mid_batch_chunk, solve_chunked  # noqa: F401  (the chunk rules are imported from here)
 from .deconvolution import (_ICA_REFUSAL, _OUT_OF_SCOPE_INITS, _init_guard, _init_unsupervised, init_BSSMF_md,
                             init_BSSMF_md_p, solve_problem, svd_factors)
 from .device import Problem, Solver, get_context
@@ -114,10 +115,7 @@ def batched_ineligible(n_u, n_rows, n_samples, n_ct, init_option, purity, mode, 
     it refuses a purity vector whatever ``purity_batched`` says unless ``mid_purity`` is set (a switch of its own, because
     the refusal without it is pinned): then ``solve_many_mid(purity=...)`` takes the vector where there is a reference to
     hold at that mass.  Touches no device."""
-    from .device import mid_solve_supported, small_solve_supported
-
-    if kernel not in ("small", "mid"):
-        raise ValueError(f'kernel must be "small" or "mid", got {kernel!r}')
+    fam = family(kernel)
     if n_u < 1:
         return "there is no unknown cell type to solve for"
     if purity is not None and np.size(purity) > 0:
@@ -137,40 +135,7 @@ def batched_ineligible(n_u, n_rows, n_samples, n_ct, init_option, purity, mode, 
     option = "uniform_" if (init_option != "uniform_" and n_u > n_samples) else init_option
     if option not in ("uniform_", "beta"):
         return f"the initialiser {init_option!r} reads the resampled data"
-    if kernel == "mid":
-        if not mid_solve_supported(n_rows, n_samples, n_ct, n_u, mode):
-            return (f"the shape {n_rows} x {n_samples} with {n_ct} + {n_u} cell types is outside the mid-size batch's envelope "
-                    f"(n_u <= {L.MID_MAX_NU}, K <= {L.MID_MAX_K}, S <= {L.MID_MAX_S}, N S <= {L.MID_MAX_ELEMENTS})")
-        return None
-    if not small_solve_supported(n_rows, n_samples, n_ct, n_u, mode):
-        return (f"the shape {n_rows} x {n_samples} with {n_ct} + {n_u} cell types is outside the batched kernel's envelope "
-                f"(n_u <= {L.SMALL_MAX_NU}, K <= {L.SMALL_MAX_K}, S <= {L.SMALL_MAX_S}, N S <= {L.SMALL_MAX_ELEMENTS})")
-    return None
-
-
-def batch_chunk(n_rows, n_u):
-    """How many solves one ``solve_many`` call of the drivers takes: enough to fill the GPU several times over, and at most
-    256 MB for the stack of profiles."""
-    return int(max(1, min(1024, (1 << 25) // max(1, n_rows * n_u))))
-
-
-def mid_batch_chunk(n_rows, n_samples, n_ct, n_u, masked=False):
-    """How many solves one ``solve_many_mid`` call of the drivers takes: as many as keep the slab workspace (W workgroups per
-    solve, each with the larger of the known and the u-dependent Gram jobs times S doubles) and the stack of profiles
-    together within 256 MB, at least 1 and at most 1024.  The purity variant (``solve_many_mid(purity=...)``) has the same
-    workspace -- it adds nothing per slab or per solve, only the S purities per call -- so the bound holds for it as it is.
-    ``masked``: a ``solve_many_mid_masked`` call, which adds a solve's train mask (N x ceil(S / 8) bytes) and its W count and
-    W hold-out partials (8 bytes each) to what the bound counts."""
-    from .device import mid_solve_plan
-
-    _, n_slabs, _ = mid_solve_plan(n_rows, n_samples)
-    K = n_ct + n_u
-    known = n_ct * (n_ct + 1) // 2 + n_ct
-    jobs = max(known, K * (K + 1) // 2 + K - known)
-    per_solve = 8 * (n_slabs * jobs * n_samples + n_rows * n_u)
-    if masked:
-        per_solve += n_rows * ((n_samples + 7) // 8) + 16 * n_slabs
-    return int(max(1, min(1024, (1 << 28) // per_solve)))
+    return fam.outside(n_rows, n_samples, n_ct, n_u, mode)
 
 
 def bt_ci(confidence_level, n_bootstrap, n_u, meth_f, counts, ref, init_option, n_iter1, n_iter2, tol, header,
@@ -213,22 +178,16 @@ def bt_ci(confidence_level, n_bootstrap, n_u, meth_f, counts, ref, init_option, 
     through ``solve_many_mid(purity=p / 100)`` in the same chunks.  Any other ``batch_kernel`` raises ValueError."""
     if profile_rows not in ("position", "cpg"):
         raise ValueError(f'profile_rows must be "position" or "cpg", got {profile_rows!r}')
-    if batch_kernel not in ("small", "mid"):
-        raise ValueError(f'batch_kernel must be "small" or "mid", got {batch_kernel!r}')
-    if batched and batch_kernel == "mid":
+    fam = family(batch_kernel, "batch_kernel")
+    if batched:
         will_align = bool(ref is None if align_unknown is None else align_unknown) and n_u >= 2
         reason = batched_ineligible(n_u, meth_f.shape[0], meth_f.shape[1], 0 if ref is None else ref.shape[1], init_option,
                                     purity, L.DMF_MODE_UNSUPERVISED if ref is None else L.DMF_MODE_PARTIAL, _observe,
-                                    will_align, profile_rows, kernel="mid", mid_purity=bool(batched_mid_purity))
+                                    will_align, profile_rows, purity_batched=bool(batched_purity), kernel=batch_kernel,
+                                    mid_purity=bool(batched_mid_purity))
         if reason is not None:
-            raise ValueError(f'bt_ci(batched=True, batch_kernel="mid"): {reason}')
-    elif batched:
-        will_align = bool(ref is None if align_unknown is None else align_unknown) and n_u >= 2
-        reason = batched_ineligible(n_u, meth_f.shape[0], meth_f.shape[1], 0 if ref is None else ref.shape[1], init_option,
-                                    purity, L.DMF_MODE_UNSUPERVISED if ref is None else L.DMF_MODE_PARTIAL, _observe,
-                                    will_align, profile_rows, purity_batched=bool(batched_purity))
-        if reason is not None:
-            raise ValueError(f"bt_ci(batched=True): {reason}")
+            prefix = "bt_ci(batched=True)" if batch_kernel == "small" else f'bt_ci(batched=True, batch_kernel="{batch_kernel}")'
+            raise ValueError(f"{prefix}: {reason}")
     by_cpg = profile_rows == "cpg"
     if ref is None:
         if n_u < 1:
@@ -285,33 +244,29 @@ def bt_ci(confidence_level, n_bootstrap, n_u, meth_f, counts, ref, init_option, 
         u_stack = None
         mine = shard.my_items(n_bootstrap, rank, world)
         shape_f = np.broadcast_to(meth_f[:1], meth_f.shape)
-        mid = batch_kernel == "mid"
-        chunk = mid_batch_chunk(n_rows, n_samples, n_ct, n_u) if mid else batch_chunk(n_rows, n_u)
-        with Problem(get_context(), meth_f, counts, ref) as full:
-            for c0 in range(0, len(mine), chunk):
-                part = mine[c0:c0 + chunk]
-                idx = np.stack([bootstrap_row_indices(seeds[i], n_rows) for i in part])
-                inits = []
-                for i in part:
-                    if ref is None:
-                        inits.append(_init_unsupervised(init_option, shape_f, n_u, seeds[i]))
-                    elif purity_frac is not None:
-                        u0, _, a0 = init_BSSMF_md_p(init_option, shape_f, np.broadcast_to(counts[:1], counts.shape),
-                                                    np.broadcast_to(ref[:1], ref.shape), n_u, purity_frac, seed=seeds[i],
-                                                    rb_alg=wls_intercept, _stack=False)
-                        inits.append((u0, a0))
-                    else:
-                        u0, _, a0 = init_BSSMF_md(init_option, shape_f, np.broadcast_to(counts[:1], counts.shape),
-                                                  np.broadcast_to(ref[:1], ref.shape), n_u, rb_alg=wls_intercept, seed=seeds[i],
-                                                  _stack=False)
-                        inits.append((u0, a0))
-                if mid:
-                    us, alphas, _, _ = full.solve_many_mid(np.stack([u0 for u0, _ in inits]), np.stack([a0 for _, a0 in inits]),
-                                                           mode, n_iter1, n_iter2, tol, idx=idx, purity=purity_frac)
+
+        def stack(part):
+            idx = np.stack([bootstrap_row_indices(seeds[i], n_rows) for i in part])
+            inits = []
+            for i in part:
+                if ref is None:
+                    inits.append(_init_unsupervised(init_option, shape_f, n_u, seeds[i]))
+                elif purity_frac is not None:
+                    u0, _, a0 = init_BSSMF_md_p(init_option, shape_f, np.broadcast_to(counts[:1], counts.shape),
+                                                np.broadcast_to(ref[:1], ref.shape), n_u, purity_frac, seed=seeds[i],
+                                                rb_alg=wls_intercept, _stack=False)
+                    inits.append((u0, a0))
                 else:
-                    us, alphas, _, _ = full.solve_many(np.stack([u0 for u0, _ in inits]), np.stack([a0 for _, a0 in inits]),
-                                                       mode, n_iter1, n_iter2, tol, idx=idx, purity=purity_frac)
-                local.extend((i, (us[j], alphas[j])) for j, i in enumerate(part))
+                    u0, _, a0 = init_BSSMF_md(init_option, shape_f, np.broadcast_to(counts[:1], counts.shape),
+                                              np.broadcast_to(ref[:1], ref.shape), n_u, rb_alg=wls_intercept, seed=seeds[i],
+                                              _stack=False)
+                    inits.append((u0, a0))
+            return np.stack([u0 for u0, _ in inits]), np.stack([a0 for _, a0 in inits]), idx
+
+        with Problem(get_context(), meth_f, counts, ref) as full:
+            solved = solve_chunked(full, fam, (n_rows, n_samples, n_ct, n_u), mine, stack, (mode, n_iter1, n_iter2, tol),
+                                   purity=purity_frac)
+        local.extend((i, (solved[0][j], solved[1][j])) for j, i in enumerate(mine))
     else:
         # The host work of the replicates ahead (MT19937 index draw of N rows; uniform N x n_u + Dirichlet init: ~10 + ~13 ms
         # at 1e6 rows) runs on worker threads while the GPU gathers and solves replicate i.  The row draw has its own

@@ -50,6 +50,7 @@ import os
 import sys
 import warnings
 from time import time
+from typing import NamedTuple
 
 import numpy as np
 import pandas as pd
@@ -64,6 +65,36 @@ logo = r"""
 /_____/\___/_/ /_/ /_/\___/\__/_/ /_/_/_/  \__, /
                                           /____/    (MI355X build)
 """
+
+
+class BatchSwitch(NamedTuple):
+    """One DEMETHIFY_BATCH* switch (the module docstring says what each is for), as ``main``'s ``batch_route`` reads it."""
+    switch: str
+    family: str  # batch.family: "small", one workgroup per solve, or "mid", several
+    applies: str  # "solves" (--restart restarts and --confidence replicates) or "--ic"
+    module: str  # where the gate constants live: they are read through the module at every call
+    gate: tuple  # (MIN name, or None for a one-sided gate, MAX name): the sizes N x S at which the route was measured faster
+    # "solves" and --purity: "own gate" (eligible, inside ``purity_gate``), "refused" (with batched_ineligible's sentence, and
+    # silently where an "only" switch is on as well: that one speaks for a purity run) or "only" (silent without --purity)
+    purity: str = None
+    purity_gate: tuple = None
+    purity_keyword: str = None  # the bt_ci keyword a purity run sets next to batched= and batch_kernel=
+    criteria: str = None  # "--ic": the name of the tuple of criteria the route is taken for
+
+
+# in the order of asking: per ``applies`` the first switch that is on and accepts takes the run, each refusal prints its note
+BATCH_SWITCHES = (
+    BatchSwitch("DEMETHIFY_BATCH", "small", "solves", "bootstrap", (None, "SMALL_BATCH_MAX_ELEMENTS"), purity="own gate",
+                purity_gate=(None, "SMALL_BATCH_PURITY_MAX_ELEMENTS"), purity_keyword="batched_purity"),
+    BatchSwitch("DEMETHIFY_BATCH_MID", "mid", "solves", "bootstrap", ("MID_BATCH_MIN_ELEMENTS", "MID_BATCH_MAX_ELEMENTS"),
+                purity="refused"),
+    BatchSwitch("DEMETHIFY_BATCH_MID_PURITY", "mid", "solves", "bootstrap",
+                ("MID_BATCH_PURITY_MIN_ELEMENTS", "MID_BATCH_PURITY_MAX_ELEMENTS"), purity="only",
+                purity_keyword="batched_mid_purity"),
+    BatchSwitch("DEMETHIFY_BATCH", "small", "--ic", "ic", (None, "SMALL_BATCH_IC_MAX_ELEMENTS"), criteria="SMALL_BATCH_IC_CRITERIA"),
+    BatchSwitch("DEMETHIFY_BATCH_MID_IC", "mid", "--ic", "ic", ("MID_BATCH_IC_MIN_ELEMENTS", "MID_BATCH_IC_MAX_ELEMENTS"),
+                criteria="MID_BATCH_IC_CRITERIA"),
+)
 
 
 def build_parser():
@@ -173,29 +204,13 @@ def main(argv=None):
     if ci_rows not in ("position", "cpg"):
         sys.stderr.write(f'Error: DEMETHIFY_CI_ROWS must be "position" or "cpg", got "{ci_rows}".\n')
         sys.exit(1)
-    # DEMETHIFY_BATCH=1: bootstrap replicates and restarts of small problems through Problem.solve_many, where eligible
-    batch_env = os.environ.get("DEMETHIFY_BATCH", "0")
-    if batch_env not in ("0", "1"):
-        sys.stderr.write(f'Error: DEMETHIFY_BATCH must be "0" or "1", got "{batch_env}".\n')
-        sys.exit(1)
-    # DEMETHIFY_BATCH_MID=1: where DEMETHIFY_BATCH's own route is not taken, replicates and restarts of mid-size problems go
-    # through Problem.solve_many_mid (several workgroups per solve), where eligible
-    batch_mid_env = os.environ.get("DEMETHIFY_BATCH_MID", "0")
-    if batch_mid_env not in ("0", "1"):
-        sys.stderr.write(f'Error: DEMETHIFY_BATCH_MID must be "0" or "1", got "{batch_mid_env}".\n')
-        sys.exit(1)
-    # DEMETHIFY_BATCH_MID_PURITY=1: where neither route above is taken, --purity replicates and restarts of mid-size problems go
-    # through Problem.solve_many_mid(purity=...), where eligible and inside a gate of its own
-    batch_mid_purity_env = os.environ.get("DEMETHIFY_BATCH_MID_PURITY", "0")
-    if batch_mid_purity_env not in ("0", "1"):
-        sys.stderr.write(f'Error: DEMETHIFY_BATCH_MID_PURITY must be "0" or "1", got "{batch_mid_purity_env}".\n')
-        sys.exit(1)
-    # DEMETHIFY_BATCH_MID_IC=1: where DEMETHIFY_BATCH's own --ic route is not taken, an --ic sweep of a mid-size problem goes
-    # through evaluate_best_ic(batched=True, batch_kernel="mid"), for the measured criteria and inside a gate of its own
-    batch_mid_ic_env = os.environ.get("DEMETHIFY_BATCH_MID_IC", "0")
-    if batch_mid_ic_env not in ("0", "1"):
-        sys.stderr.write(f'Error: DEMETHIFY_BATCH_MID_IC must be "0" or "1", got "{batch_mid_ic_env}".\n')
-        sys.exit(1)
+    switched_on = {}  # the DEMETHIFY_BATCH* switches of BATCH_SWITCHES
+    for switch in dict.fromkeys(row.switch for row in BATCH_SWITCHES):
+        value = os.environ.get(switch, "0")
+        if value not in ("0", "1"):
+            sys.stderr.write(f'Error: {switch} must be "0" or "1", got "{value}".\n')
+            sys.exit(1)
+        switched_on[switch] = value == "1"
     if args.plot:
         sys.stderr.write("Note: --plot is ignored, plotting (seaborn/colorcet) is outside this build's scope.\n")
 
@@ -219,7 +234,9 @@ def main(argv=None):
     # imported late so that ``--help`` and argument errors work on a box without the GPU library
     from . import _lib as L
     from . import shard, staging
+    from . import batch
     from . import bootstrap as bootstrap_mod
+    from . import ic as ic_mod
     from .bootstrap import bt_ci
     from . import init_func
     from .deconvolution import _init_guard, _init_unsupervised, init_BSSMF_md, init_BSSMF_md_p, rd, set_seed
@@ -228,125 +245,67 @@ def main(argv=None):
     from .init_func import wls_intercept
 
     time_start = time()
+    gate_modules = {"bootstrap": bootstrap_mod, "ic": ic_mod}
     n_u = args.nbunknown[0]
     ic_n_u = None
 
-    def batch_route(what, align=False, profile_rows="position"):
-        """DEMETHIFY_BATCH=1: does `what` go through Problem.solve_many?  A one-line note says why not."""
-        if batch_env != "1":
-            return False
+    def batch_route(applies, what, align=False, profile_rows="position"):
+        """The first row of BATCH_SWITCHES for `applies` whose switch is on and which takes `what`, or None for the per-solve
+        path; every switch that is on and refuses says why in a one-line note."""
         n_rows, n_samples = meth_f.shape
-        reason = bootstrap_mod.batched_ineligible(
-            n_u, n_rows, n_samples, ref.shape[1] if args.ref else 0, args.init, args.purity,
-            L.DMF_MODE_PARTIAL if args.ref else L.DMF_MODE_UNSUPERVISED, None, align, profile_rows, purity_batched=True)
-        # (--purity has a gate of its own: its batched kernel was measured on its own)
-        gate_name = "SMALL_BATCH_PURITY_MAX_ELEMENTS" if args.purity else "SMALL_BATCH_MAX_ELEMENTS"
-        gate = getattr(bootstrap_mod, gate_name)
-        if reason is None and n_rows * n_samples > gate:
-            reason = f"{n_rows} x {n_samples} elements are more than {gate_name} = {gate}"
-        if reason is not None and rank == 0:
-            print(f"Note: DEMETHIFY_BATCH=1 is not used for {what}: {reason}; taking the per-solve path.")
-        return reason is None
+        rows = [row for row in BATCH_SWITCHES if row.applies == applies and switched_on[row.switch]]
+        for row in rows:
+            if args.purity and row.purity == "refused" and any(other.purity == "only" for other in rows):
+                continue
+            if not args.purity and row.purity == "only":
+                continue
+            module = gate_modules[row.module]
+            if row.criteria is not None:
+                reason = None
+                if args.ic not in getattr(module, row.criteria):
+                    reason = f"{args.ic} was not measured faster through {batch.family(row.family).called} (ic.{row.criteria})"
+            else:
+                reason = bootstrap_mod.batched_ineligible(
+                    n_u, n_rows, n_samples, ref.shape[1] if args.ref else 0, args.init, args.purity,
+                    L.DMF_MODE_PARTIAL if args.ref else L.DMF_MODE_UNSUPERVISED, None, align, profile_rows,
+                    purity_batched=row.purity == "own gate", kernel=row.family, mid_purity=row.purity == "only")
+            if reason is None:
+                lo_name, hi_name = row.purity_gate if args.purity and row.purity_gate else row.gate
+                lo, hi = None if lo_name is None else getattr(module, lo_name), getattr(module, hi_name)
+                if lo is None and n_rows * n_samples > hi:
+                    reason = f"{n_rows} x {n_samples} elements are more than {hi_name} = {hi}"
+                elif lo is not None and not lo <= n_rows * n_samples <= hi:
+                    reason = (f"{n_rows} x {n_samples} elements are outside [{lo_name}, {hi_name}] = [{lo}, {hi}]"
+                              + (" (the gate is closed)" if lo > hi else ""))
+            if reason is None:
+                return row
+            if rank == 0:
+                print(f"Note: {row.switch}=1 is not used for {what}: {reason}; taking the per-solve path.")
+        return None
 
-    def batch_mid_route(what, align=False, profile_rows="position"):
-        """DEMETHIFY_BATCH_MID=1, asked after DEMETHIFY_BATCH's own route was not taken: does `what` go through
-        Problem.solve_many_mid?  A one-line note says why not."""
-        if batch_mid_env != "1" or (args.purity and batch_mid_purity_env == "1"):  # (the purity route speaks for itself)
-            return False
-        n_rows, n_samples = meth_f.shape
-        reason = bootstrap_mod.batched_ineligible(
-            n_u, n_rows, n_samples, ref.shape[1] if args.ref else 0, args.init, args.purity,
-            L.DMF_MODE_PARTIAL if args.ref else L.DMF_MODE_UNSUPERVISED, None, align, profile_rows, kernel="mid")
-        lo, hi = bootstrap_mod.MID_BATCH_MIN_ELEMENTS, bootstrap_mod.MID_BATCH_MAX_ELEMENTS
-        if reason is None and not lo <= n_rows * n_samples <= hi:
-            reason = (f"{n_rows} x {n_samples} elements are outside [MID_BATCH_MIN_ELEMENTS, MID_BATCH_MAX_ELEMENTS] = "
-                      f"[{lo}, {hi}]" + (" (the gate is closed)" if lo > hi else ""))
-        if reason is not None and rank == 0:
-            print(f"Note: DEMETHIFY_BATCH_MID=1 is not used for {what}: {reason}; taking the per-solve path.")
-        return reason is None
-
-    def batch_mid_purity_route(what, align=False, profile_rows="position"):
-        """DEMETHIFY_BATCH_MID_PURITY=1, asked last and for --purity runs only: does `what` go through
-        Problem.solve_many_mid(purity=...)?  A one-line note says why not."""
-        if batch_mid_purity_env != "1" or not args.purity:
-            return False
-        n_rows, n_samples = meth_f.shape
-        reason = bootstrap_mod.batched_ineligible(
-            n_u, n_rows, n_samples, ref.shape[1] if args.ref else 0, args.init, args.purity,
-            L.DMF_MODE_PARTIAL if args.ref else L.DMF_MODE_UNSUPERVISED, None, align, profile_rows, kernel="mid", mid_purity=True)
-        lo, hi = bootstrap_mod.MID_BATCH_PURITY_MIN_ELEMENTS, bootstrap_mod.MID_BATCH_PURITY_MAX_ELEMENTS
-        if reason is None and not lo <= n_rows * n_samples <= hi:
-            reason = (f"{n_rows} x {n_samples} elements are outside [MID_BATCH_PURITY_MIN_ELEMENTS, "
-                      f"MID_BATCH_PURITY_MAX_ELEMENTS] = [{lo}, {hi}]" + (" (the gate is closed)" if lo > hi else ""))
-        if reason is not None and rank == 0:
-            print(f"Note: DEMETHIFY_BATCH_MID_PURITY=1 is not used for {what}: {reason}; taking the per-solve path.")
-        return reason is None
+    def batch_keywords(row):
+        """What the route `row` adds to a bt_ci or evaluate_best_ic call: a keyword is passed only when its route is taken,
+        so without the switches the call is what it was."""
+        if row is None:
+            return {}
+        kw = {"batched": True} if row.family == "small" else {"batched": True, "batch_kernel": row.family}
+        if row.purity_keyword and args.purity:
+            kw[row.purity_keyword] = True
+        return kw
 
     def bootstrap(anchor=None):
-        align = not args.ref and n_u >= 2
-        batched = batch_route("--confidence", align=align, profile_rows=ci_rows)
-        if not batched and batch_mid_route("--confidence", align=align, profile_rows=ci_rows):
-            bt_ci(args.confidence[0], args.confidence[1], n_u, meth_f, counts, ref, args.init, args.iterations[0],
-                  args.iterations[1], args.termination, header if args.ref else [], outdir, args.methfreq, args.purity,
-                  args.seed, materialize=False, anchor=anchor, profile_rows=ci_rows, batched=True, batch_kernel="mid")
-            return
-        if not batched and batch_mid_purity_route("--confidence", align=align, profile_rows=ci_rows):
-            bt_ci(args.confidence[0], args.confidence[1], n_u, meth_f, counts, ref, args.init, args.iterations[0],
-                  args.iterations[1], args.termination, header if args.ref else [], outdir, args.methfreq, args.purity,
-                  args.seed, materialize=False, anchor=anchor, profile_rows=ci_rows, batched=True, batch_kernel="mid",
-                  batched_mid_purity=True)
-            return
+        row = batch_route("solves", "--confidence", align=not args.ref and n_u >= 2, profile_rows=ci_rows)
         bt_ci(args.confidence[0], args.confidence[1], n_u, meth_f, counts, ref, args.init, args.iterations[0],
               args.iterations[1], args.termination, header if args.ref else [], outdir, args.methfreq, args.purity,
-              args.seed, materialize=False, anchor=anchor, profile_rows=ci_rows, batched=batched,
-              batched_purity=batched and bool(args.purity))
+              args.seed, materialize=False, anchor=anchor, profile_rows=ci_rows, **batch_keywords(row))
 
     if args.confidence and args.ref:
         bootstrap()
     elif args.confidence and n_u < 1:
         sys.exit(f'Invalid number of unknown value! : "{args.nbunknown}" ')
 
-    def ic_batch_route():
-        """DEMETHIFY_BATCH=1 with --ic: does the sweep go through evaluate_best_ic(batched=True)?  Candidates outside the
-        kernel's envelope take the per-solve path inside it; the size gate is the measured one of ic.py."""
-        if batch_env != "1":
-            return False
-        from . import ic as ic_mod
-
-        reason = None
-        if args.ic not in ic_mod.SMALL_BATCH_IC_CRITERIA:
-            reason = f"{args.ic} was not measured faster through the batch (ic.SMALL_BATCH_IC_CRITERIA)"
-        elif meth_f.size > ic_mod.SMALL_BATCH_IC_MAX_ELEMENTS:
-            reason = (f"{meth_f.shape[0]} x {meth_f.shape[1]} elements are more than SMALL_BATCH_IC_MAX_ELEMENTS = "
-                      f"{ic_mod.SMALL_BATCH_IC_MAX_ELEMENTS}")
-        if reason is not None and rank == 0:
-            print(f"Note: DEMETHIFY_BATCH=1 is not used for --ic: {reason}; taking the per-solve path.")
-        return reason is None
-
-    def ic_batch_mid_route():
-        """DEMETHIFY_BATCH_MID_IC=1 with --ic, asked after DEMETHIFY_BATCH's own --ic route was not taken: does the sweep go
-        through evaluate_best_ic(batched=True, batch_kernel="mid")?  Candidates outside the mid-size batch's envelope take
-        the per-solve path inside it; the criteria and the size range are the measured ones of ic.py."""
-        if batch_mid_ic_env != "1":
-            return False
-        from . import ic as ic_mod
-
-        reason = None
-        lo, hi = ic_mod.MID_BATCH_IC_MIN_ELEMENTS, ic_mod.MID_BATCH_IC_MAX_ELEMENTS
-        if args.ic not in ic_mod.MID_BATCH_IC_CRITERIA:
-            reason = f"{args.ic} was not measured faster through the mid-size batch (ic.MID_BATCH_IC_CRITERIA)"
-        elif not lo <= meth_f.size <= hi:
-            reason = (f"{meth_f.shape[0]} x {meth_f.shape[1]} elements are outside [MID_BATCH_IC_MIN_ELEMENTS, "
-                      f"MID_BATCH_IC_MAX_ELEMENTS] = [{lo}, {hi}]" + (" (the gate is closed)" if lo > hi else ""))
-        if reason is not None and rank == 0:
-            print(f"Note: DEMETHIFY_BATCH_MID_IC=1 is not used for --ic: {reason}; taking the per-solve path.")
-        return reason is None
-
     if args.ic:
-        # (a keyword is passed only when its route is taken: without the switches the call is what it was)
-        ic_kw = {"batched": True} if ic_batch_route() else {}
-        if not ic_kw and ic_batch_mid_route():
-            ic_kw = {"batched": True, "batch_kernel": "mid"}
+        ic_kw = batch_keywords(batch_route("--ic", "--ic"))
         ref_estimate, proportions, ic_n_u, _scores = evaluate_best_ic(
             meth_f, ref, counts, args.init, args.ic, args.seed, iter1=args.iterations[0], iter2=args.iterations[1],
             tol=args.termination, n_restarts=nb_r, n_u_values=ic_range, **ic_kw)
@@ -359,11 +318,9 @@ def main(argv=None):
         K = (0 if unsupervised else ref.shape[1]) + n_u
         if args.restart > 1 and rank == 0:
             print(f"restart k > 0 uses seed + k (upstream repeats the same seed); {args.restart} restarts")
-        batch_restarts = args.restart > 1 and batch_route("--restart")
-        mid_restarts = args.restart > 1 and not batch_restarts and (batch_mid_route("--restart")
-                                                                    or batch_mid_purity_route("--restart"))
+        restarts_row = batch_route("solves", "--restart") if args.restart > 1 else None
         with Problem(get_context(), meth_f, counts, None if unsupervised else ref) as problem:
-            if args.restart > 1 and not batch_restarts and not mid_restarts:
+            if args.restart > 1 and restarts_row is None:
                 staging.reserve(((meth_f.shape[0], n_u), (K, meth_f.shape[1])), count=2)
 
             # --init uniform on a large problem: u0 is drawn on the host as init_BSSMF_md / init_BSSMF_md_p draw it (set_seed,
@@ -371,6 +328,16 @@ def main(argv=None):
             # already is (solve_one: the context is not to be used from the worker thread)
             device_init = (not unsupervised and args.init == "uniform" and n_u <= meth_f.shape[1]
                            and init_func.device_wls(meth_f.shape[0], meth_f.shape[1], K))
+
+            def draw_init(seed_k):
+                if unsupervised:
+                    return _init_unsupervised(args.init, meth_f, n_u, seed_k)
+                if purity is not None:
+                    u0, _, a0 = init_BSSMF_md_p(args.init, meth_f, counts, ref, n_u, purity, rb_alg=wls_intercept,
+                                                seed=seed_k, _stack=False)
+                else:
+                    u0, _, a0 = init_BSSMF_md(args.init, meth_f, counts, ref, n_u, rb_alg=wls_intercept, seed=seed_k, _stack=False)
+                return u0, a0
 
             def prepare(k):
                 # the restart's initialisation (legacy-numpy draws, NNLS), drawn and uploaded one restart ahead of the
@@ -380,13 +347,7 @@ def main(argv=None):
                     set_seed(seed_k)
                     u0 = rd.uniform(size=(meth_f.shape[0], n_u))
                     return staging.to_device((u0,), problem.ctx)[0], u0
-                if unsupervised:
-                    u0, a0 = _init_unsupervised(args.init, meth_f, n_u, seed_k)
-                elif purity is not None:
-                    u0, _, a0 = init_BSSMF_md_p(args.init, meth_f, counts, ref, n_u, purity, rb_alg=wls_intercept,
-                                                seed=seed_k, _stack=False)
-                else:
-                    u0, _, a0 = init_BSSMF_md(args.init, meth_f, counts, ref, n_u, rb_alg=wls_intercept, seed=seed_k, _stack=False)
+                u0, a0 = draw_init(seed_k)
                 if args.restart > 1:
                     return staging.to_device((u0, a0), problem.ctx)
                 return u0, a0
@@ -419,47 +380,21 @@ def main(argv=None):
                     u, alpha, _, _ = s.get()
                 return u, alpha, cost
 
-            def solve_batch(ks, mid=False):
-                # this rank's restarts, one workgroup each (mid: several each, Problem.solve_many_mid): the initialisers are
-                # drawn one after the other, as prepare draws them
+            def solve_batch(ks):
+                # this rank's restarts through the batch of the route taken: the initialisers are drawn one after the other,
+                # as prepare draws them
+                def stack(part):
+                    inits = [draw_init(shard.restart_seed(args.seed, k)) for k in part]
+                    return np.stack([u0 for u0, _ in inits]), np.stack([a0 for _, a0 in inits]), None
+
                 mode = L.DMF_MODE_UNSUPERVISED if unsupervised else L.DMF_MODE_PARTIAL
-                if mid:
-                    chunk = bootstrap_mod.mid_batch_chunk(meth_f.shape[0], meth_f.shape[1], K - n_u, n_u)
-                else:
-                    chunk = bootstrap_mod.batch_chunk(meth_f.shape[0], n_u)
-                parts = []
-                for c0 in range(0, len(ks), chunk):
-                    inits = []
-                    for k in ks[c0:c0 + chunk]:
-                        seed_k = shard.restart_seed(args.seed, k)
-                        if unsupervised:
-                            inits.append(_init_unsupervised(args.init, meth_f, n_u, seed_k))
-                        elif purity is not None:
-                            u0, _, a0 = init_BSSMF_md_p(args.init, meth_f, counts, ref, n_u, purity, rb_alg=wls_intercept,
-                                                        seed=seed_k, _stack=False)
-                            inits.append((u0, a0))
-                        else:
-                            u0, _, a0 = init_BSSMF_md(args.init, meth_f, counts, ref, n_u, rb_alg=wls_intercept, seed=seed_k,
-                                                      _stack=False)
-                            inits.append((u0, a0))
-                    if mid:
-                        # (a purity vector is passed only on the purity route: without it the call is what it was)
-                        purity_kw = {} if unsupervised or purity is None else {"purity": purity}
-                        parts.append(problem.solve_many_mid(np.stack([u0 for u0, _ in inits]), np.stack([a0 for _, a0 in inits]),
-                                                            mode, args.iterations[0], args.iterations[1], args.termination,
-                                                            **purity_kw)[:3])
-                        continue
-                    parts.append(problem.solve_many(np.stack([u0 for u0, _ in inits]), np.stack([a0 for _, a0 in inits]), mode,
-                                                    args.iterations[0], args.iterations[1], args.termination,
-                                                    purity=None if unsupervised else purity)[:3])
-                return tuple(np.concatenate([part[j] for part in parts]) for j in range(3))
+                return batch.solve_chunked(problem, batch.family(restarts_row.family), (*meth_f.shape, K - n_u, n_u), ks, stack,
+                                           (mode, args.iterations[0], args.iterations[1], args.termination),
+                                           purity=None if unsupervised else purity)[:3]
 
             shapes = ((meth_f.shape[0], n_u), (K, meth_f.shape[1]))
-            if batch_restarts:
+            if restarts_row is not None:
                 ref_estimate, proportions, _best, _costs = shard.sharded_restarts_batched(args.restart, solve_batch, shapes)
-            elif mid_restarts:
-                ref_estimate, proportions, _best, _costs = shard.sharded_restarts_batched(
-                    args.restart, lambda ks: solve_batch(ks, mid=True), shapes)
             else:
                 ref_estimate, proportions, _best, _costs = shard.sharded_restarts(
                     args.restart, solve_one, shapes, prepare=prepare, solve_end=solve_end)

@@ -679,6 +679,50 @@ class Problem:
             t_dev.close()
         return u0
 
+    # the C entry points of the batch families: (plain, purity, masked)
+    _BATCH_ENTRIES = {"small": ("dmf_solve_small", "dmf_solve_small_purity", "dmf_solve_small_masked"),
+                      "mid": ("dmf_solve_mid", "dmf_solve_mid_purity", "dmf_solve_mid_masked")}
+
+    def _solve_batch(self, family, u0s, alpha0s, mode, n_iter1, n_iter2, tol, tuning, idx=None, purity=None, train_masks=None):
+        """The one body of ``solve_many``, ``solve_many_mid`` and their masked siblings: the checks (every ValueError before
+        the library is touched), the output arrays, and the family's entry point for the variant -- masked where
+        ``train_masks`` is given (``idx`` and ``purity`` are then not looked at), else purity where ``purity`` is.  ``tuning``:
+        the family's integers between ``tol`` and the stream in the C argument list."""
+        u0s = np.ascontiguousarray(u0s, dtype=np.float64)
+        alpha0s = np.ascontiguousarray(alpha0s, dtype=np.float64)
+        if u0s.ndim != 3 or u0s.shape[1] != self.N:
+            raise ValueError(f"u0s is B x {self.N} x n_u, got shape {u0s.shape}")
+        B, _, n_u = u0s.shape
+        K = self.n_c + n_u
+        if alpha0s.shape != (B, K, self.S):
+            raise ValueError(f"alpha0s shape {alpha0s.shape} != {(B, K, self.S)}")
+        plain, with_purity, masked = self._BATCH_ENTRIES[family]
+        if train_masks is not None:
+            name, per_solve, shared = masked, self._packed_train_masks(train_masks, B), ()
+        else:
+            if idx is not None:
+                idx = np.ascontiguousarray(idx, dtype=np.int64)
+                if idx.shape != (B, self.N):
+                    raise ValueError(f"idx shape {idx.shape} != {(B, self.N)}")
+            name, per_solve, shared = plain, idx, ()
+            if purity is not None:
+                purity = np.ascontiguousarray(purity, dtype=np.float64)
+                if purity.shape != (self.S,):
+                    raise ValueError(f"purity needs one value per sample ({self.S}), got shape {purity.shape}")
+                if int(mode) != L.DMF_MODE_PARTIAL:
+                    raise ValueError("a purity constraint needs the partial-reference mode (DMF_MODE_PARTIAL)")
+                if self.n_c < 1:
+                    raise ValueError("a purity constraint needs a reference: there is no known block to hold at that mass")
+                name, shared = with_purity, (_ptr(purity),)
+        out = [np.empty((B, self.N, n_u), dtype=np.float64), np.empty((B, K, self.S), dtype=np.float64),
+               np.empty(B, dtype=np.float64), np.empty(B, dtype=np.int64)]  # u, alpha, cost, iters
+        if train_masks is not None:
+            out += [np.empty(B, dtype=np.float64), np.empty(B, dtype=np.int64)]  # holdout_sum_sq, n_test
+        entry = getattr(self._lib, name)
+        L.check(entry(self.ctx._h, self._h, B, _ptr(per_solve), _ptr(u0s), _ptr(alpha0s), *shared, n_u, int(mode), int(n_iter1),
+                      int(n_iter2), float(tol), *(int(t) for t in tuning), 0, *(_ptr(o) for o in out)), name)
+        return tuple(out)
+
     def solve_many(self, u0s, alpha0s, mode, n_iter1, n_iter2, tol, idx=None, iters_per_launch=0, purity=None):
         """B independent solves of this problem in one call, one workgroup per solve (dmf_solve_small) ->
         (u[B, N, n_u], alpha[B, K, S], cost[B], iters[B]).  ``u0s`` (B, N, n_u) and ``alpha0s`` (B, K, S): the starting
@@ -692,40 +736,7 @@ class Problem:
         (dmf_solve_small_purity, ``mdwbssmf_deconv_p``) -- every sample's known block keeps mass ``purity[s]`` and its unknown
         block ``1 - purity[s]``, the alpha phase is Frank-Wolfe.  Partial mode on a problem with a reference only, and a
         vector of S values: anything else raises ValueError before any device call."""
-        u0s = np.ascontiguousarray(u0s, dtype=np.float64)
-        alpha0s = np.ascontiguousarray(alpha0s, dtype=np.float64)
-        if u0s.ndim != 3 or u0s.shape[1] != self.N:
-            raise ValueError(f"u0s is B x {self.N} x n_u, got shape {u0s.shape}")
-        B, _, n_u = u0s.shape
-        K = self.n_c + n_u
-        if alpha0s.shape != (B, K, self.S):
-            raise ValueError(f"alpha0s shape {alpha0s.shape} != {(B, K, self.S)}")
-        if idx is not None:
-            idx = np.ascontiguousarray(idx, dtype=np.int64)
-            if idx.shape != (B, self.N):
-                raise ValueError(f"idx shape {idx.shape} != {(B, self.N)}")
-        if purity is not None:
-            purity = np.ascontiguousarray(purity, dtype=np.float64)
-            if purity.shape != (self.S,):
-                raise ValueError(f"purity needs one value per sample ({self.S}), got shape {purity.shape}")
-            if int(mode) != L.DMF_MODE_PARTIAL:
-                raise ValueError("a purity constraint needs the partial-reference mode (DMF_MODE_PARTIAL)")
-            if self.n_c < 1:
-                raise ValueError("a purity constraint needs a reference: there is no known block to hold at that mass")
-        u = np.empty((B, self.N, n_u), dtype=np.float64)
-        alpha = np.empty((B, K, self.S), dtype=np.float64)
-        cost = np.empty(B, dtype=np.float64)
-        iters = np.empty(B, dtype=np.int64)
-        if purity is not None:
-            L.check(self._lib.dmf_solve_small_purity(self.ctx._h, self._h, B, _ptr(idx), _ptr(u0s), _ptr(alpha0s), _ptr(purity),
-                                                     n_u, int(mode), int(n_iter1), int(n_iter2), float(tol),
-                                                     int(iters_per_launch), 0, _ptr(u), _ptr(alpha), _ptr(cost), _ptr(iters)),
-                    "dmf_solve_small_purity")
-            return u, alpha, cost, iters
-        L.check(self._lib.dmf_solve_small(self.ctx._h, self._h, B, _ptr(idx), _ptr(u0s), _ptr(alpha0s), n_u, int(mode),
-                                          int(n_iter1), int(n_iter2), float(tol), int(iters_per_launch), 0, _ptr(u),
-                                          _ptr(alpha), _ptr(cost), _ptr(iters)), "dmf_solve_small")
-        return u, alpha, cost, iters
+        return self._solve_batch("small", u0s, alpha0s, mode, n_iter1, n_iter2, tol, (iters_per_launch,), idx=idx, purity=purity)
 
     def solve_many_mid(self, u0s, alpha0s, mode, n_iter1, n_iter2, tol, idx=None, rows_per_workgroup=0, check_every=0,
                        purity=None):
@@ -740,40 +751,8 @@ class Problem:
         ``purity`` (S fractions, shared by the B solves; None = no constraint, the call as it is without the keyword): the
         purity-constrained solve (dmf_solve_mid_purity, ``mdwbssmf_deconv_p``), checked as ``solve_many`` checks it -- a vector
         of S values, partial mode, a problem with a reference, anything else raises ValueError before any device call."""
-        u0s = np.ascontiguousarray(u0s, dtype=np.float64)
-        alpha0s = np.ascontiguousarray(alpha0s, dtype=np.float64)
-        if u0s.ndim != 3 or u0s.shape[1] != self.N:
-            raise ValueError(f"u0s is B x {self.N} x n_u, got shape {u0s.shape}")
-        B, _, n_u = u0s.shape
-        K = self.n_c + n_u
-        if alpha0s.shape != (B, K, self.S):
-            raise ValueError(f"alpha0s shape {alpha0s.shape} != {(B, K, self.S)}")
-        if idx is not None:
-            idx = np.ascontiguousarray(idx, dtype=np.int64)
-            if idx.shape != (B, self.N):
-                raise ValueError(f"idx shape {idx.shape} != {(B, self.N)}")
-        if purity is not None:
-            purity = np.ascontiguousarray(purity, dtype=np.float64)
-            if purity.shape != (self.S,):
-                raise ValueError(f"purity needs one value per sample ({self.S}), got shape {purity.shape}")
-            if int(mode) != L.DMF_MODE_PARTIAL:
-                raise ValueError("a purity constraint needs the partial-reference mode (DMF_MODE_PARTIAL)")
-            if self.n_c < 1:
-                raise ValueError("a purity constraint needs a reference: there is no known block to hold at that mass")
-        u = np.empty((B, self.N, n_u), dtype=np.float64)
-        alpha = np.empty((B, K, self.S), dtype=np.float64)
-        cost = np.empty(B, dtype=np.float64)
-        iters = np.empty(B, dtype=np.int64)
-        if purity is not None:
-            L.check(self._lib.dmf_solve_mid_purity(self.ctx._h, self._h, B, _ptr(idx), _ptr(u0s), _ptr(alpha0s), _ptr(purity), n_u,
-                                                   int(mode), int(n_iter1), int(n_iter2), float(tol), int(rows_per_workgroup),
-                                                   int(check_every), 0, _ptr(u), _ptr(alpha), _ptr(cost), _ptr(iters)),
-                    "dmf_solve_mid_purity")
-            return u, alpha, cost, iters
-        L.check(self._lib.dmf_solve_mid(self.ctx._h, self._h, B, _ptr(idx), _ptr(u0s), _ptr(alpha0s), n_u, int(mode),
-                                        int(n_iter1), int(n_iter2), float(tol), int(rows_per_workgroup), int(check_every), 0,
-                                        _ptr(u), _ptr(alpha), _ptr(cost), _ptr(iters)), "dmf_solve_mid")
-        return u, alpha, cost, iters
+        return self._solve_batch("mid", u0s, alpha0s, mode, n_iter1, n_iter2, tol, (rows_per_workgroup, check_every), idx=idx,
+                                 purity=purity)
 
     def solve_many_masked(self, u0s, alpha0s, train_masks, mode, n_iter1, n_iter2, tol, iters_per_launch=0):
         """B independent solves of this problem, each on its own hold-out mask, in one call (dmf_solve_small_masked: the
@@ -784,26 +763,7 @@ class Problem:
         iterate on the held-out elements of the full data and ``n_test[b]`` their number (the fold's error is their
         quotient).  Everything else is ``solve_many``'s.  Shape errors raise ValueError before any device call; a mask that
         keeps no element is refused by the library (DMF_ERR_BAD_ARG) before any solve starts."""
-        u0s = np.ascontiguousarray(u0s, dtype=np.float64)
-        alpha0s = np.ascontiguousarray(alpha0s, dtype=np.float64)
-        if u0s.ndim != 3 or u0s.shape[1] != self.N:
-            raise ValueError(f"u0s is B x {self.N} x n_u, got shape {u0s.shape}")
-        B, _, n_u = u0s.shape
-        K = self.n_c + n_u
-        if alpha0s.shape != (B, K, self.S):
-            raise ValueError(f"alpha0s shape {alpha0s.shape} != {(B, K, self.S)}")
-        bits = self._packed_train_masks(train_masks, B)
-        u = np.empty((B, self.N, n_u), dtype=np.float64)
-        alpha = np.empty((B, K, self.S), dtype=np.float64)
-        cost = np.empty(B, dtype=np.float64)
-        iters = np.empty(B, dtype=np.int64)
-        sum_sq = np.empty(B, dtype=np.float64)
-        n_test = np.empty(B, dtype=np.int64)
-        L.check(self._lib.dmf_solve_small_masked(self.ctx._h, self._h, B, _ptr(bits), _ptr(u0s), _ptr(alpha0s), n_u, int(mode),
-                                                 int(n_iter1), int(n_iter2), float(tol), int(iters_per_launch), 0, _ptr(u),
-                                                 _ptr(alpha), _ptr(cost), _ptr(iters), _ptr(sum_sq), _ptr(n_test)),
-                "dmf_solve_small_masked")
-        return u, alpha, cost, iters, sum_sq, n_test
+        return self._solve_batch("small", u0s, alpha0s, mode, n_iter1, n_iter2, tol, (iters_per_launch,), train_masks=train_masks)
 
     def _packed_train_masks(self, train_masks, B):
         """The train masks of B solves as the masked batch entries take them: uint8 (B, N, ceil(S / 8)) in ``pack_mask``'s
@@ -828,26 +788,8 @@ class Problem:
         ``solve_many_masked``'s; ``rows_per_workgroup``, ``check_every`` and the shapes taken are ``solve_many_mid``'s.  No
         ``idx`` and no ``purity``.  Shape errors raise ValueError before any device call; a mask that keeps no element is
         refused by the library (DMF_ERR_BAD_ARG) before any solve starts."""
-        u0s = np.ascontiguousarray(u0s, dtype=np.float64)
-        alpha0s = np.ascontiguousarray(alpha0s, dtype=np.float64)
-        if u0s.ndim != 3 or u0s.shape[1] != self.N:
-            raise ValueError(f"u0s is B x {self.N} x n_u, got shape {u0s.shape}")
-        B, _, n_u = u0s.shape
-        K = self.n_c + n_u
-        if alpha0s.shape != (B, K, self.S):
-            raise ValueError(f"alpha0s shape {alpha0s.shape} != {(B, K, self.S)}")
-        bits = self._packed_train_masks(train_masks, B)
-        u = np.empty((B, self.N, n_u), dtype=np.float64)
-        alpha = np.empty((B, K, self.S), dtype=np.float64)
-        cost = np.empty(B, dtype=np.float64)
-        iters = np.empty(B, dtype=np.int64)
-        sum_sq = np.empty(B, dtype=np.float64)
-        n_test = np.empty(B, dtype=np.int64)
-        L.check(self._lib.dmf_solve_mid_masked(self.ctx._h, self._h, B, _ptr(bits), _ptr(u0s), _ptr(alpha0s), n_u, int(mode),
-                                               int(n_iter1), int(n_iter2), float(tol), int(rows_per_workgroup),
-                                               int(check_every), 0, _ptr(u), _ptr(alpha), _ptr(cost), _ptr(iters), _ptr(sum_sq),
-                                               _ptr(n_test)), "dmf_solve_mid_masked")
-        return u, alpha, cost, iters, sum_sq, n_test
+        return self._solve_batch("mid", u0s, alpha0s, mode, n_iter1, n_iter2, tol, (rows_per_workgroup, check_every),
+                                 train_masks=train_masks)
 
     def update_u(self, u, u_prev, alpha, n_iter2, a1, l_w_prev, l_w, mode=L.DMF_MODE_PARTIAL):
         u = np.ascontiguousarray(u, dtype=np.float64).reshape(self.N, -1)

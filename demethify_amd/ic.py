@@ -16,6 +16,7 @@ import numpy as np
 from . import _lib as L
 from . import shard
 from . import init_func
+from .batch import family, solve_chunked
 from .deconvolution import _init_unsupervised, cost_f_w, init_BSSMF_md, solve_problem
 from .device import Problem, Solver, get_context
 from .staging import Prefetcher
@@ -212,21 +213,16 @@ def batched_ic_ineligible(n_u, n_rows, n_samples, n_ct, mode, kernel="small"):
     stands between a sweep and the batch: every initialiser runs on host arrays before the call).  ``kernel``: "small" (the
     default) or "mid" -- ``Problem.solve_many_mid`` / ``Problem.solve_many_mid_masked``, several workgroups per solve, with
     an envelope of their own.  Touches no device."""
-    from .device import mid_solve_supported, small_solve_supported
-
-    if kernel not in ("small", "mid"):
-        raise ValueError(f'kernel must be "small" or "mid", got {kernel!r}')
+    fam = family(kernel)
     if n_u < 1:
         return "there is no unknown cell type to solve for"
-    if kernel == "mid":
-        if not mid_solve_supported(n_rows, n_samples, n_ct, n_u, mode):
-            return (f"the shape {n_rows} x {n_samples} with {n_ct} + {n_u} cell types is outside the mid-size batch's envelope "
-                    f"(n_u <= {L.MID_MAX_NU}, K <= {L.MID_MAX_K}, S <= {L.MID_MAX_S}, N S <= {L.MID_MAX_ELEMENTS})")
-        return None
-    if not small_solve_supported(n_rows, n_samples, n_ct, n_u, mode):
-        return (f"the shape {n_rows} x {n_samples} with {n_ct} + {n_u} cell types is outside the batched kernel's envelope "
-                f"(n_u <= {L.SMALL_MAX_NU}, K <= {L.SMALL_MAX_K}, S <= {L.SMALL_MAX_S}, N S <= {L.SMALL_MAX_ELEMENTS})")
-    return None
+    return fam.outside(n_rows, n_samples, n_ct, n_u, mode)
+
+
+def _stack_inits(part, n_rows, n_u):
+    """(u0s, alpha0s) of a slice of (u0, alpha0, ...) tuples, as the batch methods take them."""
+    return (np.stack([np.asarray(item[0], dtype=np.float64).reshape(n_rows, n_u) for item in part]),
+            np.stack([item[1] for item in part]))
 
 
 def _bcv_batched(meth_f, n_u, counts, iter1, iter2, tol, n_folds, seed, ref, init_option, fraction, problem, batch_kernel):
@@ -234,31 +230,22 @@ def _bcv_batched(meth_f, n_u, counts, iter1, iter2, tol, n_folds, seed, ref, ini
     not depend on the solves, so the generator's stream is the serial one), the folds upstream skips are dropped, the rest
     are solved by ``problem.solve_many_masked`` (``batch_kernel`` "mid": ``problem.solve_many_mid_masked``) in chunks, and
     ic.py:80-86 is replayed in fold order."""
-    from .bootstrap import batch_chunk, mid_batch_chunk
-
     folds = []
     for _ in range(n_folds):
         fold = _bcv_draw_fold(meth_f, counts, ref, n_u, init_option, seed, fraction)
         if fold is not None:
             folds.append(fold)
     mode = L.DMF_MODE_PARTIAL if ref is not None else L.DMF_MODE_UNSUPERVISED
-    if batch_kernel == "mid":
-        chunk = mid_batch_chunk(meth_f.shape[0], meth_f.shape[1], 0 if ref is None else ref.shape[1], n_u, masked=True)
-        solve_many_masked = problem.solve_many_mid_masked
-    else:
-        chunk = batch_chunk(meth_f.shape[0], n_u)
-        solve_many_masked = problem.solve_many_masked
+    n_rows, n_samples = meth_f.shape
+    solved = solve_chunked(problem, family(batch_kernel), (n_rows, n_samples, 0 if ref is None else ref.shape[1], n_u), folds,
+                           lambda part: (*_stack_inits([f[1:] for f in part], n_rows, n_u), np.stack([f[0] for f in part])),
+                           (mode, iter1, iter2, tol), masked=True)
     total_press, best_u, best_alpha, min_error = 0, None, None, float("inf")
-    for c0 in range(0, len(folds), chunk):
-        part = folds[c0:c0 + chunk]
-        u, alpha, _, _, sum_sq, n_test = solve_many_masked(
-            np.stack([np.asarray(f[1], dtype=np.float64).reshape(meth_f.shape[0], n_u) for f in part]),
-            np.stack([f[2] for f in part]), np.stack([f[0] for f in part]), mode, iter1, iter2, tol)
-        for b in range(len(part)):
-            test_error = sum_sq[b] / n_test[b]
-            total_press += test_error
-            if test_error < min_error:
-                min_error, best_u, best_alpha = test_error, u[b], alpha[b]
+    for b in range(len(folds)):
+        test_error = solved[4][b] / solved[5][b]
+        total_press += test_error
+        if test_error < min_error:
+            min_error, best_u, best_alpha = test_error, solved[0][b], solved[1][b]
     return total_press, best_u, best_alpha
 
 
@@ -282,8 +269,7 @@ def bicross_validation(meth_f, n_u, counts, iter1, iter2, tol, n_folds=10, seed=
     ``batch_kernel`` (with ``batched``): "small", the default, or "mid" -- the folds go through
     ``Problem.solve_many_mid_masked``, several workgroups per fold (DESIGN.md section 6.3), inside that family's envelope;
     any other value raises ValueError."""
-    if batch_kernel not in ("small", "mid"):
-        raise ValueError(f'batch_kernel must be "small" or "mid", got {batch_kernel!r}')
+    family(batch_kernel, "batch_kernel")
     if batched:
         reason = batched_ic_ineligible(n_u, meth_f.shape[0], meth_f.shape[1], 0 if ref is None else ref.shape[1],
                                        L.DMF_MODE_UNSUPERVISED if ref is None else L.DMF_MODE_PARTIAL, kernel=batch_kernel)
@@ -329,29 +315,15 @@ def bicross_validation(meth_f, n_u, counts, iter1, iter2, tol, n_folds=10, seed=
 
 
 def _note_per_solve(candidates, rank, kernel="small"):
-    if candidates and rank == 0 and kernel == "mid":
-        print(f"note: candidates n_u = {candidates} are outside the mid-size batch's envelope (n_u <= {L.MID_MAX_NU}, "
-              f"K <= {L.MID_MAX_K}, S <= {L.MID_MAX_S}, N S <= {L.MID_MAX_ELEMENTS}): they take the per-solve path")
-    elif candidates and rank == 0:
-        print(f"note: candidates n_u = {candidates} are outside the batched kernel's envelope (n_u <= {L.SMALL_MAX_NU}, "
-              f"K <= {L.SMALL_MAX_K}, S <= {L.SMALL_MAX_S}, N S <= {L.SMALL_MAX_ELEMENTS}): they take the per-solve path")
+    if candidates and rank == 0:
+        print(f"note: candidates n_u = {candidates} are {family(kernel).envelope}: they take the per-solve path")
 
 
 def _solve_many_chunked(problem, inits, mode, iter1, iter2, tol, n_u, kernel="small"):
     """``problem.solve_many`` on a list of (u0, alpha0), at most bootstrap.batch_chunk solves per call -> (u, alpha, cost);
     ``kernel`` "mid": ``problem.solve_many_mid``, at most bootstrap.mid_batch_chunk solves per call."""
-    from .bootstrap import batch_chunk, mid_batch_chunk
-
-    if kernel == "mid":
-        chunk, solve_many = mid_batch_chunk(problem.N, problem.S, problem.n_c, n_u), problem.solve_many_mid
-    else:
-        chunk, solve_many = batch_chunk(problem.N, n_u), problem.solve_many
-    parts = []
-    for c0 in range(0, len(inits), chunk):
-        part = inits[c0:c0 + chunk]
-        parts.append(solve_many(np.stack([np.asarray(u0, dtype=np.float64).reshape(problem.N, n_u) for u0, _ in part]),
-                                        np.stack([a0 for _, a0 in part]), mode, iter1, iter2, tol)[:3])
-    return tuple(np.concatenate([part[j] for part in parts]) for j in range(3))
+    return solve_chunked(problem, family(kernel), (problem.N, problem.S, problem.n_c, n_u), inits,
+                         lambda part: (*_stack_inits(part, problem.N, n_u), None), (mode, iter1, iter2, tol))[:3]
 
 
 def evaluate_best_ic(meth_f, ref, counts, init_option, ic, seed, iter1, iter2, tol, n_restarts=5,
@@ -371,8 +343,7 @@ def evaluate_best_ic(meth_f, ref, counts, init_option, ic, seed, iter1, iter2, t
     its envelope in the place of the one-launch batch: CCC restarts and the AIC / BIC solve through
     ``Problem.solve_many_mid``, BCV folds through ``Problem.solve_many_mid_masked``.  Any other value raises ValueError.
     """
-    if batch_kernel not in ("small", "mid"):
-        raise ValueError(f'batch_kernel must be "small" or "mid", got {batch_kernel!r}')
+    family(batch_kernel, "batch_kernel")
     default_range = n_u_values is None
     if default_range:
         n_u_values = range(1, 25 + 1)
